@@ -34,7 +34,9 @@ region and replayed inside it (K kernels back to back; K separate launches if ca
 replayed as a hipGraph (five batches of >= 200 ms, median reported as roofline.sustained_launch_ms), so the chip is in its
 sustained clock / power state, not in a boost burst. "cpu_baseline" times the reference's own SSE2 path (oracle/_ref, built from
 the reference sources) on this box's host cores on a bounded sample -- rank 0, N = 1 only.
-Inputs are synthetic uniform-random uint8 already resident in HBM when the timed region starts.
+Inputs are synthetic uniform-random uint8 already resident in HBM when the timed region starts, drawn from fixed seeds: with
+the same arguments every run computes the same outputs, and `--dump-outputs DIR` writes those of the last timed step (a
+seeded sample of the GEMM's rows, dump_outputs()) so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -619,6 +621,26 @@ def emit(line, full_out):
     return text
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000   # --dump-outputs: all files together
+DUMP_ROWS = 1024                    # rows of the 4096 x 4096 headline output it writes (16 MB as float32)
+DUMP_ROWS_SEED = 0xD0               # which rows: a fixed, seeded choice, the same in every run
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy in float32 (exact for the uint8 outputs of the hot path), at most
+    DUMP_MAX_BYTES in all. Returns the paths written."""
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float32) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(directory, exist_ok=True)
+    paths = []
+    for name, a in arrays.items():
+        paths.append(os.path.join(directory, name + ".npy"))
+        np.save(paths[-1], a)
+    return paths
+
+
 def gather_floats(value, world):
     """[value of rank 0, ..., value of rank world-1] on every rank (all_gather over the harness process group)."""
     if world <= 1:
@@ -717,9 +739,16 @@ def main():
                     help="--layer mode only: output scale (requantization scale = 0.25 / this; 0.5 = the reference bench)")
     ap.add_argument("--layer", type=int, default=0,
                     help="measurement aid: time only MobileNetV2 sweep layer N (1-based) and print a short JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (rank 0's 4096 x 4096 GEMM output: "
+                         f"{DUMP_ROWS} rows chosen with a fixed seed) as DIR/q8gemm_output.npy, float32")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and (args.layer or stub_mode()):
+        ap.error("--dump-outputs writes the headline GEMM's output: not with --layer or the harness stub")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started plainly with --gpus N: become the launcher of N ranks (one process per GPU, RCCL over xGMI for
@@ -860,6 +889,11 @@ def main():
     if timed_graph is not None:
         lib.graph_destroy(timed_graph)
     lib.set_stream(torch.cuda.current_stream().cuda_stream)
+    if args.dump_outputs and rank == 0:
+        # every step writes the whole of `c` (same inputs), so after the synchronize above it holds the last step's output
+        rows = np.sort(np.random.default_rng(DUMP_ROWS_SEED).choice(M, DUMP_ROWS, replace=False))
+        for path in dump_outputs(args.dump_outputs, {"q8gemm_output": c.view(M, N).cpu().numpy()[rows]}):
+            print(f"# output of the last timed step written to {path}", file=sys.stderr)
     ms_per_step = job_time_ms(local_ms, world)
     gemm_kernel = lib.operator_kernel(op)
     # the same K launches by HIP events on the launch stream: kernel time without the host's share of the region

@@ -9,6 +9,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -195,3 +196,27 @@ def test_secondary_block_is_flat_and_carries_every_config():
     assert len(bench.RESNET18) == 11 and len(bench.RESNET50) == 23 and len(bench.SHUFFLENET_V1_G2) == 19
     assert (28, 28, 3, 3, 1, 1, 1, 128, 128) in bench.RESNET18 and (7, 7, 3, 3, 1, 1, 1, 512, 512) in bench.RESNET50
     assert (224, 224, 7, 7, 2, 1, 1, 3, 64) == bench.RESNET18[0] == bench.RESNET50[0]
+
+
+def test_dump_outputs_writes_float32_files_within_the_budget(tmp_path):
+    """--dump-outputs: DIR/<name>.npy, float32, the values unchanged; an output over the 64 MB budget is refused unwritten"""
+    sys.path.insert(0, ROOT)
+    import bench
+    rows = np.random.default_rng(1).integers(0, 256, size=(bench.DUMP_ROWS, 4096), dtype=np.uint8)
+    paths = bench.dump_outputs(str(tmp_path / "out"), {"q8gemm_output": rows})
+    assert paths == [str(tmp_path / "out" / "q8gemm_output.npy")]
+    got = np.load(paths[0])
+    assert got.dtype == np.float32 and np.array_equal(got, rows)
+    assert os.path.getsize(paths[0]) <= bench.DUMP_MAX_BYTES
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), {"a": np.zeros(bench.DUMP_MAX_BYTES // 8, np.uint8),
+                                                   "b": np.zeros(bench.DUMP_MAX_BYTES // 8 + 1, np.uint8)})
+    assert not (tmp_path / "big").exists()
+
+
+def test_dump_outputs_is_refused_where_the_gemm_does_not_run(tmp_path):
+    """the harness stub computes nothing: asking it for outputs is an error, never an empty directory"""
+    res = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "0",
+                          "--dump-outputs", str(tmp_path / "out")], env=_env(), capture_output=True, text=True, timeout=120)
+    assert res.returncode != 0 and "--dump-outputs" in res.stderr
+    assert not (tmp_path / "out").exists()
