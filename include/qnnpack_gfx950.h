@@ -22,6 +22,74 @@
 extern "C" {
 #endif
 
+/* Windowed pooling (reference include/qnnpack.h:162-218, prototypes unchanged; the rest of the reference's qnnpack.h
+ * subset is in qnnpack.h). Semantics and status codes are the reference's (src/average-pooling.c, src/max-pooling.c):
+ *   average pooling: sum (x - input_zero_point) over the taps inside the image, padding taps counting as zero but
+ *     counting in the divisor (pooling_height * pooling_width), quantized as global average pooling is;
+ *   max pooling: max over the window with every tap's coordinates clamped into the image (a window wholly in padding
+ *     returns the nearest edge pixel), then clamped to [output_min, output_max].
+ * Computed by HIP kernels (no indirection buffer); `threadpool` is ignored. Where the reference checks nothing and
+ * would read out of range, setup answers invalid_parameter: NULL tensors, a pixel stride below the channel count, a
+ * padded input smaller than the (dilated) window. Tensors beyond the kernels' index range (padded extent >= 2^31,
+ * output width * channels >= 2^31, batch * output height >= 2^32) are unsupported_parameter. */
+enum qnnp_status qnnp_create_average_pooling2d_nhwc_q8(
+    uint32_t input_padding_top,
+    uint32_t input_padding_right,
+    uint32_t input_padding_bottom,
+    uint32_t input_padding_left,
+    uint32_t pooling_height,
+    uint32_t pooling_width,
+    uint32_t stride_height,
+    uint32_t stride_width,
+    size_t channels,
+    uint8_t input_zero_point,
+    float input_scale,
+    uint8_t output_zero_point,
+    float output_scale,
+    uint8_t output_min,
+    uint8_t output_max,
+    uint32_t flags,
+    qnnp_operator_t* average_pooling);
+
+enum qnnp_status qnnp_setup_average_pooling2d_nhwc_q8(
+    qnnp_operator_t average_pooling,
+    size_t batch_size,
+    size_t input_height,
+    size_t input_width,
+    const uint8_t* input,
+    size_t input_stride,
+    uint8_t* output,
+    size_t output_stride,
+    pthreadpool_t threadpool);
+
+enum qnnp_status qnnp_create_max_pooling2d_nhwc_u8(
+    uint32_t input_padding_top,
+    uint32_t input_padding_right,
+    uint32_t input_padding_bottom,
+    uint32_t input_padding_left,
+    uint32_t pooling_height,
+    uint32_t pooling_width,
+    uint32_t stride_height,
+    uint32_t stride_width,
+    uint32_t dilation_height,
+    uint32_t dilation_width,
+    size_t channels,
+    uint8_t output_min,
+    uint8_t output_max,
+    uint32_t flags,
+    qnnp_operator_t* max_pooling);
+
+enum qnnp_status qnnp_setup_max_pooling2d_nhwc_u8(
+    qnnp_operator_t max_pooling,
+    size_t batch_size,
+    size_t input_height,
+    size_t input_width,
+    const uint8_t* input,
+    size_t input_stride,
+    uint8_t* output,
+    size_t output_stride,
+    pthreadpool_t threadpool);
+
 /* Devices. The library keeps one context (launch stream, asynchrony flag) per gfx950 GPU of the node.
  *   BEFORE qnnp_initialize: names the PRIMARY device qnnp_initialize binds (default: env QNNP_GFX950_DEVICE,
  *     else the calling thread's current HIP device).

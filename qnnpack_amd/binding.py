@@ -92,6 +92,21 @@ class QnnpackLibrary:
             c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)]
         L.qnnp_setup_fully_connected_nc_q8.restype = c_int
         L.qnnp_setup_fully_connected_nc_q8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
+        # windowed pooling (reference include/qnnpack.h:162-218; the product declares them in qnnpack_gfx950.h). Bound when
+        # present: an older product build named by QNNP_GFX950_LIBRARY may predate them.
+        if hasattr(L, "qnnp_create_max_pooling2d_nhwc_u8") or not os.environ.get("QNNP_GFX950_LIBRARY"):
+            L.qnnp_create_average_pooling2d_nhwc_q8.restype = c_int
+            L.qnnp_create_average_pooling2d_nhwc_q8.argtypes = (
+                [c_uint32] * 8 + [c_size_t, c_uint8, c_float, c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)])
+            L.qnnp_setup_average_pooling2d_nhwc_q8.restype = c_int
+            L.qnnp_setup_average_pooling2d_nhwc_q8.argtypes = [
+                c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]
+            L.qnnp_create_max_pooling2d_nhwc_u8.restype = c_int
+            L.qnnp_create_max_pooling2d_nhwc_u8.argtypes = (
+                [c_uint32] * 10 + [c_size_t, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)])
+            L.qnnp_setup_max_pooling2d_nhwc_u8.restype = c_int
+            L.qnnp_setup_max_pooling2d_nhwc_u8.argtypes = [
+                c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]
         L.qnnp_run_operator.restype = c_int
         L.qnnp_run_operator.argtypes = [c_void_p, c_void_p]
         L.qnnp_delete_operator.restype = c_int
@@ -254,6 +269,59 @@ class QnnpackLibrary:
         st = self.setup_fully_connected_nc_q8_status(*args)
         if st != Status.success:
             raise QnnpackError("qnnp_setup_fully_connected_nc_q8", st)
+
+    def create_average_pooling2d_nhwc_q8_status(
+            self, pad_top, pad_right, pad_bottom, pad_left, pooling_height, pooling_width, stride_height, stride_width,
+            channels, input_zero_point, input_scale, output_zero_point, output_scale, output_min, output_max, flags=0):
+        handle = c_void_p(None)
+        st = self.lib.qnnp_create_average_pooling2d_nhwc_q8(
+            pad_top, pad_right, pad_bottom, pad_left, pooling_height, pooling_width, stride_height, stride_width,
+            channels, input_zero_point, input_scale, output_zero_point, output_scale, output_min, output_max, flags,
+            ctypes.byref(handle))
+        return Status(st), handle.value
+
+    def create_average_pooling2d_nhwc_q8(self, *args, **kwargs) -> int:
+        st, handle = self.create_average_pooling2d_nhwc_q8_status(*args, **kwargs)
+        if st != Status.success:
+            raise QnnpackError("qnnp_create_average_pooling2d_nhwc_q8", st)
+        return handle
+
+    def setup_average_pooling2d_nhwc_q8_status(
+            self, op, batch_size, input_height, input_width, input, input_stride, output, output_stride) -> Status:
+        return Status(self.lib.qnnp_setup_average_pooling2d_nhwc_q8(
+            op, batch_size, input_height, input_width, address_of(input), input_stride,
+            address_of(output), output_stride, None))
+
+    def setup_average_pooling2d_nhwc_q8(self, *args) -> None:
+        st = self.setup_average_pooling2d_nhwc_q8_status(*args)
+        if st != Status.success:
+            raise QnnpackError("qnnp_setup_average_pooling2d_nhwc_q8", st)
+
+    def create_max_pooling2d_nhwc_u8_status(
+            self, pad_top, pad_right, pad_bottom, pad_left, pooling_height, pooling_width, stride_height, stride_width,
+            dilation_height, dilation_width, channels, output_min, output_max, flags=0):
+        handle = c_void_p(None)
+        st = self.lib.qnnp_create_max_pooling2d_nhwc_u8(
+            pad_top, pad_right, pad_bottom, pad_left, pooling_height, pooling_width, stride_height, stride_width,
+            dilation_height, dilation_width, channels, output_min, output_max, flags, ctypes.byref(handle))
+        return Status(st), handle.value
+
+    def create_max_pooling2d_nhwc_u8(self, *args, **kwargs) -> int:
+        st, handle = self.create_max_pooling2d_nhwc_u8_status(*args, **kwargs)
+        if st != Status.success:
+            raise QnnpackError("qnnp_create_max_pooling2d_nhwc_u8", st)
+        return handle
+
+    def setup_max_pooling2d_nhwc_u8_status(
+            self, op, batch_size, input_height, input_width, input, input_stride, output, output_stride) -> Status:
+        return Status(self.lib.qnnp_setup_max_pooling2d_nhwc_u8(
+            op, batch_size, input_height, input_width, address_of(input), input_stride,
+            address_of(output), output_stride, None))
+
+    def setup_max_pooling2d_nhwc_u8(self, *args) -> None:
+        st = self.setup_max_pooling2d_nhwc_u8_status(*args)
+        if st != Status.success:
+            raise QnnpackError("qnnp_setup_max_pooling2d_nhwc_u8", st)
 
     def run_operator_status(self, op, threadpool=None) -> Status:
         return Status(self.lib.qnnp_run_operator(op, threadpool))

@@ -5,7 +5,7 @@
  *
  * Replaces reference src/global-average-pooling.c:20-107 (create) and :109-148 (setup): same validation
  * order and status codes. The quantization parameters are the scalar member of
- * qnnp_compute_avgpool_quantization_params (reference src/qnnpack/requantization.h:200-222, :252-265),
+ * qnnp_compute_avgpool_quantization_params (reference src/qnnpack/requantization.h:200-222, :252-265; requantization.h),
  * recomputed at every setup from the pooled width exactly as the reference does (:138-145). The
  * reference's zero buffer (:79-85) has no equivalent: the device kernel never reads beyond `width` pixels.
  */
@@ -21,29 +21,12 @@
 #include "hip/qnnp_hip.h"
 #include "log.h"
 #include "operator.h"
+#include "requantization.h"
 #include "state.h"
 
 static inline bool scale_is_valid(float scale)
 {
   return scale > 0.0f && isnormal(scale);
-}
-
-/* reference requantization.h:200-222 + scalar members :252-265 */
-static struct qnnp_hip_avgpool_params compute_avgpool_params(
-    int32_t bias, float scale, uint8_t output_zero_point, uint8_t output_min, uint8_t output_max)
-{
-  uint32_t scale_bits;
-  memcpy(&scale_bits, &scale, sizeof(scale_bits));
-  struct qnnp_hip_avgpool_params p;
-  p.bias = bias;
-  p.multiplier = ((int32_t) scale_bits & INT32_C(0x007FFFFF)) | INT32_C(0x00800000);   /* [2^23, 2^24) */
-  const int32_t shift = 127 + 23 - (int32_t) (scale_bits >> 23);                        /* [16, 55] */
-  p.right_shift = (uint32_t) shift;
-  p.rounding = INT64_C(1) << (p.right_shift - 1);
-  p.output_min_less_zero_point = (int32_t) (uint32_t) output_min - (int32_t) (uint32_t) output_zero_point;
-  p.output_max_less_zero_point = (int32_t) (uint32_t) output_max - (int32_t) (uint32_t) output_zero_point;
-  p.output_zero_point = (int32_t) (uint32_t) output_zero_point;
-  return p;
 }
 
 static enum qnnp_status qnnp_create_global_average_pooling_nwc_q8_impl(
@@ -158,7 +141,7 @@ static enum qnnp_status qnnp_setup_global_average_pooling_nwc_q8_impl(
   op->input_pixel_stride = input_stride;
   op->output = output;
   op->output_pixel_stride = output_stride;
-  op->avgpool_params = compute_avgpool_params(
+  op->avgpool_params = qnnp_compute_avgpool_params(
       -(int32_t) width * (int32_t) (uint32_t) op->input_zero_point, scale,
       op->output_zero_point, op->output_min, op->output_max);
 

@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "add_math.hip.h"
+#include "avgpool_math.hip.h"
 #include "qnnp_hip.h"
 
 namespace qnnp {
@@ -63,17 +64,6 @@ void q8_vadd_strided_kernel(const qnnp_hip_vadd_args p)
     p.sum[row * p.sum_stride + c] =
         static_cast<uint8_t>(add_quantize(p.a[row * p.a_stride + c], p.b[row * p.b_stride + c], p.params));
   }
-}
-
-/* src/qnnpack/requantization.h:482-498 */
-__device__ __forceinline__ uint32_t avgpool_quantize(int32_t n, const qnnp_hip_avgpool_params& q)
-{
-  const int64_t product = static_cast<int64_t>(n) * static_cast<int64_t>(q.multiplier);
-  const int64_t adjusted = product - static_cast<int64_t>(n < 0);
-  int32_t y = static_cast<int32_t>((adjusted + q.rounding) >> q.right_shift);
-  y = y < q.output_min_less_zero_point ? q.output_min_less_zero_point : y;
-  y = y > q.output_max_less_zero_point ? q.output_max_less_zero_point : y;
-  return static_cast<uint32_t>(y + q.output_zero_point) & 0xFFu;
 }
 
 /*

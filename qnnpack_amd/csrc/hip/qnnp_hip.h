@@ -324,6 +324,34 @@ struct qnnp_hip_gavgpool_args {
 };
 int qnnp_hip_gavgpool_run(const struct qnnp_hip_gavgpool_args* args, const char** kernel_name);
 
+/* windowed max / average pooling (q8pool.hip, linked into libqnnpack_gfx950.so only -- see the Makefile): replace
+ * u8maxpool_ukernel_{16x9p8q,sub16}__sse2 / q8avgpool_ukernel_{up8x9,mp8x9p7q,up8xm}__sse2 and the max / average
+ * pooling cases of src/operator-run.c:845-940. The window is computed in the kernel (no indirection table). For output
+ * pixel (n, oy, ox) and channel c, with y0 = oy*stride_h - pad_top, x0 = ox*stride_w - pad_left:
+ *   max:     taps (y0 + ky*dilation_h, x0 + kx*dilation_w), each coordinate CLAMPED into the image (reference
+ *            src/indirection.c:192-230); out = max(min(max over taps, output_max), output_min)
+ *   average: taps (y0 + ky, x0 + kx) inside the image only (the others read the zero point: they add 0);
+ *            out = qnnp_avgpool_quantize(sum (x - input_zero_point)) with the scale over the WHOLE window
+ */
+struct qnnp_hip_pool_args {
+  const uint8_t* input;
+  uint8_t* output;
+  uint32_t batch;
+  uint32_t input_height, input_width;
+  uint32_t output_height, output_width;
+  uint32_t channels;
+  uint32_t kernel_height, kernel_width;
+  uint32_t stride_height, stride_width;
+  uint32_t dilation_height, dilation_width;   /* max pooling; 1 for average pooling */
+  uint32_t pad_top, pad_left;
+  uint64_t input_stride, output_stride;       /* bytes between pixels */
+  uint32_t output_min, output_max;            /* max pooling clamp */
+  int32_t input_zero_point;                   /* average pooling */
+  struct qnnp_hip_avgpool_params params;      /* average pooling (params.bias unused: the zero point is per tap) */
+};
+int qnnp_hip_maxpool_run(const struct qnnp_hip_pool_args* args, const char** kernel_name);
+int qnnp_hip_avgpool_run(const struct qnnp_hip_pool_args* args, const char** kernel_name);
+
 /* ---- fused inverted-residual block ---------------------------------------
  * [pointwise expand ->] depthwise 3x3 (pad 1, stride 1 | 2) -> pointwise project [-> + block input], one launch,
  * the expanded tensors live only in LDS (q8fused.hip). Arithmetic per stage is that of the stand-alone operators

@@ -333,7 +333,8 @@ static int launch_kernel(struct qnnp_operator* op, const void* input, const void
       return qnnp_hip_gavgpool_run(&args, &op->kernel_name);
     }
     default:
-      return QNNP_HIP_EINVAL;
+      /* windowed max / average pooling (operator.h launch_hook) */
+      return op->launch_hook != NULL ? op->launch_hook(op, input, output) : QNNP_HIP_EINVAL;
   }
 }
 

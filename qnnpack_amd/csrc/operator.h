@@ -24,6 +24,8 @@ enum qnnp_ukernel_type {
   qnnp_ukernel_type_add,
   qnnp_ukernel_type_global_average_pooling,
   qnnp_ukernel_type_fused_block,
+  qnnp_ukernel_type_max_pooling,        /* max-pooling.c */
+  qnnp_ukernel_type_average_pooling,    /* average-pooling.c */
 };
 
 /* One output phase of a strided deconvolution (deconvolution.c): the output pixels whose (oy + pad_top) % stride_h
@@ -179,6 +181,11 @@ struct qnnp_operator {
   int setup_valid;        /* 1 after a successful setup; cleared where a setup starts to change the operator, so a
                            * failed setup cannot be run against half-updated geometry / tables */
   struct qnnp_hip_dwconv_plan dw_plan;   /* depthwise launch plan, computed at the first run after a setup */
+
+  /* launch of operator types whose code is not part of every build (windowed pooling: max-pooling.c,
+   * average-pooling.c): set by their create, called by launch_kernel's default arm (operator-run.c) with device
+   * pointers. Keeps operator-run.c free of references to their kernels, so builds without them still link. */
+  int (*launch_hook)(struct qnnp_operator* op, const void* input, void* output);
 };
 
 /* Decide where a caller pointer lives and (re)size the device staging buffer a host pointer needs:

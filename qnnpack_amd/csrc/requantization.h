@@ -56,3 +56,25 @@ static inline uint32_t qnnp_accumulator_bits(const int32_t* bias, size_t count, 
   while (bits < 40 && (UINT64_C(1) << bits) < bound) bits++;
   return bits <= 31 ? bits : 0;
 }
+
+/*
+ * Scalar member of qnnp_compute_avgpool_quantization_params (reference src/qnnpack/requantization.h:200-222, :252-265):
+ * a scale in [2^-32, 256) becomes a 24-bit multiplier in [2^23, 2^24) and a right shift in [16, 55]. Consumed by
+ * avgpool_quantize (hip/avgpool_math.hip.h): global average pooling and windowed average pooling.
+ */
+static inline struct qnnp_hip_avgpool_params qnnp_compute_avgpool_params(
+    int32_t bias, float scale, uint8_t output_zero_point, uint8_t output_min, uint8_t output_max)
+{
+  uint32_t scale_bits;
+  memcpy(&scale_bits, &scale, sizeof(scale_bits));
+  struct qnnp_hip_avgpool_params p;
+  p.bias = bias;
+  p.multiplier = ((int32_t) scale_bits & INT32_C(0x007FFFFF)) | INT32_C(0x00800000);   /* [2^23, 2^24) */
+  const int32_t shift = 127 + 23 - (int32_t) (scale_bits >> 23);                        /* [16, 55] */
+  p.right_shift = (uint32_t) shift;
+  p.rounding = INT64_C(1) << (p.right_shift - 1);
+  p.output_min_less_zero_point = (int32_t) (uint32_t) output_min - (int32_t) (uint32_t) output_zero_point;
+  p.output_max_less_zero_point = (int32_t) (uint32_t) output_max - (int32_t) (uint32_t) output_zero_point;
+  p.output_zero_point = (int32_t) (uint32_t) output_zero_point;
+  return p;
+}
