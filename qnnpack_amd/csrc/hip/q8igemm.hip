@@ -510,14 +510,37 @@ int dispatch_vec(const IgemmParams& p, uint32_t groups, uint32_t vec, hipStream_
   }
 }
 
-}  // namespace
+// What qnnp_hip_igemm_run derives from its arguments before it picks a kernel
+struct IgemmSetup {
+  IgemmParams p;           // the standard weight image
+  IgemmParams pc;          // the zero-point-centred image, where `centred`
+  bool centred;
+  bool pad3;               // 3-channel slot mode
+  uint32_t vec;            // activation load width
+  qnnp::ConvGeom geom;
+};
 
-extern "C" int qnnp_hip_igemm_run(const struct qnnp_hip_igemm_args* a, const char** kernel_name)
+// Kernel zero points 127 / 128: the zero-point-centred image (convolution.c / fully-connected.c), with its own bias pair and no
+// row term. False: the operator has none.
+bool centred_params(const IgemmParams& p, const struct qnnp_hip_igemm_args* a, IgemmParams* pc)
+{
+  if (a->centre_flip == 0 || a->packed_w_centred == nullptr || a->bias2_centred == nullptr || a->bias2_pair == 0) return false;
+  *pc = p;
+  pc->packed_w = a->packed_w_centred;
+  pc->bias2 = a->bias2_centred;
+  pc->bias2u = a->bias2_centred + static_cast<size_t>(a->groups) * a->n_pad;
+  pc->a_flip = (a->centre_flip & 0xFFu) * 0x01010101u;
+  pc->row_coeff = 0;
+  return true;
+}
+
+// Argument checks and the parameters every kernel starts from
+int derive(const struct qnnp_hip_igemm_args* a, IgemmSetup& s)
 {
   if (a == nullptr || a->rows == 0 || a->groups == 0 || a->groups > 65535u) return QNNP_HIP_EINVAL;
   if (a->n_pad % 32 != 0 || a->k_pad % BK != 0 || a->k_pad < a->k_total) return QNNP_HIP_EINVAL;
 
-  IgemmParams p;
+  IgemmParams& p = s.p;
   p.input = a->input;
   p.output = a->output;
   p.packed_w = a->packed_w;
@@ -604,6 +627,7 @@ extern "C" int qnnp_hip_igemm_run(const struct qnnp_hip_igemm_args* a, const cha
   } else if (a->n % 4 == 0 && a->output_stride % 4 == 0 && out_addr % 4 == 0) {
     p.store_mode = 1;
   }
+  s.pad3 = pad3; s.vec = vec;
 
   // Fused residual add: carried by the pointwise streaming kernels' epilogues (what a MobileNet-style project layer runs
   // on) when the residual rows are laid out like the output rows; everything else reports "not folded" and the caller
@@ -622,191 +646,182 @@ extern "C" int qnnp_hip_igemm_run(const struct qnnp_hip_igemm_args* a, const cha
       p.add = *a->residual_add;
     }
   }
-  auto folded = [&]() { if (p.residual != nullptr) *a->residual_folded = 1; };
-
-  hipStream_t stream = reinterpret_cast<hipStream_t>(qnnp_hip_get_stream());
-  const char* name = nullptr;
-  // Dense convolutions with power-of-two channel counts: LDS-tiled direct convolution (input read once).
-  qnnp::ConvGeom geom;
+  qnnp::ConvGeom& geom = s.geom;
   geom.H = a->input_height; geom.W = a->input_width; geom.OH = a->output_height; geom.OW = a->output_width;
   geom.KH = a->kernel_height; geom.KW = a->kernel_width; geom.sh = a->stride_height; geom.sw = a->stride_width;
   geom.dh = a->dilation_height; geom.dw = a->dilation_width; geom.pad_top = a->pad_top; geom.pad_left = a->pad_left;
-  const bool lds_ok = a->offsets != nullptr && !pad3 && a->rows_per_image > 0 &&
-      a->output_stride % 16 == 0 && qnnp::convlds_supported(p, geom, a->groups, vec);
+  s.centred = centred_params(p, a, &s.pc);
+  return QNNP_HIP_OK;
+}
+
+// A plan: the launcher (Generic: this file's tile kernel), the weight image it runs on (Rowsum: the standard image and its row
+// term with a_flip = 0x80808080, q8gemm256x.hip's ROWSUM flavour) and the launcher's flavour argument: wave / row-slot flavour,
+// 128-row tile width, gemm256c opt, or gemm256_launch's `lean` (0 never, 1 where supported, 2 forced) with the kBig* flags.
+enum class Kernel : uint8_t { Generic, Wave, Ws16s, Patch, Lds, Rows16, Rows32, C3, Mid, U, Pw, LongK, Gw, Big, BigC, BigX };
+enum class Image : uint8_t { Standard, Centred, Rows, Rowsum };
+constexpr uint32_t kBigWaves4 = 4u, kBigRows128 = 8u, kBigPingpong = 16u;
+struct IgemmPlan { Kernel kernel; Image image; uint32_t option; };
+
+// "gemm_kernel" codes (include/qnnpack_gfx950_test.h). 0 is the automatic choice; codes not named here (1, and 13 / 31 when
+// they reach this function) take the generic tile kernel.
+enum : int {
+  kCodeBig = 2, kCodeLds = 3, kCodeBigWaves4 = 4, kCodePw = 5, kCodeGw = 6, kCodeC3 = 7, kCodeWave = 8, kCodeLongK = 9,
+  kCodeBigRows128 = 10, kCodeBigPingpong = 11, kCodeWaveReg = 12, kCodeRows = 14, kCodeBigLean = 15, kCodeBigWaves4Lean = 16,
+  kCodeBigC = 20, kCodeBigCAB = 21, kCodePatch = 22, kCodeBigX = 23, kCodeMid = 24, kCodeMid64 = 25, kCodeMid128 = 26,
+  kCodeWaveWs32 = 27, kCodeBigXRowsum = 28, kCodeU = 29, kCodeRowsLds = 30, kCodeWs16s = 32,
+};
+
+// What each code forces. 4 / 10 / 11 / 16 are refused by gemm256_launch outside measurement builds.
+IgemmPlan forced_plan(int code, Image wave_image)
+{
+  switch (code) {
+    case kCodeBig: return {Kernel::Big, Image::Standard, 0u};   // the general flavour, for A/B
+    case kCodeBigWaves4: return {Kernel::Big, Image::Standard, kBigWaves4};
+    case kCodeBigRows128: return {Kernel::Big, Image::Standard, kBigRows128};
+    case kCodeBigPingpong: return {Kernel::Big, Image::Standard, kBigPingpong};
+    case kCodeBigLean: return {Kernel::Big, Image::Standard, 2u};
+    case kCodeBigWaves4Lean: return {Kernel::Big, Image::Standard, kBigWaves4 | 2u};
+    case kCodeBigC: return {Kernel::BigC, Image::Centred, 0u};
+    case kCodeBigCAB: return {Kernel::BigC, Image::Centred, 2u};
+    case kCodeBigX: return {Kernel::BigX, Image::Centred, 0u};
+    case kCodeBigXRowsum: return {Kernel::BigX, Image::Rowsum, 0u};
+    case kCodeMid: return {Kernel::Mid, Image::Centred, 0u};
+    case kCodeMid64: return {Kernel::Mid, Image::Centred, 64u};
+    case kCodeMid128: return {Kernel::Mid, Image::Centred, 128u};
+    case kCodeU: return {Kernel::U, Image::Standard, 0u};
+    case kCodePw: return {Kernel::Pw, Image::Standard, 0u};
+    case kCodeLongK: return {Kernel::LongK, Image::Standard, 0u};
+    case kCodeGw: return {Kernel::Gw, Image::Standard, 0u};
+    case kCodeC3: return {Kernel::C3, Image::Standard, 0u};
+    case kCodeLds: return {Kernel::Lds, Image::Standard, 0u};
+    case kCodePatch: return {Kernel::Patch, Image::Standard, 0u};
+    case kCodeWs16s: return {Kernel::Ws16s, Image::Centred, 0u};
+    case kCodeWave: return {Kernel::Wave, wave_image, 0u};
+    case kCodeWaveReg: return {Kernel::Wave, wave_image, 1u};    // the round-2 register-path kernel
+    case kCodeWaveWs32: return {Kernel::Wave, wave_image, 2u};   // the 32x32x32 weight-stationary kernel (A/B)
+    case kCodeRows: return {Kernel::Rows16, Image::Rows, 1u};     // the register-path kernel
+    case kCodeRowsLds: return {Kernel::Rows16, Image::Rows, 2u};  // the LDS-staged kernel or nothing
+    default: return {Kernel::Generic, Image::Standard, 0u};
+  }
+}
+
+// The parameters of a plan's image; `built` holds the ones made here
+const IgemmParams& image_params(const IgemmSetup& s, const struct qnnp_hip_igemm_args* a, Image image, IgemmParams& built)
+{
+  if (image == Image::Standard) return s.p;
+  if (image == Image::Centred) return s.pc;
+  built = s.p;
+  if (image == Image::Rowsum) built.a_flip = 0x80808080u;
+  if (image == Image::Rows && a->bias2_rows != nullptr) {   // the row-slot image centred on kernel zero point 127: no row term
+    built.bias2 = a->bias2_rows;
+    built.bias2u = a->bias2_rows + a->n_pad;
+    built.row_coeff = 0;
+    built.a_flip = 0x7F7F7F7Fu;
+  }
+  return built;
+}
+
+// The 256x256 kernels on a recentred image (q8gemm256c.hip / q8gemm256x.hip), beyond what the 256x256 kernel itself needs
+bool big_image_ok(const IgemmSetup& s, const struct qnnp_hip_igemm_args* a, Image image)
+{
+  IgemmParams built;
+  const bool has_image = image == Image::Centred ? s.centred : s.p.bias2u != nullptr;
+  return has_image && qnnp::gemm256c_supported(image_params(s, a, image, built), s.vec);
+}
+
+// Whether a kernel takes the operator: its *_supported predicate and what the dispatch adds to it
+bool supported(const IgemmSetup& s, const struct qnnp_hip_igemm_args* a, Kernel k, Image image = Image::Standard)
+{
+  const IgemmParams& p = s.p;
+  const bool direct = a->offsets != nullptr && !s.pad3 && a->rows_per_image > 0;   // the direct convolutions
+  const uint32_t batch = direct ? a->rows / a->rows_per_image : 0u;
+  switch (k) {
+    case Kernel::Wave: return direct && p.store_mode == 2 && qnnp::convwave_supported(p, s.geom, a->groups, s.vec, batch);
+    case Kernel::Ws16s: return s.centred && a->groups == 1 && direct && qnnp::convws16s_supported(s.pc, s.geom, a->groups, s.vec, batch);
+    case Kernel::Patch: return direct && qnnp::convpatch_supported(p, s.geom, a->groups, s.vec, batch);
+    case Kernel::Lds: return direct && a->output_stride % 16 == 0 && qnnp::convlds_supported(p, s.geom, a->groups, s.vec);
+    // (store_mode 1 with channels % 8 == 0: ShuffleNet's 3 -> 24 layer -- the kernel checks the 8-byte alignment it needs itself)
+    case Kernel::Rows16:
+      return s.pad3 && (p.store_mode == 2 || (p.store_mode == 1 && a->n % 8u == 0)) &&
+             qnnp::conv_c3rows_supported(p, s.geom, a->groups, a->packed_w_rows16, a->kc);
+    case Kernel::Rows32: return s.pad3 && p.store_mode == 2 && qnnp::conv_c3rows32_supported(p, s.geom, a->groups, a->packed_w_rows16, a->kc);
+    case Kernel::C3: return s.pad3 && qnnp::convstream_c3_supported(p, a->groups);
+    case Kernel::Mid: return !s.pad3 && s.centred && a->groups == 1 && qnnp::gemm128x_supported(s.pc, s.vec);
+    case Kernel::U: return !s.pad3 && qnnp::gemm128u_supported(p);
+    case Kernel::Pw: return !s.pad3 && qnnp::pwstream_supported(p, a->groups, s.vec) && (p.d2s_sh == 0 || s.vec == 16);
+    case Kernel::LongK: return !s.pad3 && qnnp::pwstream_longk_supported(p, a->groups, s.vec);
+    case Kernel::Gw: return !s.pad3 && qnnp::pwstream_gw_supported(p, a->groups, s.vec);
+    case Kernel::Big: return !s.pad3 && qnnp::gemm256_supported(p, s.vec);
+    case Kernel::BigC: case Kernel::BigX: return supported(s, a, Kernel::Big) && big_image_ok(s, a, image);
+    case Kernel::Generic: break;
+  }
+  return true;
+}
+
+// The kernel choice. It makes no HIP call. QNNP_HIP_EINVAL: a forced kernel that does not take the operator.
+int make_plan(const IgemmSetup& s, const struct qnnp_hip_igemm_args* a, IgemmPlan* plan)
+{
+  const Image wave_image = s.centred && a->groups == 1 ? Image::Centred : Image::Standard;
+  if (s.p.d2s_sh != 0 && a->variant != kCodePw) return QNNP_HIP_EINVAL;   // depth-to-space exists in the streaming kernel only
+  if (a->variant != 0) {
+    *plan = forced_plan(a->variant, wave_image);
+    // 14 / 30: the 32-byte-slot flavour for 5- and 7-row windows (ResNet's 7x7 entry layer) where the 16-byte one refuses
+    if (plan->kernel == Kernel::Rows16 && !supported(s, a, Kernel::Rows16)) plan->kernel = Kernel::Rows32;
+    return supported(s, a, plan->kernel, plan->image) ? QNNP_HIP_OK : QNNP_HIP_EINVAL;
+  }
+  auto pick = [plan](Kernel k, Image image = Image::Standard, uint32_t option = 0u) { *plan = IgemmPlan{k, image, option}; return QNNP_HIP_OK; };
+  auto pick_mid = [&]() { return pick(Kernel::Mid, Image::Centred); };
   // 3x3 / stride 1 / dilation 1 windows with 32 or 64 channels in and out (BASELINE configs[2]): one wave per 8x8 block of
   // positions, patches streamed by LDS-DMA, no barriers (q8convwave.hip) -- 31 us against 37.7 us for the LDS-tiled
-  // kernel on configs[2], same box. Other windows the wave kernel accepts run on it only when forced ("gemm_kernel" = 8).
-  const bool wave_shape = a->offsets != nullptr && !pad3 && a->rows_per_image > 0 && p.store_mode == 2 &&
-      qnnp::convwave_supported(p, geom, a->groups, vec, a->rows / a->rows_per_image);
-  const bool wave_k33 = geom.KH == 3 && geom.KW == 3 && geom.sh == 1 && geom.sw == 1 && geom.dh == 1 && geom.dw == 1;
-  // ("gemm_kernel" = 12: the same family with the round-2 register-path kernel instead of the weight-stationary one)
-  const bool wave_forced = a->variant == 8 || a->variant == 12 || a->variant == 27;   // 27: the 32x32x32 weight-stationary kernel (A/B)
-  const bool wave_ok = wave_shape && (wave_forced || (a->variant == 0 && wave_k33 && a->rows >= 16384u));
-  if (wave_forced && !wave_ok) return QNNP_HIP_EINVAL;
-  if (wave_ok) {
-    // kernel zero points 127 / 128: the zero-point-centred image (convolution.c builds it for single-group convolutions
-    // without K padding), taken by the weight-stationary kernel
-    IgemmParams pc = p;
-    const bool centred = a->centre_flip != 0 && a->packed_w_centred != nullptr && a->bias2_centred != nullptr &&
-        a->bias2_pair != 0 && a->groups == 1;
-    if (centred) {
-      pc.packed_w = a->packed_w_centred;
-      pc.bias2 = a->bias2_centred;
-      pc.bias2u = a->bias2_centred + static_cast<size_t>(a->groups) * a->n_pad;
-      pc.a_flip = (a->centre_flip & 0xFFu) * 0x01010101u;
-      pc.row_coeff = 0;
-    }
-    const int rc_wave = qnnp::convwave_launch(p, geom, a->rows / a->rows_per_image, stream, &name, a->variant == 12 ? 1 : (a->variant == 27 ? 2 : 0),
-                                              centred ? &pc : nullptr);
-    if (kernel_name != nullptr) *kernel_name = name;
-    return rc_wave;
-  }
-  // (round 6) dense 3x3 / stride 1 with 16 / 32 / 48 / 64 input channels and a centred image (SqueezeNet's fire modules): the weight-stationary
-  // kernel with the channel count as a template argument (q8convws16s.hip); "gemm_kernel" = 32 forces it, 1 / 3 / 22 keep what it replaces
-  {
-    IgemmParams ps = p;
-    const bool centred = a->centre_flip != 0 && a->packed_w_centred != nullptr && a->bias2_centred != nullptr &&
-        a->bias2_pair != 0 && a->groups == 1;
-    if (centred) {
-      ps.packed_w = a->packed_w_centred;
-      ps.bias2 = a->bias2_centred;
-      ps.bias2u = a->bias2_centred + static_cast<size_t>(a->groups) * a->n_pad;
-      ps.a_flip = (a->centre_flip & 0xFFu) * 0x01010101u;
-      ps.row_coeff = 0;
-    }
-    const bool s_ok = centred && a->offsets != nullptr && !pad3 && a->rows_per_image > 0 &&
-        qnnp::convws16s_supported(ps, geom, a->groups, vec, a->rows / a->rows_per_image);
-    if (a->variant == 32 && !s_ok) return QNNP_HIP_EINVAL;
-    // (auto: everything but 64 -> 32 / 64, which the block above has taken; 64 -> 256 leaves the patch kernel: 27 x 27 24.7 -> 19.5 us,
-    //  13 x 13 9.4 -> 9.0: profiles/r06/conv3x3_small_channels_r06y.txt)
-    if (s_ok && (a->variant == 32 || (a->variant == 0 && a->rows >= 16384u))) {
-      const int rc_s = qnnp::convws16s_launch(ps, geom, a->rows / a->rows_per_image, stream, &name);
-      if (kernel_name != nullptr) *kernel_name = name;
-      return rc_s;
-    }
-  }
-  // Dense 3x3 with many channels (ResNet's 128 / 256 / 512-channel layers): patch in LDS, weights streamed (q8convpatch.hip);
-  // "gemm_kernel" = 22 forces it, 1 / 2 / 3 keep the kernels it replaces.
-  const bool patch_ok = a->offsets != nullptr && !pad3 && a->rows_per_image > 0 &&
-      qnnp::convpatch_supported(p, geom, a->groups, vec, a->rows / a->rows_per_image);
-  if (a->variant == 22 && !patch_ok) return QNNP_HIP_EINVAL;
-  if (patch_ok && (a->variant == 22 || (a->variant == 0 && a->rows >= 4096u))) {
-    const int rc_patch = qnnp::convpatch_launch(p, geom, a->rows / a->rows_per_image, stream, &name);
-    if (kernel_name != nullptr) *kernel_name = name;
-    return rc_patch;
-  }
-  if (a->variant == 3 && !lds_ok) return QNNP_HIP_EINVAL;
-  if (lds_ok && (a->variant == 3 || (a->variant == 0 && a->kernel_height * a->kernel_width > 1))) {
-    const int rc_lds = qnnp::convlds_launch(p, geom, a->rows / a->rows_per_image, stream, &name);
-    if (kernel_name != nullptr) *kernel_name = name;
-    return rc_lds;
-  }
-  // 3-channel images (first layers) with dense pixels: one 16-byte fetch per kernel row (q8convc3.hip);
-  // "gemm_kernel" = 14 forces it, 7 keeps the tap-gather kernel below
-  // (store_mode 1 with channels % 8 == 0: ShuffleNet's 3 -> 24 layer -- the kernel checks the 8-byte alignment it needs itself)
-  const bool rows16_ok = pad3 && (p.store_mode == 2 || (p.store_mode == 1 && a->n % 8u == 0)) &&
-      qnnp::conv_c3rows_supported(p, geom, a->groups, a->packed_w_rows16, a->kc);
-  if ((a->variant == 14 || a->variant == 30) && !rows16_ok && !(pad3 && p.store_mode == 2 && qnnp::conv_c3rows32_supported(p, geom, a->groups, a->packed_w_rows16, a->kc))) return QNNP_HIP_EINVAL;
-  if (rows16_ok && (a->variant == 14 || a->variant == 30 || (a->variant == 0 && a->rows >= 2048))) {
-    qnnp::IgemmParams p16 = p;
-    if (a->bias2_rows != nullptr) {          // the image is centred on kernel zero point 127: its own bias pair, no row term
-      p16.bias2 = a->bias2_rows;
-      p16.bias2u = a->bias2_rows + a->n_pad;
-      p16.row_coeff = 0;
-      p16.a_flip = 0x7F7F7F7Fu;
-    }
-    const int rc_r16 = qnnp::conv_c3rows_launch(p16, geom, a->packed_w_rows16, stream, &name, a->variant == 14 ? 1 : (a->variant == 30 ? 2 : 0));
-    if (kernel_name != nullptr) *kernel_name = name;
-    return rc_r16;
-  }
-  // ... and its 32-byte-slot flavour for 5- and 7-row windows (ResNet's 7x7 entry layer); "gemm_kernel" = 14 forces it too
-  const bool rows32_ok = pad3 && p.store_mode == 2 && qnnp::conv_c3rows32_supported(p, geom, a->groups, a->packed_w_rows16, a->kc);
-  // (30 = its LDS-staged flavour or nothing; 14 = the register-path kernel; auto: the LDS-staged one where its plan takes the shape)
-  if (a->variant == 30 && !rows32_ok) return QNNP_HIP_EINVAL;
-  if (rows32_ok && (a->variant == 14 || a->variant == 30 || (a->variant == 0 && a->rows >= 2048))) {
-    qnnp::IgemmParams p32 = p;
-    if (a->bias2_rows != nullptr) {          // the image is centred on kernel zero point 127: its own bias pair, no row term
-      p32.bias2 = a->bias2_rows;
-      p32.bias2u = a->bias2_rows + a->n_pad;
-      p32.row_coeff = 0;
-      p32.a_flip = 0x7F7F7F7Fu;
-    }
-    const int rc_r32 = qnnp::conv_c3rows32_launch(p32, geom, a->packed_w_rows16, stream, &name, a->variant == 14 ? 1 : (a->variant == 30 ? 2 : 0));
-    if (kernel_name != nullptr) *kernel_name = name;
-    return rc_r32;
-  }
+  // kernel on configs[2], same box. Other windows the wave kernel accepts run on it only when forced.
+  const qnnp::ConvGeom& g = s.geom;
+  const bool wave_k33 = g.KH == 3 && g.KW == 3 && g.sh == 1 && g.sw == 1 && g.dh == 1 && g.dw == 1;
+  if (wave_k33 && a->rows >= 16384u && supported(s, a, Kernel::Wave)) return pick(Kernel::Wave, wave_image);
+  // (round 6) dense 3x3 / stride 1 with 16 / 32 / 48 / 64 input channels and a centred image (SqueezeNet's fire modules): the
+  // weight-stationary kernel with the channel count as a template argument (q8convws16s.hip)
+  // (auto: everything but 64 -> 32 / 64, which the rule above has taken; 64 -> 256 leaves the patch kernel: 27 x 27 24.7 -> 19.5 us,
+  //  13 x 13 9.4 -> 9.0: profiles/r06/conv3x3_small_channels_r06y.txt)
+  if (a->rows >= 16384u && supported(s, a, Kernel::Ws16s)) return pick(Kernel::Ws16s, Image::Centred);
+  // Dense 3x3 with many channels (ResNet's 128 / 256 / 512-channel layers): patch in LDS, weights streamed (q8convpatch.hip)
+  if (a->rows >= 4096u && supported(s, a, Kernel::Patch)) return pick(Kernel::Patch);
+  // Dense convolutions with power-of-two channel counts: LDS-tiled direct convolution (input read once).
+  if (a->kernel_height * a->kernel_width > 1 && supported(s, a, Kernel::Lds)) return pick(Kernel::Lds);
+  // 3-channel images (first layers) with dense pixels: one 16-byte fetch per kernel row (q8convc3.hip), then its 32-byte-slot
+  // flavour for 5- and 7-row windows; each the LDS-staged kernel where its plan takes the shape
+  if (a->rows >= 2048u && supported(s, a, Kernel::Rows16)) return pick(Kernel::Rows16, Image::Rows);
+  if (a->rows >= 2048u && supported(s, a, Kernel::Rows32)) return pick(Kernel::Rows32, Image::Rows);
   // 3-channel images (first layers): barrier-free streaming kernel with an in-register tap gather.
-  const bool c3_ok = pad3 && qnnp::convstream_c3_supported(p, a->groups);
-  if (a->variant == 7 && !c3_ok) return QNNP_HIP_EINVAL;
-  if (c3_ok && (a->variant == 7 || (a->variant == 0 && a->rows >= 2048))) {
-    const int rc_c3 = qnnp::convstream_c3_launch(p, stream, &name);
-    if (kernel_name != nullptr) *kernel_name = name;
-    return rc_c3;
-  }
+  if (a->rows >= 2048u && supported(s, a, Kernel::C3)) return pick(Kernel::C3);
   // Mid-size GEMMs on the zero-point-centred image: 128-row tiles of four waves, two or three workgroups per CU (q8gemm128x.hip,
-  // round 6); "gemm_kernel" = 24 forces it (25 / 26: with 64- / 128-channel tiles). Where auto takes it (measured at batch 128,
-  // profiles/r06/mid_gemm_by_forced_kernel_r06d.txt) is decided below, next to the kernel it replaces.
-  qnnp::IgemmParams pmid = p;
-  bool mid_ok = !pad3 && a->centre_flip != 0 && a->packed_w_centred != nullptr && a->bias2_centred != nullptr && a->bias2_pair != 0 &&
-      a->groups == 1 && p.d2s_sh == 0;
-  if (mid_ok) {
-    pmid.packed_w = a->packed_w_centred;
-    pmid.bias2 = a->bias2_centred;
-    pmid.bias2u = a->bias2_centred + static_cast<size_t>(a->groups) * a->n_pad;
-    pmid.a_flip = (a->centre_flip & 0xFFu) * 0x01010101u;
-    pmid.row_coeff = 0;
-    mid_ok = qnnp::gemm128x_supported(pmid, vec);
-  }
-  const bool mid_forced = a->variant == 24 || a->variant == 25 || a->variant == 26;     // 25 / 26: 64- / 128-wide tiles (A/B)
-  if (mid_forced && !mid_ok) return QNNP_HIP_EINVAL;
-  auto launch_mid = [&]() {
-    const int rc_mid = qnnp::gemm128x_launch(pmid, a->groups, stream, &name, a->variant == 25 ? 64u : (a->variant == 26 ? 128u : 0u));
-    if (kernel_name != nullptr) *kernel_name = name;
-    return rc_mid;
-  };
-  if (mid_forced) return launch_mid();
+  // round 6). Where auto takes it (measured at batch 128, profiles/r06/mid_gemm_by_forced_kernel_r06d.txt) is decided below,
+  // next to the kernel it replaces.
+  const bool mid_ok = supported(s, a, Kernel::Mid);
   // (strided 1x1 convolutions over few rows -- ResNet-18's 28x28 128 -> 256 and 14x14 256 -> 512 shortcuts, 25 k / 6 k output pixels:
   //  7.9 -> 6.1 us and 8.2 -> 5.4 against the streaming kernel's table rows; with 100 k rows the streaming kernel keeps them)
-  if (a->variant == 0 && mid_ok && a->offsets != nullptr && a->rows <= 32768u && a->k_total >= 128u && a->k_total <= 256u && a->rows >= 2048u) return launch_mid();
+  if (mid_ok && a->offsets != nullptr && a->rows <= 32768u && a->k_total >= 128u && a->k_total <= 256u && a->rows >= 2048u) return pick_mid();
   // (round 6: pointwise layers whose channel count forces BYTE stores on the streaming kernel -- ShuffleNet v2's 24 -> 58 / 122 at 56 x 56:
   //  56.3 / 122.1 us -- run on the register-staged 128-row GEMM instead: 36.3 / 78.6 us, profiles/r06/ugemm_by_forced_kernel_r06p.txt)
   // (... and, with the transposed 16-byte stores of that kernel, the streaming kernel's DWORD-store shapes -- channel counts of 4 mod 8 --
   //  from 56 channels up: 56 x 56 24 -> 60 / 68 20.9 / 24.5 -> 17.1 / 22.4 us (profiles/r06/ugemm_transposed_stores_r06v.txt); 24 -> 36
   //  stays, 12.0 against 13.8, and so do multiples of 8 -- 24 -> 88 12.9 against 23.8, 88 -> 88 8.2 against 10.0: run r06w's lists)
   // (SqueezeNet's 13 x 13 512 -> 1000 with a centred image: the 128-row centred GEMM with dword-aligned stores, 25.7 against 27.8 us)
-  if (a->variant == 0 && mid_ok && p.store_mode == 1 && a->n >= 256u && a->k_total >= 256u && a->rows >= 2048u && a->offsets == nullptr) return launch_mid();
+  if (mid_ok && s.p.store_mode == 1 && a->n >= 256u && a->k_total >= 256u && a->rows >= 2048u && a->offsets == nullptr) return pick_mid();
   // (... and wide ones: a channel run of 360 -- ShuffleNet v1 g8's 12 -> 45 as a dense 96 -> 360 -- 31.3 us on the streaming kernel, 21.0 here;
   //  SqueezeNet's 13 x 13 512 -> 1000 35.1 us on the 256-wide GEMM's padding path, 25.5 here: run r06z's lists against r06w's)
-  if (a->variant == 0 && !pad3 && (p.store_mode == 0 || (p.store_mode == 1 && ((a->n % 8u != 0u && a->n >= 56u) || a->n >= 256u))) && a->rows >= 2048u && p.d2s_sh == 0 &&
-      a->residual == nullptr && qnnp::gemm128u_supported(p)) {
-    const int rc_u = qnnp::gemm128u_launch(p, a->groups, stream, &name, 0u);
-    if (kernel_name != nullptr) *kernel_name = name;
-    return rc_u;
-  }
+  if ((s.p.store_mode == 0 || (s.p.store_mode == 1 && ((a->n % 8u != 0u && a->n >= 56u) || a->n >= 256u))) && a->rows >= 2048u &&
+      a->residual == nullptr && supported(s, a, Kernel::U)) return pick(Kernel::U);
   // Short-K pointwise / fully-connected layers over many rows: barrier-free streaming kernel.
-  const bool pw_ok = !pad3 && qnnp::pwstream_supported(p, a->groups, vec) && (p.d2s_sh == 0 || vec == 16);
-  if ((a->variant == 5 || p.d2s_sh != 0) && !pw_ok) return QNNP_HIP_EINVAL;   /* depth-to-space exists in this kernel only */
-  if (p.d2s_sh != 0 && a->variant != 5) return QNNP_HIP_EINVAL;
+  const bool pw_ok = supported(s, a, Kernel::Pw);
   // (round 6: few rows x many channels -- ShuffleNet's last 1x1, 7x7 192 -> 1024 at 6 k rows: the streaming kernel runs one chain per
   //  wave, 8.3 us; the 128-row GEMMs 6.0 (centred image) / 6.8 us (standard image): profiles/r06/ugemm_transposed_stores_r06v.txt)
-  const bool few_rows_wide = a->variant == 0 && !pad3 && a->rows >= 2048u && a->rows <= 8192u && a->n >= 512u && a->k_total >= 192u &&
-      p.d2s_sh == 0 && a->residual == nullptr && a->offsets == nullptr;
-  if (few_rows_wide && pw_ok && mid_ok) return launch_mid();
-  if (few_rows_wide && pw_ok && qnnp::gemm128u_supported(p)) {
-    const int rc_u = qnnp::gemm128u_launch(p, a->groups, stream, &name, 0u);
-    if (kernel_name != nullptr) *kernel_name = name;
-    return rc_u;
-  }
-  if (pw_ok && (a->variant == 5 || (a->variant == 0 && a->rows >= 2048))) {
-    const int rc_pw = qnnp::pwstream_launch(p, vec, stream, &name);
-    if (kernel_name != nullptr) *kernel_name = name;
-    if (rc_pw == QNNP_HIP_OK) folded();
-    return rc_pw;
-  }
+  const bool few_rows_wide = !s.pad3 && a->rows >= 2048u && a->rows <= 8192u && a->n >= 512u && a->k_total >= 192u &&
+      a->residual == nullptr && a->offsets == nullptr;
+  if (few_rows_wide && pw_ok && mid_ok) return pick_mid();
+  if (few_rows_wide && pw_ok && supported(s, a, Kernel::U)) return pick(Kernel::U);
+  if (pw_ok && a->rows >= 2048u) return pick(Kernel::Pw);
   // Long reductions over few rows with 16-byte aligned rows on both sides: weights of a channel column in LDS, every
-  // K block of a unit's rows in flight at once ("gemm_kernel" = 9 forces it).
-  const bool lk_ok = !pad3 && qnnp::pwstream_longk_supported(p, a->groups, vec);
-  if (a->variant == 9 && !lk_ok) return QNNP_HIP_EINVAL;
+  // K block of a unit's rows in flight at once.
+  const bool lk_ok = supported(s, a, Kernel::LongK);
   // (auto where it measured ahead, batch 128 MobileNetV2: the 14x14 project layers -- 784 row blocks, K = 384 / 576:
   //  8.6 against 10.1 us, 10.8 against 13.0 -- and 7x7x320 -> 1280 with its 40 channel blocks, 11.1 against 12.5 on
   //  the tiled kernel; with ~200 row blocks and few channel blocks the one-wave-per-block kernel below keeps the lead:
@@ -817,115 +832,98 @@ extern "C" int qnnp_hip_igemm_run(const struct qnnp_hip_igemm_args* a, const cha
   //  profiles/r05/pointwise_rows_by_forced_kernel_r05var.txt)
   //  -- when the channels fill whole 256-wide tiles: MobileNetV2's 7x7 960 -> 320 (a quarter of its second tile is padding) stays
   //  on the one-wave kernel, 11.2 against 13.0 us)
-  const bool big_first = a->variant == 0 && !pad3 && a->n >= 256 && a->n % 256u == 0 && a->k_total >= 512 && a->rows >= 2048 &&
-      qnnp::gemm256_supported(p, vec);
+  const bool big_first = a->n >= 256 && a->n % 256u == 0 && a->k_total >= 512 && a->rows >= 2048 && supported(s, a, Kernel::Big);
   // (round 5: many rows with FEW channels -- ResNet-50's 28x28 512 -> 128: the weights of the whole row fit LDS and the flavour with
   //  the next unit's rows in flight streams them; 35 us on the generic tile kernel before)
   const bool lk_many_rows = a->rows > 65536u && a->n_pad <= 128u && a->k_total <= 640u;
   const bool lk_auto = !big_first && (a->rows <= 65536u || lk_many_rows) && (lk_units >= 512u || a->n_pad >= 512u);
   // (round 6: what the long-K kernel took automatically goes to the 128-row centred GEMM where that exists -- MobileNetV2's 14x14 project
   //  layers 7.2 -> 5.6, 8.1 -> 6.2, 9.7 -> 7.3 us, 7x7x320 -> 1280 12.4 -> 7.9, ResNet-50's 28x28 512 -> 128 32.6 -> 21.2)
-  if (a->variant == 0 && lk_ok && lk_auto && mid_ok && a->rows >= 2048u) return launch_mid();
+  if (lk_ok && lk_auto && mid_ok && a->rows >= 2048u) return pick_mid();
   // (... and without a centred image -- K = 464: ShuffleNet v2 x1.0's 7x7 464 -> 1024 -- to the register-staged one: 13.5 -> 10.7 us)
-  if (few_rows_wide && lk_ok && lk_auto && qnnp::gemm128u_supported(p)) {
-    const int rc_u = qnnp::gemm128u_launch(p, a->groups, stream, &name, 0u);
-    if (kernel_name != nullptr) *kernel_name = name;
-    return rc_u;
-  }
-  if (lk_ok && (a->variant == 9 || (a->variant == 0 && lk_auto))) {
-    const int rc_lk = qnnp::pwstream_longk_launch(p, stream, &name);
-    if (kernel_name != nullptr) *kernel_name = name;
-    if (rc_lk == QNNP_HIP_OK) folded();
-    return rc_lk;
-  }
+  if (few_rows_wide && lk_ok && lk_auto && supported(s, a, Kernel::U)) return pick(Kernel::U);
+  if (lk_ok && lk_auto) return pick(Kernel::LongK);
   // Small problems with a long reduction (late MobileNet layers, classifier heads): one wave per 32x32 block,
   // operands from L2 -- the tiled kernels would launch fewer workgroups than there are CUs.
-  const bool gw_ok = !pad3 && qnnp::pwstream_gw_supported(p, a->groups, vec);
-  if (a->variant == 6 && !gw_ok) return QNNP_HIP_EINVAL;
+  const bool gw_ok = supported(s, a, Kernel::Gw);
   // (selected when the 128-row x 128-channel tiling of the generic kernel would not even give ~1.5 workgroups
   //  per CU; MobileNetV2 layer 30 -- 490 tiles -- measured faster on the tiled kernel, layers 19-29 on this one)
   const uint64_t generic_tiles = static_cast<uint64_t>((a->rows + 127u) / 128u) * ((a->n_pad + 127u) / 128u);
   // (round 6: with >= 256 channels the 128-row centred GEMM is ahead -- 7x7x960 -> 320 10.5 -> 8.0 us; 160 channels stay here, 5.9 / 7.0
   //  against 6.0 / 7.8)
-  if (a->variant == 0 && gw_ok && generic_tiles <= 400u && !big_first && mid_ok && a->n >= 256u && a->rows >= 2048u) return launch_mid();
-  if (gw_ok && (a->variant == 6 || (a->variant == 0 && generic_tiles <= 400u && !big_first))) {
-    const int rc_gw = qnnp::pwstream_gw_launch(p, stream, &name);
-    if (kernel_name != nullptr) *kernel_name = name;
-    if (rc_gw == QNNP_HIP_OK) folded();
-    return rc_gw;
-  }
+  if (gw_ok && generic_tiles <= 400u && !big_first && mid_ok && a->n >= 256u && a->rows >= 2048u) return pick_mid();
+  if (gw_ok && generic_tiles <= 400u && !big_first) return pick(Kernel::Gw);
   // Large MFMA-bound problems take the 256x256 LDS-DMA kernel; everything else the generic one.
-  const bool big_ok = !pad3 && qnnp::gemm256_supported(p, vec);
+  const bool big_ok = supported(s, a, Kernel::Big);
   // (strided 1x1 convolutions -- a table row per output pixel, one tap -- from K = 256: ResNet-50's 56x56 stride-2 256 -> 512
   //  70.8 -> 51.3 us on the offset-table flavour of the 256-wide kernel)
   const bool strided_pw = a->offsets != nullptr && a->ks == 1 && a->n % 256u == 0 && a->k_total >= 256;
   const bool big_auto = a->n >= 256 && (a->k_total >= 512 || strided_pw) && a->rows >= 2048;
-  const bool big_forced = a->variant == 2 || a->variant == 4 || a->variant == 10 || a->variant == 11 || a->variant == 15 || a->variant == 16;   // 10: 128 x 256 tiles, two workgroups per CU; 11: ping-pong schedule; 15: lean flavour
-  if (big_forced && !big_ok) return QNNP_HIP_EINVAL;
-  int rc;
-  // Operators with a zero-point-centred weight image (kernel zero point 127 or 128, q8gemm256c.hip): no row term at all.
-  // Round 6: auto takes the v_mfma_i32_16x16x64_i8 flavour (q8gemm256x.hip: 59.1 -> 52.6 us on 4096^3, same box, interleaved;
-  // "gemm_kernel" 23 forces it); 20 keeps the 32x32x32 one (q8gemm256c.hip), 21 = that one's A/B structure (fragment reads in one burst).
-  const bool c_forced = a->variant == 20 || a->variant == 21 || a->variant == 23;
   // (round 6: launches of at most ~100 tiles of 256 x 256 leave most CUs idle for the length of a long K loop -- ResNet-50's 7x7 2048 -> 512,
   //  50 tiles: 22.1 -> 15.0 us on 128-row tiles, 14x14 1024 -> 256, 98 tiles: 17.1 -> 16.0; from ~200 tiles on the wide kernel leads)
-  if (a->variant == 0 && big_auto && mid_ok &&
-      static_cast<uint64_t>((a->rows + 255u) / 256u) * ((a->n_pad + 255u) / 256u) <= 100u) return launch_mid();
-  if (c_forced || (a->variant == 0 && big_auto && a->centre_flip != 0)) {
-    qnnp::IgemmParams pc = p;
-    const uint32_t opt = a->variant == 21 ? 2u : 0u;
-    bool c_ok = a->centre_flip != 0 && a->packed_w_centred != nullptr && a->bias2_centred != nullptr && a->bias2_pair != 0;
-    if (c_ok) {
-      pc.packed_w = a->packed_w_centred;
-      pc.bias2 = a->bias2_centred;
-      pc.bias2u = a->bias2_centred + static_cast<size_t>(a->groups) * a->n_pad;
-      pc.a_flip = (a->centre_flip & 0xFFu) * 0x01010101u;
-      pc.row_coeff = 0;
-      c_ok = big_ok && qnnp::gemm256c_supported(pc, vec);
-    }
-    if (c_ok) {
-      rc = (a->variant == 23 || a->variant == 0) ? qnnp::gemm256x_launch(pc, a->groups, stream, &name)
-                            : qnnp::gemm256c_launch(pc, a->groups, stream, &name, opt);
-      if (kernel_name != nullptr) *kernel_name = name;
-      return rc;
-    }
-    if (c_forced) return QNNP_HIP_EINVAL;
-  }
-  // Round 6: every OTHER kernel zero point on the 16x16x64 kernel as well -- the standard image and its row term (ROWSUM flavour of
-  // q8gemm256x.hip; "gemm_kernel" 28 forces it, 15 keeps the lean 32x32x32 kernel it replaces).
-  if (a->variant == 28 || (a->variant == 0 && big_auto && big_ok)) {
-    qnnp::IgemmParams pr = p;
-    pr.a_flip = 0x80808080u;
-    const bool r_ok = big_ok && p.bias2u != nullptr && a->groups >= 1 && qnnp::gemm256c_supported(pr, vec);
-    if (r_ok) {
-      rc = qnnp::gemm256x_launch(pr, a->groups, stream, &name);
-      if (kernel_name != nullptr) *kernel_name = name;
-      return rc;
-    }
-    if (a->variant == 28) return QNNP_HIP_EINVAL;
-  }
+  if (big_auto && mid_ok && static_cast<uint64_t>((a->rows + 255u) / 256u) * ((a->n_pad + 255u) / 256u) <= 100u) return pick_mid();
+  // Operators with a zero-point-centred weight image (kernel zero point 127 or 128, q8gemm256c.hip): no row term at all.
+  // Round 6: auto takes the v_mfma_i32_16x16x64_i8 flavour (q8gemm256x.hip: 59.1 -> 52.6 us on 4096^3, same box, interleaved;
+  // 20 keeps the 32x32x32 one).
+  if (big_auto && a->centre_flip != 0 && big_ok && big_image_ok(s, a, Image::Centred)) return pick(Kernel::BigX, Image::Centred);
+  // Round 6: every OTHER kernel zero point on the 16x16x64 kernel as well -- the standard image and its row term (15 keeps the lean
+  // 32x32x32 kernel it replaces).
+  if (big_auto && big_ok && big_image_ok(s, a, Image::Rowsum)) return pick(Kernel::BigX, Image::Rowsum);
   // Round 6: what is left of the 1x1 / fully connected class -- grouped, odd channel counts, unaligned rows -- on the 128 x 128 kernel
-  // that stages its activation tile through registers (q8gemm128u.hip; "gemm_kernel" 29 forces it, 1 keeps the generic tile kernel).
-  {
-    const bool u_ok = !pad3 && qnnp::gemm128u_supported(p);
-    if (a->variant == 29 && !u_ok) return QNNP_HIP_EINVAL;
-    if (u_ok && (a->variant == 29 || (a->variant == 0 && !(big_ok && big_auto)))) {
-      rc = qnnp::gemm128u_launch(p, a->groups, stream, &name, 0u);
-      if (kernel_name != nullptr) *kernel_name = name;
-      return rc;
-    }
-  }
-  if (big_ok && (big_forced || (a->variant == 0 && big_auto))) {
-    rc = qnnp::gemm256_launch(p, a->groups, stream, &name, a->variant == 4 || a->variant == 16, a->variant == 10, a->variant == 11,
-                               (a->variant == 15 || a->variant == 16) ? 2 : (a->variant == 0 ? 1 : 0));   // 16: the 4-wave flavour, lean;   // ("gemm_kernel" = 2 keeps the general flavour for A/B)
-  } else {
-    if (pad3) {
-      rc = dispatch_tile<4, true, true>(p, a->groups, stream, &name);
-    } else {
-      rc = (a->offsets != nullptr) ? dispatch_vec<true>(p, a->phases != nullptr ? a->nphases * a->groups : a->groups, vec, stream, &name)
-                                   : dispatch_vec<false>(p, a->groups, vec, stream, &name);
-    }
+  // that stages its activation tile through registers (q8gemm128u.hip; 1 keeps the generic tile kernel).
+  if (!(big_ok && big_auto) && supported(s, a, Kernel::U)) return pick(Kernel::U);
+  if (big_ok && big_auto) return pick(Kernel::Big, Image::Standard, 1u);
+  return pick(Kernel::Generic);
+}
+
+int launch(const IgemmSetup& s, const struct qnnp_hip_igemm_args* a, const IgemmPlan& plan, const char** kernel_name)
+{
+  const IgemmParams& p = s.p;
+  IgemmParams built;
+  const IgemmParams& q = image_params(s, a, plan.image, built);
+  hipStream_t stream = reinterpret_cast<hipStream_t>(qnnp_hip_get_stream());
+  const uint32_t batch = a->rows_per_image > 0 ? a->rows / a->rows_per_image : 0u;
+  const char* name = nullptr;
+  int rc = QNNP_HIP_EINVAL;
+  switch (plan.kernel) {
+    case Kernel::Wave: rc = qnnp::convwave_launch(p, s.geom, batch, stream, &name, plan.option, plan.image == Image::Centred ? &s.pc : nullptr); break;
+    case Kernel::Ws16s: rc = qnnp::convws16s_launch(q, s.geom, batch, stream, &name); break;
+    case Kernel::Patch: rc = qnnp::convpatch_launch(q, s.geom, batch, stream, &name); break;
+    case Kernel::Lds: rc = qnnp::convlds_launch(q, s.geom, batch, stream, &name); break;
+    case Kernel::Rows16: rc = qnnp::conv_c3rows_launch(q, s.geom, a->packed_w_rows16, stream, &name, plan.option); break;
+    case Kernel::Rows32: rc = qnnp::conv_c3rows32_launch(q, s.geom, a->packed_w_rows16, stream, &name, plan.option); break;
+    case Kernel::C3: rc = qnnp::convstream_c3_launch(q, stream, &name); break;
+    case Kernel::Mid: rc = qnnp::gemm128x_launch(q, a->groups, stream, &name, plan.option); break;
+    case Kernel::U: rc = qnnp::gemm128u_launch(q, a->groups, stream, &name, plan.option); break;
+    case Kernel::Pw: rc = qnnp::pwstream_launch(q, s.vec, stream, &name); break;
+    case Kernel::LongK: rc = qnnp::pwstream_longk_launch(q, stream, &name); break;
+    case Kernel::Gw: rc = qnnp::pwstream_gw_launch(q, stream, &name); break;
+    case Kernel::Big:
+      rc = qnnp::gemm256_launch(q, a->groups, stream, &name, (plan.option & kBigWaves4) != 0, (plan.option & kBigRows128) != 0,
+                                (plan.option & kBigPingpong) != 0, plan.option & 3u);
+      break;
+    case Kernel::BigC: rc = qnnp::gemm256c_launch(q, a->groups, stream, &name, plan.option); break;
+    case Kernel::BigX: rc = qnnp::gemm256x_launch(q, a->groups, stream, &name); break;
+    case Kernel::Generic:
+      if (s.pad3) rc = dispatch_tile<4, true, true>(p, a->groups, stream, &name);
+      else if (a->offsets != nullptr) rc = dispatch_vec<true>(p, a->phases != nullptr ? a->nphases * a->groups : a->groups, s.vec, stream, &name);
+      else rc = dispatch_vec<false>(p, a->groups, s.vec, stream, &name);
+      break;
   }
   if (kernel_name != nullptr) *kernel_name = name;
+  // the pointwise streaming kernels carry the fused residual add in their epilogues
+  if (rc == QNNP_HIP_OK && p.residual != nullptr && (plan.kernel == Kernel::Pw || plan.kernel == Kernel::LongK || plan.kernel == Kernel::Gw))
+    *a->residual_folded = 1;
   return rc;
+}
+
+}  // namespace
+
+extern "C" int qnnp_hip_igemm_run(const struct qnnp_hip_igemm_args* a, const char** kernel_name)
+{
+  IgemmSetup s;
+  IgemmPlan plan;
+  int rc = derive(a, s);
+  if (rc == QNNP_HIP_OK) rc = make_plan(s, a, &plan);
+  return rc == QNNP_HIP_OK ? launch(s, a, plan, kernel_name) : rc;
 }
