@@ -60,7 +60,8 @@ extern "C" {
  *                        a negative result kept for its A/B: slower than 6 on every layer)
  *                    8 = the register sliding-window kernel (3) on UNALIGNED dwords: 3x3 windows, any channel count >= 4, any pixel
  *                        stride / base address (what auto picks where nothing aligned takes the shape), 9 = the four-channel generic
- *                        kernel kept for such shapes (A/B)
+ *                        kernel kept for such shapes (A/B): any window, stride and base address, >= 4 channels, a channel pad of
+ *                        whole dwords and 32-bit offsets; unsupported_parameter otherwise (never the LDS or byte-per-thread kernel)
  *                    (1 keeps the byte-per-thread direct kernel; auto takes its four-channel flavour for C >= 4 and windows other than 3x3)
  * Unknown family or code -> invalid_parameter. 0 = the automatic choice, always. */
 enum qnnp_status qnnp_gfx950_test_force_kernel(const char* family, int code);

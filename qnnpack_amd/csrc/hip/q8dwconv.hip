@@ -2563,6 +2563,14 @@ uint32_t lds_budget()
   return budget;
 }
 
+// The four-channel generic kernel: at least four channels, a channel pad of whole dwords and 32-bit offsets into both tensors
+bool direct4_fits(const DwParams& p, const struct qnnp_hip_dwconv_args* a)
+{
+  const uint64_t ib = static_cast<uint64_t>(p.batch) * p.H * p.W * p.in_stride;
+  const uint64_t groups4 = static_cast<uint64_t>(p.batch) * p.OH * p.OW * ((p.C + 3u) / 4u);
+  return p.C >= 4 && ib + 8 < (UINT64_C(1) << 31) && groups4 + 256u * 8192u < (UINT64_C(1) << 32) && a->c_pad % 4 == 0;
+}
+
 // Kernel choice and launch geometry for one (shape, variant, alignment); fills `p` and `plan`.
 int make_plan(DwParams& p, const struct qnnp_hip_dwconv_args* a, uintptr_t in_addr, uintptr_t out_addr,
               struct qnnp_hip_dwconv_plan* plan)
@@ -2579,6 +2587,10 @@ int make_plan(DwParams& p, const struct qnnp_hip_dwconv_args* a, uintptr_t in_ad
     // (round 6) the sliding-window kernel on unaligned dwords, forced (auto: below, where nothing aligned takes the shape)
     if (!k33 || a->c_pad % 4 != 0 || !plan_row(p, true)) return QNNP_HIP_EINVAL;
     plan->kernel = kPlanRowAny;
+  } else if (a->variant == 9) {
+    // the four-channel generic kernel, forced: any window, stride and base address its offsets cover, or nothing
+    if (!direct4_fits(p, a)) return QNNP_HIP_EINVAL;
+    plan->kernel = kPlanDirect4;
   } else if (a->variant == 7) {
     // (round 6) the 16x16x64 matrix-core walk, forced
     if (!k33 || !plan_m16(p, in_addr, out_addr)) return QNNP_HIP_EINVAL;
@@ -2622,7 +2634,7 @@ int make_plan(DwParams& p, const struct qnnp_hip_dwconv_args* a, uintptr_t in_ad
       plan->kernel = k33 ? kPlanLds33 : kPlanLds55;
     } else {
       // (round 6) 3x3 windows of any channel count >= 4 and any alignment: the sliding-window kernel on unaligned dwords
-      // ("dwconv_kernel" 8 forces it -- on aligned tensors too --, 1 / 9 keep the generic kernels below)
+      // ("dwconv_kernel" 8 forces it -- on aligned tensors too --, 1 keeps the generic kernel below, 9 forces its four-channel flavour)
       if (a->variant == 0 && k33 && a->c_pad % 4 == 0 && plan_row(p, true)) {
         plan->kernel = kPlanRowAny;
         plan->CS = p.CS; plan->TOH = p.TOH; plan->IR = p.IR; plan->IC = p.IC; plan->PP = p.PP;
@@ -2630,10 +2642,7 @@ int make_plan(DwParams& p, const struct qnnp_hip_dwconv_args* a, uintptr_t in_ad
         return QNNP_HIP_OK;
       }
       // (round 6) four channels per thread where the tensors allow 32-bit offsets; "dwconv_kernel" 1 keeps the byte-per-thread kernel
-      const uint64_t ib = static_cast<uint64_t>(p.batch) * p.H * p.W * p.in_stride;
-      const uint64_t groups4 = static_cast<uint64_t>(p.batch) * p.OH * p.OW * ((p.C + 3u) / 4u);
-      plan->kernel = (a->variant != 1 && p.C >= 4 && ib + 8 < (UINT64_C(1) << 31) && groups4 + 256u * 8192u < (UINT64_C(1) << 32) && a->c_pad % 4 == 0)
-          ? kPlanDirect4 : kPlanDirect;
+      plan->kernel = (a->variant != 1 && direct4_fits(p, a)) ? kPlanDirect4 : kPlanDirect;
     }
   }
   plan->CS = p.CS; plan->TOH = p.TOH; plan->IR = p.IR; plan->IC = p.IC; plan->PP = p.PP;

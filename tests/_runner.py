@@ -39,9 +39,10 @@ def conv_expected(case: ConvCase, inp=None, kernel=None, bias=None):
 
 
 def conv_run(lib, case: ConvCase, quant, out_hw, inp=None, kernel=None, bias=None,
-             to_device=None, from_device=None, threadpool=None):
+             to_device=None, from_device=None, threadpool=None, in_offset=None, out_offset=None):
     """Run the case through `lib`. With to_device/from_device the tensors live in device
-    memory (zero-copy path); otherwise host numpy buffers are passed (staged path)."""
+    memory (zero-copy path); otherwise host numpy buffers are passed (staged path).
+    With in_offset / out_offset the tensors live in guarded device buffers at those byte offsets (placed_run)."""
     if inp is None:
         inp, kernel, bias = conv_tensors(case)
     oscale, ozp = quant
@@ -55,7 +56,10 @@ def conv_run(lib, case: ConvCase, quant, out_hw, inp=None, kernel=None, bias=Non
         case.dilation[0], case.dilation[1], case.groups, case.gic, case.goc,
         case.izp, 1.0, case.kzp, 1.0, kernel, bias, ozp, float(oscale), case.qmin, case.qmax, 0)
     try:
-        if to_device is not None and rows:
+        if in_offset is not None and rows:
+            out = placed_run(lib, op, inp, out, in_offset, out_offset, case.name, lambda d_in, d_out: lib.setup_convolution2d_nhwc_q8(
+                op, case.batch, case.input_size[0], case.input_size[1], d_in, case.in_stride, d_out, case.out_stride))
+        elif to_device is not None and rows:
             d_in, d_out = to_device(inp), to_device(out)
             lib.setup_convolution2d_nhwc_q8(op, case.batch, case.input_size[0], case.input_size[1],
                                             d_in, case.in_stride, d_out, case.out_stride)
@@ -94,7 +98,7 @@ def deconv_expected(case: DeconvCase, inp=None, kernel=None, bias=None):
 
 
 def deconv_run(lib, case: DeconvCase, quant, out_hw, inp=None, kernel=None, bias=None,
-               to_device=None, from_device=None, threadpool=None):
+               to_device=None, from_device=None, threadpool=None, in_offset=None, out_offset=None):
     if inp is None:
         inp, kernel, bias = deconv_tensors(case)
     oscale, ozp = quant
@@ -109,7 +113,10 @@ def deconv_run(lib, case: DeconvCase, quant, out_hw, inp=None, kernel=None, bias
         case.dilation[0], case.dilation[1], case.groups, case.gic, case.goc,
         case.izp, 1.0, case.kzp, 1.0, kernel, bias, ozp, float(oscale), case.qmin, case.qmax, 0)
     try:
-        if to_device is not None and rows:
+        if in_offset is not None and rows:
+            out = placed_run(lib, op, inp, out, in_offset, out_offset, case.name, lambda d_in, d_out: lib.setup_deconvolution2d_nhwc_q8(
+                op, case.batch, case.input_size[0], case.input_size[1], d_in, case.in_stride, d_out, case.out_stride))
+        elif to_device is not None and rows:
             d_in, d_out = to_device(inp), to_device(out)
             lib.setup_deconvolution2d_nhwc_q8(op, case.batch, case.input_size[0], case.input_size[1],
                                               d_in, case.in_stride, d_out, case.out_stride)
@@ -141,7 +148,8 @@ def fc_expected(case: FcCase, inp=None, kernel=None, bias=None):
     return out, (oscale, ozp)
 
 
-def fc_run(lib, case: FcCase, quant, inp=None, kernel=None, bias=None, to_device=None, from_device=None):
+def fc_run(lib, case: FcCase, quant, inp=None, kernel=None, bias=None, to_device=None, from_device=None,
+           in_offset=None, out_offset=None):
     if inp is None:
         inp, kernel, bias = fc_tensors(case)
     oscale, ozp = quant
@@ -151,7 +159,10 @@ def fc_run(lib, case: FcCase, quant, inp=None, kernel=None, bias=None, to_device
         case.input_channels, case.output_channels, case.izp, 1.0, case.kzp, 1.0, kernel, bias,
         ozp, float(oscale), case.qmin, case.qmax, 0)
     try:
-        if to_device is not None and case.batch:
+        if in_offset is not None and case.batch:
+            out = placed_run(lib, op, inp, out, in_offset, out_offset, case.name, lambda d_in, d_out: lib.setup_fully_connected_nc_q8(
+                op, case.batch, d_in, case.in_stride, d_out, case.out_stride))
+        elif to_device is not None and case.batch:
             d_in, d_out = to_device(inp), to_device(out)
             lib.setup_fully_connected_nc_q8(op, case.batch, d_in, case.in_stride, d_out, case.out_stride)
             lib.run_operator(op)
@@ -165,6 +176,30 @@ def fc_run(lib, case: FcCase, quant, inp=None, kernel=None, bias=None, to_device
     finally:
         lib.delete_operator(op)
     return out, kernel_name
+
+
+def placed_run(lib, op, inp, out, in_offset, out_offset, what, setup):
+    """Set up and run `op` on `inp` and `out` (FILL) in guarded device buffers (_gpu.Guarded) at byte offsets
+    in_offset / out_offset, via setup(d_in, d_out); return the output. Nothing outside the output may change: the guards
+    of both buffers, the input itself, and -- when setup or run refuses (QnnpackError, re-raised) -- the output either."""
+    from _gpu import Guarded
+    from qnnpack_amd import QnnpackError
+    d_in, d_out = Guarded(inp, in_offset), Guarded(out, out_offset or 0)
+    where = f"{what} at offsets ({in_offset}, {out_offset})"
+    try:
+        setup(d_in.view, d_out.view)
+        lib.run_operator(op)
+    except QnnpackError:
+        got = d_out.read()
+        bad = np.flatnonzero(got != FILL)
+        assert bad.size == 0, f"{where}: refused, but {bad.size} output bytes were written (first at {int(bad[0])})"
+        d_out.assert_intact(f"{where} (refused), output")
+        raise
+    got = d_out.read()
+    d_out.assert_intact(f"{where}, output")
+    d_in.assert_intact(f"{where}, input")
+    assert np.array_equal(d_in.read(), np.ascontiguousarray(inp).view(np.uint8).reshape(-1)), f"{where}: the input was written"
+    return got
 
 
 def assert_bytes_equal(actual: np.ndarray, expected: np.ndarray, what: str):

@@ -38,8 +38,20 @@ def _auto_kernel(case):
     return "q8_dwconv_row_3x3_any" if k33 and case.groups >= 4 and max(case.padding) <= 2 else "q8_dwconv_direct4"
 
 
-@pytest.mark.parametrize("variant", [0, 9, 1], ids=["auto", "four_channels_per_thread", "byte_per_thread"])
-@pytest.mark.parametrize("case", CASES, ids=lambda c: c.name)
+# dword-aligned 3x3 / 5x5 tensors, where the LDS-tiled kernel would take the shape: forced, the four-channel kernel runs
+# them itself (q8dwconv.hip:make_plan handles code 9 before the LDS rule)
+ALIGNED_CASES = [
+    _dw("d4_c32_aligned", (14, 14), 32, batch=2),
+    _dw("d4_c64_aligned", (14, 14), 64, batch=2),
+    _dw("d4_c32_5x5_aligned", (14, 14), 32, k=(5, 5), batch=2),
+    _dw("d4_c64_5x5_aligned", (14, 14), 64, k=(5, 5), batch=2),
+]
+
+VARIANT_IDS = {0: "auto", 9: "four_channels_per_thread", 1: "byte_per_thread"}
+
+
+@pytest.mark.parametrize("case,variant", [pytest.param(c, v, id=f"{c.name}-{VARIANT_IDS[v]}") for c in CASES for v in (0, 9, 1)] +
+                         [pytest.param(c, 9, id=f"{c.name}-{VARIANT_IDS[9]}") for c in ALIGNED_CASES])
 def test_generic_depthwise_matches_oracle(qnnp, case, variant):
     kernel = {0: _auto_kernel(case), 9: "q8_dwconv_direct4", 1: "q8_dwconv_direct"}[variant]
     inp, kern, bias = conv_tensors(case)
