@@ -206,17 +206,12 @@ enum qnnp_status qnnp_create_add_nc_q8(
   if (!qnnp_state.initialized) {
     return qnnp_create_add_nc_q8_impl(channels, a_zero_point, a_scale, b_zero_point, b_scale, sum_zero_point, sum_scale, sum_min, sum_max, flags, add_out);   /* logs and answers qnnp_status_uninitialized */
   }
-  const int token = qnnp_hip_enter(qnnp_hip_device());
-  if (token < 0) {
-    return qnnp_status_unsupported_hardware;
+  int token;
+  enum qnnp_status status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
+  if (status != qnnp_status_success) {
+    return status;
   }
-  if (qnnp_hip_graph_capturing()) {
-    /* inside qnnp_gfx950_graph_begin ... graph_end on this device only operator launches are recordable: an upload
-     * would become a graph node reading host memory that is freed right after this call */
-    qnnp_hip_leave(token);
-    return qnnp_status_invalid_parameter;
-  }
-  const enum qnnp_status status = qnnp_create_add_nc_q8_impl(channels, a_zero_point, a_scale, b_zero_point, b_scale, sum_zero_point, sum_scale, sum_min, sum_max, flags, add_out);
+  status = qnnp_create_add_nc_q8_impl(channels, a_zero_point, a_scale, b_zero_point, b_scale, sum_zero_point, sum_scale, sum_min, sum_max, flags, add_out);
   qnnp_hip_leave(token);
   return status;
 }
@@ -234,17 +229,12 @@ enum qnnp_status qnnp_setup_add_nc_q8(
   if (!qnnp_state.initialized || op == NULL) {
     return qnnp_setup_add_nc_q8_impl(op, batch_size, a, a_stride, b, b_stride, sum, sum_stride);   /* answers qnnp_status_uninitialized / invalid_parameter */
   }
-  const int token = qnnp_hip_enter(op->device);
-  if (token < 0) {
-    return qnnp_status_invalid_parameter;   /* not a live operator of this library instance */
+  int token;
+  enum qnnp_status status = qnnp_enter_for_update(op->device, qnnp_status_invalid_parameter, &token);
+  if (status != qnnp_status_success) {
+    return status;
   }
-  if (qnnp_hip_graph_capturing()) {
-    /* inside qnnp_gfx950_graph_begin ... graph_end on this device only operator launches are recordable: an upload
-     * would become a graph node reading host memory that is freed right after this call */
-    qnnp_hip_leave(token);
-    return qnnp_status_invalid_parameter;
-  }
-  const enum qnnp_status status = qnnp_setup_add_nc_q8_impl(op, batch_size, a, a_stride, b, b_stride, sum, sum_stride);
+  status = qnnp_setup_add_nc_q8_impl(op, batch_size, a, a_stride, b, b_stride, sum, sum_stride);
   /* the implementation cleared setup_valid where it began to change the operator: a failed setup leaves it
    * unrunnable instead of half updated (run answers invalid_parameter) */
   if (status == qnnp_status_success) {

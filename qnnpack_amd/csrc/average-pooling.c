@@ -269,15 +269,12 @@ enum qnnp_status qnnp_create_average_pooling2d_nhwc_q8(
         input_padding_left, pooling_height, pooling_width, stride_height, stride_width, channels, input_zero_point,
         input_scale, output_zero_point, output_scale, output_min, output_max, flags, average_pooling);   /* logs and answers qnnp_status_uninitialized */
   }
-  const int token = qnnp_hip_enter(qnnp_hip_device());
-  if (token < 0) {
-    return qnnp_status_unsupported_hardware;
+  int token;
+  enum qnnp_status status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
+  if (status != qnnp_status_success) {
+    return status;
   }
-  if (qnnp_hip_graph_capturing()) {
-    qnnp_hip_leave(token);
-    return qnnp_status_invalid_parameter;   /* only operator launches are recordable inside a capture */
-  }
-  const enum qnnp_status status = qnnp_create_average_pooling2d_nhwc_q8_impl(input_padding_top, input_padding_right,
+  status = qnnp_create_average_pooling2d_nhwc_q8_impl(input_padding_top, input_padding_right,
       input_padding_bottom, input_padding_left, pooling_height, pooling_width, stride_height, stride_width, channels,
       input_zero_point, input_scale, output_zero_point, output_scale, output_min, output_max, flags, average_pooling);
   qnnp_hip_leave(token);
@@ -300,15 +297,12 @@ enum qnnp_status qnnp_setup_average_pooling2d_nhwc_q8(
     return qnnp_setup_average_pooling2d_nhwc_q8_impl(average_pooling, batch_size, input_height, input_width, input, input_stride,
         output, output_stride);   /* answers qnnp_status_uninitialized / invalid_parameter */
   }
-  const int token = qnnp_hip_enter(average_pooling->device);
-  if (token < 0) {
-    return qnnp_status_invalid_parameter;   /* not a live operator of this library instance */
+  int token;
+  enum qnnp_status status = qnnp_enter_for_update(average_pooling->device, qnnp_status_invalid_parameter, &token);
+  if (status != qnnp_status_success) {
+    return status;
   }
-  if (qnnp_hip_graph_capturing()) {
-    qnnp_hip_leave(token);
-    return qnnp_status_invalid_parameter;   /* a staging upload would become a graph node */
-  }
-  const enum qnnp_status status = qnnp_setup_average_pooling2d_nhwc_q8_impl(average_pooling, batch_size, input_height,
+  status = qnnp_setup_average_pooling2d_nhwc_q8_impl(average_pooling, batch_size, input_height,
       input_width, input, input_stride, output, output_stride);
   /* a failed setup leaves the operator unrunnable instead of half updated (run answers invalid_parameter) */
   if (status == qnnp_status_success) {

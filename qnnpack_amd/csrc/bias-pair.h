@@ -11,7 +11,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "hip/qnnp_hip.h"
+#include "upload.h"
 
 /* device copy of {bias2, bias2 + 2^31}; NULL on failure */
 static inline int32_t* qnnp_upload_bias_pair(const int32_t* host_bias, size_t count)
@@ -23,11 +23,7 @@ static inline int32_t* qnnp_upload_bias_pair(const int32_t* host_bias, size_t co
   for (size_t i = 0; i < count; i++) {
     pair[count + i] = (int32_t) ((uint32_t) host_bias[i] ^ UINT32_C(0x80000000));
   }
-  int32_t* d = (int32_t*) qnnp_hip_alloc(2 * bytes);
-  if (d != NULL && qnnp_hip_h2d(d, pair, 2 * bytes, 0) != QNNP_HIP_OK) {
-    qnnp_hip_free(d);
-    d = NULL;
-  }
+  int32_t* d = (int32_t*) qnnp_upload(pair, 2 * bytes);
   free(pair);
   return d;
 }

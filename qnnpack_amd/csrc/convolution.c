@@ -31,6 +31,7 @@
 #include "pack.h"
 #include "requantization.h"
 #include "state.h"
+#include "upload.h"
 
 /* reference src/convolution.c:29-37 */
 static inline size_t compute_output_dimension(
@@ -43,6 +44,259 @@ static inline size_t compute_output_dimension(
 static inline bool scale_is_valid(float scale)
 {
   return scale > 0.0f && isnormal(scale);
+}
+
+/* ---- depthwise images ------------------------------------------------------------------------------------------------
+ * the tap-major int16 image and its bias (required), the int8 dot-product image of 3x3 / 5x5 windows with weights in
+ * int8 range (required where it applies) and the matrix-core weight parts (required) */
+static enum qnnp_status pack_depthwise(struct qnnp_operator* op, const uint8_t* kernel, const int32_t* bias)
+{
+  const uint32_t groups = op->groups, kh = op->kernel_height, kw = op->kernel_width;
+  const size_t kernel_size = (size_t) kh * kw;
+  const uint32_t c_pad = qnnp_round_up_u32(groups, 16);
+  const size_t w_bytes = sizeof(int16_t) * kernel_size * c_pad;
+  const size_t b_bytes = sizeof(int32_t) * c_pad;
+  int16_t* host_weights = (int16_t*) malloc(w_bytes);
+  int32_t* host_bias = (int32_t*) malloc(b_bytes);
+  enum qnnp_status status = qnnp_status_out_of_memory;
+  if (host_weights == NULL || host_bias == NULL) {
+    qnnp_log_error("out of host memory: %zu bytes for packed weights", w_bytes + b_bytes);
+    goto done;
+  }
+  qnnp_pack_dwconv_w(groups, c_pad, kh, kw, op->input_zero_point, op->kernel_zero_point, kernel, bias, host_weights, host_bias);
+  op->c_pad = c_pad;
+  op->dw_wrange = qnnp_dwconv_weight_range(host_weights, kernel_size * c_pad);
+  op->d_weights = qnnp_upload(host_weights, w_bytes);
+  op->d_bias = (int32_t*) qnnp_upload(host_bias, b_bytes);
+  if (op->d_weights == NULL || op->d_bias == NULL) {
+    qnnp_log_error("device allocation or upload failed: %zu bytes of packed depthwise weights on the device", w_bytes + b_bytes);
+    goto done;
+  }
+  /* 3x3 with weights in int8 range: the register image of the int8 dot-product walk (pack.h); 5x5 likewise: eight rows
+   * (pack.h qnnp_pack_dwconv_dot4_5x5) */
+  if (kh == kw && (kh == 3 || kh == 5) && op->dw_wrange != 0) {
+    const size_t q_bytes = sizeof(uint32_t) * (kh == 3 ? 4 : 8) * c_pad;
+    uint32_t* host_q = (uint32_t*) malloc(q_bytes);
+    if (host_q != NULL) {
+      if (kh == 3) {
+        qnnp_pack_dwconv_dot4(c_pad, op->dw_wrange, host_weights, host_bias, host_q);
+      } else {
+        qnnp_pack_dwconv_dot4_5x5(c_pad, op->dw_wrange, host_weights, host_bias, host_q);
+      }
+      op->d_dw_dot4 = qnnp_upload(host_q, q_bytes);
+      free(host_q);
+    }
+    if (op->d_dw_dot4 == NULL) {
+      qnnp_log_error("device allocation or upload failed: %zu bytes of depthwise dot-product weights on the device", q_bytes);
+      goto done;
+    }
+  }
+  /* second image: int8 weight parts + folded bias for the matrix-core depthwise kernel */
+  const uint32_t c_pad32 = qnnp_round_up_u32(groups, 32);
+  const size_t x_bytes = (size_t) 3 * kernel_size * c_pad32;
+  const size_t bm_bytes = sizeof(int32_t) * c_pad32;
+  int8_t* host_x = (int8_t*) malloc(x_bytes);
+  int32_t* host_bm = (int32_t*) malloc(bm_bytes);
+  if (host_x != NULL && host_bm != NULL) {
+    op->dwm_parts = qnnp_pack_dwconv_mfma(groups, c_pad32, kh, kw, op->input_zero_point, op->kernel_zero_point, kernel, bias,
+        host_x, host_bm);
+    op->c_pad32 = c_pad32;
+    op->d_dwm_x = qnnp_upload(host_x, x_bytes);
+    op->d_dwm_bias = (int32_t*) qnnp_upload(host_bm, bm_bytes);
+  }
+  free(host_x);
+  free(host_bm);
+  if (op->d_dwm_x == NULL || op->d_dwm_bias == NULL) {
+    qnnp_log_error("device allocation or upload failed: %zu bytes of depthwise weight parts on the device", x_bytes + bm_bytes);
+    goto done;
+  }
+  status = qnnp_status_success;
+done:
+  free(host_weights);
+  free(host_bias);
+  return status;
+}
+
+/* ---- GEMM images ---------------------------------------------------------------------------------------------------- */
+
+/* Grouped 1x1 as one dense GEMM (round 6). A group of 12 ... 68 channels fills a fifth ... a half of a 64-byte K step and a
+ * 128-channel tile, every group's tile stages its own copy of the rows, and its output pieces are 12 ... 68 bytes; the dense
+ * [groups * GOC][groups * GIC] matrix with the groups' blocks on its diagonal and the KERNEL ZERO POINT everywhere else
+ * ((w - kzp) = 0: the grouped result bit for bit) reads every input byte once and writes whole pixels, at `groups` times the
+ * multiplies -- which these layers do not notice: ShuffleNet v1's 28x28 layers at batch 128 run 15 ... 59 us grouped and 12 ... 27
+ * dense (profiles/r06/grouped_1x1_dense_equivalents_r06v.txt); from 14x14 down the two are level or the grouped form leads, so
+ * operator-run.c takes this image from 65536 rows up. Built for up to 1024 channels on either side (<= 1 MiB of weights).
+ * Optional: without it the operator keeps its grouped image. */
+static void pack_dense_optional(struct qnnp_operator* op, const uint8_t* kernel, const int32_t* bias)
+{
+  const size_t gic = op->group_input_channels, goc = op->group_output_channels;
+  const uint32_t cin = (uint32_t) (op->groups * gic), cout = (uint32_t) (op->groups * goc);
+  const uint32_t n_pad_d = qnnp_round_up_u32(cout, 32), k_pad_d = qnnp_round_up_u32(cin, 64);
+  const size_t wd_bytes = qnnp_igemm_packed_weights_size(1, n_pad_d, k_pad_d);
+  uint8_t* dense = (uint8_t*) malloc((size_t) cout * cin);
+  int8_t* host_wd = (int8_t*) malloc(wd_bytes);
+  int32_t* host_bd = (int32_t*) malloc(sizeof(int32_t) * n_pad_d);
+  if (dense != NULL && host_wd != NULL && host_bd != NULL) {
+    memset(dense, op->kernel_zero_point, (size_t) cout * cin);
+    for (uint32_t g = 0; g < op->groups; g++) {
+      for (size_t oc = 0; oc < goc; oc++) {
+        memcpy(dense + (g * goc + oc) * cin + g * gic, kernel + (g * goc + oc) * gic, gic);
+      }
+    }
+    qnnp_pack_igemm_w_slots(1, cout, 1, cin, cin, n_pad_d, k_pad_d, op->input_zero_point, op->kernel_zero_point, dense, bias,
+        host_wd, host_bd);
+    op->d_weights_dense = qnnp_upload(host_wd, wd_bytes);
+    op->d_bias_dense = qnnp_upload_bias_pair(host_bd, n_pad_d);
+  }
+  free(dense);
+  free(host_wd);
+  free(host_bd);
+  if (op->d_weights_dense != NULL && op->d_bias_dense != NULL) {
+    op->dense_n_pad = n_pad_d;
+    op->dense_k_pad = k_pad_d;
+    return;
+  }
+  qnnp_log_warning("no room for %zu bytes of dense weights on the device: the operator keeps the grouped image", wd_bytes);
+  qnnp_hip_free(op->d_weights_dense);
+  qnnp_hip_free(op->d_bias_dense);
+  op->d_weights_dense = NULL;
+  op->d_bias_dense = NULL;
+}
+
+/* The second, kernel-zero-point-127 image + bias pair of the zero-point-centred kernels (pack.h
+ * qnnp_pack_igemm_w_centred127). Optional: without it the operator runs on the standard image (row term in the
+ * kernel). */
+static void pack_centred127_optional(struct qnnp_operator* op, const uint8_t* kernel, const int32_t* bias, uint32_t k_total)
+{
+  const size_t w_bytes = qnnp_igemm_packed_weights_size(1, op->n_pad, op->k_pad);
+  const size_t b_bytes = sizeof(int32_t) * op->n_pad;
+  int8_t* host_wc = (int8_t*) malloc(w_bytes);
+  int32_t* host_bc = (int32_t*) malloc(b_bytes);
+  if (host_wc != NULL && host_bc != NULL) {
+    qnnp_pack_igemm_w_centred127((uint32_t) op->group_output_channels, k_total, op->k_pad, op->n_pad, op->input_zero_point,
+        kernel, bias, host_wc, host_bc);
+    op->d_weights_centred = qnnp_upload(host_wc, w_bytes);
+    op->d_bias_centred = qnnp_upload_bias_pair(host_bc, op->n_pad);
+  }
+  free(host_wc);
+  free(host_bc);
+  if (op->d_weights_centred != NULL && op->d_bias_centred != NULL) {
+    op->centre_flip = 0x7F;
+    return;
+  }
+  qnnp_log_warning("no room for %zu bytes of centred weights on the device: the operator keeps the standard image", w_bytes + 2 * b_bytes);
+  qnnp_hip_free(op->d_weights_centred);
+  qnnp_hip_free(op->d_bias_centred);
+  op->d_weights_centred = NULL;
+  op->d_bias_centred = NULL;
+}
+
+/* First layers (3-channel inputs in 4-byte tap slots): the row-slot image beside the tap-slot one (hip/q8convc3.hip takes
+ * it when pixels are dense) -- 16-byte row slots, or 32-byte ones for the larger windows (5x5, ResNet's 7x7 entry layer):
+ * same pointer, the window decides which image it is. Centred on kernel zero point 127 it has its own bias pair and no
+ * row term in the kernel (pack.h). Required where it applies. */
+static enum qnnp_status pack_rows(struct qnnp_operator* op, const uint8_t* kernel, const int32_t* bias)
+{
+  const uint32_t kh = op->kernel_height, kw = op->kernel_width, n_pad = op->n_pad, goc = (uint32_t) op->group_output_channels;
+  const int undilated = op->dilation_height == 1 && op->dilation_width == 1;
+  const int rows16 = kh <= 4 && kw * 3 <= 16 && undilated && n_pad <= 64;
+  const int rows32 = (kh == 5 || kh == 7) && kw * 3 <= 32 && undilated && n_pad <= (kh == 7 ? 96u : 64u);
+  if (op->kc_slot != 4 || !(rows16 || rows32)) {
+    return qnnp_status_success;
+  }
+  const size_t r_bytes = rows16 ? (size_t) n_pad * 64 : qnnp_conv_rows32_size(n_pad, kh);
+  int8_t* host_rows = (int8_t*) malloc(r_bytes);
+  if (host_rows == NULL) {
+    qnnp_log_error("out of host memory: %zu bytes for packed weights", r_bytes);
+    return qnnp_status_out_of_memory;
+  }
+  int placed = 1;
+  if (op->kernel_zero_point == 127) {
+    int32_t* host_bc = (int32_t*) malloc((size_t) n_pad * sizeof(int32_t));
+    placed = host_bc != NULL;
+    if (placed) {
+      if (rows16) {
+        qnnp_pack_conv_rows16_centred127(goc, kh, kw, 3, n_pad, op->input_zero_point, kernel, bias, host_rows, host_bc);
+      } else {
+        qnnp_pack_conv_rows32_centred127(goc, kh, kw, 3, n_pad, op->input_zero_point, kernel, bias, host_rows, host_bc);
+      }
+      op->d_bias_rows = qnnp_upload_bias_pair(host_bc, n_pad);
+      placed = op->d_bias_rows != NULL;
+    }
+    free(host_bc);
+  } else if (rows16) {
+    qnnp_pack_conv_rows16(goc, kh, kw, 3, n_pad, kernel, host_rows);
+  } else {
+    qnnp_pack_conv_rows32(goc, kh, kw, 3, n_pad, kernel, host_rows);
+  }
+  if (placed) {
+    op->d_weights_rows16 = qnnp_upload(host_rows, r_bytes);
+  }
+  free(host_rows);
+  if (op->d_weights_rows16 == NULL) {
+    qnnp_log_error("device allocation or upload failed: %zu bytes of packed weights on the device", r_bytes);
+    return qnnp_status_out_of_memory;
+  }
+  return qnnp_status_success;
+}
+
+/* the MFMA fragment image and its bias pair (required), then the optional dense and centred images and the row-slot one */
+static enum qnnp_status pack_gemm(struct qnnp_operator* op, const uint8_t* kernel, const int32_t* bias)
+{
+  const uint32_t groups = op->groups, kh = op->kernel_height, kw = op->kernel_width;
+  const size_t gic = op->group_input_channels, goc = op->group_output_channels;
+  const size_t kernel_size = (size_t) kh * kw;
+  /* 3-channel inputs (first layers): one unaligned 4-byte fetch per tap, see pack.h "channel slots" */
+  const uint32_t kc_slot = (op->ukernel_type == qnnp_ukernel_type_conv && groups == 1 && gic == 3) ? 4u : (uint32_t) gic;
+  const uint32_t k_total = (uint32_t) (kernel_size * kc_slot);
+  const uint32_t n_pad = qnnp_round_up_u32((uint32_t) goc, 32);
+  const uint32_t k_pad = qnnp_round_up_u32(k_total, 64);
+  const size_t w_bytes = qnnp_igemm_packed_weights_size(groups, n_pad, k_pad);
+  const size_t b_bytes = sizeof(int32_t) * (size_t) groups * n_pad;
+  int8_t* host_weights = (int8_t*) malloc(w_bytes);
+  int32_t* host_bias = (int32_t*) malloc(b_bytes);
+  if (host_weights == NULL || host_bias == NULL) {
+    free(host_weights);
+    free(host_bias);
+    qnnp_log_error("out of host memory: %zu bytes for packed weights", w_bytes + b_bytes);
+    return qnnp_status_out_of_memory;
+  }
+  qnnp_pack_igemm_w_slots(groups, (uint32_t) goc, (uint32_t) kernel_size, (uint32_t) gic, kc_slot, n_pad, k_pad,
+      op->input_zero_point, op->kernel_zero_point, kernel, bias, host_weights, host_bias);
+  op->n_pad = n_pad;
+  op->k_pad = k_pad;
+  op->kc_slot = kc_slot;
+  op->d_weights = qnnp_upload(host_weights, w_bytes);
+  op->d_bias = qnnp_upload_bias_pair(host_bias, (size_t) groups * n_pad);   /* bias-pair.h */
+  free(host_weights);
+  free(host_bias);
+  if (op->d_weights == NULL || op->d_bias == NULL) {
+    qnnp_log_error("device allocation or upload failed: %zu bytes of packed weights on the device", w_bytes + 2 * b_bytes);
+    return qnnp_status_out_of_memory;
+  }
+  if (op->ukernel_type == qnnp_ukernel_type_gemm && groups > 1 && groups * gic <= 1024 && groups * goc <= 1024) {
+    pack_dense_optional(op, kernel, bias);
+  }
+  /* Zero-point-centred image (pack.h qnnp_pack_igemm_w_centred127; hip/q8gemm256c.hip, the weight-stationary 3x3
+   * kernel of hip/q8convwave.hip): single group, whole 32-deep K blocks, kernel zero point 128 (the standard image IS the centred
+   * one) or 127 (a second image + bias pair). The [output channel][kh][kw][input channel] kernel tensor is the GEMM
+   * layout the packer takes. */
+  /* (round 6: hip/q8convws16s.hip -- 3x3 windows over 16 / 32 / 48 / 64 input channels, SqueezeNet's fire modules -- takes the image
+   * WITH K padding: 9 x 16 and 9 x 48 bytes are not whole 32-byte blocks; the padding meets zero weights in either image) */
+  const int small_3x3 = kh == 3 && kw == 3 && gic % 16 == 0 && gic <= 64 && goc % 16 == 0 && goc <= 256;
+  if (groups == 1 && kc_slot == (uint32_t) gic && (k_total % 32 == 0 || small_3x3)) {
+    if (op->kernel_zero_point == 128) {
+      op->centre_flip = 0x80;
+    } else if (op->kernel_zero_point == 127 &&
+               /* (a second image only where a kernel takes it: the 3x3 weight-stationary kernel, the 256x256 GEMM) */
+               (small_3x3 ||
+                (kernel_size == 1 && k_total == k_pad && k_total >= 512 && n_pad % 256 == 0) ||
+                /* ... and the 128-wide tiling of hip/q8gemm128x.hip: any K % 64 == 0 */
+                (kernel_size == 1 && k_total == k_pad && k_total % 64 == 0 && goc % 4 == 0))) {
+      pack_centred127_optional(op, kernel, bias, k_total);
+    }
+  }
+  return pack_rows(op, kernel, bias);
 }
 
 static enum qnnp_status qnnp_create_convolution2d_nhwc_q8_impl(
@@ -74,11 +328,9 @@ static enum qnnp_status qnnp_create_convolution2d_nhwc_q8_impl(
 {
   (void) flags; /* accepted and ignored, as in the reference (convolution.c:63) */
   qnnp_operator_t op = NULL;
-  void* host_weights = NULL;
-  int32_t* host_bias = NULL;
   enum qnnp_status status = qnnp_status_uninitialized;
 
-  /* reference convolution.c:69-72 */
+  /* 1. validate. reference convolution.c:69-72 */
   if (!qnnp_state.initialized) {
     qnnp_log_error("qnnp_create_convolution2d_nhwc_q8 called before qnnp_initialize succeeded");
     goto error;
@@ -142,296 +394,11 @@ static enum qnnp_status qnnp_create_convolution2d_nhwc_q8_impl(
 
   status = qnnp_status_out_of_memory;
   op = calloc(1, sizeof(struct qnnp_operator));
-  if (op != NULL) op->device = qnnp_hip_device();   /* the context this create runs in (entry point below) */
   if (op == NULL) {
     qnnp_log_error("out of host memory: %zu bytes for qnnp_operator structure", sizeof(struct qnnp_operator));
     goto error;
   }
-
-  /*
-   * Operator-type selection. Reference convolution.c:180-189 sends 3x3 / 5x5
-   * depthwise to dwconv, unpadded stride-1 1x1 to gemm and the rest to conv.
-   * The device depthwise kernel is not limited to 9 or 25 taps, so every
-   * depthwise convolution (one input and one output channel per group) takes
-   * it; results are identical, only the kernel differs.
-   */
-  const bool any_padding =
-      (input_padding_left | input_padding_top | input_padding_right | input_padding_bottom) != 0;
-  enum qnnp_ukernel_type ukernel_type;
-  if (group_input_channels == 1 && group_output_channels == 1 && groups > 1) {
-    ukernel_type = qnnp_ukernel_type_dwconv;
-  } else if (kernel_size == 1 && subsampling_height == 1 && subsampling_width == 1 && !any_padding) {
-    ukernel_type = qnnp_ukernel_type_gemm;
-  } else {
-    ukernel_type = qnnp_ukernel_type_conv;
-  }
-
-  if (ukernel_type == qnnp_ukernel_type_dwconv) {
-    const uint32_t c_pad = qnnp_round_up_u32(groups, 16);
-    const size_t w_bytes = sizeof(int16_t) * kernel_size * c_pad;
-    const size_t b_bytes = sizeof(int32_t) * c_pad;
-    host_weights = malloc(w_bytes);
-    host_bias = malloc(b_bytes);
-    if (host_weights == NULL || host_bias == NULL) {
-      qnnp_log_error("out of host memory: %zu bytes for packed weights", w_bytes + b_bytes);
-      goto error;
-    }
-    qnnp_pack_dwconv_w(groups, c_pad, kernel_height, kernel_width,
-        input_zero_point, kernel_zero_point, kernel, bias, (int16_t*) host_weights, host_bias);
-    op->c_pad = c_pad;
-    op->dw_wrange = qnnp_dwconv_weight_range((const int16_t*) host_weights, kernel_size * c_pad);
-    op->d_weights = qnnp_hip_alloc(w_bytes);
-    op->d_bias = (int32_t*) qnnp_hip_alloc(b_bytes);
-    if (op->d_weights == NULL || op->d_bias == NULL ||
-        qnnp_hip_h2d(op->d_weights, host_weights, w_bytes, 0) != QNNP_HIP_OK ||
-        qnnp_hip_h2d(op->d_bias, host_bias, b_bytes, 0) != QNNP_HIP_OK) {
-      qnnp_log_error("device allocation or upload failed: %zu bytes of packed depthwise weights on the device", w_bytes + b_bytes);
-      goto error;
-    }
-    /* 3x3 with weights in int8 range: the register image of the int8 dot-product walk (pack.h) */
-    if (kernel_height == 3 && kernel_width == 3 && op->dw_wrange != 0) {
-      const size_t q_bytes = sizeof(uint32_t) * 4 * c_pad;
-      uint32_t* host_q = (uint32_t*) malloc(q_bytes);
-      int ok = host_q != NULL;
-      if (ok) {
-        qnnp_pack_dwconv_dot4(c_pad, op->dw_wrange, (const int16_t*) host_weights, host_bias, host_q);
-        op->d_dw_dot4 = qnnp_hip_alloc(q_bytes);
-        ok = op->d_dw_dot4 != NULL && qnnp_hip_h2d(op->d_dw_dot4, host_q, q_bytes, 0) == QNNP_HIP_OK;
-      }
-      free(host_q);
-      if (!ok) {
-        qnnp_log_error("device allocation or upload failed: %zu bytes of depthwise dot-product weights on the device", q_bytes);
-        goto error;
-      }
-    }
-    /* 5x5 likewise: eight rows (pack.h qnnp_pack_dwconv_dot4_5x5) */
-    if (kernel_height == 5 && kernel_width == 5 && op->dw_wrange != 0) {
-      const size_t q_bytes = sizeof(uint32_t) * 8 * c_pad;
-      uint32_t* host_q = (uint32_t*) malloc(q_bytes);
-      int ok = host_q != NULL;
-      if (ok) {
-        qnnp_pack_dwconv_dot4_5x5(c_pad, op->dw_wrange, (const int16_t*) host_weights, host_bias, host_q);
-        op->d_dw_dot4 = qnnp_hip_alloc(q_bytes);
-        ok = op->d_dw_dot4 != NULL && qnnp_hip_h2d(op->d_dw_dot4, host_q, q_bytes, 0) == QNNP_HIP_OK;
-      }
-      free(host_q);
-      if (!ok) {
-        qnnp_log_error("device allocation or upload failed: %zu bytes of depthwise dot-product weights on the device", q_bytes);
-        goto error;
-      }
-    }
-    /* second image: int8 weight parts + folded bias for the matrix-core depthwise kernel */
-    {
-      const uint32_t c_pad32 = qnnp_round_up_u32(groups, 32);
-      const size_t x_bytes = (size_t) 3 * kernel_size * c_pad32;
-      const size_t bm_bytes = sizeof(int32_t) * c_pad32;
-      int8_t* host_x = (int8_t*) malloc(x_bytes);
-      int32_t* host_bm = (int32_t*) malloc(bm_bytes);
-      int ok = host_x != NULL && host_bm != NULL;
-      if (ok) {
-        op->dwm_parts = qnnp_pack_dwconv_mfma(groups, c_pad32, kernel_height, kernel_width,
-            input_zero_point, kernel_zero_point, kernel, bias, host_x, host_bm);
-        op->c_pad32 = c_pad32;
-        op->d_dwm_x = qnnp_hip_alloc(x_bytes);
-        op->d_dwm_bias = (int32_t*) qnnp_hip_alloc(bm_bytes);
-        ok = op->d_dwm_x != NULL && op->d_dwm_bias != NULL &&
-            qnnp_hip_h2d(op->d_dwm_x, host_x, x_bytes, 0) == QNNP_HIP_OK &&
-            qnnp_hip_h2d(op->d_dwm_bias, host_bm, bm_bytes, 0) == QNNP_HIP_OK;
-      }
-      free(host_x);
-      free(host_bm);
-      if (!ok) {
-        qnnp_log_error("device allocation or upload failed: %zu bytes of depthwise weight parts on the device", x_bytes + bm_bytes);
-        goto error;
-      }
-    }
-  } else {
-    /* 3-channel inputs (first layers): one unaligned 4-byte fetch per tap, see pack.h "channel slots" */
-    const uint32_t kc_slot = (ukernel_type == qnnp_ukernel_type_conv && groups == 1 && group_input_channels == 3) ?
-        4u : (uint32_t) group_input_channels;
-    const uint32_t k_total = (uint32_t) (kernel_size * kc_slot);
-    const uint32_t n_pad = qnnp_round_up_u32((uint32_t) group_output_channels, 32);
-    const uint32_t k_pad = qnnp_round_up_u32(k_total, 64);
-    const size_t w_bytes = qnnp_igemm_packed_weights_size(groups, n_pad, k_pad);
-    const size_t b_bytes = sizeof(int32_t) * (size_t) groups * n_pad;
-    host_weights = malloc(w_bytes);
-    host_bias = malloc(b_bytes);
-    if (host_weights == NULL || host_bias == NULL) {
-      qnnp_log_error("out of host memory: %zu bytes for packed weights", w_bytes + b_bytes);
-      goto error;
-    }
-    qnnp_pack_igemm_w_slots(groups, (uint32_t) group_output_channels, (uint32_t) kernel_size,
-        (uint32_t) group_input_channels, kc_slot, n_pad, k_pad,
-        input_zero_point, kernel_zero_point, kernel, bias, (int8_t*) host_weights, host_bias);
-    op->n_pad = n_pad;
-    op->k_pad = k_pad;
-    op->kc_slot = kc_slot;
-    op->d_weights = qnnp_hip_alloc(w_bytes);
-    op->d_bias = qnnp_upload_bias_pair((const int32_t*) host_bias, (size_t) groups * n_pad);   /* bias-pair.h */
-    if (op->d_weights == NULL || op->d_bias == NULL ||
-        qnnp_hip_h2d(op->d_weights, host_weights, w_bytes, 0) != QNNP_HIP_OK) {
-      qnnp_log_error("device allocation or upload failed: %zu bytes of packed weights on the device", w_bytes + 2 * b_bytes);
-      goto error;
-    }
-    /* Grouped 1x1 as one dense GEMM (round 6). A group of 12 ... 68 channels fills a fifth ... a half of a 64-byte K step and a
-     * 128-channel tile, every group's tile stages its own copy of the rows, and its output pieces are 12 ... 68 bytes; the dense
-     * [groups * GOC][groups * GIC] matrix with the groups' blocks on its diagonal and the KERNEL ZERO POINT everywhere else
-     * ((w - kzp) = 0: the grouped result bit for bit) reads every input byte once and writes whole pixels, at `groups` times the
-     * multiplies -- which these layers do not notice: ShuffleNet v1's 28x28 layers at batch 128 run 15 ... 59 us grouped and 12 ... 27
-     * dense (profiles/r06/grouped_1x1_dense_equivalents_r06v.txt); from 14x14 down the two are level or the grouped form leads, so
-     * operator-run.c takes this image from 65536 rows up. Built for up to 1024 channels on either side (<= 1 MiB of weights). */
-    if (ukernel_type == qnnp_ukernel_type_gemm && groups > 1 && (size_t) groups * group_input_channels <= 1024 &&
-        (size_t) groups * group_output_channels <= 1024) {
-      const uint32_t cin = (uint32_t) (groups * group_input_channels), cout = (uint32_t) (groups * group_output_channels);
-      const uint32_t n_pad_d = qnnp_round_up_u32(cout, 32), k_pad_d = qnnp_round_up_u32(cin, 64);
-      const size_t wd_bytes = qnnp_igemm_packed_weights_size(1, n_pad_d, k_pad_d);
-      uint8_t* dense = (uint8_t*) malloc((size_t) cout * cin);
-      int8_t* host_wd = (int8_t*) malloc(wd_bytes);
-      int32_t* host_bd = (int32_t*) malloc(sizeof(int32_t) * n_pad_d);
-      int placed = dense != NULL && host_wd != NULL && host_bd != NULL;
-      if (placed) {
-        memset(dense, kernel_zero_point, (size_t) cout * cin);
-        for (uint32_t g = 0; g < groups; g++) {
-          for (uint32_t oc = 0; oc < group_output_channels; oc++) {
-            memcpy(dense + ((size_t) g * group_output_channels + oc) * cin + (size_t) g * group_input_channels,
-                   kernel + ((size_t) g * group_output_channels + oc) * group_input_channels, group_input_channels);
-          }
-        }
-        qnnp_pack_igemm_w_slots(1, cout, 1, cin, cin, n_pad_d, k_pad_d, input_zero_point, kernel_zero_point, dense, bias,
-            host_wd, host_bd);
-        op->d_weights_dense = qnnp_hip_alloc(wd_bytes);
-        op->d_bias_dense = qnnp_upload_bias_pair(host_bd, n_pad_d);
-        placed = op->d_weights_dense != NULL && op->d_bias_dense != NULL &&
-            qnnp_hip_h2d(op->d_weights_dense, host_wd, wd_bytes, 0) == QNNP_HIP_OK;
-      }
-      free(dense);
-      free(host_wd);
-      free(host_bd);
-      if (placed) {
-        op->dense_n_pad = n_pad_d;
-        op->dense_k_pad = k_pad_d;
-      } else {
-        /* an optimisation, not a requirement: the operator keeps its grouped image */
-        qnnp_log_warning("no room for %zu bytes of dense weights on the device: the operator keeps the grouped image", wd_bytes);
-        qnnp_hip_free(op->d_weights_dense);
-        qnnp_hip_free(op->d_bias_dense);
-        op->d_weights_dense = NULL;
-        op->d_bias_dense = NULL;
-      }
-    }
-    /* Zero-point-centred image (pack.h qnnp_pack_igemm_w_centred127; hip/q8gemm256c.hip, the weight-stationary 3x3
-     * kernel of hip/q8convwave.hip): single group, whole 32-deep K blocks, kernel zero point 128 (the standard image IS the centred
-     * one) or 127 (a second image + bias pair). The [output channel][kh][kw][input channel] kernel tensor is the GEMM
-     * layout the packer takes. */
-    /* (round 6: hip/q8convws16s.hip -- 3x3 windows over 16 / 32 / 48 / 64 input channels, SqueezeNet's fire modules -- takes the image
-     * WITH K padding: 9 x 16 and 9 x 48 bytes are not whole 32-byte blocks; the padding meets zero weights in either image) */
-    const int small_3x3 = kernel_height == 3 && kernel_width == 3 && group_input_channels % 16 == 0 && group_input_channels <= 64 &&
-        group_output_channels % 16 == 0 && group_output_channels <= 256;
-    if (groups == 1 && kc_slot == (uint32_t) group_input_channels && (k_total % 32 == 0 || small_3x3)) {
-      if (kernel_zero_point == 128) {
-        op->centre_flip = 0x80;
-      } else if (kernel_zero_point == 127 &&
-                 /* (a second image only where a kernel takes it: the 3x3 weight-stationary kernel, the 256x256 GEMM) */
-                 (small_3x3 ||
-                  (kernel_size == 1 && k_total == k_pad && k_total >= 512 && n_pad % 256 == 0) ||
-                  /* ... and the 128-wide tiling of hip/q8gemm128x.hip: any K % 64 == 0 */
-                  (kernel_size == 1 && k_total == k_pad && k_total % 64 == 0 && group_output_channels % 4 == 0))) {
-        int8_t* host_wc = (int8_t*) malloc(w_bytes);
-        int32_t* host_bc = (int32_t*) malloc(b_bytes);
-        int placed = host_wc != NULL && host_bc != NULL;
-        if (placed) {
-          qnnp_pack_igemm_w_centred127((uint32_t) group_output_channels, k_total, k_pad, n_pad, input_zero_point, kernel, bias,
-              host_wc, host_bc);
-          op->d_weights_centred = qnnp_hip_alloc(w_bytes);
-          op->d_bias_centred = qnnp_upload_bias_pair(host_bc, n_pad);
-          placed = op->d_weights_centred != NULL && op->d_bias_centred != NULL &&
-              qnnp_hip_h2d(op->d_weights_centred, host_wc, w_bytes, 0) == QNNP_HIP_OK;
-        }
-        free(host_wc);
-        free(host_bc);
-        if (placed) {
-          op->centre_flip = 0x7F;
-        } else {
-          /* the centred image is an optimisation, not a requirement: without it the operator runs on the standard
-           * image (row term in the kernel) -- drop what was placed and carry on */
-          qnnp_log_warning("no room for %zu bytes of centred weights on the device: the operator keeps the standard image", w_bytes + 2 * b_bytes);
-          qnnp_hip_free(op->d_weights_centred);
-          qnnp_hip_free(op->d_bias_centred);
-          op->d_weights_centred = NULL;
-          op->d_bias_centred = NULL;
-        }
-      }
-    }
-    if (kc_slot == 4 && kernel_height <= 4 && kernel_width * 3 <= 16 && dilation_height == 1 && dilation_width == 1 &&
-        n_pad <= 64) {
-      /* first layers: the row-slot image beside the tap-slot one (hip/q8convc3.hip takes it when pixels are dense) */
-      const size_t r_bytes = (size_t) n_pad * 64;
-      int8_t* host_rows = (int8_t*) malloc(r_bytes);
-      if (host_rows == NULL) {
-        qnnp_log_error("out of host memory: %zu bytes for packed weights", r_bytes);
-        goto error;
-      }
-      int placed = 1;
-      if (kernel_zero_point == 127) {
-        /* centred on the kernel zero point: no row term in the kernel (pack.h) */
-        int32_t* host_bc = (int32_t*) malloc((size_t) n_pad * sizeof(int32_t));
-        placed = host_bc != NULL;
-        if (placed) {
-          qnnp_pack_conv_rows16_centred127((uint32_t) group_output_channels, kernel_height, kernel_width, 3, n_pad, input_zero_point,
-              kernel, bias, host_rows, host_bc);
-          op->d_bias_rows = qnnp_upload_bias_pair(host_bc, n_pad);
-          placed = op->d_bias_rows != NULL;
-        }
-        free(host_bc);
-      } else {
-        qnnp_pack_conv_rows16((uint32_t) group_output_channels, kernel_height, kernel_width, 3, n_pad, kernel, host_rows);
-      }
-      op->d_weights_rows16 = qnnp_hip_alloc(r_bytes);
-      placed = placed && op->d_weights_rows16 != NULL && qnnp_hip_h2d(op->d_weights_rows16, host_rows, r_bytes, 0) == QNNP_HIP_OK;
-      free(host_rows);
-      if (!placed) {
-        qnnp_log_error("device allocation or upload failed: %zu bytes of packed weights on the device", r_bytes);
-        goto error;
-      }
-    } else if (kc_slot == 4 && (kernel_height == 5 || kernel_height == 7) && kernel_width * 3 <= 32 &&
-               dilation_height == 1 && dilation_width == 1 && n_pad <= (kernel_height == 7 ? 96u : 64u)) {
-      /* ... and with 32-byte row slots for the larger windows (5x5, ResNet's 7x7 entry layer): same pointer, the window
-       * decides which image it is (hip/q8convc3.hip) */
-      const size_t r_bytes = qnnp_conv_rows32_size(n_pad, kernel_height);
-      int8_t* host_rows = (int8_t*) malloc(r_bytes);
-      if (host_rows == NULL) {
-        qnnp_log_error("out of host memory: %zu bytes for packed weights", r_bytes);
-        goto error;
-      }
-      int placed = 1;
-      if (kernel_zero_point == 127) {
-        /* centred on the kernel zero point: no row term in the kernel (pack.h) */
-        int32_t* host_bc = (int32_t*) malloc((size_t) n_pad * sizeof(int32_t));
-        placed = host_bc != NULL;
-        if (placed) {
-          qnnp_pack_conv_rows32_centred127((uint32_t) group_output_channels, kernel_height, kernel_width, 3, n_pad, input_zero_point,
-              kernel, bias, host_rows, host_bc);
-          op->d_bias_rows = qnnp_upload_bias_pair(host_bc, n_pad);
-          placed = op->d_bias_rows != NULL;
-        }
-        free(host_bc);
-      } else {
-        qnnp_pack_conv_rows32((uint32_t) group_output_channels, kernel_height, kernel_width, 3, n_pad, kernel, host_rows);
-      }
-      op->d_weights_rows16 = qnnp_hip_alloc(r_bytes);
-      placed = placed && op->d_weights_rows16 != NULL && qnnp_hip_h2d(op->d_weights_rows16, host_rows, r_bytes, 0) == QNNP_HIP_OK;
-      free(host_rows);
-      if (!placed) {
-        qnnp_log_error("device allocation or upload failed: %zu bytes of packed weights on the device", r_bytes);
-        goto error;
-      }
-    }
-  }
-  free(host_weights);
-  free(host_bias);
-  host_weights = NULL;
-  host_bias = NULL;
-
+  op->device = qnnp_hip_device();   /* the context this create runs in (entry point below) */
   op->input_padding_top = input_padding_top;
   op->input_padding_right = input_padding_right;
   op->input_padding_bottom = input_padding_bottom;
@@ -450,15 +417,35 @@ static enum qnnp_status qnnp_create_convolution2d_nhwc_q8_impl(
   op->requant = qnnp_compute_requant(convolution_scale, output_zero_point, output_min, output_max);
   op->requant.accumulator_bits = qnnp_accumulator_bits(bias, (size_t) groups * group_output_channels,
       kernel_size * group_input_channels);
-  op->ukernel_type = ukernel_type;
+
+  /*
+   * 2. Operator-type selection. Reference convolution.c:180-189 sends 3x3 / 5x5
+   * depthwise to dwconv, unpadded stride-1 1x1 to gemm and the rest to conv.
+   * The device depthwise kernel is not limited to 9 or 25 taps, so every
+   * depthwise convolution (one input and one output channel per group) takes
+   * it; results are identical, only the kernel differs.
+   */
+  const bool any_padding =
+      (input_padding_left | input_padding_top | input_padding_right | input_padding_bottom) != 0;
+  if (group_input_channels == 1 && group_output_channels == 1 && groups > 1) {
+    op->ukernel_type = qnnp_ukernel_type_dwconv;
+  } else if (kernel_size == 1 && subsampling_height == 1 && subsampling_width == 1 && !any_padding) {
+    op->ukernel_type = qnnp_ukernel_type_gemm;
+  } else {
+    op->ukernel_type = qnnp_ukernel_type_conv;
+  }
+
+  /* 3. / 4. the device images */
+  status = op->ukernel_type == qnnp_ukernel_type_dwconv ? pack_depthwise(op, kernel, bias) : pack_gemm(op, kernel, bias);
+  if (status != qnnp_status_success) {
+    goto error;
+  }
 
   /* reference convolution.c:372: the handle is written only on success */
   *convolution_out = op;
   return qnnp_status_success;
 
 error:
-  free(host_weights);
-  free(host_bias);
   qnnp_delete_operator(op);
   return status;
 }
@@ -573,30 +560,24 @@ static enum qnnp_status qnnp_setup_convolution2d_nhwc_q8_impl(
       if (same_geometry) {
         return qnnp_status_success;  /* table is pointer- and batch-invariant */
       }
-      int32_t* host_table = (int32_t*) malloc(sizeof(int32_t) * entries);
+      const size_t bytes = sizeof(int32_t) * entries;
+      int32_t* host_table = (int32_t*) malloc(bytes);
       if (host_table == NULL) {
-        qnnp_log_error("out of host memory: %zu bytes for the offset table", sizeof(int32_t) * entries);
+        qnnp_log_error("out of host memory: %zu bytes for the offset table", bytes);
         return qnnp_status_out_of_memory;
       }
-      if (op->offsets_capacity < entries) {
-        qnnp_hip_free(op->d_offsets);
-        op->offsets_capacity = 0;
-        /* (+ 16 bytes: the 3-channel streaming kernel reads a lane's four consecutive entries with one 16-byte
-         *  load, which for the last pixel's second K block starts on its 9th entry and runs past the table) */
-        op->d_offsets = (int32_t*) qnnp_hip_alloc(sizeof(int32_t) * entries + 16);
-        if (op->d_offsets == NULL) {
-          free(host_table);
-          qnnp_log_error("out of host memory: %zu bytes for the device offset table", sizeof(int32_t) * entries);
-          return qnnp_status_out_of_memory;
-        }
-        op->offsets_capacity = entries;
-      }
       qnnp_indirection_init_conv2d_offsets(op, host_table);
-      const int rc = qnnp_hip_h2d(op->d_offsets, host_table, sizeof(int32_t) * entries, 0);
+      /* (+ 16 bytes: the 3-channel streaming kernel reads a lane's four consecutive entries with one 16-byte
+       *  load, which for the last pixel's second K block starts on its 9th entry and runs past the table) */
+      const int uploaded = qnnp_upload_table((void**) &op->d_offsets, &op->offsets_capacity, entries, bytes + 16, host_table, bytes);
       free(host_table);
-      if (rc != QNNP_HIP_OK) {
-        op->offsets_in_h = 0;
-        qnnp_log_error("failed to upload the offset table");
+      if (!uploaded) {
+        if (op->d_offsets == NULL) {
+          qnnp_log_error("out of host memory: %zu bytes for the device offset table", bytes);
+        } else {
+          op->offsets_in_h = 0;
+          qnnp_log_error("failed to upload the offset table");
+        }
         return qnnp_status_out_of_memory;
       }
       op->offsets_in_h = input_height;
@@ -643,17 +624,12 @@ enum qnnp_status qnnp_create_convolution2d_nhwc_q8(
   if (!qnnp_state.initialized) {
     return qnnp_create_convolution2d_nhwc_q8_impl(input_padding_top, input_padding_right, input_padding_bottom, input_padding_left, kernel_height, kernel_width, subsampling_height, subsampling_width, dilation_height, dilation_width, groups, group_input_channels, group_output_channels, input_zero_point, input_scale, kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max, flags, convolution_out);   /* logs and answers qnnp_status_uninitialized */
   }
-  const int token = qnnp_hip_enter(qnnp_hip_device());
-  if (token < 0) {
-    return qnnp_status_unsupported_hardware;
+  int token;
+  enum qnnp_status status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
+  if (status != qnnp_status_success) {
+    return status;
   }
-  if (qnnp_hip_graph_capturing()) {
-    /* inside qnnp_gfx950_graph_begin ... graph_end on this device only operator launches are recordable: an upload
-     * would become a graph node reading host memory that is freed right after this call */
-    qnnp_hip_leave(token);
-    return qnnp_status_invalid_parameter;
-  }
-  const enum qnnp_status status = qnnp_create_convolution2d_nhwc_q8_impl(input_padding_top, input_padding_right, input_padding_bottom, input_padding_left, kernel_height, kernel_width, subsampling_height, subsampling_width, dilation_height, dilation_width, groups, group_input_channels, group_output_channels, input_zero_point, input_scale, kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max, flags, convolution_out);
+  status = qnnp_create_convolution2d_nhwc_q8_impl(input_padding_top, input_padding_right, input_padding_bottom, input_padding_left, kernel_height, kernel_width, subsampling_height, subsampling_width, dilation_height, dilation_width, groups, group_input_channels, group_output_channels, input_zero_point, input_scale, kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max, flags, convolution_out);
   qnnp_hip_leave(token);
   return status;
 }
@@ -672,17 +648,12 @@ enum qnnp_status qnnp_setup_convolution2d_nhwc_q8(
   if (!qnnp_state.initialized || op == NULL) {
     return qnnp_setup_convolution2d_nhwc_q8_impl(op, batch_size, input_height, input_width, input, input_pixel_stride, output, output_pixel_stride, threadpool);   /* answers qnnp_status_uninitialized / invalid_parameter */
   }
-  const int token = qnnp_hip_enter(op->device);
-  if (token < 0) {
-    return qnnp_status_invalid_parameter;   /* not a live operator of this library instance */
+  int token;
+  enum qnnp_status status = qnnp_enter_for_update(op->device, qnnp_status_invalid_parameter, &token);
+  if (status != qnnp_status_success) {
+    return status;
   }
-  if (qnnp_hip_graph_capturing()) {
-    /* inside qnnp_gfx950_graph_begin ... graph_end on this device only operator launches are recordable: an upload
-     * would become a graph node reading host memory that is freed right after this call */
-    qnnp_hip_leave(token);
-    return qnnp_status_invalid_parameter;
-  }
-  const enum qnnp_status status = qnnp_setup_convolution2d_nhwc_q8_impl(op, batch_size, input_height, input_width, input, input_pixel_stride, output, output_pixel_stride, threadpool);
+  status = qnnp_setup_convolution2d_nhwc_q8_impl(op, batch_size, input_height, input_width, input, input_pixel_stride, output, output_pixel_stride, threadpool);
   /* the implementation cleared setup_valid where it began to change the operator: a failed setup leaves it
    * unrunnable instead of half updated (run answers invalid_parameter) */
   if (status == qnnp_status_success) {

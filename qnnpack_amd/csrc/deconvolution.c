@@ -40,6 +40,7 @@
 #include "pack.h"
 #include "requantization.h"
 #include "state.h"
+#include "upload.h"
 
 /* reference src/deconvolution.c:25-37 */
 static inline size_t compute_output_dimension(
@@ -52,6 +53,199 @@ static inline size_t compute_output_dimension(
 static inline bool scale_is_valid(float scale)
 {
   return scale > 0.0f && isnormal(scale);
+}
+
+/* One packed sub-kernel per output phase (conv_order: the kernel in convolution order, [g][oc][tap][ic]). */
+static enum qnnp_status pack_phases(struct qnnp_operator* op, const uint8_t* conv_order, const int32_t* bias)
+{
+  const uint32_t kh = op->kernel_height, kw = op->kernel_width, sh = op->stride_height, sw = op->stride_width;
+  const size_t groups = op->groups, gic = op->group_input_channels, goc = op->group_output_channels;
+  const size_t kernel_size = (size_t) kh * kw, group_weights = goc * kernel_size * gic;
+  const size_t b_bytes = sizeof(int32_t) * groups * op->n_pad;
+  uint8_t* sub = (uint8_t*) malloc(group_weights * groups + gic * goc * groups);
+  int32_t* host_bias = (int32_t*) malloc(b_bytes);
+  enum qnnp_status status = qnnp_status_out_of_memory;
+  if (sub == NULL || host_bias == NULL) {
+    qnnp_log_error("out of host memory: %zu bytes for the phase kernels", group_weights * groups);
+    goto done;
+  }
+  for (uint32_t py = 0; py < sh; py++) {
+    for (uint32_t px = 0; px < sw; px++) {
+      struct qnnp_deconv_phase* ph = &op->phase[py * sw + px];
+      uint32_t taps = 0;
+      for (uint32_t ky = 0; ky < kh; ky++) {
+        if ((ky * op->dilation_height) % sh != py) continue;
+        for (uint32_t kx = 0; kx < kw; kx++) {
+          if ((kx * op->dilation_width) % sw != px) continue;
+          ph->tap_ky[taps] = (uint8_t) ky;
+          ph->tap_kx[taps] = (uint8_t) kx;
+          taps++;
+        }
+      }
+      const int empty = taps == 0;
+      if (empty) {
+        /* no tap ever reaches this phase: one tap of weight == kernel zero point, always padding (255 = no tap) */
+        ph->tap_ky[0] = ph->tap_kx[0] = 255;
+        taps = 1;
+      }
+      ph->taps = taps;
+      for (size_t g = 0; g < groups; g++) {
+        for (size_t oc = 0; oc < goc; oc++) {
+          for (uint32_t t = 0; t < taps; t++) {
+            uint8_t* dst = sub + ((g * goc + oc) * taps + t) * gic;
+            if (empty) {
+              memset(dst, op->kernel_zero_point, gic);
+            } else {
+              const size_t tap = (size_t) ph->tap_ky[t] * kw + ph->tap_kx[t];
+              memcpy(dst, conv_order + g * group_weights + (oc * kernel_size + tap) * gic, gic);
+            }
+          }
+        }
+      }
+      ph->k_pad = qnnp_round_up_u32(taps * op->kc_slot, 64);
+      const size_t w_bytes = qnnp_igemm_packed_weights_size((uint32_t) groups, op->n_pad, ph->k_pad);
+      int8_t* packed = (int8_t*) malloc(w_bytes);
+      if (packed != NULL) {
+        qnnp_pack_igemm_w_slots((uint32_t) groups, (uint32_t) goc, taps, (uint32_t) gic, op->kc_slot, op->n_pad, ph->k_pad,
+            op->input_zero_point, op->kernel_zero_point, sub, bias, packed, host_bias);
+        ph->d_weights = qnnp_upload(packed, w_bytes);
+        ph->d_bias = qnnp_upload_bias_pair(host_bias, groups * op->n_pad);   /* bias-pair.h */
+        free(packed);
+      }
+      op->deconv_phases = py * sw + px + 1;   /* so that delete frees what exists so far */
+      if (ph->d_weights == NULL || ph->d_bias == NULL) {
+        qnnp_log_error("device allocation or upload failed: %zu bytes of packed phase weights on the device", w_bytes + b_bytes);
+        goto done;
+      }
+    }
+  }
+  status = qnnp_status_success;
+done:
+  free(sub);
+  free(host_bias);
+  return status;
+}
+
+/* Kernel == stride (the usual 2x upsampling): every output pixel has exactly one tap and every input pixel
+ * feeds stride_h*stride_w output pixels, so the whole operator is ONE pointwise GEMM over the input pixels with
+ * phases * n_pad columns (phase-major) whose 32-channel blocks are stored depth-to-space (q8pwconv.hip).
+ * Packed beside the phase kernels; the run falls back to those if the streaming kernel cannot take the tensors. */
+static enum qnnp_status pack_depth_to_space(struct qnnp_operator* op, const uint8_t* conv_order, const int32_t* bias)
+{
+  const uint32_t phases = op->stride_height * op->stride_width, n_pad = op->n_pad;
+  const size_t gic = op->group_input_channels, goc = op->group_output_channels;
+  const size_t kernel_size = (size_t) op->kernel_height * op->kernel_width;
+  const uint32_t d2s_cols = phases * n_pad;
+  const uint32_t d2s_k_pad = qnnp_round_up_u32((uint32_t) gic, 64);
+  const bool any_padding =
+      (op->input_padding_top | op->input_padding_right | op->input_padding_bottom | op->input_padding_left) != 0;
+  if (!(op->groups == 1 && op->kernel_height == op->stride_height && op->kernel_width == op->stride_width &&
+        op->dilation_height == 1 && op->dilation_width == 1 && !any_padding &&
+        op->adjustment_height == 0 && op->adjustment_width == 0 && gic <= 256 && gic % 16 == 0 &&
+        (size_t) d2s_cols * ((gic + 31) / 32 * 32) + (size_t) d2s_cols * 4 + 1024 <= 64 * 1024)) {
+    return qnnp_status_success;   /* the phase kernels only */
+  }
+  uint8_t* mat = (uint8_t*) malloc((size_t) d2s_cols * gic);
+  int32_t* cols_bias = (int32_t*) calloc(d2s_cols, sizeof(int32_t));
+  const size_t dw_bytes = qnnp_igemm_packed_weights_size(1, d2s_cols, d2s_k_pad);
+  const size_t db_bytes = sizeof(int32_t) * d2s_cols;
+  int8_t* packed = (int8_t*) malloc(dw_bytes);
+  int32_t* packed_bias = (int32_t*) malloc(db_bytes);
+  if (mat != NULL && cols_bias != NULL && packed != NULL && packed_bias != NULL) {
+    memset(mat, op->kernel_zero_point, (size_t) d2s_cols * gic);     /* padding columns: w - kzp == 0 */
+    for (uint32_t ph = 0; ph < phases; ph++) {
+      const size_t tap = (size_t) (ph / op->stride_width) * op->kernel_width + ph % op->stride_width;   /* (ky, kx) = (py, px) */
+      for (size_t oc = 0; oc < goc; oc++) {
+        memcpy(mat + ((size_t) ph * n_pad + oc) * gic, conv_order + (oc * kernel_size + tap) * gic, gic);
+        cols_bias[(size_t) ph * n_pad + oc] = bias[oc];
+      }
+    }
+    qnnp_pack_igemm_w_slots(1, d2s_cols, 1, (uint32_t) gic, op->kc_slot, d2s_cols, d2s_k_pad,
+        op->input_zero_point, op->kernel_zero_point, mat, cols_bias, packed, packed_bias);
+    op->d_weights = qnnp_upload(packed, dw_bytes);
+    op->d_bias = qnnp_upload_bias_pair(packed_bias, d2s_cols);   /* bias-pair.h */
+  }
+  free(mat);
+  free(cols_bias);
+  free(packed);
+  free(packed_bias);
+  if (op->d_weights == NULL || op->d_bias == NULL) {
+    qnnp_log_error("device allocation or upload failed: %zu bytes of packed depth-to-space weights on the device", dw_bytes + db_bytes);
+    return qnnp_status_out_of_memory;
+  }
+  op->k_pad = d2s_k_pad;
+  op->deconv_d2s = 1;
+  return qnnp_status_success;
+}
+
+/* stride 1, or too many phases / taps to split: one packed kernel over all taps */
+static enum qnnp_status pack_whole(struct qnnp_operator* op, const uint8_t* conv_order, const int32_t* bias)
+{
+  const uint32_t groups = op->groups;
+  const size_t kernel_size = (size_t) op->kernel_height * op->kernel_width;
+  const uint32_t k_pad = qnnp_round_up_u32((uint32_t) (kernel_size * op->kc_slot), 64);
+  const size_t w_bytes = qnnp_igemm_packed_weights_size(groups, op->n_pad, k_pad);
+  const size_t b_bytes = sizeof(int32_t) * (size_t) groups * op->n_pad;
+  int8_t* host_weights = (int8_t*) malloc(w_bytes);
+  int32_t* host_bias = (int32_t*) malloc(b_bytes);
+  if (host_weights == NULL || host_bias == NULL) {
+    free(host_weights);
+    free(host_bias);
+    qnnp_log_error("out of host memory: %zu bytes for packed weights", w_bytes + b_bytes);
+    return qnnp_status_out_of_memory;
+  }
+  qnnp_pack_igemm_w_slots(groups, (uint32_t) op->group_output_channels, (uint32_t) kernel_size,
+      (uint32_t) op->group_input_channels, op->kc_slot, op->n_pad, k_pad, op->input_zero_point, op->kernel_zero_point,
+      conv_order, bias, host_weights, host_bias);
+  op->k_pad = k_pad;
+  op->d_weights = qnnp_upload(host_weights, w_bytes);
+  op->d_bias = qnnp_upload_bias_pair(host_bias, (size_t) groups * op->n_pad);   /* bias-pair.h */
+  free(host_weights);
+  free(host_bias);
+  if (op->d_weights == NULL || op->d_bias == NULL) {
+    qnnp_log_error("device allocation or upload failed: %zu bytes of packed weights on the device", w_bytes + b_bytes);
+    return qnnp_status_out_of_memory;
+  }
+  return qnnp_status_success;
+}
+
+/* The device images: the kernel in convolution order goes through the packer of the phase kernels (+ the depth-to-space
+ * GEMM) of a strided deconvolution, else through the one of a single kernel over all taps. */
+static enum qnnp_status pack_deconvolution(struct qnnp_operator* op, const uint8_t* kernel, const int32_t* bias)
+{
+  const size_t groups = op->groups, kernel_size = (size_t) op->kernel_height * op->kernel_width;
+  /* [g][ic][tap][oc] -> [g][oc][tap][ic] */
+  const size_t gic = op->group_input_channels, goc = op->group_output_channels;
+  const size_t group_weights = goc * kernel_size * gic;
+  uint8_t* conv_order = (uint8_t*) malloc(group_weights * groups);
+  if (conv_order == NULL) {
+    qnnp_log_error("out of host memory: %zu bytes for the transposed kernel", group_weights * groups);
+    return qnnp_status_out_of_memory;
+  }
+  for (size_t g = 0; g < groups; g++) {
+    for (size_t ic = 0; ic < gic; ic++) {
+      for (size_t tap = 0; tap < kernel_size; tap++) {
+        const uint8_t* row = kernel + g * group_weights + (ic * kernel_size + tap) * goc;
+        for (size_t oc = 0; oc < goc; oc++) {
+          conv_order[g * group_weights + (oc * kernel_size + tap) * gic + ic] = row[oc];
+        }
+      }
+    }
+  }
+  op->kc_slot = (uint32_t) gic;
+  op->n_pad = qnnp_round_up_u32((uint32_t) goc, 32);
+  const uint32_t phases = op->stride_height * op->stride_width;
+  enum qnnp_status status;
+  if (phases > 1 && phases <= QNNP_MAX_DECONV_PHASES && kernel_size <= 64) {
+    status = pack_phases(op, conv_order, bias);
+    if (status == qnnp_status_success) {
+      status = pack_depth_to_space(op, conv_order, bias);
+    }
+  } else {
+    status = pack_whole(op, conv_order, bias);
+  }
+  free(conv_order);
+  return status;
 }
 
 static enum qnnp_status qnnp_create_deconvolution2d_nhwc_q8_impl(
@@ -85,9 +279,6 @@ static enum qnnp_status qnnp_create_deconvolution2d_nhwc_q8_impl(
 {
   (void) flags;
   qnnp_operator_t op = NULL;
-  uint8_t* conv_order = NULL;
-  void* host_weights = NULL;
-  int32_t* host_bias = NULL;
   enum qnnp_status status = qnnp_status_uninitialized;
 
   /* reference deconvolution.c:69-72 */
@@ -153,182 +344,11 @@ static enum qnnp_status qnnp_create_deconvolution2d_nhwc_q8_impl(
 
   status = qnnp_status_out_of_memory;
   op = calloc(1, sizeof(struct qnnp_operator));
-  if (op != NULL) op->device = qnnp_hip_device();   /* the context this create runs in (entry point below) */
   if (op == NULL) {
     qnnp_log_error("out of host memory: %zu bytes for qnnp_operator structure", sizeof(struct qnnp_operator));
     goto error;
   }
-
-  /* [g][ic][tap][oc] -> [g][oc][tap][ic] */
-  const size_t gic = group_input_channels, goc = group_output_channels;
-  const size_t group_weights = goc * kernel_size * gic;
-  conv_order = (uint8_t*) malloc(group_weights * groups);
-  if (conv_order == NULL) {
-    qnnp_log_error("out of host memory: %zu bytes for the transposed kernel", group_weights * groups);
-    goto error;
-  }
-  for (size_t g = 0; g < groups; g++) {
-    const uint8_t* src = kernel + g * group_weights;
-    uint8_t* dst = conv_order + g * group_weights;
-    for (size_t ic = 0; ic < gic; ic++) {
-      for (size_t tap = 0; tap < kernel_size; tap++) {
-        const uint8_t* row = src + (ic * kernel_size + tap) * goc;
-        for (size_t oc = 0; oc < goc; oc++) {
-          dst[(oc * kernel_size + tap) * gic + ic] = row[oc];
-        }
-      }
-    }
-  }
-
-  const uint32_t kc_slot = (uint32_t) gic;
-  const uint32_t n_pad = qnnp_round_up_u32((uint32_t) goc, 32);
-  const uint32_t phases = stride_height * stride_width;
-  if (phases > 1 && phases <= QNNP_MAX_DECONV_PHASES && kernel_size <= 64) {
-    /* one packed sub-kernel per output phase */
-    const size_t b_bytes = sizeof(int32_t) * (size_t) groups * n_pad;
-    uint8_t* sub = (uint8_t*) malloc(group_weights * groups + gic * goc * groups);
-    host_bias = malloc(b_bytes);
-    if (sub == NULL || host_bias == NULL) {
-      free(sub);
-      qnnp_log_error("out of host memory: %zu bytes for the phase kernels", group_weights * groups);
-      goto error;
-    }
-    for (uint32_t py = 0; py < stride_height; py++) {
-      for (uint32_t px = 0; px < stride_width; px++) {
-        struct qnnp_deconv_phase* ph = &op->phase[py * stride_width + px];
-        uint32_t taps = 0;
-        for (uint32_t ky = 0; ky < kernel_height; ky++) {
-          if ((ky * dilation_height) % stride_height != py) continue;
-          for (uint32_t kx = 0; kx < kernel_width; kx++) {
-            if ((kx * dilation_width) % stride_width != px) continue;
-            ph->tap_ky[taps] = (uint8_t) ky;
-            ph->tap_kx[taps] = (uint8_t) kx;
-            taps++;
-          }
-        }
-        const int empty = taps == 0;
-        if (empty) {
-          /* no tap ever reaches this phase: one tap of weight == kernel zero point, always padding (255 = no tap) */
-          ph->tap_ky[0] = ph->tap_kx[0] = 255;
-          taps = 1;
-        }
-        ph->taps = taps;
-        for (size_t g = 0; g < groups; g++) {
-          for (size_t oc = 0; oc < goc; oc++) {
-            for (uint32_t t = 0; t < taps; t++) {
-              uint8_t* dst = sub + ((g * goc + oc) * taps + t) * gic;
-              if (empty) {
-                memset(dst, kernel_zero_point, gic);
-              } else {
-                const size_t tap = (size_t) ph->tap_ky[t] * kernel_width + ph->tap_kx[t];
-                memcpy(dst, conv_order + g * group_weights + (oc * kernel_size + tap) * gic, gic);
-              }
-            }
-          }
-        }
-        ph->k_pad = qnnp_round_up_u32(taps * kc_slot, 64);
-        const size_t w_bytes = qnnp_igemm_packed_weights_size(groups, n_pad, ph->k_pad);
-        void* packed = malloc(w_bytes);
-        int ok = packed != NULL;
-        if (ok) {
-          qnnp_pack_igemm_w_slots(groups, (uint32_t) goc, taps, (uint32_t) gic, kc_slot, n_pad, ph->k_pad,
-              input_zero_point, kernel_zero_point, sub, bias, (int8_t*) packed, host_bias);
-          ph->d_weights = qnnp_hip_alloc(w_bytes);
-          ph->d_bias = qnnp_upload_bias_pair((const int32_t*) host_bias, (size_t) groups * n_pad);   /* bias-pair.h */
-          ok = ph->d_weights != NULL && ph->d_bias != NULL &&
-              qnnp_hip_h2d(ph->d_weights, packed, w_bytes, 0) == QNNP_HIP_OK;
-        }
-        free(packed);
-        op->deconv_phases = py * stride_width + px + 1;   /* so that delete frees what exists so far */
-        if (!ok) {
-          free(sub);
-          qnnp_log_error("device allocation or upload failed: %zu bytes of packed phase weights on the device", w_bytes + b_bytes);
-          goto error;
-        }
-      }
-    }
-    free(sub);
-    op->n_pad = n_pad;
-    op->kc_slot = kc_slot;
-
-    /* Kernel == stride (the usual 2x upsampling): every output pixel has exactly one tap and every input pixel
-     * feeds stride_h*stride_w output pixels, so the whole operator is ONE pointwise GEMM over the input pixels with
-     * phases * n_pad columns (phase-major) whose 32-channel blocks are stored depth-to-space (q8pwconv.hip).
-     * Packed beside the phase kernels; the run falls back to those if the streaming kernel cannot take the tensors. */
-    const bool any_padding =
-        (input_padding_top | input_padding_right | input_padding_bottom | input_padding_left) != 0;
-    const uint32_t d2s_cols = phases * n_pad;
-    const uint32_t d2s_k_pad = qnnp_round_up_u32((uint32_t) gic, 64);
-    if (groups == 1 && kernel_height == stride_height && kernel_width == stride_width &&
-        dilation_height == 1 && dilation_width == 1 && !any_padding &&
-        adjustment_height == 0 && adjustment_width == 0 && gic <= 256 && gic % 16 == 0 &&
-        (size_t) d2s_cols * ((gic + 31) / 32 * 32) + (size_t) d2s_cols * 4 + 1024 <= 64 * 1024) {
-      uint8_t* mat = (uint8_t*) malloc((size_t) d2s_cols * gic);
-      int32_t* cols_bias = (int32_t*) calloc(d2s_cols, sizeof(int32_t));
-      const size_t dw_bytes = qnnp_igemm_packed_weights_size(1, d2s_cols, d2s_k_pad);
-      const size_t db_bytes = sizeof(int32_t) * d2s_cols;
-      void* packed = malloc(dw_bytes);
-      int32_t* packed_bias = (int32_t*) malloc(db_bytes);
-      int ok = mat != NULL && cols_bias != NULL && packed != NULL && packed_bias != NULL;
-      if (ok) {
-        memset(mat, kernel_zero_point, (size_t) d2s_cols * gic);     /* padding columns: w - kzp == 0 */
-        for (uint32_t ph = 0; ph < phases; ph++) {
-          const size_t tap = (size_t) (ph / stride_width) * kernel_width + ph % stride_width;   /* (ky, kx) = (py, px) */
-          for (size_t oc = 0; oc < goc; oc++) {
-            memcpy(mat + ((size_t) ph * n_pad + oc) * gic, conv_order + (oc * kernel_size + tap) * gic, gic);
-            cols_bias[(size_t) ph * n_pad + oc] = bias[oc];
-          }
-        }
-        qnnp_pack_igemm_w_slots(1, d2s_cols, 1, (uint32_t) gic, kc_slot, d2s_cols, d2s_k_pad,
-            input_zero_point, kernel_zero_point, mat, cols_bias, (int8_t*) packed, packed_bias);
-        op->d_weights = qnnp_hip_alloc(dw_bytes);
-        op->d_bias = qnnp_upload_bias_pair(packed_bias, db_bytes / sizeof(int32_t));   /* bias-pair.h */
-        ok = op->d_weights != NULL && op->d_bias != NULL &&
-            qnnp_hip_h2d(op->d_weights, packed, dw_bytes, 0) == QNNP_HIP_OK;
-      }
-      free(mat);
-      free(cols_bias);
-      free(packed);
-      free(packed_bias);
-      if (!ok) {
-        qnnp_log_error("device allocation or upload failed: %zu bytes of packed depth-to-space weights on the device", dw_bytes + db_bytes);
-        goto error;
-      }
-      op->k_pad = d2s_k_pad;
-      op->deconv_d2s = 1;
-    }
-    goto packed_done;
-  }
-  const uint32_t k_total = (uint32_t) (kernel_size * kc_slot);
-  const uint32_t k_pad = qnnp_round_up_u32(k_total, 64);
-  const size_t w_bytes = qnnp_igemm_packed_weights_size(groups, n_pad, k_pad);
-  const size_t b_bytes = sizeof(int32_t) * (size_t) groups * n_pad;
-  host_weights = malloc(w_bytes);
-  host_bias = malloc(b_bytes);
-  if (host_weights == NULL || host_bias == NULL) {
-    qnnp_log_error("out of host memory: %zu bytes for packed weights", w_bytes + b_bytes);
-    goto error;
-  }
-  qnnp_pack_igemm_w_slots(groups, (uint32_t) goc, (uint32_t) kernel_size, (uint32_t) gic, kc_slot, n_pad, k_pad,
-      input_zero_point, kernel_zero_point, conv_order, bias, (int8_t*) host_weights, host_bias);
-  op->n_pad = n_pad;
-  op->k_pad = k_pad;
-  op->kc_slot = kc_slot;
-  op->d_weights = qnnp_hip_alloc(w_bytes);
-  op->d_bias = qnnp_upload_bias_pair((const int32_t*) host_bias, (size_t) groups * n_pad);   /* bias-pair.h */
-  if (op->d_weights == NULL || op->d_bias == NULL ||
-      qnnp_hip_h2d(op->d_weights, host_weights, w_bytes, 0) != QNNP_HIP_OK) {
-    qnnp_log_error("device allocation or upload failed: %zu bytes of packed weights on the device", w_bytes + b_bytes);
-    goto error;
-  }
-packed_done:
-  free(conv_order);
-  free(host_weights);
-  free(host_bias);
-  conv_order = NULL;
-  host_weights = NULL;
-  host_bias = NULL;
-
+  op->device = qnnp_hip_device();   /* the context this create runs in (entry point below) */
   op->input_padding_top = input_padding_top;
   op->input_padding_right = input_padding_right;
   op->input_padding_bottom = input_padding_bottom;
@@ -352,13 +372,15 @@ packed_done:
   op->ukernel_type = qnnp_ukernel_type_conv;   /* reference deconvolution.c:203 */
   op->transposed = 1;
 
+  status = pack_deconvolution(op, kernel, bias);
+  if (status != qnnp_status_success) {
+    goto error;
+  }
+
   *deconvolution_out = op;
   return qnnp_status_success;
 
 error:
-  free(conv_order);
-  free(host_weights);
-  free(host_bias);
   qnnp_delete_operator(op);
   return status;
 }
@@ -402,6 +424,68 @@ static enum qnnp_status upload_phase_table(struct qnnp_operator* op)
     qnnp_log_error("failed to upload the phase table");
     return qnnp_status_out_of_memory;
   }
+  return qnnp_status_success;
+}
+
+/* The per-phase offset tables and output-row lists of the geometry bound to `op` (setup). */
+static enum qnnp_status build_phase_tables(struct qnnp_operator* op)
+{
+  const size_t input_height = op->input_height, input_width = op->input_width, input_pixel_stride = op->input_pixel_stride;
+  op->offsets_in_h = 0;
+  const size_t sh = op->stride_height, sw = op->stride_width;
+  for (uint32_t i = 0; i < op->deconv_phases; i++) {
+    struct qnnp_deconv_phase* ph = &op->phase[i];
+    const size_t py = i / sw, px = i % sw;
+    /* first output row / column of the phase: (o + pad) % stride == phase */
+    const size_t oy0 = (py + sh - op->input_padding_top % sh) % sh;
+    const size_t ox0 = (px + sw - op->input_padding_left % sw) % sw;
+    const size_t rows_y = oy0 < op->output_height ? (op->output_height - oy0 + sh - 1) / sh : 0;
+    const size_t rows_x = ox0 < op->output_width ? (op->output_width - ox0 + sw - 1) / sw : 0;
+    ph->rows = rows_y * rows_x;
+    if (ph->rows == 0) continue;
+    int32_t* host_offsets = (int32_t*) malloc(sizeof(int32_t) * ph->rows * ph->taps);
+    int32_t* host_rows = (int32_t*) malloc(sizeof(int32_t) * ph->rows);
+    if (host_offsets == NULL || host_rows == NULL) {
+      free(host_offsets);
+      free(host_rows);
+      qnnp_log_error("out of host memory: %zu bytes for a phase table", sizeof(int32_t) * ph->rows * (ph->taps + 1));
+      return qnnp_status_out_of_memory;
+    }
+    size_t r = 0;
+    for (size_t oy = oy0; oy < op->output_height; oy += sh) {
+      for (size_t ox = ox0; ox < op->output_width; ox += sw, r++) {
+        host_rows[r] = (int32_t) (oy * op->output_width + ox);
+        for (uint32_t t = 0; t < ph->taps; t++) {
+          int32_t entry = QNNP_OFFSET_PADDING;
+          if (ph->tap_ky[t] != 255) {
+            /* reference src/indirection.c:171-177; the divisions are exact by construction of the phase */
+            const size_t y = oy + op->input_padding_top - (size_t) ph->tap_ky[t] * op->dilation_height;
+            const size_t x = ox + op->input_padding_left - (size_t) ph->tap_kx[t] * op->dilation_width;
+            const size_t iy = y / sh, ix = x / sw;
+            if (iy * sh == y && iy < input_height && ix * sw == x && ix < input_width) {
+              entry = (int32_t) ((iy * input_width + ix) * input_pixel_stride);
+            }
+          }
+          host_offsets[r * ph->taps + t] = entry;
+        }
+      }
+    }
+    const size_t entries = ph->rows * ph->taps;
+    const int ok =
+        qnnp_upload_table((void**) &ph->d_offsets, &ph->offsets_capacity, entries, sizeof(int32_t) * entries, host_offsets,
+            sizeof(int32_t) * entries) &&
+        qnnp_upload_table((void**) &ph->d_out_rows, &ph->rows_capacity, ph->rows, sizeof(int32_t) * ph->rows, host_rows,
+            sizeof(int32_t) * ph->rows);
+    free(host_offsets);
+    free(host_rows);
+    if (!ok) {
+      qnnp_log_error("failed to place a phase table on the device");
+      return qnnp_status_out_of_memory;
+    }
+  }
+  op->offsets_in_h = input_height;
+  op->offsets_in_w = input_width;
+  op->offsets_in_stride = input_pixel_stride;
   return qnnp_status_success;
 }
 
@@ -493,70 +577,14 @@ static enum qnnp_status qnnp_setup_deconvolution2d_nhwc_q8_impl(
   op->variant = 1;   /* the offset-table kernel: the table, not the geometry, defines this operator */
   op->deconv_stream = qnnp_state.opt_gemm_kernel == 13 ? 2 : (qnnp_state.opt_gemm_kernel == 1 ? 1 : 0);
   if (op->deconv_phases != 0) {
-    if (op->offsets_in_h == input_height && op->offsets_in_w == input_width &&
-        op->offsets_in_stride == input_pixel_stride) {
-      return upload_phase_table(op);  /* offset tables are pointer- and batch-invariant; the row counts are not */
-    }
-    op->offsets_in_h = 0;
-    const size_t sh = op->stride_height, sw = op->stride_width;
-    for (uint32_t i = 0; i < op->deconv_phases; i++) {
-      struct qnnp_deconv_phase* ph = &op->phase[i];
-      const size_t py = i / sw, px = i % sw;
-      /* first output row / column of the phase: (o + pad) % stride == phase */
-      const size_t oy0 = (py + sh - op->input_padding_top % sh) % sh;
-      const size_t ox0 = (px + sw - op->input_padding_left % sw) % sw;
-      const size_t rows_y = oy0 < op->output_height ? (op->output_height - oy0 + sh - 1) / sh : 0;
-      const size_t rows_x = ox0 < op->output_width ? (op->output_width - ox0 + sw - 1) / sw : 0;
-      ph->rows = rows_y * rows_x;
-      if (ph->rows == 0) continue;
-      int32_t* host_offsets = (int32_t*) malloc(sizeof(int32_t) * ph->rows * ph->taps);
-      int32_t* host_rows = (int32_t*) malloc(sizeof(int32_t) * ph->rows);
-      if (host_offsets == NULL || host_rows == NULL) {
-        free(host_offsets);
-        free(host_rows);
-        qnnp_log_error("out of host memory: %zu bytes for a phase table", sizeof(int32_t) * ph->rows * (ph->taps + 1));
-        return qnnp_status_out_of_memory;
-      }
-      size_t r = 0;
-      for (size_t oy = oy0; oy < op->output_height; oy += sh) {
-        for (size_t ox = ox0; ox < op->output_width; ox += sw, r++) {
-          host_rows[r] = (int32_t) (oy * op->output_width + ox);
-          for (uint32_t t = 0; t < ph->taps; t++) {
-            int32_t entry = QNNP_OFFSET_PADDING;
-            if (ph->tap_ky[t] != 255) {
-              /* reference src/indirection.c:171-177; the divisions are exact by construction of the phase */
-              const size_t y = oy + op->input_padding_top - (size_t) ph->tap_ky[t] * op->dilation_height;
-              const size_t x = ox + op->input_padding_left - (size_t) ph->tap_kx[t] * op->dilation_width;
-              const size_t iy = y / sh, ix = x / sw;
-              if (iy * sh == y && iy < input_height && ix * sw == x && ix < input_width) {
-                entry = (int32_t) ((iy * input_width + ix) * input_pixel_stride);
-              }
-            }
-            host_offsets[r * ph->taps + t] = entry;
-          }
-        }
-      }
-      if (ph->rows_capacity < ph->rows) {
-        qnnp_hip_free(ph->d_offsets);
-        qnnp_hip_free(ph->d_out_rows);
-        ph->rows_capacity = 0;
-        ph->d_offsets = (int32_t*) qnnp_hip_alloc(sizeof(int32_t) * ph->rows * ph->taps);
-        ph->d_out_rows = (int32_t*) qnnp_hip_alloc(sizeof(int32_t) * ph->rows);
-        if (ph->d_offsets != NULL && ph->d_out_rows != NULL) ph->rows_capacity = ph->rows;
-      }
-      const int ok = ph->rows_capacity >= ph->rows &&
-          qnnp_hip_h2d(ph->d_offsets, host_offsets, sizeof(int32_t) * ph->rows * ph->taps, 0) == QNNP_HIP_OK &&
-          qnnp_hip_h2d(ph->d_out_rows, host_rows, sizeof(int32_t) * ph->rows, 0) == QNNP_HIP_OK;
-      free(host_offsets);
-      free(host_rows);
-      if (!ok) {
-        qnnp_log_error("failed to place a phase table on the device");
-        return qnnp_status_out_of_memory;
+    /* offset tables are pointer- and batch-invariant; the row counts are not */
+    if (op->offsets_in_h != input_height || op->offsets_in_w != input_width ||
+        op->offsets_in_stride != input_pixel_stride) {
+      const enum qnnp_status status = build_phase_tables(op);
+      if (status != qnnp_status_success) {
+        return status;
       }
     }
-    op->offsets_in_h = input_height;
-    op->offsets_in_w = input_width;
-    op->offsets_in_stride = input_pixel_stride;
     return upload_phase_table(op);
   }
   const size_t kernel_size = (size_t) op->kernel_height * op->kernel_width;
@@ -567,28 +595,22 @@ static enum qnnp_status qnnp_setup_deconvolution2d_nhwc_q8_impl(
   if (same_geometry) {
     return qnnp_status_success;  /* the table is pointer- and batch-invariant */
   }
-  int32_t* host_table = (int32_t*) malloc(sizeof(int32_t) * entries);
+  const size_t bytes = sizeof(int32_t) * entries;
+  int32_t* host_table = (int32_t*) malloc(bytes);
   if (host_table == NULL) {
-    qnnp_log_error("out of host memory: %zu bytes for the offset table", sizeof(int32_t) * entries);
+    qnnp_log_error("out of host memory: %zu bytes for the offset table", bytes);
     return qnnp_status_out_of_memory;
   }
-  if (op->offsets_capacity < entries) {
-    qnnp_hip_free(op->d_offsets);
-    op->offsets_capacity = 0;
-    op->d_offsets = (int32_t*) qnnp_hip_alloc(sizeof(int32_t) * entries);
-    if (op->d_offsets == NULL) {
-      free(host_table);
-      qnnp_log_error("out of host memory: %zu bytes for the device offset table", sizeof(int32_t) * entries);
-      return qnnp_status_out_of_memory;
-    }
-    op->offsets_capacity = entries;
-  }
   qnnp_indirection_init_deconv2d_offsets(op, host_table);
-  const int rc = qnnp_hip_h2d(op->d_offsets, host_table, sizeof(int32_t) * entries, 0);
+  const int uploaded = qnnp_upload_table((void**) &op->d_offsets, &op->offsets_capacity, entries, bytes, host_table, bytes);
   free(host_table);
-  if (rc != QNNP_HIP_OK) {
-    op->offsets_in_h = 0;
-    qnnp_log_error("failed to upload the offset table");
+  if (!uploaded) {
+    if (op->d_offsets == NULL) {
+      qnnp_log_error("out of host memory: %zu bytes for the device offset table", bytes);
+    } else {
+      op->offsets_in_h = 0;
+      qnnp_log_error("failed to upload the offset table");
+    }
     return qnnp_status_out_of_memory;
   }
   op->offsets_in_h = input_height;
@@ -633,17 +655,12 @@ enum qnnp_status qnnp_create_deconvolution2d_nhwc_q8(
   if (!qnnp_state.initialized) {
     return qnnp_create_deconvolution2d_nhwc_q8_impl(input_padding_top, input_padding_right, input_padding_bottom, input_padding_left, adjustment_height, adjustment_width, kernel_height, kernel_width, stride_height, stride_width, dilation_height, dilation_width, groups, group_input_channels, group_output_channels, input_zero_point, input_scale, kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max, flags, deconvolution_out);   /* logs and answers qnnp_status_uninitialized */
   }
-  const int token = qnnp_hip_enter(qnnp_hip_device());
-  if (token < 0) {
-    return qnnp_status_unsupported_hardware;
+  int token;
+  enum qnnp_status status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
+  if (status != qnnp_status_success) {
+    return status;
   }
-  if (qnnp_hip_graph_capturing()) {
-    /* inside qnnp_gfx950_graph_begin ... graph_end on this device only operator launches are recordable: an upload
-     * would become a graph node reading host memory that is freed right after this call */
-    qnnp_hip_leave(token);
-    return qnnp_status_invalid_parameter;
-  }
-  const enum qnnp_status status = qnnp_create_deconvolution2d_nhwc_q8_impl(input_padding_top, input_padding_right, input_padding_bottom, input_padding_left, adjustment_height, adjustment_width, kernel_height, kernel_width, stride_height, stride_width, dilation_height, dilation_width, groups, group_input_channels, group_output_channels, input_zero_point, input_scale, kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max, flags, deconvolution_out);
+  status = qnnp_create_deconvolution2d_nhwc_q8_impl(input_padding_top, input_padding_right, input_padding_bottom, input_padding_left, adjustment_height, adjustment_width, kernel_height, kernel_width, stride_height, stride_width, dilation_height, dilation_width, groups, group_input_channels, group_output_channels, input_zero_point, input_scale, kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max, flags, deconvolution_out);
   qnnp_hip_leave(token);
   return status;
 }
@@ -662,17 +679,12 @@ enum qnnp_status qnnp_setup_deconvolution2d_nhwc_q8(
   if (!qnnp_state.initialized || op == NULL) {
     return qnnp_setup_deconvolution2d_nhwc_q8_impl(op, batch_size, input_height, input_width, input, input_pixel_stride, output, output_pixel_stride, threadpool);   /* answers qnnp_status_uninitialized / invalid_parameter */
   }
-  const int token = qnnp_hip_enter(op->device);
-  if (token < 0) {
-    return qnnp_status_invalid_parameter;   /* not a live operator of this library instance */
+  int token;
+  enum qnnp_status status = qnnp_enter_for_update(op->device, qnnp_status_invalid_parameter, &token);
+  if (status != qnnp_status_success) {
+    return status;
   }
-  if (qnnp_hip_graph_capturing()) {
-    /* inside qnnp_gfx950_graph_begin ... graph_end on this device only operator launches are recordable: an upload
-     * would become a graph node reading host memory that is freed right after this call */
-    qnnp_hip_leave(token);
-    return qnnp_status_invalid_parameter;
-  }
-  const enum qnnp_status status = qnnp_setup_deconvolution2d_nhwc_q8_impl(op, batch_size, input_height, input_width, input, input_pixel_stride, output, output_pixel_stride, threadpool);
+  status = qnnp_setup_deconvolution2d_nhwc_q8_impl(op, batch_size, input_height, input_width, input, input_pixel_stride, output, output_pixel_stride, threadpool);
   /* the implementation cleared setup_valid where it began to change the operator: a failed setup leaves it
    * unrunnable instead of half updated (run answers invalid_parameter) */
   if (status == qnnp_status_success) {

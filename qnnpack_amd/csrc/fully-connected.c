@@ -117,10 +117,9 @@ static enum qnnp_status qnnp_create_fully_connected_nc_q8_impl(
   op->n_pad = n_pad;
   op->k_pad = k_pad;
   op->kc_slot = (uint32_t) input_channels;
-  op->d_weights = qnnp_hip_alloc(w_bytes);
+  op->d_weights = qnnp_upload(host_weights, w_bytes);
   op->d_bias = qnnp_upload_bias_pair(host_bias, n_pad);      /* bias-pair.h */
-  if (op->d_weights == NULL || op->d_bias == NULL ||
-      qnnp_hip_h2d(op->d_weights, host_weights, w_bytes, 0) != QNNP_HIP_OK) {
+  if (op->d_weights == NULL || op->d_bias == NULL) {
     qnnp_log_error("device allocation or upload failed: %zu bytes of packed weights on the device", w_bytes + 2 * b_bytes);
     goto error;
   }
@@ -134,10 +133,9 @@ static enum qnnp_status qnnp_create_fully_connected_nc_q8_impl(
              ((n_pad % 256 == 0 && input_channels >= 512) || (input_channels % 64 == 0 && output_channels % 16 == 0))) {
     qnnp_pack_igemm_w_centred127((uint32_t) output_channels, (uint32_t) input_channels, (uint32_t) input_channels, n_pad,
         input_zero_point, kernel, bias, host_weights, host_bias);
-    op->d_weights_centred = qnnp_hip_alloc(w_bytes);
+    op->d_weights_centred = qnnp_upload(host_weights, w_bytes);
     op->d_bias_centred = qnnp_upload_bias_pair(host_bias, n_pad);
-    if (op->d_weights_centred == NULL || op->d_bias_centred == NULL ||
-        qnnp_hip_h2d(op->d_weights_centred, host_weights, w_bytes, 0) != QNNP_HIP_OK) {
+    if (op->d_weights_centred == NULL || op->d_bias_centred == NULL) {
       /* the centred image is an optimisation, not a requirement: without it the operator runs on the standard image
        * (the lean kernel with its row term) -- drop what was placed and carry on */
       qnnp_log_warning("no room for %zu bytes of centred weights on the device: the operator keeps the standard image", w_bytes + 2 * b_bytes);
@@ -264,17 +262,12 @@ enum qnnp_status qnnp_create_fully_connected_nc_q8(
   if (!qnnp_state.initialized) {
     return qnnp_create_fully_connected_nc_q8_impl(input_channels, output_channels, input_zero_point, input_scale, kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max, flags, fully_connected_out);   /* logs and answers qnnp_status_uninitialized */
   }
-  const int token = qnnp_hip_enter(qnnp_hip_device());
-  if (token < 0) {
-    return qnnp_status_unsupported_hardware;
+  int token;
+  enum qnnp_status status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
+  if (status != qnnp_status_success) {
+    return status;
   }
-  if (qnnp_hip_graph_capturing()) {
-    /* inside qnnp_gfx950_graph_begin ... graph_end on this device only operator launches are recordable: an upload
-     * would become a graph node reading host memory that is freed right after this call */
-    qnnp_hip_leave(token);
-    return qnnp_status_invalid_parameter;
-  }
-  const enum qnnp_status status = qnnp_create_fully_connected_nc_q8_impl(input_channels, output_channels, input_zero_point, input_scale, kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max, flags, fully_connected_out);
+  status = qnnp_create_fully_connected_nc_q8_impl(input_channels, output_channels, input_zero_point, input_scale, kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max, flags, fully_connected_out);
   qnnp_hip_leave(token);
   return status;
 }
@@ -290,17 +283,12 @@ enum qnnp_status qnnp_setup_fully_connected_nc_q8(
   if (!qnnp_state.initialized || op == NULL) {
     return qnnp_setup_fully_connected_nc_q8_impl(op, batch_size, input, input_stride, output, output_stride);   /* answers qnnp_status_uninitialized / invalid_parameter */
   }
-  const int token = qnnp_hip_enter(op->device);
-  if (token < 0) {
-    return qnnp_status_invalid_parameter;   /* not a live operator of this library instance */
+  int token;
+  enum qnnp_status status = qnnp_enter_for_update(op->device, qnnp_status_invalid_parameter, &token);
+  if (status != qnnp_status_success) {
+    return status;
   }
-  if (qnnp_hip_graph_capturing()) {
-    /* inside qnnp_gfx950_graph_begin ... graph_end on this device only operator launches are recordable: an upload
-     * would become a graph node reading host memory that is freed right after this call */
-    qnnp_hip_leave(token);
-    return qnnp_status_invalid_parameter;
-  }
-  const enum qnnp_status status = qnnp_setup_fully_connected_nc_q8_impl(op, batch_size, input, input_stride, output, output_stride);
+  status = qnnp_setup_fully_connected_nc_q8_impl(op, batch_size, input, input_stride, output, output_stride);
   /* the implementation cleared setup_valid where it began to change the operator: a failed setup leaves it
    * unrunnable instead of half updated (run answers invalid_parameter) */
   if (status == qnnp_status_success) {

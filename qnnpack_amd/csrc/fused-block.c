@@ -23,6 +23,7 @@
 #include "operator.h"
 #include "pack.h"
 #include "state.h"
+#include "upload.h"
 
 static int is_pointwise(const struct qnnp_operator* op)
 {
@@ -156,11 +157,7 @@ static void build_strip_images(struct qnnp_operator* op)
   ok = ok && strip_depthwise(dw, ch, hidden_pad, (int8_t*) (host + op->strip_w2), (int32_t*) (host + op->strip_b2));
   ok = ok && strip_pointwise(pr, cout, ch, (int8_t*) (host + op->strip_w3), (int32_t*) (host + op->strip_b3));
   if (ok) {
-    op->d_strip = qnnp_hip_alloc(total);
-    if (op->d_strip != NULL && qnnp_hip_h2d(op->d_strip, host, total, 0) != QNNP_HIP_OK) {
-      qnnp_hip_free(op->d_strip);
-      op->d_strip = NULL;
-    }
+    op->d_strip = qnnp_upload(host, total);
   }
   free(host);
   if (op->d_strip != NULL) {
@@ -365,17 +362,14 @@ enum qnnp_status qnnp_gfx950_create_fused_block(
   /* The block borrows its members' device images and adds its own (build_strip_images: alloc + upload), so everything
    * device-side must happen on THEIR device -- not on whichever one the calling thread has selected. Members on
    * different devices are refused by the implementation; a NULL depthwise as well. */
-  const int token = qnnp_hip_enter(depthwise != NULL ? depthwise->device : qnnp_hip_device());
-  if (token < 0) {
-    return depthwise != NULL ? qnnp_status_invalid_parameter : qnnp_status_unsupported_hardware;
+  int token;
+  enum qnnp_status status = depthwise != NULL ?
+      qnnp_enter_for_update(depthwise->device, qnnp_status_invalid_parameter, &token) :
+      qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
+  if (status != qnnp_status_success) {
+    return status;
   }
-  if (qnnp_hip_graph_capturing()) {
-    /* inside qnnp_gfx950_graph_begin ... graph_end on this device only operator launches are recordable: an upload
-     * would become a graph node reading host memory that is freed right after this call */
-    qnnp_hip_leave(token);
-    return qnnp_status_invalid_parameter;
-  }
-  const enum qnnp_status status = qnnp_gfx950_create_fused_block_impl(expand, depthwise, project, residual_add, fused_out);
+  status = qnnp_gfx950_create_fused_block_impl(expand, depthwise, project, residual_add, fused_out);
   qnnp_hip_leave(token);
   return status;
 }
@@ -387,17 +381,12 @@ enum qnnp_status qnnp_gfx950_setup_fused_block(
   if (!qnnp_state.initialized || op == NULL) {
     return qnnp_gfx950_setup_fused_block_impl(op, batch_size, input_height, input_width, input, input_stride, output, output_stride);   /* answers qnnp_status_uninitialized / invalid_parameter */
   }
-  const int token = qnnp_hip_enter(op->device);
-  if (token < 0) {
-    return qnnp_status_invalid_parameter;   /* not a live operator of this library instance */
+  int token;
+  enum qnnp_status status = qnnp_enter_for_update(op->device, qnnp_status_invalid_parameter, &token);
+  if (status != qnnp_status_success) {
+    return status;
   }
-  if (qnnp_hip_graph_capturing()) {
-    /* inside qnnp_gfx950_graph_begin ... graph_end on this device only operator launches are recordable: an upload
-     * would become a graph node reading host memory that is freed right after this call */
-    qnnp_hip_leave(token);
-    return qnnp_status_invalid_parameter;
-  }
-  const enum qnnp_status status = qnnp_gfx950_setup_fused_block_impl(op, batch_size, input_height, input_width, input, input_stride, output, output_stride);
+  status = qnnp_gfx950_setup_fused_block_impl(op, batch_size, input_height, input_width, input, input_stride, output, output_stride);
   /* the implementation cleared setup_valid where it began to change the operator: a failed setup leaves it
    * unrunnable instead of half updated (run answers invalid_parameter) */
   if (status == qnnp_status_success) {

@@ -40,6 +40,7 @@ struct qnnp_deconv_phase {
   int32_t* d_offsets;       /* [rows][taps] */
   int32_t* d_out_rows;      /* [rows] output pixel inside the image */
   size_t rows;              /* output pixels of this phase per image (0: phase absent for this geometry) */
+  size_t offsets_capacity;  /* grow-only: d_offsets in entries, d_out_rows in rows */
   size_t rows_capacity;
 };
 
@@ -192,6 +193,23 @@ struct qnnp_operator {
  * success; out_of_memory (staging); invalid_parameter (device memory of a GPU other than the operator's).
  * (operator-run.c) */
 enum qnnp_status qnnp_bind_endpoint(const void* ptr, size_t span, int* on_device, void** stage, size_t* capacity);
+
+/* The device guard of the public create / setup entry points: enters `device` (qnnp_hip_leave(*token) undoes it) and
+ * answers success, or `no_device` when that device cannot be entered, or invalid_parameter inside a graph capture on it
+ * (qnnp_gfx950_graph_begin ... graph_end: only operator launches are recordable there -- an upload would become a graph
+ * node reading host memory that is freed right after the call). Nothing is left entered on a refusal. */
+static inline enum qnnp_status qnnp_enter_for_update(int device, enum qnnp_status no_device, int* token)
+{
+  *token = qnnp_hip_enter(device);
+  if (*token < 0) {
+    return no_device;
+  }
+  if (qnnp_hip_graph_capturing()) {
+    qnnp_hip_leave(*token);
+    return qnnp_status_invalid_parameter;
+  }
+  return qnnp_status_success;
+}
 
 /* fused-block.c */
 int qnnp_fused_block_launch(struct qnnp_operator* op, const void* input, void* output);

@@ -62,15 +62,12 @@ enum qnnp_status qnnp_gfx950_attach_residual_add(
   if (residual_stride > UINT32_MAX) {
     return qnnp_status_unsupported_parameter;
   }
-  const int token = qnnp_hip_enter(convolution->device);
-  if (token < 0) {
-    return qnnp_status_invalid_parameter;
+  int token;
+  enum qnnp_status status = qnnp_enter_for_update(convolution->device, qnnp_status_invalid_parameter, &token);
+  if (status != qnnp_status_success) {
+    return status;
   }
-  enum qnnp_status status = qnnp_status_success;
-  if (qnnp_hip_graph_capturing()) {
-    status = qnnp_status_invalid_parameter;           /* only launches are recordable (convolution.c) */
-  } else if (!convolution->input_on_device || !convolution->output_on_device ||
-             qnnp_hip_is_device_pointer(residual) != 1) {
+  if (!convolution->input_on_device || !convolution->output_on_device || qnnp_hip_is_device_pointer(residual) != 1) {
     /* the fused form exists for device-resident pipelines; host endpoints keep the two-operator form */
     qnnp_log_error("failed to attach residual add: input, output and residual must be memory of the operator's device");
     status = qnnp_status_unsupported_parameter;

@@ -52,18 +52,38 @@ int qnnp_hip_get_async(void) { return g_async; }
 int qnnp_hip_stream_sync(void) { return QNNP_HIP_OK; }
 const uint8_t* qnnp_hip_fill_table(void) { return NULL; }
 
+/* ---- test controls (host_asan_test.c, host_asan_pool_test.c): failure injection, a pretend graph capture and a count
+ * of live "device" allocations. qnnp_stub_fail_nth(n): the n-th qnnp_hip_alloc / qnnp_hip_h2d from now on (0 = the next
+ * one) fails, once; n < 0 disarms. qnnp_stub_fail_pending(): 1 while that failure has not happened yet. */
+static long g_fail_in = -1;
+static int g_capturing = 0;
+static size_t g_live = 0;
+void qnnp_stub_fail_nth(long n) { g_fail_in = n; }
+int qnnp_stub_fail_pending(void) { return g_fail_in >= 0; }
+void qnnp_stub_set_capturing(int on) { g_capturing = on != 0; }
+size_t qnnp_stub_live_allocs(void) { return g_live; }
+static int injected_failure(void) { return g_fail_in >= 0 && g_fail_in-- == 0; }
+
 /* every "device" allocation carries a tag in front so that is_device_pointer can tell it from caller memory */
 #define STUB_MAGIC UINT64_C(0x51AB51AB51AB51AB)
 void* qnnp_hip_alloc(size_t bytes)
 {
+  if (injected_failure()) return NULL;
   uint64_t* p = (uint64_t*) malloc(bytes + 16);
   if (p == NULL) return NULL;
   p[0] = STUB_MAGIC;
   p[1] = bytes;
+  g_live++;
   return p + 2;
 }
-void qnnp_hip_free(void* p) { if (p != NULL) free((uint64_t*) p - 2); }
-int qnnp_hip_h2d(void* dst, const void* src, size_t bytes, int async) { (void) async; memcpy(dst, src, bytes); return QNNP_HIP_OK; }
+void qnnp_hip_free(void* p) { if (p != NULL) { free((uint64_t*) p - 2); g_live--; } }
+int qnnp_hip_h2d(void* dst, const void* src, size_t bytes, int async)
+{
+  (void) async;
+  if (injected_failure()) return QNNP_HIP_ELAUNCH;
+  memcpy(dst, src, bytes);
+  return QNNP_HIP_OK;
+}
 int qnnp_hip_d2h(void* dst, const void* src, size_t bytes, int async) { (void) async; memcpy(dst, src, bytes); return QNNP_HIP_OK; }
 int qnnp_hip_memset(void* dst, int value, size_t bytes) { memset(dst, value, bytes); return QNNP_HIP_OK; }
 int qnnp_hip_is_device_pointer(const void* p) { (void) p; return 0; }   /* the test hands host tensors: staged path */
@@ -73,7 +93,7 @@ int qnnp_hip_timer_start(void* timer) { (void) timer; return QNNP_HIP_OK; }
 int qnnp_hip_timer_stop_ms(void* timer, float* ms) { (void) timer; *ms = 1.0f; return QNNP_HIP_OK; }
 void qnnp_hip_timer_destroy(void* timer) { free(timer); }
 
-int qnnp_hip_graph_capturing(void) { return 0; }
+int qnnp_hip_graph_capturing(void) { return g_capturing; }
 int qnnp_hip_graph_begin(void) { return QNNP_HIP_EINVAL; }   /* no graphs in the stub: timing falls back to the plain loop */
 int qnnp_hip_graph_end(void** graph) { (void) graph; return QNNP_HIP_EINVAL; }
 int qnnp_hip_graph_device(void* graph) { (void) graph; return 0; }

@@ -14,6 +14,10 @@
 #include <qnnpack.h>
 #include <qnnpack_gfx950.h>
 
+/* tests/hip_stub.c test controls */
+void qnnp_stub_set_capturing(int on);
+size_t qnnp_stub_live_allocs(void);
+
 #define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "%s:%d: check failed: %s\n", __FILE__, __LINE__, #cond); exit(1); } } while (0)
 
 static uint8_t* bytes(size_t n)
@@ -141,6 +145,25 @@ int main(void)
     walk(avg, 2, 3, 1, 2, 7, 1);
     walk(avg, 0, 5, 3, 1, 1, 0);
     walk(avg, 4, 3, 1, 1, 16, 3);    /* windows wholly in padding */
+  }
+  /* inside a graph capture (tests/hip_stub.c) create and setup refuse with invalid_parameter and allocate nothing */
+  for (int avg = 0; avg <= 1; avg++) {
+    qnnp_operator_t pool = create(avg, 1, 3, 3, 1, 1, 8), none = NULL;
+    uint8_t* x = bytes(2 * 5 * 5 * 8), * y = bytes(2 * 5 * 5 * 8);
+    const size_t live = qnnp_stub_live_allocs();
+    qnnp_stub_set_capturing(1);
+    CHECK((avg ? qnnp_create_average_pooling2d_nhwc_q8(1, 1, 1, 1, 3, 3, 1, 1, 8, 121, 0.5f, 133, 0.75f, 0, 255, 0, &none)
+               : qnnp_create_max_pooling2d_nhwc_u8(1, 1, 1, 1, 3, 3, 1, 1, 1, 1, 8, 0, 255, 0, &none)) ==
+          qnnp_status_invalid_parameter);
+    CHECK(none == NULL);
+    CHECK(setup(avg, pool, 2, 5, 5, x, 8, y, 8) == qnnp_status_invalid_parameter);
+    CHECK(qnnp_stub_live_allocs() == live);
+    qnnp_stub_set_capturing(0);
+    CHECK(setup(avg, pool, 2, 5, 5, x, 8, y, 8) == qnnp_status_success);
+    CHECK(qnnp_run_operator(pool, NULL) == qnnp_status_success);
+    free(x);
+    free(y);
+    CHECK(qnnp_delete_operator(pool) == qnnp_status_success);
   }
   CHECK(qnnp_deinitialize() == qnnp_status_success);
   printf("host-sanitizers-pool-ok\n");

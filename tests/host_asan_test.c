@@ -6,6 +6,7 @@
  * Any heap overflow, use-after-free, leak or undefined arithmetic in the packers, offset tables, phase splitting,
  * staging logic or error paths aborts the program. Prints "host-sanitizers-ok" on success.
  */
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -13,6 +14,14 @@
 
 #include <qnnpack.h>
 #include <qnnpack_gfx950.h>
+
+#include "operator.h"   /* (qnnpack_amd/csrc: the sweeps below check which device images a create built) */
+
+/* tests/hip_stub.c test controls */
+void qnnp_stub_fail_nth(long n);
+int qnnp_stub_fail_pending(void);
+void qnnp_stub_set_capturing(int on);
+size_t qnnp_stub_live_allocs(void);
 
 static uint32_t rng_state = 0x1234567u;
 static uint8_t rnd8(void) { rng_state = rng_state * 1664525u + 1013904223u; return (uint8_t) (rng_state >> 24); }
@@ -93,6 +102,223 @@ static void deconv_case(uint32_t pad, uint32_t adj, uint32_t k, uint32_t stride,
     free(out);
   }
   CHECK(qnnp_delete_operator(op) == qnnp_status_success);
+}
+
+/* ---- failure injection: every device allocation and upload a create or setup makes may fail ------------------------
+ * For n = 0, 1, 2, ... the n-th qnnp_hip_alloc / qnnp_hip_h2d fails (tests/hip_stub.c) until a create no longer reaches
+ * it. A create must then answer success or out_of_memory; out_of_memory leaves the handle alone and nothing allocated
+ * (ASan reports leaked host memory at exit); a successful create -- optional images may be missing -- must set up, run
+ * and delete. */
+enum sweep_kind { SWEEP_CONV, SWEEP_DECONV, SWEEP_FC, SWEEP_FUSED };
+struct sweep_case {
+  enum sweep_kind kind;
+  uint32_t pad, kh, kw, stride, dil, groups;
+  size_t gic, goc;
+  uint8_t kzp;
+  size_t h, w;        /* input extent of the setup (fully connected: h = batch) */
+  size_t image;       /* offsetof(struct qnnp_operator, <device image>) the case is there to reach, 0: none */
+};
+
+static qnnp_operator_t const UNTOUCHED = (qnnp_operator_t) (uintptr_t) 0x5A5A5A5A;
+
+static enum qnnp_status sweep_create(const struct sweep_case* c, const uint8_t* kernel, const int32_t* bias,
+                                     qnnp_operator_t* op, qnnp_operator_t members[4])
+{
+  switch (c->kind) {
+    case SWEEP_CONV:
+      return qnnp_create_convolution2d_nhwc_q8(c->pad, c->pad, c->pad, c->pad, c->kh, c->kw, c->stride, c->stride, c->dil,
+          c->dil, c->groups, c->gic, c->goc, 121, 0.5f, c->kzp, 0.5f, kernel, bias, 130, 0.75f, 0, 255, 0, op);
+    case SWEEP_DECONV:
+      return qnnp_create_deconvolution2d_nhwc_q8(c->pad, c->pad, c->pad, c->pad, 0, 0, c->kh, c->kw, c->stride, c->stride,
+          1, 1, c->groups, c->gic, c->goc, 121, 0.5f, c->kzp, 0.5f, kernel, bias, 130, 0.75f, 0, 255, 0, op);
+    case SWEEP_FC:
+      return qnnp_create_fully_connected_nc_q8(c->gic, c->goc, 121, 0.5f, c->kzp, 0.5f, kernel, bias, 130, 0.75f, 0, 255,
+          0, op);
+    case SWEEP_FUSED:
+    {
+      /* 16 -> 96 expand, 3x3 depthwise, 96 -> 16 project, + input: the members' creates are swept as well */
+      enum qnnp_status s;
+      s = qnnp_create_convolution2d_nhwc_q8(0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 16, 96, 127, 0.5f, c->kzp, 0.5f, kernel, bias,
+          127, 0.5f, 0, 255, 0, &members[0]);
+      if (s == qnnp_status_success) {
+        s = qnnp_create_convolution2d_nhwc_q8(1, 1, 1, 1, 3, 3, 1, 1, 1, 1, 96, 1, 1, 127, 0.5f, c->kzp, 0.5f, kernel, bias,
+            127, 0.5f, 0, 255, 0, &members[1]);
+      }
+      if (s == qnnp_status_success) {
+        s = qnnp_create_convolution2d_nhwc_q8(0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 96, 16, 127, 0.5f, c->kzp, 0.5f, kernel, bias,
+            127, 0.5f, 0, 255, 0, &members[2]);
+      }
+      if (s == qnnp_status_success) {
+        s = qnnp_create_add_nc_q8(16, 127, 0.5f, 127, 0.5f, 127, 0.75f, 0, 255, 0, &members[3]);
+      }
+      if (s == qnnp_status_success) {
+        s = qnnp_gfx950_create_fused_block(members[0], members[1], members[2], members[3], op);
+      }
+      return s;
+    }
+  }
+  return qnnp_status_invalid_parameter;
+}
+
+static size_t sweep_out_dim(const struct sweep_case* c, size_t in)
+{
+  if (c->kind == SWEEP_DECONV) return c->stride * (in - 1) + c->kh - 2 * c->pad;
+  return out_dim(in, 2 * c->pad, c->kh, c->dil, c->stride);
+}
+
+static enum qnnp_status sweep_setup(const struct sweep_case* c, qnnp_operator_t op, size_t h, size_t w, const uint8_t* in,
+                                    uint8_t* out)
+{
+  const size_t cin = c->groups * c->gic, cout = c->groups * c->goc;
+  switch (c->kind) {
+    case SWEEP_CONV: return qnnp_setup_convolution2d_nhwc_q8(op, 2, h, w, in, cin, out, cout, NULL);
+    case SWEEP_DECONV: return qnnp_setup_deconvolution2d_nhwc_q8(op, 2, h, w, in, cin, out, cout, NULL);
+    case SWEEP_FC: return qnnp_setup_fully_connected_nc_q8(op, h, in, cin, out, cout);
+    case SWEEP_FUSED: return qnnp_gfx950_setup_fused_block(op, 2, h, w, in, 16, out, 16);
+  }
+  return qnnp_status_invalid_parameter;
+}
+
+static size_t sweep_in_bytes(const struct sweep_case* c, size_t h, size_t w)
+{
+  if (c->kind == SWEEP_FC) return h * c->gic;
+  return 2 * h * w * (c->kind == SWEEP_FUSED ? 16 : c->groups * c->gic);
+}
+
+static size_t sweep_out_bytes(const struct sweep_case* c, size_t h, size_t w)
+{
+  if (c->kind == SWEEP_FC) return h * c->goc;
+  if (c->kind == SWEEP_FUSED) return 2 * h * w * 16;
+  return 2 * sweep_out_dim(c, h) * sweep_out_dim(c, w) * c->groups * c->goc;
+}
+
+static void delete_all(qnnp_operator_t op, qnnp_operator_t members[4])
+{
+  if (op != UNTOUCHED) CHECK(qnnp_delete_operator(op) == qnnp_status_success);
+  for (int i = 0; i < 4; i++) {
+    if (members[i] != NULL) CHECK(qnnp_delete_operator(members[i]) == qnnp_status_success);
+    members[i] = NULL;
+  }
+}
+
+/* set up at (h, w) with the n-th device call failing (n < 0: none; *reached: that call happened); a failed setup must
+ * leave the operator unrunnable. Returns 1 for out_of_memory. */
+static int setup_and_run(const struct sweep_case* c, qnnp_operator_t op, size_t h, size_t w, long n, int* reached)
+{
+  uint8_t* in = random_bytes(sweep_in_bytes(c, h, w));
+  uint8_t* out = random_bytes(sweep_out_bytes(c, h, w));
+  qnnp_stub_fail_nth(n);
+  const enum qnnp_status s = sweep_setup(c, op, h, w, in, out);
+  const int failed = !qnnp_stub_fail_pending() && n >= 0;
+  qnnp_stub_fail_nth(-1);
+  if (reached != NULL) *reached = failed;
+  if (s == qnnp_status_success) {
+    CHECK(qnnp_run_operator(op, NULL) == qnnp_status_success);
+  } else {
+    CHECK(s == qnnp_status_out_of_memory && failed);
+    CHECK(qnnp_run_operator(op, NULL) == qnnp_status_invalid_parameter);
+  }
+  free(in);
+  free(out);
+  return s == qnnp_status_out_of_memory;
+}
+
+static void sweep(const struct sweep_case* c)
+{
+  const size_t kernel_bytes = c->kind == SWEEP_FUSED ? 96 * 16 : c->kind == SWEEP_FC ? c->gic * c->goc :
+      c->groups * c->gic * c->kh * c->kw * c->goc;
+  uint8_t* kernel = random_bytes(kernel_bytes);
+  int32_t* bias = random_bias(c->kind == SWEEP_FUSED ? 96 : c->groups * c->goc);
+  if (c->kind == SWEEP_CONV && c->gic == 1 && c->goc == 1) {
+    for (size_t i = 0; i < kernel_bytes; i++) kernel[i] = (uint8_t) (c->kzp - 100 + kernel[i] % 200);   /* w - kzp fits int8 */
+  }
+  int create_ooms = 0, setup_ooms = 0;
+  for (long n = 0; ; n++) {
+    const size_t live = qnnp_stub_live_allocs();
+    qnnp_operator_t op = UNTOUCHED, members[4] = {NULL, NULL, NULL, NULL};
+    qnnp_stub_fail_nth(n);
+    const enum qnnp_status s = sweep_create(c, kernel, bias, &op, members);
+    const int reached = !qnnp_stub_fail_pending();
+    qnnp_stub_fail_nth(-1);
+    if (s == qnnp_status_out_of_memory) {
+      CHECK(op == UNTOUCHED);
+      delete_all(op, members);
+      CHECK(qnnp_stub_live_allocs() == live);
+      create_ooms++;
+    } else {
+      CHECK(s == qnnp_status_success && op != UNTOUCHED);
+      if (!reached && c->image != 0) {
+        CHECK(*(void**) ((char*) op + c->image) != NULL);   /* the case reaches the image it is there for */
+      }
+      CHECK(setup_and_run(c, op, c->h, c->w, -1, NULL) == 0);
+      delete_all(op, members);
+      CHECK(qnnp_stub_live_allocs() == live);
+    }
+    if (!reached) break;
+  }
+  CHECK(create_ooms > 0);
+
+  /* setup: small geometry first, then a larger one (the device tables and staging grow) with the n-th call failing,
+   * then that geometry again without failures */
+  for (long n = 0; ; n++) {
+    const size_t live = qnnp_stub_live_allocs();
+    qnnp_operator_t op = UNTOUCHED, members[4] = {NULL, NULL, NULL, NULL};
+    CHECK(sweep_create(c, kernel, bias, &op, members) == qnnp_status_success);
+    CHECK(setup_and_run(c, op, c->h, c->w, -1, NULL) == 0);
+    const size_t h2 = c->h + 5, w2 = c->w + 3;
+    int reached = 0;
+    setup_ooms += setup_and_run(c, op, h2, w2, n, &reached);
+    CHECK(setup_and_run(c, op, h2, w2, -1, NULL) == 0);
+    delete_all(op, members);
+    CHECK(qnnp_stub_live_allocs() == live);
+    if (!reached) break;
+  }
+  CHECK(setup_ooms > 0);
+  free(kernel);
+  free(bias);
+}
+
+/* Inside a graph capture every create and setup refuses with invalid_parameter, writes no handle and allocates nothing. */
+static void capture_refusals(void)
+{
+  uint8_t* k = random_bytes(96 * 16);
+  int32_t* b = random_bias(96);
+  uint8_t* x = random_bytes(2 * 8 * 8 * 96);
+  uint8_t* y = random_bytes(2 * 8 * 8 * 96);
+  qnnp_operator_t conv = NULL, dw = NULL, project = NULL, deconv = NULL, fc = NULL, add = NULL, gap = NULL, fused = NULL;
+  CHECK(qnnp_create_convolution2d_nhwc_q8(0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 16, 96, 127, 0.5f, 127, 0.5f, k, b, 127, 0.5f, 0, 255, 0, &conv) == qnnp_status_success);
+  CHECK(qnnp_create_convolution2d_nhwc_q8(1, 1, 1, 1, 3, 3, 1, 1, 1, 1, 96, 1, 1, 127, 0.5f, 127, 0.5f, k, b, 127, 0.5f, 0, 255, 0, &dw) == qnnp_status_success);
+  CHECK(qnnp_create_convolution2d_nhwc_q8(0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 96, 16, 127, 0.5f, 127, 0.5f, k, b, 127, 0.5f, 0, 255, 0, &project) == qnnp_status_success);
+  CHECK(qnnp_create_deconvolution2d_nhwc_q8(0, 0, 0, 0, 0, 0, 2, 2, 2, 2, 1, 1, 1, 16, 8, 127, 0.5f, 127, 0.5f, k, b, 127, 0.5f, 0, 255, 0, &deconv) == qnnp_status_success);
+  CHECK(qnnp_create_fully_connected_nc_q8(16, 16, 127, 0.5f, 127, 0.5f, k, b, 127, 0.5f, 0, 255, 0, &fc) == qnnp_status_success);
+  CHECK(qnnp_create_add_nc_q8(96, 127, 0.5f, 127, 0.5f, 127, 0.75f, 0, 255, 0, &add) == qnnp_status_success);
+  CHECK(qnnp_create_global_average_pooling_nwc_q8(16, 127, 0.5f, 127, 0.75f, 0, 255, 0, &gap) == qnnp_status_success);
+  CHECK(qnnp_gfx950_create_fused_block(conv, dw, project, NULL, &fused) == qnnp_status_success);
+  CHECK(qnnp_setup_convolution2d_nhwc_q8(dw, 2, 8, 8, x, 96, y, 96, NULL) == qnnp_status_success);
+
+  const size_t live = qnnp_stub_live_allocs();
+  qnnp_operator_t op = UNTOUCHED;
+  qnnp_stub_set_capturing(1);
+  CHECK(qnnp_create_convolution2d_nhwc_q8(1, 1, 1, 1, 3, 3, 1, 1, 1, 1, 1, 16, 16, 127, 0.5f, 127, 0.5f, k, b, 127, 0.5f, 0, 255, 0, &op) == qnnp_status_invalid_parameter);
+  CHECK(qnnp_create_deconvolution2d_nhwc_q8(0, 0, 0, 0, 0, 0, 2, 2, 2, 2, 1, 1, 1, 16, 8, 127, 0.5f, 127, 0.5f, k, b, 127, 0.5f, 0, 255, 0, &op) == qnnp_status_invalid_parameter);
+  CHECK(qnnp_create_fully_connected_nc_q8(16, 16, 127, 0.5f, 127, 0.5f, k, b, 127, 0.5f, 0, 255, 0, &op) == qnnp_status_invalid_parameter);
+  CHECK(qnnp_create_add_nc_q8(96, 127, 0.5f, 127, 0.5f, 127, 0.75f, 0, 255, 0, &op) == qnnp_status_invalid_parameter);
+  CHECK(qnnp_create_global_average_pooling_nwc_q8(16, 127, 0.5f, 127, 0.75f, 0, 255, 0, &op) == qnnp_status_invalid_parameter);
+  CHECK(qnnp_gfx950_create_fused_block(conv, dw, project, NULL, &op) == qnnp_status_invalid_parameter);
+  CHECK(op == UNTOUCHED);
+  CHECK(qnnp_setup_convolution2d_nhwc_q8(conv, 2, 8, 8, x, 16, y, 96, NULL) == qnnp_status_invalid_parameter);
+  CHECK(qnnp_setup_deconvolution2d_nhwc_q8(deconv, 2, 8, 8, x, 16, y, 8, NULL) == qnnp_status_invalid_parameter);
+  CHECK(qnnp_setup_fully_connected_nc_q8(fc, 4, x, 16, y, 16) == qnnp_status_invalid_parameter);
+  CHECK(qnnp_setup_add_nc_q8(add, 4, x, 96, x, 96, y, 96) == qnnp_status_invalid_parameter);
+  CHECK(qnnp_setup_global_average_pooling_nwc_q8(gap, 2, 8, x, 16, y, 16) == qnnp_status_invalid_parameter);
+  CHECK(qnnp_gfx950_setup_fused_block(fused, 2, 8, 8, x, 16, y, 16) == qnnp_status_invalid_parameter);
+  CHECK(qnnp_gfx950_attach_residual_add(dw, add, x, 96) == qnnp_status_invalid_parameter);
+  CHECK(qnnp_stub_live_allocs() == live);
+  qnnp_stub_set_capturing(0);
+
+  qnnp_operator_t ops[] = {conv, dw, project, deconv, fc, add, gap, fused};
+  for (size_t i = 0; i < sizeof(ops) / sizeof(ops[0]); i++) CHECK(qnnp_delete_operator(ops[i]) == qnnp_status_success);
+  free(k); free(b); free(x); free(y);
 }
 
 int main(void)
@@ -187,6 +413,30 @@ int main(void)
     CHECK(qnnp_delete_operator(dw) == qnnp_status_success);
     CHECK(qnnp_delete_operator(project) == qnnp_status_success);
     CHECK(qnnp_delete_operator(add) == qnnp_status_success);
+  }
+
+  /* failure injection over creates and setups that take every device image path */
+  {
+#define IMAGE(field) offsetof(struct qnnp_operator, field)
+    static const struct sweep_case cases[] = {
+      /* kind        pad kh kw s  d  groups gic  goc  kzp  h   w   image */
+      {SWEEP_CONV,   1, 3, 3, 1, 1, 40,    1,   1,   128, 9,  10, IMAGE(d_dw_dot4)},          /* depthwise 3x3, int8-range weights */
+      {SWEEP_CONV,   2, 5, 5, 2, 1, 24,    1,   1,   127, 11, 9,  IMAGE(d_dw_dot4)},          /* depthwise 5x5, int8-range weights */
+      {SWEEP_CONV,   3, 7, 7, 1, 1, 33,    1,   1,   121, 10, 12, IMAGE(d_dwm_x)},            /* depthwise 7x7 */
+      {SWEEP_CONV,   1, 3, 3, 2, 1, 1,     3,   32,  127, 13, 11, IMAGE(d_bias_rows)},        /* 3 channels, 16-byte row slots */
+      {SWEEP_CONV,   3, 7, 7, 2, 1, 1,     3,   64,  127, 15, 14, IMAGE(d_bias_rows)},        /* 3 channels, 32-byte row slots */
+      {SWEEP_CONV,   0, 1, 1, 1, 1, 4,     24,  40,  121, 6,  7,  IMAGE(d_weights_dense)},    /* grouped 1x1, dense image */
+      {SWEEP_CONV,   0, 1, 1, 1, 1, 1,     512, 256, 127, 3,  4,  IMAGE(d_weights_centred)},  /* centred 1x1 */
+      {SWEEP_CONV,   1, 3, 3, 1, 1, 1,     48,  64,  127, 7,  6,  IMAGE(d_weights_centred)},  /* small 3x3 (ws16s), centred */
+      {SWEEP_DECONV, 0, 2, 2, 2, 1, 1,     16,  8,   127, 5,  6,  IMAGE(d_weights)},          /* depth-to-space */
+      {SWEEP_DECONV, 1, 3, 3, 2, 1, 1,     8,   12,  127, 5,  4,  IMAGE(phase[1].d_weights)}, /* phases */
+      {SWEEP_DECONV, 1, 3, 3, 1, 1, 2,     6,   5,   121, 6,  7,  IMAGE(d_weights)},          /* stride 1: one table */
+      {SWEEP_FC,     0, 1, 1, 1, 1, 1,     1024,256, 127, 5,  1,  IMAGE(d_weights_centred)},  /* fully connected, centred */
+      {SWEEP_FUSED,  0, 3, 3, 1, 1, 1,     16,  16,  127, 8,  9,  IMAGE(d_strip)},            /* fused block */
+    };
+#undef IMAGE
+    for (size_t i = 0; i < sizeof(cases) / sizeof(cases[0]); i++) sweep(&cases[i]);
+    capture_refusals();
   }
 
   CHECK(qnnp_deinitialize() == qnnp_status_success);
