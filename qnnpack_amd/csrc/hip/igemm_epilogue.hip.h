@@ -23,12 +23,11 @@
 #include <stdint.h>
 
 #include "add_math.hip.h"
+#include "device_ops.hip.h"
 #include "igemm_params.h"
 #include "requant.hip.h"
 
 namespace qnnp {
-
-typedef int epi_v16i __attribute__((ext_vector_type(16)));
 
 /* PRE_BIASED: what the accumulator was INITIALISED with (the MFMA adds into it), i.e. which adds the epilogue
  * skips: 0 = nothing (add bias and row term here), 1 = bias + row term (`bias` / `rowterm` ignored),
@@ -37,7 +36,7 @@ typedef int epi_v16i __attribute__((ext_vector_type(16)));
  * (operand a; same channel offsets as the output row, 4-byte aligned) before they are stored. */
 template <int SHIFT0, bool FULL_RANGE, bool NO_REQUANT = false, int PRE_BIASED = 0, bool RESIDUAL = false>
 __device__ __forceinline__ void igemm_store_tile(
-    const epi_v16i& acc, const int4 (&bias)[4], int32_t rowterm,
+    const v16i& acc, const int4 (&bias)[4], int32_t rowterm,
     uint8_t* out_row,        /* output + m*stride + g*n */
     uint32_t ncol0,          /* first channel of this 32-channel tile */
     uint32_t khalf,          /* lane >> 5 */
@@ -135,7 +134,7 @@ __device__ __forceinline__ void igemm_store_pk4(
  * that carries 2^31, `addend` = lane_addend(row term of this lane's row). */
 template <int SEQ, bool FULL_RANGE, bool RESIDUAL = false>
 __device__ __forceinline__ void igemm_store_tile_lane(
-    const epi_v16i& acc, uint64_t addend, uint8_t* out_row, uint32_t ncol0, uint32_t khalf, bool row_ok,
+    const v16i& acc, uint64_t addend, uint8_t* out_row, uint32_t ncol0, uint32_t khalf, bool row_ok,
     const IgemmParams& p, const uint8_t* res_row = nullptr, const qnnp_hip_add_params* add = nullptr)
 {
   uint32_t pk[4];
@@ -162,7 +161,7 @@ __device__ __forceinline__ void igemm_store_tile_lane(
  */
 template <int SHIFT0, bool FULL_RANGE, bool NO_REQUANT = false, int PRE_BIASED = 0>
 __device__ __forceinline__ void igemm_stage_tile_rq(
-    const epi_v16i& acc, const int4 (&bias)[4], int32_t rowterm,
+    const v16i& acc, const int4 (&bias)[4], int32_t rowterm,
     uint8_t* lds_row,        /* LDS image + tile_row * pitch */
     uint32_t col0,           /* first channel of this 32-channel tile inside the workgroup tile */
     uint32_t khalf, const RequantDev& rq,
@@ -197,7 +196,7 @@ __device__ __forceinline__ void igemm_stage_tile_rq(
  * that carries 2^31, `addend` = lane_addend(row term of this lane's row). */
 template <int SEQ, bool FULL_RANGE>
 __device__ __forceinline__ void igemm_stage_tile_lane(
-    const epi_v16i& acc, uint64_t addend, uint8_t* lds_row, uint32_t col0, uint32_t khalf, const IgemmParams& p,
+    const v16i& acc, uint64_t addend, uint8_t* lds_row, uint32_t col0, uint32_t khalf, const IgemmParams& p,
     bool write_ok = true)
 {
   uint32_t pk[4];
@@ -216,7 +215,7 @@ __device__ __forceinline__ void igemm_stage_tile_lane(
 
 template <int SHIFT0, bool FULL_RANGE, bool NO_REQUANT = false, int PRE_BIASED = 0>
 __device__ __forceinline__ void igemm_stage_tile(
-    const epi_v16i& acc, const int4 (&bias)[4], int32_t rowterm, uint8_t* lds_row, uint32_t col0,
+    const v16i& acc, const int4 (&bias)[4], int32_t rowterm, uint8_t* lds_row, uint32_t col0,
     uint32_t khalf, const IgemmParams& p, bool write_ok = true)
 {
   igemm_stage_tile_rq<SHIFT0, FULL_RANGE, NO_REQUANT, PRE_BIASED>(acc, bias, rowterm, lds_row, col0, khalf, p.rq, write_ok);

@@ -32,7 +32,20 @@ namespace qnnp {
     if ((p).trace != nullptr && (threadIdx.x & 63u) == 0 && (item) < 4)                          \
       (p).trace[((block) * 4 + (item)) * 8 + (slot)] = __builtin_readcyclecounter();            \
   } while (0)
+/* lane 0 of waves 0 and 4 of every workgroup as items 0 and 1; the _WALL form as items 2 and 3 */
+#define QNNP_TRACE_WAVE04(p, lane, wave, slot)                                                  \
+  do {                                                                                           \
+    if ((p).trace != nullptr && (lane) == 0 && ((wave) & 3u) == 0)                               \
+      (p).trace[(blockIdx.x * 4 + ((wave) >> 2)) * 8 + (slot)] = __builtin_readcyclecounter();   \
+  } while (0)
+#define QNNP_TRACE_WAVE04_WALL(p, lane, wave, slot)                                             \
+  do {                                                                                           \
+    if ((p).trace != nullptr && (lane) == 0 && ((wave) & 3u) == 0)                               \
+      (p).trace[(blockIdx.x * 4 + 2 + ((wave) >> 2)) * 8 + (slot)] = wall_clock64();             \
+  } while (0)
 #else
+#define QNNP_TRACE_WAVE04(p, lane, wave, slot) do { } while (0)
+#define QNNP_TRACE_WAVE04_WALL(p, lane, wave, slot) do { } while (0)
 #define QNNP_TRACE_WAVE(p, block, item, slot) do { } while (0)
 #define QNNP_TRACE(p, block, item, slot) do { } while (0)
 #define QNNP_TRACE_WALL(p, block, item, slot) do { } while (0)

@@ -14,12 +14,13 @@
 
 #include <vector>
 
+#include "device_ops.hip.h"
 #include "qnnp_hip.h"
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
+using qnnp::v4i;
+using qnnp::v16i;
 
 __global__ __launch_bounds__(512) void mfma_probe_kernel(const v4i* in, int* out, int iters)
 {
@@ -102,6 +103,9 @@ extern "C" int qnnp_gfx950_mfma_probe(int random_operands, int iters, float* top
  * 6.3 TB/s; bench.py reports it as roofline.hbm_copy_gbs / extra.*.frac_of_copy_kernel.
  */
 namespace {
+
+using qnnp::v4i;
+using qnnp::v16i;
 
 __global__ __launch_bounds__(256) void copy_probe_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, size_t n16)
 {

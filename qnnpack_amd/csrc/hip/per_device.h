@@ -1,9 +1,12 @@
 /*
- * per_device.h -- "once per device" guard for launch-side set-up (HIP-internal, C++ only).
+ * per_device.h -- launch-side helpers (HIP-internal, C++ only): the "once per device" guard for launch-side set-up,
+ * the dynamic-LDS opt-in built on it, the launch status and the compute-unit count.
  * hipFuncSetAttribute (the > 64 KiB dynamic-LDS opt-in) is a PER-DEVICE property of a kernel: a process that drives
  * several GPUs (runtime.hip) must set it on each of them, and several threads may reach the same launch helper.
  */
 #pragma once
+
+#include <hip/hip_runtime.h>
 
 #include <atomic>
 #include <cstdint>
@@ -32,5 +35,27 @@ struct PerDeviceOnce {
     return Scope{&done, bit};
   }
 };
+
+/* Opt Kernel in to `bytes` of dynamic LDS on the active device, once per (kernel, device). A refusal is cleared from
+ * the error state: the launch that needed the opt-in then fails on its own, and launch_status() reports it. */
+template <auto Kernel>
+void allow_dynamic_lds(int bytes)
+{
+  static PerDeviceOnce once;
+  if (auto scope = once.begin()) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+      (void) hipGetLastError();
+  }
+}
+
+/* the result of the launch just made */
+inline int launch_status() { return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH; }
+
+/* compute units of the active device, 256 when no device context is bound */
+inline uint32_t active_cu_count()
+{
+  const int cus = qnnp_hip_compute_units();
+  return cus > 0 ? static_cast<uint32_t>(cus) : 256u;
+}
 
 }  // namespace qnnp

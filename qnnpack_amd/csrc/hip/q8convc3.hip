@@ -30,15 +30,14 @@
 
 #include <type_traits>
 
+#include "device_ops.hip.h"
 #include "igemm_params.h"
+#include "per_device.h"
 #include "requant.hip.h"
 
 namespace qnnp {
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int kC3Waves = 4;
 constexpr int kC3Threads = kC3Waves * 64;
@@ -55,8 +54,6 @@ struct C3Geom {
   const int8_t* w_rows16;     // MFMA fragments of the [ky][16] K layout: [n_pad / 32][2][64 lanes][16 bytes]
   uint32_t abl;               // measurement builds only (QNNP_C3R_ABL): 1 = 16-byte aligned loads, 2 = no stores, 4 = no loads
 };
-
-__device__ __forceinline__ uint32_t div_magic(uint32_t n, uint32_t inv) { return inv != 0u ? __umulhi(n, inv) : n; }
 
 // bytes [lo, hi) of a dword (lo, hi relative to the dword's first byte, any integers): 0xFF in each such byte
 __device__ __forceinline__ uint32_t byte_range_mask(int32_t lo, int32_t hi)
@@ -160,10 +157,8 @@ void q8_conv_c3rows_kernel(const IgemmParams p, const C3Geom cg)
   }
 
   const uint32_t in_bytes = static_cast<uint32_t>(p.input_end - p.input);          // (launcher: < 2^31)
-  const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(p.input), 0, static_cast<int>(in_bytes), 0x00020000);
-  const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      p.output, 0, static_cast<int>((p.rows - 1u) * p.output_stride + p.n), 0x00020000);   // (launcher: < 2^31)
+  const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.input, static_cast<int>(in_bytes));
+  const __amdgpu_buffer_rsrc_t out_rsrc = buffer_rsrc(p.output, static_cast<int>((p.rows - 1u) * p.output_stride + p.n));   // (launcher: < 2^31)
 
   // ---- per-lane constants: byte offset of the lane's two row slots relative to the unit's first window, of its output
   //      pixel relative to the unit's first one ----
@@ -438,7 +433,7 @@ int launch_c3rows(const IgemmParams& p, const C3Geom& cg, hipStream_t stream)
     hipLaunchKernelGGL((q8_conv_c3rows_kernel<NB, ND, RCP, decltype(seq)::value, decltype(full)::value>), dim3(grid),
                        dim3(kC3Threads), 0, stream, p, cg);
   });
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 /*
@@ -490,10 +485,8 @@ void q8_conv_c3rows32_kernel(const IgemmParams p, const C3Geom cg)
                     static_cast<int>(byte_range_mask(-8, nreal - 8) & 0x01010101u), static_cast<int>(byte_range_mask(-12, nreal - 12) & 0x01010101u)};
 
   const uint32_t in_bytes = static_cast<uint32_t>(p.input_end - p.input);          // (launcher: < 2^31, a multiple of 4)
-  const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(p.input), 0, static_cast<int>(in_bytes), 0x00020000);
-  const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      p.output, 0, static_cast<int>((p.rows - 1u) * p.output_stride + p.n), 0x00020000);   // (launcher: < 2^31)
+  const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.input, static_cast<int>(in_bytes));
+  const __amdgpu_buffer_rsrc_t out_rsrc = buffer_rsrc(p.output, static_cast<int>((p.rows - 1u) * p.output_stride + p.n));   // (launcher: < 2^31)
 
   const uint32_t row_bytes = cg.W * 3u;
   const uint32_t lane_in = prow * cg.sh * row_bytes + pcol * cg.sw * 3u + h * 16u;   // this lane's half of row slot 0, relative to the unit's first window
@@ -653,7 +646,7 @@ int launch_c3rows32(const IgemmParams& p, const C3Geom& cg, hipStream_t stream)
     hipLaunchKernelGGL((q8_conv_c3rows32_kernel<NB, KR, decltype(seq)::value, decltype(full)::value>), dim3(grid),
                        dim3(kC3Threads), 0, stream, p, cg);
   });
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 
@@ -749,8 +742,7 @@ void q8_conv_c3rows32_lds_kernel(const IgemmParams p, const C3Geom cg, const C3L
   __syncthreads();
   QNNP_TRACE_WAVE(p, blockIdx.x, wave, 2);
 
-  const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      p.output, 0, static_cast<int>((p.rows - 1u) * p.output_stride + p.n), 0x00020000);
+  const __amdgpu_buffer_rsrc_t out_rsrc = buffer_rsrc(p.output, static_cast<int>((p.rows - 1u) * p.output_stride + p.n));
   // this lane's half of row slot 0 of the band's first unit, in LDS: row prow * sh, column pcol * sw - pad_left behind the data start
   const uint32_t lane_lds = prow * cg.sh * lg.pitch + lg.c0 * 16u + pcol * cg.sw * 3u + h * 16u - cg.pad_left * 3u;
 
@@ -830,7 +822,7 @@ bool c3lds_plan(const IgemmParams& p, const C3Geom& cg, C3LdsGeom* out)
   lg.cpr = lg.c0 + lg.dchunks + (right + 15u) / 16u + 1u;
   if ((lg.cpr & 1u) == 0u) lg.cpr++;
   lg.pitch = lg.cpr * 16u;
-  lg.inv_cpr = static_cast<uint32_t>(((UINT64_C(1) << 32) + lg.cpr - 1) / lg.cpr);
+  lg.inv_cpr = reciprocal_ceil(lg.cpr);
   // pairs per band: as many as keep a band under 24 KiB (several workgroups per CU), units per band a multiple of the waves if possible
   uint32_t best = 0;
   for (uint32_t ppb = 1; ppb <= cg.pairs && ppb <= 16u; ppb++) {
@@ -848,7 +840,7 @@ bool c3lds_plan(const IgemmParams& p, const C3Geom& cg, C3LdsGeom* out)
   lg.ppb = best;
   lg.nrows = (2u * best - 1u) * cg.sh + cg.KH;
   lg.bands = (cg.pairs + best - 1u) / best;
-  lg.inv_bands = lg.bands > 1 ? static_cast<uint32_t>(((UINT64_C(1) << 32) + lg.bands - 1) / lg.bands) : 0u;
+  lg.inv_bands = reciprocal_ceil(lg.bands);
   const uint64_t wgs = static_cast<uint64_t>(p.rows / (cg.OH * cg.OW)) * lg.bands;
   if (wgs * lg.bands >= (UINT64_C(1) << 32) || static_cast<uint64_t>(lg.nrows) * lg.cpr * lg.cpr >= (UINT64_C(1) << 32)) return false;
   *out = lg;
@@ -865,7 +857,7 @@ int launch_c3rows32_lds(const IgemmParams& p, const C3Geom& cg, const C3LdsGeom&
     hipLaunchKernelGGL((q8_conv_c3rows32_lds_kernel<NB, KR, decltype(seq)::value, decltype(full)::value>), dim3(grid),
                        dim3(kC3Threads), lds_bytes, stream, p, cg, lg);
   });
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 
@@ -944,8 +936,7 @@ void q8_conv_c3rows_lds_kernel(const IgemmParams p, const C3Geom cg, const C3Lds
   }
   __syncthreads();
 
-  const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      p.output, 0, static_cast<int>((p.rows - 1u) * p.output_stride + p.n), 0x00020000);
+  const __amdgpu_buffer_rsrc_t out_rsrc = buffer_rsrc(p.output, static_cast<int>((p.rows - 1u) * p.output_stride + p.n));
   // this lane's slot of window row h of the band's first unit: row prow * sh + h, column pcol * sw - pad_left behind the data start
   const uint32_t lane_lds = (prow * cg.sh + h) * lg.pitch + lg.c0 * 16u + pcol * cg.sw * 3u - cg.pad_left * 3u;
 
@@ -1047,7 +1038,7 @@ int launch_c3rows_lds(const IgemmParams& p, const C3Geom& cg, const C3LdsGeom& l
     hipLaunchKernelGGL((q8_conv_c3rows_lds_kernel<NB, decltype(seq)::value, decltype(full)::value>), dim3(grid),
                        dim3(kC3Threads), lds_bytes, stream, p, cg, lg);
   });
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 }  // namespace
@@ -1083,8 +1074,8 @@ int conv_c3rows_launch(const IgemmParams& p, const ConvGeom& g, const int8_t* w_
   cg.pad_top = g.pad_top; cg.pad_left = g.pad_left;
   cg.segs = (g.OW + 15u) / 16u;
   cg.pairs = (g.OH + 1u) / 2u;
-  cg.inv_segs = cg.segs > 1 ? static_cast<uint32_t>(((UINT64_C(1) << 32) + cg.segs - 1) / cg.segs) : 0u;
-  cg.inv_pairs = cg.pairs > 1 ? static_cast<uint32_t>(((UINT64_C(1) << 32) + cg.pairs - 1) / cg.pairs) : 0u;
+  cg.inv_segs = reciprocal_ceil(cg.segs);
+  cg.inv_pairs = reciprocal_ceil(cg.pairs);
   cg.w_rows16 = w_rows16;
   cg.abl = 0;
 #ifdef QNNP_ENABLE_ABLATION
@@ -1139,8 +1130,8 @@ int conv_c3rows32_launch(const IgemmParams& p, const ConvGeom& g, const int8_t* 
   cg.pad_top = g.pad_top; cg.pad_left = g.pad_left;
   cg.segs = (g.OW + 15u) / 16u;
   cg.pairs = (g.OH + 1u) / 2u;
-  cg.inv_segs = cg.segs > 1 ? static_cast<uint32_t>(((UINT64_C(1) << 32) + cg.segs - 1) / cg.segs) : 0u;
-  cg.inv_pairs = cg.pairs > 1 ? static_cast<uint32_t>(((UINT64_C(1) << 32) + cg.pairs - 1) / cg.pairs) : 0u;
+  cg.inv_segs = reciprocal_ceil(cg.segs);
+  cg.inv_pairs = reciprocal_ceil(cg.pairs);
   cg.w_rows16 = w_rows32;
   cg.abl = 0;
   const bool two = p.n_pad > 32;

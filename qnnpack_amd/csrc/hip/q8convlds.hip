@@ -28,6 +28,7 @@
 
 #include <stdint.h>
 
+#include "device_ops.hip.h"
 #include "igemm_epilogue.hip.h"
 #include "igemm_params.h"
 #include "per_device.h"
@@ -36,9 +37,6 @@
 namespace qnnp {
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int kThreads = 256;
 constexpr int kPosPerBlock = 256;      // 4 waves x 2 groups x 32 positions
@@ -323,19 +321,13 @@ void q8_conv_lds_mfma_kernel(const IgemmParams p, const ConvGeom g, const uint32
 template <int TN, bool PIPE, int ABL = 0>
 int launch_one(const IgemmParams& p, const ConvGeom& g, const Plan& pl, uint32_t batch, hipStream_t stream)
 {
-  static qnnp::PerDeviceOnce attr_once;   // function attributes are per device
-  if (auto once_scope = attr_once.begin()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&q8_conv_lds_mfma_kernel<TN, PIPE, ABL>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      (void) hipGetLastError();
-    }
-  }
+  allow_dynamic_lds<&q8_conv_lds_mfma_kernel<TN, PIPE, ABL>>(160 * 1024);
   const uint32_t total_items = batch * pl.blocks_per_image;
   const uint32_t resident = p.cu_count * (kLdsLimit >= 2 * pl.lds_bytes ? 2u : 1u);
   const uint32_t grid = total_items < resident ? total_items : resident;
   hipLaunchKernelGGL((q8_conv_lds_mfma_kernel<TN, PIPE, ABL>), dim3(grid), dim3(kThreads),
                      pl.lds_bytes, stream, p, g, pl.blocks_per_image, total_items, pl.ic, pl.w_bytes);
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 template <int TN>

@@ -42,6 +42,7 @@
 
 #include <type_traits>
 
+#include "device_ops.hip.h"
 #include "igemm_params.h"
 #include "per_device.h"
 #include "requant.hip.h"
@@ -49,9 +50,6 @@
 namespace qnnp {
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr uint32_t pt_stages(int kstep) { return kstep == 128 ? 2u : 4u; }   // ring slots by bytes of K per step
 constexpr uint32_t kPtFlip = 0x80808080u;
@@ -78,62 +76,23 @@ struct PatchArgs {
                               // 32 = no patch pass (no re-centring, no sums), 64 = no epilogue stores
 };
 
-__device__ __forceinline__ uint32_t pt_div(uint32_t n, uint32_t inv) { return inv != 0u ? __umulhi(n, inv) : n; }
-inline uint32_t pt_magic(uint32_t d) { return d > 1 ? static_cast<uint32_t>(((UINT64_C(1) << 32) + d - 1) / d) : 0u; }
-
-__device__ __forceinline__ uint32_t pt_lds_off(const void* p)
-{
-  return static_cast<uint32_t>(reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) uint8_t*) p));
-}
-
-/* LDS-DMA, 16 bytes per lane, flat per-lane source address; inline asm so that hipcc does not guard later LDS accesses
- * with vmcnt(0) (q8convwave.hip dma16). M0 is written and left: nothing else in this kernel reads it
- * (tests/test_kernel_resources.py). */
-__device__ __forceinline__ void pt_dma16(const uint8_t* src, uint32_t lds_dst_uniform)
-{
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_dst_uniform);
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(src), "s"(dst) : "memory");
-}
-/* the saddr form: wave-uniform 64-bit base + 32-bit lane offset (the weight stream: no per-piece vector arithmetic) */
-__device__ __forceinline__ uint64_t pt_scalar64(uint64_t v)          // a wave-uniform value, in scalar registers for good
-{
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
-  return (static_cast<uint64_t>(hi) << 32) | lo;
-}
-__device__ __forceinline__ void pt_dma16_saddr(uint64_t base_scalar, uint32_t lane_offset, uint32_t lds_dst_scalar)
-{
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(lane_offset), "s"(base_scalar), "s"(lds_dst_scalar) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void pt_wait_vmcnt()
-{
-  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
-  asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory");
-}
+/* LDS-DMA: dma16_flat for the patch, and the saddr form dma16_saddr_ordered for the weight stream (no per-piece vector
+ * arithmetic). M0 is written and left: nothing else in this kernel reads it (tests/test_kernel_resources.py). */
 /* Fragment reads the compiler does not track, with counted waits that are tied to the registers they guard (the "+v"
  * operands make the MFMAs that consume them depend on the wait). Why by hand: with the reads as plain loads hipcc put
  * s_waitcnt lgkmcnt(1) / (0) in front of a half's MFMAs AFTER the next half's reads had been issued -- every step waited for
  * the LDS round trip of fragments it would only need 128 cycles later. A wave's LDS operations return in order. */
 template <int OFF>
-__device__ __forceinline__ v4i pt_ds_read16(uint32_t addr)
+__device__ __forceinline__ v4i ds_read16(uint32_t addr)
 {
   v4i x;
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(x) : "v"(addr), "n"(OFF) : "memory");
   return x;
 }
 template <int N>
-__device__ __forceinline__ void pt_wait_lgkm(v4i& x0, v4i& x1, v4i& x2, v4i& x3)
+__device__ __forceinline__ void wait_lgkm(v4i& x0, v4i& x1, v4i& x2, v4i& x3)
 {
   asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3) : "n"(N) : "memory");
-}
-__device__ __forceinline__ void pt_ds_write16(uint32_t off, v4i x)
-{
-  asm volatile("ds_write_b128 %0, %1" :: "v"(off), "v"(x) : "memory");
-}
-__device__ __forceinline__ void pt_ds_write4(uint32_t off, int32_t v)
-{
-  asm volatile("ds_write_b32 %0, %1" :: "v"(off), "v"(v) : "memory");
 }
 
 /* NTB = 32-channel blocks of the N-tile: 8 (waves as 2 position pairs x 4 channel pairs, <= 128 positions) or
@@ -181,11 +140,11 @@ void q8_conv_patch_kernel(const IgemmParams p, const ConvGeom g, const PatchArgs
   const uint32_t khalf = lane >> 5;
   const uint32_t wm = wave / kWNG, wn = wave % kWNG;  // this wave: position blocks 2 wm, 2 wm + 1; channel blocks 2 wn, 2 wn + 1
 
-  const uint32_t tile_m = pt_div(blockIdx.x, a.inv_tiles_n);
+  const uint32_t tile_m = div_magic(blockIdx.x, a.inv_tiles_n);
   const uint32_t tile_n = blockIdx.x - tile_m * a.tiles_n;
   uint32_t img0, row0;
   if (a.imgs > 1) { img0 = tile_m * a.imgs; row0 = 0; }
-  else { img0 = pt_div(tile_m, a.inv_tiles_r); row0 = (tile_m - img0 * a.tiles_r) * a.rows; }
+  else { img0 = div_magic(tile_m, a.inv_tiles_r); row0 = (tile_m - img0 * a.tiles_r) * a.rows; }
 
   const uint32_t C = CHUNK ? 128u : p.kc;             // channels the patch holds
   const uint32_t cpp = C >> 4;
@@ -193,7 +152,7 @@ void q8_conv_patch_kernel(const IgemmParams p, const ConvGeom g, const PatchArgs
   const uint32_t kblocks = p.k_pad >> 5;
   const uint32_t nb_tile = tile_n * NTB;              // first 32-channel block of the tile
 
-  const uint32_t lds0 = pt_lds_off(lds);              // (LDS-DMA destinations and the asm accesses address the allocation itself)
+  const uint32_t lds0 = lds_offset(lds);              // (LDS-DMA destinations and the asm accesses address the allocation itself)
   int32_t* pix = reinterpret_cast<int32_t*>(lds + a.pix_off);
   int32_t* bias_lds = reinterpret_cast<int32_t*>(lds + a.bias_off);
 
@@ -204,7 +163,7 @@ void q8_conv_patch_kernel(const IgemmParams p, const ConvGeom g, const PatchArgs
 #pragma unroll
   for (int i = 0; i < kPpw; i++) {
     const uint32_t j = wave + i * kPtWaves;
-    w_src[i] = pt_scalar64(reinterpret_cast<uint64_t>(p.packed_w) + (static_cast<uint64_t>(nb_tile + j / kSub) * kblocks + j % kSub) * 1024u);
+    w_src[i] = scalar_ptr(reinterpret_cast<uint64_t>(p.packed_w) + (static_cast<uint64_t>(nb_tile + j / kSub) * kblocks + j % kSub) * 1024u);
     w_dst[i] = __builtin_amdgcn_readfirstlane(lds0 + a.ring_off + j * 1024u);
   }
   const uint32_t lane16 = lane * 16u;
@@ -214,9 +173,9 @@ void q8_conv_patch_kernel(const IgemmParams p, const ConvGeom g, const PatchArgs
 #pragma unroll
     for (int i = 0; i < kPpw; i++) {
       if constexpr (CHUNK) {
-        pt_dma16_saddr(w_src[i] + (st_tap * a.nch + st_ch) * (kSub * 1024u), lane16, w_dst[i] + wr_off);
+        dma16_saddr_ordered(w_src[i] + (st_tap * a.nch + st_ch) * (kSub * 1024u), lane16, w_dst[i] + wr_off);
       } else {
-        pt_dma16_saddr(w_src[i], lane16, w_dst[i] + wr_off);
+        dma16_saddr_ordered(w_src[i], lane16, w_dst[i] + wr_off);
         w_src[i] += kSub * 1024u;
       }
     }
@@ -239,11 +198,11 @@ void q8_conv_patch_kernel(const IgemmParams p, const ConvGeom g, const PatchArgs
     const uint32_t pieces = (a.chunks + 63u) >> 6;
     auto source = [&](uint32_t piece, bool* inside_out) __attribute__((always_inline)) -> const uint8_t* {
       const uint32_t v = min(piece * 64u + lane, a.chunks - 1u);
-      const uint32_t q = pt_div(v, a.inv_cpp1);
+      const uint32_t q = div_magic(v, a.inv_cpp1);
       const uint32_t c = v - q * (cpp + 1u);
-      const uint32_t il = pt_div(q, a.inv_pimg);
+      const uint32_t il = div_magic(q, a.inv_pimg);
       const uint32_t rem = q - il * a.pimg;
-      const uint32_t prr = pt_div(rem, a.inv_pw);
+      const uint32_t prr = div_magic(rem, a.inv_pw);
       const uint32_t pc = rem - prr * a.pw;
       const int32_t iy = static_cast<int32_t>(row0 * g.sh + prr) - static_cast<int32_t>(g.pad_top);
       const int32_t ix = static_cast<int32_t>(pc) - static_cast<int32_t>(g.pad_left);
@@ -266,7 +225,7 @@ void q8_conv_patch_kernel(const IgemmParams p, const ConvGeom g, const PatchArgs
             src_cache[i] = source(piece, &inside);
             src_inside |= inside ? (1u << i) : 0u;
           }
-          pt_dma16(src_cache[i] + (((src_inside >> i) & 1u) != 0u ? ch * 128u : 0u), lds0 + piece * 1024u);
+          dma16_flat(src_cache[i] + (((src_inside >> i) & 1u) != 0u ? ch * 128u : 0u), lds0 + piece * 1024u);
         }
       }
       first = wave + static_cast<uint32_t>(kCache) * kPtWaves;
@@ -274,16 +233,16 @@ void q8_conv_patch_kernel(const IgemmParams p, const ConvGeom g, const PatchArgs
     for (uint32_t piece = first; piece < pieces; piece += kPtWaves) {
       bool inside;
       const uint8_t* src = source(piece, &inside);
-      pt_dma16(src + (inside ? ch * 128u : 0u), lds0 + piece * 1024u);
+      dma16_flat(src + (inside ? ch * 128u : 0u), lds0 + piece * 1024u);
     }
     if (ch == 0 && wave == kPtWaves - 1 && lane < NTB * 8u) {
       const int32_t* b = (rq_is_lane<SEQ>() ? p.bias2u : p.bias2) + nb_tile * 32u;
-      pt_dma16(reinterpret_cast<const uint8_t*>(b) + lane * 16u, lds0 + a.bias_off);
+      dma16_flat(reinterpret_cast<const uint8_t*>(b) + lane * 16u, lds0 + a.bias_off);
     }
   };
   load_patch(0);
   PT_STAMP(1);
-  pt_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   asm volatile("s_barrier" ::: "memory");
   PT_STAMP(2);
 
@@ -321,7 +280,7 @@ void q8_conv_patch_kernel(const IgemmParams p, const ConvGeom g, const PatchArgs
                 s = __builtin_amdgcn_sad_u8(y.w, 0u, s);
               }
               y.x ^= static_cast<int>(kPtFlip); y.y ^= static_cast<int>(kPtFlip); y.z ^= static_cast<int>(kPtFlip); y.w ^= static_cast<int>(kPtFlip);
-              pt_ds_write16(lds0 + mine[u] + c * 16u, y);
+              ds_write16(lds0 + mine[u] + c * 16u, y);
             }
             if (sums) {
               s += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(s), 0xB1, 0xF, 0xF, false));
@@ -329,7 +288,7 @@ void q8_conv_patch_kernel(const IgemmParams p, const ConvGeom g, const PatchArgs
               if ((t & 3u) == 0u) {
                 int32_t sum = static_cast<int32_t>(s) - 128 * 128;
                 if (ch != 0) sum += pix[t >> 2];      // (the same thread wrote it a chunk ago)
-                pt_ds_write4(lds0 + a.pix_off + (t >> 2) * 4u, sum);
+                ds_write4(lds0 + a.pix_off + (t >> 2) * 4u, sum);
               }
             }
           }
@@ -351,13 +310,13 @@ void q8_conv_patch_kernel(const IgemmParams p, const ConvGeom g, const PatchArgs
           s = __builtin_amdgcn_sad_u8(x.w, 0u, s);
         }
         x.x ^= static_cast<int>(kPtFlip); x.y ^= static_cast<int>(kPtFlip); x.z ^= static_cast<int>(kPtFlip); x.w ^= static_cast<int>(kPtFlip);
-        pt_ds_write16(lds0 + mine + c * 16u, x);
+        ds_write16(lds0 + mine + c * 16u, x);
       }
       if (sums) {
         s += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(s), 0xB1, 0xF, 0xF, false));      // quad_perm [1,0,3,2]
         s += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(s), 0x4E, 0xF, 0xF, false));      // quad_perm [2,3,0,1]
         if ((t & 3u) == 0u) {
-          pt_ds_write4(lds0 + a.pix_off + q * 4u, static_cast<int32_t>(s) - 128 * static_cast<int32_t>(C));
+          ds_write4(lds0 + a.pix_off + q * 4u, static_cast<int32_t>(s) - 128 * static_cast<int32_t>(C));
         }
       }
     }
@@ -375,18 +334,18 @@ void q8_conv_patch_kernel(const IgemmParams p, const ConvGeom g, const PatchArgs
 #pragma unroll
   for (int mi = 0; mi < 2; mi++) {
     const uint32_t pos = (wm * 2u + mi) * 32u + (lane & 31u);
-    const uint32_t il = pt_div(pos, a.inv_rw);
+    const uint32_t il = div_magic(pos, a.inv_rw);
     const uint32_t rem = pos - il * (a.rows * g.OW);
-    const uint32_t r = pt_div(rem, a.inv_ow);
+    const uint32_t r = div_magic(rem, a.inv_ow);
     const uint32_t x = rem - r * g.OW;
     q0[mi] = pos < a.pos ? il * a.pimg + r * g.sh * a.pw + x * g.sw : 0u;
     abase0[mi] = lds0 + q0[mi] * ps + khalf * 16u;
 #pragma unroll
     for (int half = 0; half < 2; half++) {
       const uint32_t spos = (wm * 2u + mi) * 32u + half * 16u + (lane & 15u);
-      const uint32_t sil = pt_div(spos, a.inv_rw);
+      const uint32_t sil = div_magic(spos, a.inv_rw);
       const uint32_t srem = spos - sil * (a.rows * g.OW);
-      const uint32_t sr = pt_div(srem, a.inv_ow);
+      const uint32_t sr = div_magic(srem, a.inv_ow);
       const uint32_t sx = srem - sr * g.OW;
       const bool ok = spos < a.pos && img0 + sil < a.batch && row0 + sr < g.OH;
       const uint32_t row16 = lane >> 4;
@@ -418,10 +377,10 @@ void q8_conv_patch_kernel(const IgemmParams p, const ConvGeom g, const PatchArgs
   auto load = [&](Frags& f, auto sub_c) __attribute__((always_inline)) {
     constexpr uint32_t sub = decltype(sub_c)::value;
     if (abl & 4u) return;
-    f.a[0] = pt_ds_read16<sub * 32>(acur[0]);
-    f.a[1] = pt_ds_read16<sub * 32>(acur[1]);
-    f.b[0] = pt_ds_read16<sub * 1024>(bcur);
-    f.b[1] = pt_ds_read16<sub * 1024 + kSub * 1024>(bcur);
+    f.a[0] = ds_read16<sub * 32>(acur[0]);
+    f.a[1] = ds_read16<sub * 32>(acur[1]);
+    f.b[0] = ds_read16<sub * 1024>(bcur);
+    f.b[1] = ds_read16<sub * 1024 + kSub * 1024>(bcur);
   };
   // The same four reads WITH their wait, as one asm block: for the places where the registers cross an irregular edge of the
   // control flow (the chunk loop's header) -- hipcc is free to copy an asm output the moment the asm ends, and a copy of a
@@ -468,12 +427,12 @@ void q8_conv_patch_kernel(const IgemmParams p, const ConvGeom g, const PatchArgs
     if constexpr (sub + 1 < kSub) {
       load(nxt, std::integral_constant<uint32_t, sub + 1>{});
     } else {
-      pt_wait_vmcnt<kVm>();
+      wait_vmcnt<kVm>();
       if (!(abl & 2u)) asm volatile("s_barrier" ::: "memory");
       if constexpr (!kLast) { advance(); load(nxt, std::integral_constant<uint32_t, 0>{}); } else { more = false; }
     }
-    if constexpr (sub + 1 < kSub || !kLast) pt_wait_lgkm<4>(cur.a[0], cur.a[1], cur.b[0], cur.b[1]);
-    else pt_wait_lgkm<0>(cur.a[0], cur.a[1], cur.b[0], cur.b[1]);
+    if constexpr (sub + 1 < kSub || !kLast) wait_lgkm<4>(cur.a[0], cur.a[1], cur.b[0], cur.b[1]);
+    else wait_lgkm<0>(cur.a[0], cur.a[1], cur.b[0], cur.b[1]);
     (void) more;
     __builtin_amdgcn_sched_barrier(0);
     mfma1(acc[0][0], cur.b[0], cur.a[0]);
@@ -505,7 +464,7 @@ void q8_conv_patch_kernel(const IgemmParams p, const ConvGeom g, const PatchArgs
       if (ch != 0) {
         asm volatile("s_barrier" ::: "memory");       // every wave has its last fragments of the previous chunk
         load_patch(ch);
-        pt_wait_vmcnt<0>();
+        wait_vmcnt<0>();
         asm volatile("s_barrier" ::: "memory");
         patch_pass(ch);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -531,8 +490,7 @@ void q8_conv_patch_kernel(const IgemmParams p, const ConvGeom g, const PatchArgs
   PT_STAMP(4);
 
   // ---- fused epilogue: row term (sum of the window's pixel sums), requantization in registers, 16-byte stores
-  const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      p.output, 0, static_cast<int>((p.rows - 1u) * p.output_stride + p.n), 0x00020000);   // (launcher: < 2^31)
+  const __amdgpu_buffer_rsrc_t out_rsrc = buffer_rsrc(p.output, static_cast<int>((p.rows - 1u) * p.output_stride + p.n));   // (launcher: < 2^31)
 #pragma unroll
   for (int mi = 0; mi < 2; mi++) {
     int32_t s = 0;
@@ -585,15 +543,9 @@ void q8_conv_patch_kernel(const IgemmParams p, const ConvGeom g, const PatchArgs
 template <int MB, int NTB, int KSTEP, int SEQ, bool FULL, bool CHUNK = false>
 int launch_patch_as(const IgemmParams& p, const ConvGeom& g, const PatchArgs& a, uint32_t lds_bytes, hipStream_t stream)
 {
-  static qnnp::PerDeviceOnce attr_once;   // function attributes are per device
-  if (auto once_scope = attr_once.begin()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&q8_conv_patch_kernel<MB, NTB, KSTEP, SEQ, FULL, CHUNK>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kPtLdsLimit)) != hipSuccess) {
-      (void) hipGetLastError();
-    }
-  }
+  allow_dynamic_lds<&q8_conv_patch_kernel<MB, NTB, KSTEP, SEQ, FULL, CHUNK>>(static_cast<int>(kPtLdsLimit));
   hipLaunchKernelGGL((q8_conv_patch_kernel<MB, NTB, KSTEP, SEQ, FULL, CHUNK>), dim3(a.tiles_m * a.tiles_n), dim3(MB * NTB * 16), lds_bytes, stream, p, g, a);
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 /* Tile geometry and LDS plan of one flavour (mb position blocks x ntb channel blocks), or false when it does not fit. */
@@ -650,14 +602,14 @@ bool plan_flavour(const IgemmParams& p, const ConvGeom& g, uint32_t batch, uint3
   if (static_cast<uint64_t>(a->tiles_m) * a->tiles_n * a->tiles_n >= (UINT64_C(1) << 32)) return false;
   if (static_cast<uint64_t>(a->tiles_m) * a->tiles_r >= (UINT64_C(1) << 32)) return false;
   if (a->chunks >= 65536u) return false;
-  a->inv_ow = pt_magic(g.OW);
-  a->inv_rw = pt_magic(a->rows * g.OW);
-  a->inv_pw = pt_magic(a->pw);
-  a->inv_pimg = pt_magic(a->pimg);
-  a->inv_tiles_r = pt_magic(a->tiles_r);
-  a->inv_tiles_n = pt_magic(a->tiles_n);
+  a->inv_ow = reciprocal_ceil(g.OW);
+  a->inv_rw = reciprocal_ceil(a->rows * g.OW);
+  a->inv_pw = reciprocal_ceil(a->pw);
+  a->inv_pimg = reciprocal_ceil(a->pimg);
+  a->inv_tiles_r = reciprocal_ceil(a->tiles_r);
+  a->inv_tiles_n = reciprocal_ceil(a->tiles_n);
   a->ps = C + 16u;
-  a->inv_cpp1 = pt_magic(cpp + 1u);
+  a->inv_cpp1 = reciprocal_ceil(cpp + 1u);
   a->csteps = C / kstep;
   a->ksteps = 9u * (p.kc / kstep);
   a->nch = chunked ? p.kc / 128u : 1u;

@@ -28,7 +28,7 @@
  *     fragment address is a per-unit register plus an immediate;
  *   - the LDS-DMA instructions are inline asm: hipcc guards every LDS access behind a global_load_lds it knows of
  *     with s_waitcnt vmcnt(0) (it cannot prove the two do not alias), which would drain the gather of the next patch
- *     and wait for the previous unit's store acknowledgements several times per unit (see dma16);
+ *     and wait for the previous unit's store acknowledgements several times per unit (device_ops.hip.h);
  *   - epilogue: row term, Q31 requantization into the (now free) patch buffer as a 64 x n output image, whole
  *     8-position runs stored with 16-byte pieces (full 128-byte lines);
  *   - units are handed out inside the workgroup by an LDS counter.
@@ -39,6 +39,7 @@
 
 #include <stdint.h>
 
+#include "device_ops.hip.h"
 #include "igemm_epilogue.hip.h"
 #include "igemm_params.h"
 #include "per_device.h"
@@ -47,9 +48,6 @@
 namespace qnnp {
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int kWaves = 9;
 constexpr int kThreads = kWaves * 64;
@@ -85,8 +83,8 @@ inline bool make_args(const IgemmParams& p, const ConvGeom& g, uint32_t batch, W
     // q = floor(n * M / 2^32) with M = ceil(2^32 / d) is exact while n * d < 2^32 (error term n*e/(d*2^32) < 1/d)
     const uint64_t tiles = static_cast<uint64_t>(a->tiles_x) * a->tiles_y;
     if (static_cast<uint64_t>(batch) * tiles * tiles >= (UINT64_C(1) << 32)) return false;
-    a->inv_tiles = tiles > 1 ? static_cast<uint32_t>(((UINT64_C(1) << 32) + tiles - 1) / tiles) : 0u;
-    a->inv_tiles_x = a->tiles_x > 1 ? static_cast<uint32_t>(((UINT64_C(1) << 32) + a->tiles_x - 1) / a->tiles_x) : 0u;
+    a->inv_tiles = reciprocal_ceil(static_cast<uint32_t>(tiles));
+    a->inv_tiles_x = reciprocal_ceil(a->tiles_x);
   }
   a->w_bytes = p.n_pad * p.k_pad;
   a->head_bytes = (a->w_bytes + p.n * 4u + 16u + 1023u) & ~1023u;
@@ -106,45 +104,8 @@ inline bool make_args(const IgemmParams& p, const ConvGeom& g, uint32_t batch, W
   return *lds_bytes <= kLdsLimit;
 }
 
-// byte offset of an LDS pointer inside the workgroup's LDS allocation (what DS instructions and M0 address)
-__device__ __forceinline__ uint32_t lds_off(const void* p)
-{
-  return static_cast<uint32_t>(reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) uint8_t*) p));
-}
-
-/* LDS-DMA, 16 bytes per lane: LDS destination = wave-uniform base (M0) + lane * 16, source address per lane.
- * Issued as inline asm ON PURPOSE: with the builtin, hipcc (ROCm 7.2) remembers that a global_load_lds is in flight
- * and puts s_waitcnt vmcnt(0) in front of every later LDS access it cannot prove disjoint -- inside this kernel's unit
- * loop that is every ds_read / ds_write / LDS atomic, each draining the gather of the next patch (and waiting for
- * the previous unit's store acknowledgements on the way). The asm form is invisible to that bookkeeping; the waits
- * this kernel needs are the explicit s_waitcnt vmcnt in the unit loop, nothing else orders a ds_read behind a DMA
- * (cdna_hip_programming.md section 5.7). M0 is restored: the compiler owns it. */
-__device__ __forceinline__ void dma16(const uint8_t* src, uint8_t* lds_wave_base)
-{
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_off(lds_wave_base));
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
-
-// 16-byte / 4-byte LDS stores the compiler does not see as LDS accesses (see the header: no vmcnt(0) in front)
-__device__ __forceinline__ void ds_write16_raw(uint32_t off, uint4 v)
-{
-  typedef int raw_v4i __attribute__((ext_vector_type(4)));
-  const raw_v4i x = {static_cast<int>(v.x), static_cast<int>(v.y), static_cast<int>(v.z), static_cast<int>(v.w)};
-  asm volatile("ds_write_b128 %0, %1" :: "v"(off), "v"(x) : "memory");
-}
-__device__ __forceinline__ void ds_write4_raw(uint32_t off, int32_t v)
-{
-  asm volatile("ds_write_b32 %0, %1" :: "v"(off), "v"(v) : "memory");
-}
-
-// n / d through the host-made reciprocal (WaveArgs): one scalar multiply instead of the ~40-instruction sequence hipcc
-// emits for a division by a run-time value -- four of those per unit sat on every wave's critical path
-__device__ __forceinline__ uint32_t div_magic(uint32_t n, uint32_t inv)
-{
-  return inv != 0u ? __umulhi(n, inv) : n;
-}
+// divides by run-time values go through the reciprocals of WaveArgs (div_magic): four of them per unit sat on every
+// wave's critical path
 
 // KS: 3 = 3x3 window, stride 1, dilation 1 (10x10 patch; every fragment address = per-unit register + immediate),
 //     0 = any geometry make_args accepts (addresses computed per tap)
@@ -220,7 +181,7 @@ void q8_conv_wave_mfma_kernel(const IgemmParams p, const ConvGeom g, const WaveA
           const bool inb = iy >= 0 && iy < static_cast<int32_t>(g.H) && ix >= 0 && ix < static_cast<int32_t>(g.W);
           src = inb ? src : fill_line;
         }
-        if (v < pvec) dma16(src, dst + u * 1024u);        // lanes past the patch write nothing (the buffer ends there)
+        if (v < pvec) dma16_flat_keep_m0(src, dst + u * 1024u);        // lanes past the patch write nothing (the buffer ends there)
       }
     }
   };
@@ -229,7 +190,7 @@ void q8_conv_wave_mfma_kernel(const IgemmParams p, const ConvGeom g, const WaveA
   {
     const uint32_t pieces = a.w_bytes >> 10;
     const uint8_t* src = reinterpret_cast<const uint8_t*>(p.packed_w) + lane * 16u;
-    for (uint32_t i = wave; i < pieces; i += kWaves) dma16(src + i * 1024u, w_lds + i * 1024u);
+    for (uint32_t i = wave; i < pieces; i += kWaves) dma16_flat_keep_m0(src + i * 1024u, w_lds + i * 1024u);
     for (uint32_t i = tid; i < p.n; i += kThreads) bias_lds[i] = p.bias2[i];
   }
   uint32_t cur = lo + wave;
@@ -289,8 +250,8 @@ void q8_conv_wave_mfma_kernel(const IgemmParams p, const ConvGeom g, const WaveA
     // Software-pipelined by one piece: one piece per trip (read -> wait -> compute -> write, the raw writes being
     // memory barriers to the compiler) cost an LDS round trip per piece, 2.4 k cycles per unit (stamps).
     {
-      const uint32_t patch_off = lds_off(patch);
-      const uint32_t pix_off = lds_off(pix);
+      const uint32_t patch_off = lds_offset(patch);
+      const uint32_t pix_off = lds_offset(pix);
       // (two pieces per trip, the read of the next piece issued before a piece is processed: two pieces live)
       auto read_piece = [&](uint32_t u) __attribute__((always_inline)) -> uint4 {
         const uint32_t v = lane + u * 64u;
@@ -307,8 +268,8 @@ void q8_conv_wave_mfma_kernel(const IgemmParams p, const ConvGeom g, const WaveA
           if (cpp > 2) sum += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(sum), 0x4E, 0xF, 0xF, false));   // lane ^ 2
           uint4 y = x;
           y.x ^= kFlip; y.y ^= kFlip; y.z ^= kFlip; y.w ^= kFlip;
-          ds_write16_raw(patch_off + v * 16u, y);
-          if ((v & (cpp - 1u)) == 0) ds_write4_raw(pix_off + (v >> log_cpp) * 4u, static_cast<int32_t>(sum) - 128 * static_cast<int32_t>(cin));
+          ds_write16(patch_off + v * 16u, y);
+          if ((v & (cpp - 1u)) == 0) ds_write4(pix_off + (v >> log_cpp) * 4u, static_cast<int32_t>(sum) - 128 * static_cast<int32_t>(cin));
         }
       };
       uint4 xa = read_piece(0);
@@ -435,7 +396,7 @@ void q8_conv_wave_mfma_kernel(const IgemmParams p, const ConvGeom g, const WaveA
     // ---- fused epilogue, 32 positions at a time: row term from the pixel sums, Q31 requantization into the staging
     //      image, whole 4-row x 8-position runs stored with 16-byte pieces ----
     uint8_t* out_img = p.output + static_cast<uint64_t>(img) * g.OH * g.OW * p.n;
-    const uint32_t stage_off = lds_off(stage);
+    const uint32_t stage_off = lds_offset(stage);
     {
       const std::integral_constant<int, SEQ> shift0{};
       const std::integral_constant<bool, FULL> full{};
@@ -466,7 +427,7 @@ void q8_conv_wave_mfma_kernel(const IgemmParams p, const ConvGeom g, const WaveA
           }
           const auto s02 = __builtin_amdgcn_permlane32_swap(pk[0], pk[2], false, false);
           const auto s13 = __builtin_amdgcn_permlane32_swap(pk[1], pk[3], false, false);
-          ds_write16_raw(stage_off + (lane & 31u) * p.n + tn * 32 + khalf * 16, make_uint4(s02[0], s02[1], s13[0], s13[1]));
+          ds_write16(stage_off + (lane & 31u) * p.n + tn * 32 + khalf * 16, make_uint4(s02[0], s02[1], s13[0], s13[1]));
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");         // image complete before it is read back
         const uint32_t pieces = 32u * cpr;
@@ -522,8 +483,8 @@ inline WaveArgs reg_args(const WaveArgs& a0, const IgemmParams& p, const ConvGeo
   a.units = batch * a.tiles_x * a.tiles_y;
   const uint64_t tiles = static_cast<uint64_t>(a.tiles_x) * a.tiles_y;
   *ok = static_cast<uint64_t>(batch) * tiles * tiles < (UINT64_C(1) << 32);
-  a.inv_tiles = tiles > 1 ? static_cast<uint32_t>(((UINT64_C(1) << 32) + tiles - 1) / tiles) : 0u;
-  a.inv_tiles_x = a.tiles_x > 1 ? static_cast<uint32_t>(((UINT64_C(1) << 32) + a.tiles_x - 1) / a.tiles_x) : 0u;
+  a.inv_tiles = reciprocal_ceil(static_cast<uint32_t>(tiles));
+  a.inv_tiles_x = reciprocal_ceil(a.tiles_x);
   const uint32_t patch = a.PH * a.PW * p.kc;
   a.patch_bytes = (patch + 255u) & ~255u;
   a.pix_bytes = (a.PH * a.PW * 4u + 255u) & ~255u;
@@ -612,8 +573,7 @@ void q8_conv_wave_reg_kernel(const IgemmParams p, const ConvGeom g, const WaveAr
   uint32_t cur = lo + wave;
   Raw raw;
   fetch_patch(min(cur, a.units - 1u), raw);
-  const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      p.output, 0, static_cast<int>(a.units / tiles * g.OH * g.OW * p.n), 0x00020000);   // (launcher: < 2^31)
+  const __amdgpu_buffer_rsrc_t out_rsrc = buffer_rsrc(p.output, static_cast<int>(a.units / tiles * g.OH * g.OW * p.n));   // (launcher: < 2^31)
   // Stores to nowhere (out-of-range offset: the hardware drops them), as many as a unit's epilogue issues. hipcc sizes
   // the vmcnt waits of the fix-up pass for the smaller of the counts outstanding on the two ways into the loop; coming
   // from here that was "NP loads", from the loop's end "NP loads + 2 TM stores", so the waits came out as
@@ -632,11 +592,11 @@ void q8_conv_wave_reg_kernel(const IgemmParams p, const ConvGeom g, const WaveAr
   {
     const uint32_t pieces = a.w_bytes >> 10;
     const uint8_t* src = reinterpret_cast<const uint8_t*>(p.packed_w) + lane * 16u;
-    for (uint32_t i = wave; i < pieces; i += kRegWaves) dma16(src + i * 1024u, w_lds + i * 1024u);
+    for (uint32_t i = wave; i < pieces; i += kRegWaves) dma16_flat_keep_m0(src + i * 1024u, w_lds + i * 1024u);
     // (the bias the same way, 16 bytes per lane of one wave: a load + LDS store would put a compiler-made vmcnt(0)
     //  -- patch, weights and all -- in front of the first unit)
     if (wave == kRegWaves - 1 && lane < p.n / 4u) {
-      dma16(reinterpret_cast<const uint8_t*>(p.bias2) + lane * 16u, reinterpret_cast<uint8_t*>(bias_lds));
+      dma16_flat_keep_m0(reinterpret_cast<const uint8_t*>(p.bias2) + lane * 16u, reinterpret_cast<uint8_t*>(bias_lds));
     }
   }
   // (a wave's first TWO units are fixed -- lo + wave and lo + waves + wave -- so that its first claim on the counter
@@ -678,8 +638,8 @@ void q8_conv_wave_reg_kernel(const IgemmParams p, const ConvGeom g, const WaveAr
 
     // ---- the fetched patch: re-centred into LDS, per-pixel channel sums (of a') beside it ----
     {
-      const uint32_t patch_off = lds_off(patch);
-      const uint32_t pix_off = lds_off(pix);
+      const uint32_t patch_off = lds_offset(patch);
+      const uint32_t pix_off = lds_offset(pix);
 #pragma unroll
       for (int u = 0; u < NP; u++) {
         const uint32_t v = lane_now + u * 64u;             // (lane_now: recomputed per unit, not held across the K loop)
@@ -691,8 +651,8 @@ void q8_conv_wave_reg_kernel(const IgemmParams p, const ConvGeom g, const WaveAr
           sum = __builtin_amdgcn_sad_u8(x.w, 0u, sum);
           sum += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(sum), 0xB1, 0xF, 0xF, false));        // lane ^ 1
           if (cpp > 2) sum += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(sum), 0x4E, 0xF, 0xF, false));   // lane ^ 2
-          ds_write16_raw(patch_off + v * 16u, make_uint4(x.x ^ kFlip, x.y ^ kFlip, x.z ^ kFlip, x.w ^ kFlip));
-          if ((v & (cpp - 1u)) == 0) ds_write4_raw(pix_off + (v >> log_cpp) * 4u, static_cast<int32_t>(sum) - 128 * static_cast<int32_t>(cin));
+          ds_write16(patch_off + v * 16u, make_uint4(x.x ^ kFlip, x.y ^ kFlip, x.z ^ kFlip, x.w ^ kFlip));
+          if ((v & (cpp - 1u)) == 0) ds_write4(pix_off + (v >> log_cpp) * 4u, static_cast<int32_t>(sum) - 128 * static_cast<int32_t>(cin));
         }
       }
     }
@@ -779,7 +739,7 @@ void q8_conv_wave_reg_kernel(const IgemmParams p, const ConvGeom g, const WaveAr
 
     // ---- fused epilogue, 32 positions at a time (as the kernel above), stores through the buffer descriptor ----
     const uint32_t out_img = img * g.OH * g.OW * p.n;
-    const uint32_t stage_off = lds_off(stage);
+    const uint32_t stage_off = lds_offset(stage);
 #pragma unroll
     for (int j = 0; j < TM; j++) {
       int32_t s = 0;
@@ -798,7 +758,7 @@ void q8_conv_wave_reg_kernel(const IgemmParams p, const ConvGeom g, const WaveAr
         }
         const auto s02 = __builtin_amdgcn_permlane32_swap(pk[0], pk[2], false, false);
         const auto s13 = __builtin_amdgcn_permlane32_swap(pk[1], pk[3], false, false);
-        ds_write16_raw(stage_off + (lane & 31u) * p.n + tn * 32 + khalf * 16, make_uint4(s02[0], s02[1], s13[0], s13[1]));
+        ds_write16(stage_off + (lane & 31u) * p.n + tn * 32 + khalf * 16, make_uint4(s02[0], s02[1], s13[0], s13[1]));
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");         // image complete before it is read back
       const uint32_t pieces = 32u * cpr;
@@ -893,10 +853,10 @@ void q8_conv_wave_ws_kernel(const IgemmParams p, const ConvGeom g, const WaveArg
   {
     const uint32_t pieces = a.w_bytes >> 10;
     const uint8_t* src = reinterpret_cast<const uint8_t*>(p.packed_w) + lane * 16u;
-    for (uint32_t i = wave; i < pieces; i += kWsWaves) dma16(src + i * 1024u, w_lds + i * 1024u);
+    for (uint32_t i = wave; i < pieces; i += kWsWaves) dma16_flat_keep_m0(src + i * 1024u, w_lds + i * 1024u);
     if (wave == kWsWaves - 1 && lane < p.n / 4u) {
       // (lane forms of the requantization: bias + 2^31, the second half of the pair table)
-      dma16(reinterpret_cast<const uint8_t*>(rq_is_lane<SEQ>() ? p.bias2u : p.bias2) + lane * 16u, reinterpret_cast<uint8_t*>(bias_lds));
+      dma16_flat_keep_m0(reinterpret_cast<const uint8_t*>(rq_is_lane<SEQ>() ? p.bias2u : p.bias2) + lane * 16u, reinterpret_cast<uint8_t*>(bias_lds));
     }
   }
   __builtin_amdgcn_sched_barrier(0);
@@ -916,8 +876,7 @@ void q8_conv_wave_ws_kernel(const IgemmParams p, const ConvGeom g, const WaveArg
 
   // ---- the gather pattern of a patch is the same for every unit: per piece u this lane's chunk v = lane + 64 u is pixel
   //      (py, px) of the patch, source chunk (v % cpp) ^ swz(py); only the patch origin moves ----
-  const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(p.input), 0, static_cast<int>(a.units / tiles * p.image_stride), 0x00020000);   // (launcher: < 2^31)
+  const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.input, static_cast<int>(a.units / tiles * p.image_stride));   // (launcher: < 2^31)
   uint32_t rel[NP], pyx[NP];
 #pragma unroll
   for (int u = 0; u < NP; u++) {
@@ -956,8 +915,8 @@ void q8_conv_wave_ws_kernel(const IgemmParams p, const ConvGeom g, const WaveArg
   // the fetched patch: (border units: pixels outside the image become the zero point,) re-centred into LDS, per-pixel
   // channel sums (of a') beside it
   auto fix_up = [&](Raw& r, const Where& w) __attribute__((always_inline)) {
-    const uint32_t patch_off = lds_off(patch);
-    const uint32_t pix_off = lds_off(pix);
+    const uint32_t patch_off = lds_offset(patch);
+    const uint32_t pix_off = lds_offset(pix);
     if (w.border) {
 #pragma unroll
       for (int u = 0; u < NP; u++) {
@@ -977,7 +936,7 @@ void q8_conv_wave_ws_kernel(const IgemmParams p, const ConvGeom g, const WaveArg
         const v4i x = r.x[u];
         if constexpr (CEN) {
           const uint32_t flip = p.a_flip;
-          ds_write16_raw(patch_off + v * 16u, make_uint4(x.x ^ flip, x.y ^ flip, x.z ^ flip, x.w ^ flip));
+          ds_write16(patch_off + v * 16u, make_uint4(x.x ^ flip, x.y ^ flip, x.z ^ flip, x.w ^ flip));
         } else {
         uint32_t sum = __builtin_amdgcn_sad_u8(x.x, 0u, 0u);
         sum = __builtin_amdgcn_sad_u8(x.y, 0u, sum);
@@ -985,8 +944,8 @@ void q8_conv_wave_ws_kernel(const IgemmParams p, const ConvGeom g, const WaveArg
         sum = __builtin_amdgcn_sad_u8(x.w, 0u, sum);
         sum += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(sum), 0xB1, 0xF, 0xF, false));        // lane ^ 1
         if (cpp > 2) sum += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(sum), 0x4E, 0xF, 0xF, false));   // lane ^ 2
-        ds_write16_raw(patch_off + v * 16u, make_uint4(x.x ^ kFlip, x.y ^ kFlip, x.z ^ kFlip, x.w ^ kFlip));
-        ds_write4_raw(pix_off + v * 4u, static_cast<int32_t>(sum) - 128 * static_cast<int32_t>(cin));   // (all cpp lanes of the pixel)
+        ds_write16(patch_off + v * 16u, make_uint4(x.x ^ kFlip, x.y ^ kFlip, x.z ^ kFlip, x.w ^ kFlip));
+        ds_write4(pix_off + v * 4u, static_cast<int32_t>(sum) - 128 * static_cast<int32_t>(cin));   // (all cpp lanes of the pixel)
         }
       }
     }
@@ -999,8 +958,7 @@ void q8_conv_wave_ws_kernel(const IgemmParams p, const ConvGeom g, const WaveArg
   Where here = locate(min(cur, a.units - 1u));
 #pragma unroll
   for (int u = 0; u < NP; u++) fetch_piece(here, u, raw);
-  const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      p.output, 0, static_cast<int>(a.units / tiles * g.OH * g.OW * p.n), 0x00020000);   // (launcher: < 2^31)
+  const __amdgpu_buffer_rsrc_t out_rsrc = buffer_rsrc(p.output, static_cast<int>(a.units / tiles * g.OH * g.OW * p.n));   // (launcher: < 2^31)
   __builtin_amdgcn_sched_barrier(0);
   WS_PRO(2);
   fix_up(raw, here);                                // needs the patch only
@@ -1216,9 +1174,9 @@ void q8_conv_wave_ws16_kernel(const IgemmParams p, const ConvGeom g, const WaveA
   {
     const uint32_t pieces = a.w_bytes >> 10;
     const uint8_t* src = reinterpret_cast<const uint8_t*>(p.packed_w) + lane * 16u;
-    for (uint32_t i = wave; i < pieces; i += kWsWaves) dma16(src + i * 1024u, w_lds + i * 1024u);
+    for (uint32_t i = wave; i < pieces; i += kWsWaves) dma16_flat_keep_m0(src + i * 1024u, w_lds + i * 1024u);
     if (wave == kWsWaves - 1 && lane < p.n / 4u) {
-      dma16(reinterpret_cast<const uint8_t*>(rq_is_lane<SEQ>() ? p.bias2u : p.bias2) + lane * 16u, reinterpret_cast<uint8_t*>(bias_lds));
+      dma16_flat_keep_m0(reinterpret_cast<const uint8_t*>(rq_is_lane<SEQ>() ? p.bias2u : p.bias2) + lane * 16u, reinterpret_cast<uint8_t*>(bias_lds));
     }
   }
   __builtin_amdgcn_sched_barrier(0);
@@ -1232,8 +1190,7 @@ void q8_conv_wave_ws16_kernel(const IgemmParams p, const ConvGeom g, const WaveA
 
   // ---- the gather pattern of a patch: per piece u this lane's chunk v = lane + 64 u is pixel (py, px) of the patch, source
   //      chunk (v & 3) ^ 2 (py & 1); only the patch origin moves ----
-  const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(p.input), 0, static_cast<int>(a.units / tiles * p.image_stride), 0x00020000);   // (launcher: < 2^31)
+  const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.input, static_cast<int>(a.units / tiles * p.image_stride));   // (launcher: < 2^31)
   uint32_t rel[NP], pyx[NP];
 #pragma unroll
   for (int u = 0; u < NP; u++) {
@@ -1269,7 +1226,7 @@ void q8_conv_wave_ws16_kernel(const IgemmParams p, const ConvGeom g, const WaveA
   };
   // the fetched patch: (border units: pixels outside the image become the zero point,) re-centred into LDS
   auto fix_up = [&](Raw& r, const Where& w) __attribute__((always_inline)) {
-    const uint32_t patch_off = lds_off(patch);
+    const uint32_t patch_off = lds_offset(patch);
     if (w.border) {
 #pragma unroll
       for (int u = 0; u < NP; u++) {
@@ -1288,7 +1245,7 @@ void q8_conv_wave_ws16_kernel(const IgemmParams p, const ConvGeom g, const WaveA
       const uint32_t v = lane + u * 64u;
       if ((u + 1) * 64u <= pvec || v < pvec) {             // (only the last piece is partly populated)
         const v4i x = r.x[u];
-        ds_write16_raw(patch_off + v * 16u, make_uint4(x.x ^ flip, x.y ^ flip, x.z ^ flip, x.w ^ flip));
+        ds_write16(patch_off + v * 16u, make_uint4(x.x ^ flip, x.y ^ flip, x.z ^ flip, x.w ^ flip));
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -1300,8 +1257,7 @@ void q8_conv_wave_ws16_kernel(const IgemmParams p, const ConvGeom g, const WaveA
   Where here = locate(min(cur, a.units - 1u));
 #pragma unroll
   for (int u = 0; u < NP; u++) fetch_piece(here, u, raw);
-  const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      p.output, 0, static_cast<int>(a.units / tiles * g.OH * g.OW * p.n), 0x00020000);   // (launcher: < 2^31)
+  const __amdgpu_buffer_rsrc_t out_rsrc = buffer_rsrc(p.output, static_cast<int>(a.units / tiles * g.OH * g.OW * p.n));   // (launcher: < 2^31)
   __builtin_amdgcn_sched_barrier(0);
   fix_up(raw, here);                                // needs the patch only
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1423,17 +1379,11 @@ void q8_conv_wave_ws16_kernel(const IgemmParams p, const ConvGeom g, const WaveA
 template <int TN16, int SEQ, bool FULL>
 int launch_ws16_as(const IgemmParams& p, const ConvGeom& g, const WaveArgs& a, hipStream_t stream)
 {
-  static qnnp::PerDeviceOnce attr_once;   // function attributes are per device
-  if (auto once_scope = attr_once.begin()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&q8_conv_wave_ws16_kernel<TN16, SEQ, FULL>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      (void) hipGetLastError();
-    }
-  }
+  allow_dynamic_lds<&q8_conv_wave_ws16_kernel<TN16, SEQ, FULL>>(160 * 1024);
   const uint32_t want = (a.units + kWsWaves - 1) / kWsWaves;
   const uint32_t grid = want < p.cu_count ? want : p.cu_count;
   hipLaunchKernelGGL((q8_conv_wave_ws16_kernel<TN16, SEQ, FULL>), dim3(grid), dim3(kWsWaves * 64), ws_lds_bytes(a), stream, p, g, a);
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 template <int TN16>
@@ -1450,17 +1400,11 @@ int launch_ws16(const IgemmParams& p, const ConvGeom& g, const WaveArgs& a, hipS
 template <int TN, int CB, int SEQ, bool FULL, bool CEN>
 int launch_ws_as(const IgemmParams& p, const ConvGeom& g, const WaveArgs& a, hipStream_t stream)
 {
-  static qnnp::PerDeviceOnce attr_once;   // function attributes are per device
-  if (auto once_scope = attr_once.begin()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&q8_conv_wave_ws_kernel<TN, CB, SEQ, FULL, CEN>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      (void) hipGetLastError();
-    }
-  }
+  allow_dynamic_lds<&q8_conv_wave_ws_kernel<TN, CB, SEQ, FULL, CEN>>(160 * 1024);
   const uint32_t want = (a.units + kWsWaves - 1) / kWsWaves;
   const uint32_t grid = want < p.cu_count ? want : p.cu_count;
   hipLaunchKernelGGL((q8_conv_wave_ws_kernel<TN, CB, SEQ, FULL, CEN>), dim3(grid), dim3(kWsWaves * 64), ws_lds_bytes(a), stream, p, g, a);
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 template <int TN, int CB>
@@ -1480,17 +1424,11 @@ int launch_reg_as(const IgemmParams& p, const ConvGeom& g, const WaveArgs& a, hi
 {
   constexpr int kRegWaves = reg_waves<TM>();
   constexpr int kRegThreads = kRegWaves * 64;
-  static qnnp::PerDeviceOnce attr_once;   // function attributes are per device
-  if (auto once_scope = attr_once.begin()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&q8_conv_wave_reg_kernel<TM, TN, CB, SEQ, FULL>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      (void) hipGetLastError();
-    }
-  }
+  allow_dynamic_lds<&q8_conv_wave_reg_kernel<TM, TN, CB, SEQ, FULL>>(160 * 1024);
   const uint32_t want = (a.units + kRegWaves - 1) / kRegWaves;
   const uint32_t grid = want < p.cu_count ? want : p.cu_count;
   hipLaunchKernelGGL((q8_conv_wave_reg_kernel<TM, TN, CB, SEQ, FULL>), dim3(grid), dim3(kRegThreads), reg_lds_bytes<TM>(a), stream, p, g, a);
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 template <int TM, int TN, int CB>
@@ -1506,17 +1444,11 @@ int launch_reg(const IgemmParams& p, const ConvGeom& g, const WaveArgs& a, hipSt
 template <int TN, int CB, int KS, int SEQ, bool FULL>
 int launch_as(const IgemmParams& p, const ConvGeom& g, const WaveArgs& a, uint32_t lds_bytes, hipStream_t stream)
 {
-  static qnnp::PerDeviceOnce attr_once;   // function attributes are per device
-  if (auto once_scope = attr_once.begin()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&q8_conv_wave_mfma_kernel<TN, CB, KS, SEQ, FULL>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      (void) hipGetLastError();
-    }
-  }
+  allow_dynamic_lds<&q8_conv_wave_mfma_kernel<TN, CB, KS, SEQ, FULL>>(160 * 1024);
   const uint32_t want = (a.units + kWaves - 1) / kWaves;
   const uint32_t grid = want < p.cu_count ? want : p.cu_count;
   hipLaunchKernelGGL((q8_conv_wave_mfma_kernel<TN, CB, KS, SEQ, FULL>), dim3(grid), dim3(kThreads), lds_bytes, stream, p, g, a);
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 template <int TN, int CB, int KS>

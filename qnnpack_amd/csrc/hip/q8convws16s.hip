@@ -31,6 +31,7 @@
 
 #include <type_traits>
 
+#include "device_ops.hip.h"
 #include "igemm_params.h"
 #include "per_device.h"
 #include "requant.hip.h"
@@ -38,8 +39,6 @@
 namespace qnnp {
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr int kSWaves = 8;
 constexpr uint32_t kSLdsLimit = 160 * 1024;
@@ -56,27 +55,6 @@ struct SArgs {
   uint32_t head_bytes;        // weights + bias, 1024-aligned: offset of the first wave's patch
   uint32_t patch_bytes;       // one wave's patch, 256-aligned
 };
-
-__device__ __forceinline__ uint32_t s_div(uint32_t n, uint32_t inv) { return inv != 0u ? __umulhi(n, inv) : n; }
-
-__device__ __forceinline__ uint32_t s_lds_off(const void* p)
-{
-  return static_cast<uint32_t>(reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) uint8_t*) p));
-}
-
-/* LDS-DMA, 16 bytes per lane (inline asm: q8convwave.hip dma16 says why); M0 restored */
-__device__ __forceinline__ void s_dma16(const uint8_t* src, uint8_t* lds_wave_base)
-{
-  const uint32_t dst = __builtin_amdgcn_readfirstlane(s_lds_off(lds_wave_base));
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
-
-__device__ __forceinline__ void s_ds_write16(uint32_t off, v4i x)
-{
-  asm volatile("ds_write_b128 %0, %1" :: "v"(off), "v"(x) : "memory");
-}
 
 template <int CPP, int TN16, int SEQ, bool FULL>
 __global__ __launch_bounds__(kSWaves * 64, 2)
@@ -96,7 +74,7 @@ void q8_conv_ws16s_kernel(const IgemmParams p, const ConvGeom g, const SArgs a)
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   uint8_t* patch = lds + a.head_bytes + wave * a.patch_bytes;
 
-  const uint32_t range = s_div(blockIdx.x, a.inv_n_tiles);
+  const uint32_t range = div_magic(blockIdx.x, a.inv_n_tiles);
   const uint32_t tile = blockIdx.x - range * a.n_tiles;
   const uint32_t kblocks = p.k_pad / 32;
 
@@ -104,9 +82,9 @@ void q8_conv_ws16s_kernel(const IgemmParams p, const ConvGeom g, const SArgs a)
   {
     const uint32_t pieces = a.w_bytes >> 10;
     const uint8_t* src = reinterpret_cast<const uint8_t*>(p.packed_w) + static_cast<size_t>(tile) * 2u * kblocks * 1024u + lane * 16u;
-    for (uint32_t i = wave; i < pieces; i += kSWaves) s_dma16(src + i * 1024u, w_lds + i * 1024u);
+    for (uint32_t i = wave; i < pieces; i += kSWaves) dma16_flat_keep_m0(src + i * 1024u, w_lds + i * 1024u);
     if (wave == kSWaves - 1 && lane < TN16 * 4u) {
-      s_dma16(reinterpret_cast<const uint8_t*>((rq_is_lane<SEQ>() ? p.bias2u : p.bias2) + tile * 64u) + lane * 16u,
+      dma16_flat_keep_m0(reinterpret_cast<const uint8_t*>((rq_is_lane<SEQ>() ? p.bias2u : p.bias2) + tile * 64u) + lane * 16u,
               reinterpret_cast<uint8_t*>(bias_lds));
     }
   }
@@ -120,8 +98,7 @@ void q8_conv_ws16s_kernel(const IgemmParams p, const ConvGeom g, const SArgs a)
   const uint32_t fg = lane >> 4;                   // K slot of an operand; channel quad of a result
 
   // ---- the gather pattern of a patch: chunk v = lane + 64 u is chunk v % CPP of patch pixel v / CPP; only the origin moves ----
-  const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(p.input), 0, static_cast<int>(a.units / tiles * p.image_stride), 0x00020000);   // (launcher: < 2^31)
+  const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.input, static_cast<int>(a.units / tiles * p.image_stride));   // (launcher: < 2^31)
   uint32_t rel[NP], pyx[NP];
 #pragma unroll
   for (int u = 0; u < NP; u++) {
@@ -136,9 +113,9 @@ void q8_conv_ws16s_kernel(const IgemmParams p, const ConvGeom g, const SArgs a)
   struct Raw { v4i x[NP]; };
   struct Where { uint32_t origin; int32_t iy0, ix0; uint32_t out_img, oy0, ox0; bool border; };   // (wave-uniform)
   auto locate = [&](uint32_t unit) __attribute__((always_inline)) -> Where {
-    const uint32_t img = s_div(unit, a.inv_tiles);
+    const uint32_t img = div_magic(unit, a.inv_tiles);
     const uint32_t rr = unit - img * tiles;
-    const uint32_t tyi = s_div(rr, a.inv_tiles_x);
+    const uint32_t tyi = div_magic(rr, a.inv_tiles_x);
     const uint32_t txi = rr - tyi * a.tiles_x;
     Where w;
     w.oy0 = tyi * 4u;
@@ -157,7 +134,7 @@ void q8_conv_ws16s_kernel(const IgemmParams p, const ConvGeom g, const SArgs a)
   };
   // the fetched patch: (border units: pixels outside the image become the zero point,) re-centred into LDS
   auto fix_up = [&](Raw& r, const Where& w) __attribute__((always_inline)) {
-    const uint32_t patch_off = s_lds_off(patch);
+    const uint32_t patch_off = lds_offset(patch);
     if (w.border) {
 #pragma unroll
       for (int u = 0; u < NP; u++) {
@@ -176,7 +153,7 @@ void q8_conv_ws16s_kernel(const IgemmParams p, const ConvGeom g, const SArgs a)
       const uint32_t v = lane + u * 64u;
       if ((u + 1) * 64u <= pvec || v < pvec) {             // (only the last piece is partly populated)
         const v4i x = r.x[u];
-        s_ds_write16(patch_off + v * 16u, v4i{x.x ^ flip, x.y ^ flip, x.z ^ flip, x.w ^ flip});
+        ds_write16(patch_off + v * 16u, v4i{x.x ^ flip, x.y ^ flip, x.z ^ flip, x.w ^ flip});
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -188,8 +165,8 @@ void q8_conv_ws16s_kernel(const IgemmParams p, const ConvGeom g, const SArgs a)
   Where here = locate(min(cur, a.units - 1u));
 #pragma unroll
   for (int u = 0; u < NP; u++) fetch_piece(here, u, raw);
-  const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      p.output, 0, static_cast<int>((a.units / tiles * g.OH * g.OW - 1u) * p.output_stride + p.n), 0x00020000);   // (launcher: < 2^31)
+  const __amdgpu_buffer_rsrc_t out_rsrc = buffer_rsrc(
+      p.output, static_cast<int>((a.units / tiles * g.OH * g.OW - 1u) * p.output_stride + p.n));   // (launcher: < 2^31)
   __builtin_amdgcn_sched_barrier(0);
   fix_up(raw, here);                                // needs the patch only
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -309,10 +286,10 @@ inline bool make_sargs(const IgemmParams& p, const ConvGeom& g, uint32_t batch, 
   const uint64_t tiles = static_cast<uint64_t>(a->tiles_x) * a->tiles_y;
   if (static_cast<uint64_t>(batch) * tiles * tiles >= (UINT64_C(1) << 32)) return false;
   a->units = batch * a->tiles_x * a->tiles_y;
-  a->inv_tiles = tiles > 1 ? static_cast<uint32_t>(((UINT64_C(1) << 32) + tiles - 1) / tiles) : 0u;
-  a->inv_tiles_x = a->tiles_x > 1 ? static_cast<uint32_t>(((UINT64_C(1) << 32) + a->tiles_x - 1) / a->tiles_x) : 0u;
+  a->inv_tiles = reciprocal_ceil(static_cast<uint32_t>(tiles));
+  a->inv_tiles_x = reciprocal_ceil(a->tiles_x);
   a->n_tiles = (p.n + 63u) / 64u;
-  a->inv_n_tiles = a->n_tiles > 1 ? static_cast<uint32_t>(((UINT64_C(1) << 32) + a->n_tiles - 1) / a->n_tiles) : 0u;
+  a->inv_n_tiles = reciprocal_ceil(a->n_tiles);
   const uint32_t want = (a->units + kSWaves - 1) / kSWaves;
   // workgroups per CU the unit ranges are cut for, measured per channel count (profiles/r06/conv3x3_small_channels_per_cu_r06zd.txt):
   // 16 channels (<= 122 registers: two 8-wave workgroups share a CU) 2 -- 55x55 16 -> 64 10.8 -> 10.3 us; 48 channels 3 -- one
@@ -341,15 +318,9 @@ int launch_s(const IgemmParams& p, const ConvGeom& g, const SArgs& a, uint32_t l
   requant_dispatch_lane(p.rq, p.lane, [&](auto seq, auto full) {
     constexpr int kSeq = decltype(seq)::value;
     constexpr bool kFull = decltype(full)::value;
-    static qnnp::PerDeviceOnce attr_once;   // function attributes are per device
-    if (auto once_scope = attr_once.begin()) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&q8_conv_ws16s_kernel<CPP, TN16, kSeq, kFull>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-        (void) hipGetLastError();
-      }
-    }
+    allow_dynamic_lds<&q8_conv_ws16s_kernel<CPP, TN16, kSeq, kFull>>(160 * 1024);
     hipLaunchKernelGGL((q8_conv_ws16s_kernel<CPP, TN16, kSeq, kFull>), dim3(a.ranges * a.n_tiles), dim3(kSWaves * 64), lds_bytes, stream, p, g, a);
-    rc = hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+    rc = launch_status();
   });
   return rc;
 }

@@ -24,6 +24,7 @@
 
 #include <stdint.h>
 
+#include "device_ops.hip.h"
 #include "igemm_epilogue.hip.h"
 #include "igemm_params.h"
 #include "per_device.h"
@@ -32,9 +33,6 @@
 namespace qnnp {
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int kWaves = 8;                     // per workgroup: the sub-kernels are staged once per eight units
 constexpr int kThreads = kWaves * 64;
@@ -244,20 +242,15 @@ void q8_deconv_s2_stream_kernel(const DeconvParams p)
 template <int CB, int KH, int KW, int SEQ, bool FULL>
 int launch_flavour(const DeconvParams& p, uint32_t lds_bytes, hipStream_t stream)
 {
-  static PerDeviceOnce attr_once;
-  if (auto once_scope = attr_once.begin()) {
-    (void) hipFuncSetAttribute(reinterpret_cast<const void*>(&q8_deconv_s2_stream_kernel<CB, KH, KW, SEQ, FULL>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kMaxLds));
-  }
+  allow_dynamic_lds<&q8_deconv_s2_stream_kernel<CB, KH, KW, SEQ, FULL>>(static_cast<int>(kMaxLds));
   const uint32_t total = p.batch * p.BH * p.BW;
   const uint32_t units = (total + 31u) / 32u;
   // one unit per wave while the waves are resident all at once; persistent beyond
-  const int cus = qnnp_hip_compute_units();
-  const uint32_t max_blocks = static_cast<uint32_t>(cus > 0 ? cus : 256) * static_cast<uint32_t>(resident(CB) * 4 / kWaves);
+  const uint32_t max_blocks = active_cu_count() * static_cast<uint32_t>(resident(CB) * 4 / kWaves);
   uint32_t blocks = (units + kWaves - 1) / kWaves;
   if (blocks > max_blocks) blocks = max_blocks;
   hipLaunchKernelGGL((q8_deconv_s2_stream_kernel<CB, KH, KW, SEQ, FULL>), dim3(blocks), dim3(kThreads), lds_bytes, stream, p);
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 template <int CB, int KH, int KW>

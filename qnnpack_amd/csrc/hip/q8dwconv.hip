@@ -37,14 +37,23 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "device_ops.hip.h"
 #include "igemm_epilogue.hip.h"
 #include "igemm_params.h"
+#include "per_device.h"
 #include "qnnp_hip.h"
 #include "requant.hip.h"
 
 extern "C" void* qnnp_hip_get_stream(void);
 
 namespace {
+
+using qnnp::buffer_rsrc;
+using qnnp::div_magic;
+using qnnp::launch_status;
+using qnnp::reciprocal_ceil;
+using qnnp::v4i;
+using qnnp::v16i;
 
 typedef short v2s __attribute__((ext_vector_type(2)));
 
@@ -144,8 +153,7 @@ void q8_dwconv_direct4_kernel(const DwParams p)
   const uint64_t total = static_cast<uint64_t>(p.batch) * p.OH * p.OW * q4;
   // (the extent rounded up to whole dwords: the dword holding the tensor's last bytes must not read as out of range)
   const uint64_t in_bytes = ((static_cast<uint64_t>(p.batch) * p.H * p.W - 1u) * p.in_stride + p.C + 3u) & ~static_cast<uint64_t>(3);
-  const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(p.input), 0, static_cast<int>(in_bytes), 0x00020000);         // (make_plan: < 2^31 bytes)
+  const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.input, static_cast<int>(in_bytes));         // (make_plan: < 2^31 bytes)
   // (32-bit index arithmetic -- make_plan: fewer than 2^32 channel groups in all -- a 64-bit division costs ~100 instructions)
   const uint32_t total32 = static_cast<uint32_t>(total);
   for (uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total32; idx += gridDim.x * blockDim.x) {
@@ -611,14 +619,14 @@ int launch_row(const DwParams& p, hipStream_t stream, bool unaligned = false)
   if (unaligned) {
     if (p.sw == 1) hipLaunchKernelGGL((q8_dwconv_row3x3_kernel<1, true>), dim3(static_cast<uint32_t>(blocks)), dim3(kRowThreads), 0, stream, p);
     else hipLaunchKernelGGL((q8_dwconv_row3x3_kernel<2, true>), dim3(static_cast<uint32_t>(blocks)), dim3(kRowThreads), 0, stream, p);
-    return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+    return launch_status();
   }
   if (p.sw == 1) {
     hipLaunchKernelGGL(q8_dwconv_row3x3_kernel<1>, dim3(static_cast<uint32_t>(blocks)), dim3(kRowThreads), 0, stream, p);
   } else {
     hipLaunchKernelGGL(q8_dwconv_row3x3_kernel<2>, dim3(static_cast<uint32_t>(blocks)), dim3(kRowThreads), 0, stream, p);
   }
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 // --------------------------------------------------------------------------
@@ -744,8 +752,7 @@ __device__ __forceinline__ void dwconv_col3x3_body(
   // Buffer addressing: a descriptor over the whole tensor (built from kernel arguments only, so it stays in SGPRs),
   // per lane a constant 32-bit byte offset inside a row, per row a SCALAR offset -- no vector address arithmetic in
   // the loop. Invalid columns are clamped to column 0 (their value is replaced below).
-  const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(p.input), 0, static_cast<int>(p.batch * p.H * row_bytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.input, static_cast<int>(p.batch * p.H * row_bytes));
   const int32_t ix0 = static_cast<int32_t>(ox * S) - static_cast<int32_t>(p.pad_left);
   uint32_t coff[3];
   coff[0] = cg + (ok0 ? static_cast<uint32_t>(ix0) : 0u) * p.in_stride;
@@ -881,8 +888,7 @@ __device__ __forceinline__ void dwconv_col3x3_body(
     }
   };
 
-  const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      p.output, 0, static_cast<int>(p.batch * p.OH * p.OW * p.out_stride), 0x00020000);
+  const __amdgpu_buffer_rsrc_t out_rsrc = buffer_rsrc(p.output, static_cast<int>(p.batch * p.OH * p.OW * p.out_stride));
   const uint32_t out_voff = ox * p.out_stride + cg;
   uint32_t out_soff = (n * p.OH + (DIL ? rho + out_rows * oy0 : oy0)) * p.OW * p.out_stride;   // scalar, advances one output row (DIL: p.dh rows) per step
 #ifdef QNNP_ENABLE_ABLATION
@@ -1191,10 +1197,9 @@ void q8_dwconv_col3x3_kernel(const DwParams p)
   uint32_t w = __builtin_amdgcn_readfirstlane(b * (kColThreads / 64) + (threadIdx.x >> 6));
   // (divisions by run-time values through host-made reciprocals: ~40 instructions each otherwise, on every wave's way
   //  to its first load; exact while dividend * divisor < 2^32, which plan_col checks)
-  auto div_by = [](uint32_t x, uint32_t inv) __attribute__((always_inline)) { return inv != 0u ? __umulhi(x, inv) : x; };
-  const uint32_t wb = div_by(w, p.inv_bands);
+  const uint32_t wb = div_magic(w, p.inv_bands);
   const uint32_t chunk = w - wb * p.bands;
-  const uint32_t n = div_by(wb, p.inv_slabs);
+  const uint32_t n = div_magic(wb, p.inv_slabs);
   const uint32_t seg = wb - n * p.slabs;
   if (n >= p.batch) return;
   const uint32_t q4 = p.C >> 2;
@@ -1202,14 +1207,14 @@ void q8_dwconv_col3x3_kernel(const DwParams p)
   // lanes past the end of the row repeat its last dword column: same loads, same results, same stores -- harmless
   uint32_t j = chunk * 64u + lane;
   if (j >= cols) j = cols - 1u;
-  const uint32_t ox = div_by(j, p.inv_q4);
+  const uint32_t ox = div_magic(j, p.inv_q4);
   const uint32_t cg = (j - ox * q4) * 4u;
   // DIL: segment index -> (segment of a residue class of the output rows, residue); `slabs` counts both
   uint32_t rho = 0, rows = p.OH, sidx = seg;
   if constexpr (DIL) {
-    sidx = div_by(seg, p.inv_dh);
+    sidx = div_magic(seg, p.inv_dh);
     rho = seg - sidx * p.dh;
-    rows = rho < p.OH ? div_by(p.OH - rho + p.dh - 1u, p.inv_dh) : 0u;       // output rows rho, rho + dh, ...
+    rows = rho < p.OH ? div_magic(p.OH - rho + p.dh - 1u, p.inv_dh) : 0u;       // output rows rho, rho + dh, ...
   }
   const uint32_t oy0 = sidx * p.TOH;
   if (DIL && oy0 >= rows) return;
@@ -1316,11 +1321,10 @@ bool col_uses_dot4(const DwParams& p)
 int launch_col(const DwParams& geometry, hipStream_t stream)
 {
   DwParams p = geometry;
-  auto reciprocal = [](uint32_t d) { return d > 1u ? static_cast<uint32_t>(((UINT64_C(1) << 32) + d - 1u) / d) : 0u; };
-  p.inv_dh = reciprocal(p.dh);
-  p.inv_bands = reciprocal(p.bands);
-  p.inv_slabs = reciprocal(p.slabs);
-  p.inv_q4 = reciprocal(p.C / 4u);
+  p.inv_dh = reciprocal_ceil(p.dh);
+  p.inv_bands = reciprocal_ceil(p.bands);
+  p.inv_slabs = reciprocal_ceil(p.slabs);
+  p.inv_q4 = reciprocal_ceil(p.C / 4u);
   p.xcd_ranges = (static_cast<uint64_t>(p.batch) * p.H * p.W * p.in_stride +
                   static_cast<uint64_t>(p.batch) * p.OH * p.OW * p.out_stride) <= (UINT64_C(96) << 20) ? 1u : 0u;
   const uint64_t waves = static_cast<uint64_t>(p.batch) * p.slabs * p.bands;
@@ -1355,7 +1359,7 @@ int launch_col(const DwParams& geometry, hipStream_t stream)
       hipLaunchKernelGGL((q8_dwconv_col3x3_kernel<2, kSeq, kFull, false, false>), dim3(blocks), dim3(kColThreads), 0, stream, p);
     }
   });
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 // --------------------------------------------------------------------------
@@ -1394,8 +1398,7 @@ __device__ __forceinline__ void dwconv_col5x5_body(
   const uint32_t fill = p.izp * 0x01010101u;
   const uint32_t row_bytes = p.W * p.in_stride;
   // buffer addressing as kernel G: per lane constant byte offsets inside a row, per row a SCALAR offset
-  const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(p.input), 0, static_cast<int>(p.batch * p.H * row_bytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.input, static_cast<int>(p.batch * p.H * row_bytes));
   const int32_t ix0 = static_cast<int32_t>(ox * S) - static_cast<int32_t>(p.pad_left);
   uint32_t coff[5];
 #pragma unroll
@@ -1460,8 +1463,7 @@ __device__ __forceinline__ void dwconv_col5x5_body(
     v[3] = __builtin_amdgcn_perm(e, v[3], 0x07030201u);
   };
 
-  const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      p.output, 0, static_cast<int>(p.batch * p.OH * p.OW * p.out_stride), 0x00020000);
+  const __amdgpu_buffer_rsrc_t out_rsrc = buffer_rsrc(p.output, static_cast<int>(p.batch * p.OH * p.OW * p.out_stride));
   const uint32_t out_voff = ox * p.out_stride + cg;
   uint32_t out_soff = (n * p.OH + oy0) * p.OW * p.out_stride;       // scalar, advances one output row per step
   const uint32_t out_step = p.OW * p.out_stride;
@@ -1605,17 +1607,16 @@ void q8_dwconv_col5x5_kernel(const DwParams p)
     b = (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + (b >> 3);
   }
   const uint32_t w = __builtin_amdgcn_readfirstlane(b * (kColThreads / 64) + (threadIdx.x >> 6));
-  auto div_by = [](uint32_t x, uint32_t inv) __attribute__((always_inline)) { return inv != 0u ? __umulhi(x, inv) : x; };
-  const uint32_t wb = div_by(w, p.inv_bands);
+  const uint32_t wb = div_magic(w, p.inv_bands);
   const uint32_t chunk = w - wb * p.bands;
-  const uint32_t n = div_by(wb, p.inv_slabs);
+  const uint32_t n = div_magic(wb, p.inv_slabs);
   const uint32_t seg = wb - n * p.slabs;
   if (n >= p.batch) return;
   const uint32_t q4 = p.C >> 2;
   const uint32_t cols = p.OW * q4;
   uint32_t j = chunk * 64u + lane;
   if (j >= cols) j = cols - 1u;                    // lanes past the end repeat the last dword column: harmless
-  const uint32_t ox = div_by(j, p.inv_q4);
+  const uint32_t ox = div_magic(j, p.inv_q4);
   const uint32_t cg = (j - ox * q4) * 4u;
   const uint32_t oy0 = seg * p.TOH;
   const uint32_t oy1 = min(p.OH, oy0 + p.TOH);
@@ -1677,10 +1678,9 @@ bool plan_col5(DwParams& p)
 int launch_col5(const DwParams& geometry, hipStream_t stream)
 {
   DwParams p = geometry;
-  auto reciprocal = [](uint32_t d) { return d > 1u ? static_cast<uint32_t>(((UINT64_C(1) << 32) + d - 1u) / d) : 0u; };
-  p.inv_bands = reciprocal(p.bands);
-  p.inv_slabs = reciprocal(p.slabs);
-  p.inv_q4 = reciprocal(p.C / 4u);
+  p.inv_bands = reciprocal_ceil(p.bands);
+  p.inv_slabs = reciprocal_ceil(p.slabs);
+  p.inv_q4 = reciprocal_ceil(p.C / 4u);
   p.xcd_ranges = (static_cast<uint64_t>(p.batch) * p.H * p.W * p.in_stride +
                   static_cast<uint64_t>(p.batch) * p.OH * p.OW * p.out_stride) <= (UINT64_C(96) << 20) ? 1u : 0u;
   const uint64_t waves = static_cast<uint64_t>(p.batch) * p.slabs * p.bands;
@@ -1694,7 +1694,7 @@ int launch_col5(const DwParams& geometry, hipStream_t stream)
       hipLaunchKernelGGL((q8_dwconv_col5x5_kernel<2, kSeq, kFull>), dim3(blocks), dim3(kColThreads), 0, stream, p);
     }
   });
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 // --------------------------------------------------------------------------
@@ -1716,8 +1716,6 @@ int launch_col5(const DwParams& geometry, hipStream_t stream)
  * of 32 consecutive output pixels of the flattened (image, row, column) index space.
  */
 constexpr int kMfThreads = 256;
-typedef int dw_v4i __attribute__((ext_vector_type(4)));
-typedef int dw_v16i __attribute__((ext_vector_type(16)));
 
 template <int KH, int KW, int PARTS>
 __global__ __launch_bounds__(kMfThreads, 4)
@@ -1746,12 +1744,12 @@ void q8_dwconv_mfma_kernel(const DwParams p)
     const bool mine = (m >> 4) == khalf;
     const uint32_t val = mine ? x << ((m & 3u) * 8u) : 0u;
     const uint32_t dw = (m & 15u) >> 2;
-    dw_v4i v;
+    v4i v;
     v.x = static_cast<int>(dw == 0 ? val : 0u);
     v.y = static_cast<int>(dw == 1 ? val : 0u);
     v.z = static_cast<int>(dw == 2 ? val : 0u);
     v.w = static_cast<int>(dw == 3 ? val : 0u);
-    *reinterpret_cast<dw_v4i*>(lds_w + f * 1024 + lane * 16) = v;
+    *reinterpret_cast<v4i*>(lds_w + f * 1024 + lane * 16) = v;
   }
   if (tid < 32) lds_bias[tid] = p.dwm_bias[cb * 32 + tid];
   __syncthreads();
@@ -1788,7 +1786,7 @@ void q8_dwconv_mfma_kernel(const DwParams p)
       const int32_t ix0 = static_cast<int32_t>(ox * p.sw) - static_cast<int32_t>(p.pad_left);
 
       // all tap operands first (independent loads in flight together), then the multiplies
-      dw_v4i a[TAPS];
+      v4i a[TAPS];
       bool ok[TAPS];
 #pragma unroll
       for (int ky = 0; ky < KH; ky++) {
@@ -1800,14 +1798,14 @@ void q8_dwconv_mfma_kernel(const DwParams p)
           const bool o = row_ok && ix >= 0 && ix < static_cast<int32_t>(p.W);
           const uint32_t pix = o ? img_off + static_cast<uint32_t>(iy) * p.W + static_cast<uint32_t>(ix) : 0u;
           ok[ky * KW + kx] = o;
-          a[ky * KW + kx] = *reinterpret_cast<const dw_v4i*>(in_c + static_cast<uint64_t>(pix) * p.in_stride);
+          a[ky * KW + kx] = *reinterpret_cast<const v4i*>(in_c + static_cast<uint64_t>(pix) * p.in_stride);
         }
       }
       // the diagonal operands are re-read from LDS for every tile ON PURPOSE: left to itself the compiler
       // hoists the 18 loop-invariant reads (72 VGPRs) out of the tile loop and spills
       uint32_t w_off = lane * 16;
       asm volatile("" : "+v"(w_off));
-      dw_v16i acc;
+      v16i acc;
 #pragma unroll
       for (int rg = 0; rg < 4; rg++) {
         const int4 b = *reinterpret_cast<const int4*>(&lds_bias[rg * 8 + khalf * 4]);
@@ -1815,14 +1813,14 @@ void q8_dwconv_mfma_kernel(const DwParams p)
       }
 #pragma unroll
       for (int t = 0; t < TAPS; t++) {
-        dw_v4i v = a[t];
+        v4i v = a[t];
         v.x = static_cast<int>((ok[t] ? static_cast<uint32_t>(v.x) : fill) ^ 0x80808080u);
         v.y = static_cast<int>((ok[t] ? static_cast<uint32_t>(v.y) : fill) ^ 0x80808080u);
         v.z = static_cast<int>((ok[t] ? static_cast<uint32_t>(v.z) : fill) ^ 0x80808080u);
         v.w = static_cast<int>((ok[t] ? static_cast<uint32_t>(v.w) : fill) ^ 0x80808080u);
 #pragma unroll
         for (int part = 0; part < PARTS; part++) {
-          const dw_v4i w = *reinterpret_cast<const dw_v4i*>(lds_w + (t * PARTS + part) * 1024 + w_off);
+          const v4i w = *reinterpret_cast<const v4i*>(lds_w + (t * PARTS + part) * 1024 + w_off);
           acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(w, v, acc, 0, 0, 0);
         }
       }
@@ -1860,7 +1858,7 @@ int launch_mfma(const DwParams& p, hipStream_t stream)
     case 2: hipLaunchKernelGGL((q8_dwconv_mfma_kernel<KH, KW, 2>), grid, dim3(kMfThreads), 0, stream, p); break;
     default: hipLaunchKernelGGL((q8_dwconv_mfma_kernel<KH, KW, 3>), grid, dim3(kMfThreads), 0, stream, p); break;
   }
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 // --------------------------------------------------------------------------
@@ -1992,7 +1990,7 @@ void q8_dwconv_mfma_lds_kernel(const DwParams p)
     const bool mine = (m >> 4) == khalf;
     const uint32_t val = mine ? x << ((m & 3u) * 8u) : 0u;
     const uint32_t dw = (m & 15u) >> 2;
-    dw_v4i v;
+    v4i v;
     v.x = static_cast<int>(dw == 0 ? val : 0u);
     v.y = static_cast<int>(dw == 1 ? val : 0u);
     v.z = static_cast<int>(dw == 2 ? val : 0u);
@@ -2006,13 +2004,13 @@ void q8_dwconv_mfma_lds_kernel(const DwParams p)
   for (int part = 0; part < PARTS; part++) {
 #pragma unroll
     for (int t = 0; t < 9; t++) {
-      const dw_v4i v = diag(xb[part * 9 + t]);
+      const v4i v = diag(xb[part * 9 + t]);
       if (part > 0) {
         const bool nz = (v.x | v.y | v.z | v.w) != 0;
         if (__builtin_amdgcn_ballot_w64(nz) != 0) extra_mask |= 1u << ((part - 1) * 9 + t);
       }
       if (part == 0) {
-        if (wave == 0) *reinterpret_cast<dw_v4i*>(w_extra + t * 1024 + lane * 16) = v;
+        if (wave == 0) *reinterpret_cast<v4i*>(w_extra + t * 1024 + lane * 16) = v;
       } else {
         // parts beyond the first are needed by few taps: kept as 32 bytes per (part, tap), the operand is
         // rebuilt from its byte on demand
@@ -2059,7 +2057,7 @@ void q8_dwconv_mfma_lds_kernel(const DwParams p)
         const uint8_t* base = tile + (oyl * p.sh) * row_pitch + (ox * p.sw) * 32u + khalf * 16u;
         uint32_t w_off = lane * 16;                // opaque per tile: keeps the compiler from hoisting the nine
         asm volatile("" : "+v"(w_off));            // loop-invariant operand reads (36 VGPRs) out of the loop
-        dw_v16i acc;
+        v16i acc;
 #pragma unroll
         for (int rg = 0; rg < 4; rg++) {
           const int4 bv = *reinterpret_cast<const int4*>(&lds_bias[rg * 8 + khalf * 4]);
@@ -2069,14 +2067,14 @@ void q8_dwconv_mfma_lds_kernel(const DwParams p)
         for (int ky = 0; ky < 3; ky++) {
 #pragma unroll
           for (int kx = 0; kx < 3; kx++) {
-            const dw_v4i a = *reinterpret_cast<const dw_v4i*>(base + (ky * p.dh) * row_pitch + (kx * p.dw) * 32u);
-            const dw_v4i w0 = *reinterpret_cast<const dw_v4i*>(w_extra + (ky * 3 + kx) * 1024 + w_off);
+            const v4i a = *reinterpret_cast<const v4i*>(base + (ky * p.dh) * row_pitch + (kx * p.dw) * 32u);
+            const v4i w0 = *reinterpret_cast<const v4i*>(w_extra + (ky * 3 + kx) * 1024 + w_off);
             acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(w0, a, acc, 0, 0, 0);
             if constexpr (PARTS > 1) {
 #pragma unroll
               for (int part = 1; part < PARTS; part++) {
                 if ((extra_mask >> ((part - 1) * 9 + ky * 3 + kx)) & 1u) {      // wave-uniform, rarely taken
-                  const dw_v4i w = diag(w_extra[9 * 1024 + ((part - 1) * 9 + ky * 3 + kx) * 32 + m]);
+                  const v4i w = diag(w_extra[9 * 1024 + ((part - 1) * 9 + ky * 3 + kx) * 32 + m]);
                   acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(w, a, acc, 0, 0, 0);
                 }
               }
@@ -2149,7 +2147,7 @@ int launch_mfma_lds(const DwParams& p, hipStream_t stream)
     case 2: hipLaunchKernelGGL((q8_dwconv_mfma_lds_kernel<2>), dim3(blocks), dim3(kMlThreads), lds_bytes, stream, p); break;
     default: hipLaunchKernelGGL((q8_dwconv_mfma_lds_kernel<3>), dim3(blocks), dim3(kMlThreads), lds_bytes, stream, p); break;
   }
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 constexpr uint32_t kDwLdsBudgetDefault = 48 * 1024;   // bytes per workgroup (3 workgroups per CU)
@@ -2211,7 +2209,7 @@ int launch_lds(const DwParams& p, bool vec16, hipStream_t stream)
     if (dw1) QNNP_DW_LAUNCH(4, true); else QNNP_DW_LAUNCH(4, false);
   }
 #undef QNNP_DW_LAUNCH
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 // --------------------------------------------------------------------------
@@ -2252,7 +2250,6 @@ template <int TN, int SEQ, bool FULL>
 __global__ __launch_bounds__(kM16Threads, TN >= 3 ? 2 : 3)
 void q8_dwconv_mfma16_3x3_kernel(const DwParams p)
 {
-  typedef int m16_v4i __attribute__((ext_vector_type(4)));
   // wave-private row buffers: a row of the wave's 18 pixels x TN chunks is fetched with ONE 16-byte load per lane -- lane i takes
   // chunk i % TN of pixel i / TN: a pixel's 16 TN bytes are contiguous, so the load touches ~6 lines per 16-lane group where the
   // fragment pattern itself (16 pixels at the pixel stride per group) touched 16-18 and bound the first build by address processing
@@ -2264,17 +2261,16 @@ void q8_dwconv_mfma16_3x3_kernel(const DwParams p)
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t fp = lane & 15u;                 // operand: position; result: position
   const uint32_t fg = lane >> 4;                  // operand: tap slot (kernel column); result: channel quad
-  auto div_by = [](uint32_t x, uint32_t inv) __attribute__((always_inline)) { return inv != 0u ? __umulhi(x, inv) : x; };
   // wave -> (image, row segment, strip of 16 columns, channel group): channel groups fastest, so that the waves of a workgroup
   // read the same pixels' lines
   const uint32_t wave_in_wg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * (kM16Threads / 64) + wave_in_wg);
   const uint32_t cgroups = p.IR, strips = p.bands;
-  const uint32_t w1 = div_by(w, p.inv_q4);        // / cgroups
+  const uint32_t w1 = div_magic(w, p.inv_q4);        // / cgroups
   const uint32_t cgrp = w - w1 * cgroups;
-  const uint32_t w2 = div_by(w1, p.inv_bands);    // / strips
+  const uint32_t w2 = div_magic(w1, p.inv_bands);    // / strips
   const uint32_t strip = w1 - w2 * strips;
-  const uint32_t n = div_by(w2, p.inv_slabs);     // / segments
+  const uint32_t n = div_magic(w2, p.inv_slabs);     // / segments
   const uint32_t seg = w2 - n * p.slabs;
   if (n >= p.batch) return;
   const uint32_t c0 = cgrp * (16u * TN);
@@ -2291,8 +2287,7 @@ void q8_dwconv_mfma16_3x3_kernel(const DwParams p)
   const int32_t lix = static_cast<int32_t>(x0 + lpix) - static_cast<int32_t>(p.pad_left);
   const bool lcol_ok = loader && lix >= 0 && lix < static_cast<int32_t>(p.W);
   const uint32_t row_bytes = p.W * p.in_stride;
-  const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(p.input), 0, static_cast<int>(p.batch * p.H * row_bytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.input, static_cast<int>(p.batch * p.H * row_bytes));
   // (an offset beyond the descriptor's extent: the load returns 0 -- plan_m16 keeps the tensor below 2^31 bytes)
   const uint32_t coff = lcol_ok ? static_cast<uint32_t>(lix) * p.in_stride + c0 + 16u * lchunk : 0x80000000u;
   const uint32_t fillraw = lcol_ok ? p.izp * 0x01010101u : 0u;                     // what a padding ROW holds at this lane's column
@@ -2302,7 +2297,7 @@ void q8_dwconv_mfma16_3x3_kernel(const DwParams p)
   const uint32_t rd_off = ((fp + min(fg, 2u)) * kPitch) * 16u;                     // + tn * 16
 
   // ---- weights: the diagonal fragments, from the dot-product image ((x_r0, x_r1, x_r2, 0) per channel) ----
-  m16_v4i wf[3][TN];
+  v4i wf[3][TN];
 #pragma unroll
   for (int ky = 0; ky < 3; ky++) {
 #pragma unroll
@@ -2310,14 +2305,14 @@ void q8_dwconv_mfma16_3x3_kernel(const DwParams p)
       const uint32_t word = p.dot4[ky * p.c_pad + c0 + 16u * tn + fp];
       const uint32_t b = ((word >> (8u * fg)) & 0xFFu) << (8u * (fp & 3u));        // (slot 3: the image's fourth byte is 0)
       const uint32_t q = fp >> 2;
-      wf[ky][tn] = m16_v4i{static_cast<int>(q == 0u ? b : 0u), static_cast<int>(q == 1u ? b : 0u),
+      wf[ky][tn] = v4i{static_cast<int>(q == 0u ? b : 0u), static_cast<int>(q == 1u ? b : 0u),
                            static_cast<int>(q == 2u ? b : 0u), static_cast<int>(q == 3u ? b : 0u)};
     }
   }
   // ---- bias of this lane's result channels 16 tn + 4 fg + r (+ 2^31 for the offset rounding forms) ----
   const uint32_t ox = x0 + fp;
   const bool pos_ok = ox < p.OW;
-  m16_v4i bias[TN];
+  v4i bias[TN];
   {
     // taps of this lane's POSITION that read outside the image: 0 was multiplied where the zero point belongs
     const int32_t ixb = static_cast<int32_t>(ox) - static_cast<int32_t>(p.pad_left);
@@ -2345,13 +2340,12 @@ void q8_dwconv_mfma16_3x3_kernel(const DwParams p)
           }
         }
       }
-      bias[tn] = m16_v4i{qnnp::with_rq_offset<SEQ>(b[0]), qnnp::with_rq_offset<SEQ>(b[1]),
+      bias[tn] = v4i{qnnp::with_rq_offset<SEQ>(b[0]), qnnp::with_rq_offset<SEQ>(b[1]),
                          qnnp::with_rq_offset<SEQ>(b[2]), qnnp::with_rq_offset<SEQ>(b[3])};
     }
   }
 
-  const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      p.output, 0, static_cast<int>(p.batch * p.OH * p.OW * p.out_stride), 0x00020000);
+  const __amdgpu_buffer_rsrc_t out_rsrc = buffer_rsrc(p.output, static_cast<int>(p.batch * p.OH * p.OW * p.out_stride));
   // after the lane transpose lane (position, g) holds channel block g: 16 bytes (lanes with g >= TN hold nothing). Stored like that,
   // a pixel's 16 TN bytes would leave in TN separate 16-byte pieces from lanes 16 apart (the first build: layer 8 at 65 us); they go
   // through the wave's LDS image once more and leave in the LOADER's lane order -- lane i = chunk i % TN of position i / TN, a
@@ -2365,14 +2359,14 @@ void q8_dwconv_mfma16_3x3_kernel(const DwParams p)
   const uint32_t out_img = n * p.OH * out_row;
 
   // ---- the walk: t = input row + pad_top; row t feeds kernel row 0 of output row t, row 1 of t - 1, row 2 of t - 2 ----
-  m16_v4i raw[6];                                 // SIX rows in flight (this lane's chunk): row t lives in raw[t % 6]
-  m16_v4i acc[3][TN];                             // output row oy accumulates in set oy % 3
+  v4i raw[6];                                 // SIX rows in flight (this lane's chunk): row t lives in raw[t % 6]
+  v4i acc[3][TN];                             // output row oy accumulates in set oy % 3
   auto request = [&](auto ph_c, int32_t t) __attribute__((always_inline)) {
     constexpr int PH = decltype(ph_c)::value;                                        // 0 .. 5
     int32_t iy = t - static_cast<int32_t>(p.pad_top);
     iy = iy < 0 ? 0 : (iy >= static_cast<int32_t>(p.H) ? static_cast<int32_t>(p.H) - 1 : iy);      // (scalar; replaced where consumed)
     const uint32_t ro = img_off + static_cast<uint32_t>(iy) * row_bytes;
-    raw[PH] = __builtin_bit_cast(m16_v4i, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, coff, ro, 0));
+    raw[PH] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, coff, ro, 0));
   };
   // The row an earlier step completed is finished one step LATER, in two halves around the next row's LDS round trip and MFMAs, so
   // that nothing in a step waits for what the step itself started (the first build ran write -> read -> MFMA -> requantize -> write
@@ -2388,10 +2382,10 @@ void q8_dwconv_mfma16_3x3_kernel(const DwParams p)
     const auto s13 = __builtin_amdgcn_permlane32_swap(q[1], q[3], false, false);
     const auto tlo = __builtin_amdgcn_permlane16_swap(s02[0], s13[0], false, false);
     const auto thi = __builtin_amdgcn_permlane16_swap(s02[1], s13[1], false, false);
-    const m16_v4i blk = {static_cast<int>(tlo[0]), static_cast<int>(tlo[1]), static_cast<int>(thi[0]), static_cast<int>(thi[1])};
-    if (fg < static_cast<uint32_t>(TN)) *reinterpret_cast<m16_v4i*>(outbuf + ow_off) = blk;
+    const v4i blk = {static_cast<int>(tlo[0]), static_cast<int>(tlo[1]), static_cast<int>(thi[0]), static_cast<int>(thi[1])};
+    if (fg < static_cast<uint32_t>(TN)) *reinterpret_cast<v4i*>(outbuf + ow_off) = blk;
   };
-  auto finish_b = [&](const m16_v4i& outv, uint32_t oy) __attribute__((always_inline)) {
+  auto finish_b = [&](const v4i& outv, uint32_t oy) __attribute__((always_inline)) {
     const auto bits = __builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int, outv);
     const uint32_t soff = out_img + oy * out_row;
     if (p.stream_out) __builtin_amdgcn_raw_buffer_store_b128(bits, out_rsrc, out_voff, soff, 2);
@@ -2404,25 +2398,25 @@ void q8_dwconv_mfma16_3x3_kernel(const DwParams p)
     constexpr int PH6 = decltype(ph_c)::value;
     constexpr int PH = PH6 % 3;
     constexpr bool CHECK = decltype(check_c)::value;
-    m16_v4i x = raw[PH6];
+    v4i x = raw[PH6];
     if constexpr (CHECK) {
       const int32_t iy = t - static_cast<int32_t>(p.pad_top);
       if (iy < 0 || iy >= static_cast<int32_t>(p.H)) {                             // (wave-uniform)
-        x = m16_v4i{static_cast<int>(fillraw), static_cast<int>(fillraw), static_cast<int>(fillraw), static_cast<int>(fillraw)};
+        x = v4i{static_cast<int>(fillraw), static_cast<int>(fillraw), static_cast<int>(fillraw), static_cast<int>(fillraw)};
       }
     }
     x.x ^= static_cast<int>(flip); x.y ^= static_cast<int>(flip); x.z ^= static_cast<int>(flip); x.w ^= static_cast<int>(flip);
     uint8_t* buf = rowbuf + PH * 1024u;
-    if (loader) *reinterpret_cast<m16_v4i*>(buf + wr_off) = x;
+    if (loader) *reinterpret_cast<v4i*>(buf + wr_off) = x;
     request(ph_c, t_next);                                                          // the row a trip ahead, into the register just consumed
     const int32_t oy_done = t - 3;
     const bool done = oy_done >= static_cast<int32_t>(oy0) && oy_done < static_cast<int32_t>(oy1);   // (wave-uniform)
     if (done) finish_a(std::integral_constant<int, PH>{});
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                         // the wave's own LDS writes before its reads
-    m16_v4i xf[TN];
+    v4i xf[TN];
 #pragma unroll
-    for (int tn = 0; tn < TN; tn++) xf[tn] = *reinterpret_cast<const m16_v4i*>(buf + rd_off + tn * 16);
-    const m16_v4i outv = *reinterpret_cast<const m16_v4i*>(outbuf + lane * 16u);
+    for (int tn = 0; tn < TN; tn++) xf[tn] = *reinterpret_cast<const v4i*>(buf + rd_off + tn * 16);
+    const v4i outv = *reinterpret_cast<const v4i*>(outbuf + lane * 16u);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 #pragma unroll
     for (int tn = 0; tn < TN; tn++) {
@@ -2479,7 +2473,7 @@ void q8_dwconv_mfma16_3x3_kernel(const DwParams p)
     const uint32_t last = static_cast<uint32_t>(t_end) % 3u;
     if (last == 0u) finish_a(P0{}); else if (last == 1u) finish_a(P1{}); else finish_a(P2{});
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    const m16_v4i outv = *reinterpret_cast<const m16_v4i*>(outbuf + lane * 16u);
+    const v4i outv = *reinterpret_cast<const v4i*>(outbuf + lane * 16u);
     finish_b(outv, oy1 - 1u);
   }
 }
@@ -2530,10 +2524,9 @@ bool plan_m16(DwParams& p, uintptr_t in_addr, uintptr_t out_addr)
 int launch_m16(const DwParams& geometry, hipStream_t stream)
 {
   DwParams p = geometry;
-  auto reciprocal = [](uint32_t d) { return d > 1u ? static_cast<uint32_t>(((UINT64_C(1) << 32) + d - 1u) / d) : 0u; };
-  p.inv_q4 = reciprocal(p.IR);
-  p.inv_bands = reciprocal(p.bands);
-  p.inv_slabs = reciprocal(p.slabs);
+  p.inv_q4 = reciprocal_ceil(p.IR);
+  p.inv_bands = reciprocal_ceil(p.bands);
+  p.inv_slabs = reciprocal_ceil(p.slabs);
   const uint64_t waves = static_cast<uint64_t>(p.batch) * p.slabs * p.bands * p.IR;
   const uint32_t blocks = static_cast<uint32_t>((waves + (kM16Threads / 64) - 1) / (kM16Threads / 64));
   qnnp::requant_dispatch_ofs(p.rq, [&](auto seq, auto full) {
@@ -2545,7 +2538,7 @@ int launch_m16(const DwParams& geometry, hipStream_t stream)
       default: hipLaunchKernelGGL((q8_dwconv_mfma16_3x3_kernel<1, kSeq, kFull>), dim3(blocks), dim3(kM16Threads), 0, stream, p); break;
     }
   });
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 enum : uint32_t { kPlanDirect = 1, kPlanLds33, kPlanLds55, kPlanRow, kPlanMfma, kPlanMfmaLds, kPlanCol, kPlanCol5, kPlanM16, kPlanDirect4, kPlanRowAny };
@@ -2679,10 +2672,7 @@ extern "C" int qnnp_hip_dwconv_run(const struct qnnp_hip_dwconv_args* a, const c
   p.trace = static_cast<unsigned long long*>(qnnp_hip_trace_buffer());
   if (const char* env = getenv("QNNP_DW_ABL")) p.abl = static_cast<uint32_t>(atoi(env));
 #endif
-  {
-    const int cus = qnnp_hip_compute_units();
-    p.cu_count = cus > 0 ? static_cast<uint32_t>(cus) : 256u;
-  }
+  p.cu_count = qnnp::active_cu_count();
 
   hipStream_t stream = reinterpret_cast<hipStream_t>(qnnp_hip_get_stream());
   const uintptr_t in_addr = reinterpret_cast<uintptr_t>(a->input);
@@ -2738,7 +2728,7 @@ extern "C" int qnnp_hip_dwconv_run(const struct qnnp_hip_dwconv_args* a, const c
       uint64_t blocks4 = (total4 + 255) / 256;
       if (blocks4 > 256u * 32u) blocks4 = 256u * 32u;
       hipLaunchKernelGGL(q8_dwconv_direct4_kernel, dim3(static_cast<uint32_t>(blocks4)), dim3(256), 0, stream, p);
-      return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+      return launch_status();
     }
     case kPlanLds33:
       if (kernel_name != nullptr) *kernel_name = "q8_dwconv_lds_3x3";
@@ -2754,5 +2744,5 @@ extern "C" int qnnp_hip_dwconv_run(const struct qnnp_hip_dwconv_args* a, const c
   uint64_t blocks = (total + 255) / 256;
   if (blocks > 256u * 16u) blocks = 256u * 16u;   // grid-stride beyond 16 workgroups per CU
   hipLaunchKernelGGL(q8_dwconv_direct_kernel, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, stream, p);
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }

@@ -23,6 +23,7 @@
 
 #include <stdint.h>
 
+#include "device_ops.hip.h"
 #include "igemm_epilogue.hip.h"
 #include "igemm_params.h"
 #include "per_device.h"
@@ -32,8 +33,6 @@ namespace qnnp {
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 typedef short v2s __attribute__((ext_vector_type(2)));
 
 constexpr int kThreads = 256;
@@ -418,18 +417,11 @@ extern "C" int qnnp_hip_fused_block_run(const struct qnnp_hip_fused_args* a, con
   p.add = a->add;
   if (p.kb3 > p.kblocks3 || (a->has_expand && p.kb1 > p.kblocks1)) return QNNP_HIP_EINVAL;
 
-  static qnnp::PerDeviceOnce attr_once;   // function attributes are per device
-  if (auto once_scope = attr_once.begin()) {
-    (void) hipFuncSetAttribute(reinterpret_cast<const void*>(&q8_fused_block_kernel<false>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
-    (void) hipFuncSetAttribute(reinterpret_cast<const void*>(&q8_fused_block_kernel<true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
-    (void) hipGetLastError();
-  }
+  allow_dynamic_lds<&q8_fused_block_kernel<false>>(kLdsLimit);
+  allow_dynamic_lds<&q8_fused_block_kernel<true>>(kLdsLimit);
   const uint64_t total_tiles = static_cast<uint64_t>(a->batch) * p.tiles_x * p.tiles_y;
   if (total_tiles > 0x7FFFFFFFull) return QNNP_HIP_EINVAL;
-  int cus = qnnp_hip_compute_units();
-  if (cus <= 0) cus = 256;
+  const uint32_t cus = active_cu_count();
   uint32_t per_cu = kLdsLimit / lds_bytes;
   if (per_cu > 4u) per_cu = 4u;
   uint64_t blocks = static_cast<uint64_t>(cus) * per_cu;
@@ -441,5 +433,5 @@ extern "C" int qnnp_hip_fused_block_run(const struct qnnp_hip_fused_args* a, con
     hipLaunchKernelGGL(q8_fused_block_kernel<false>, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), lds_bytes, stream, p);
   }
   if (kernel_name != nullptr) *kernel_name = "q8_fused_block";
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }

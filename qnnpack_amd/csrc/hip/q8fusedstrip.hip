@@ -35,6 +35,7 @@
 #include <stdlib.h>
 
 #include "add_math.hip.h"
+#include "device_ops.hip.h"
 #include "igemm_epilogue.hip.h"
 #include "igemm_params.h"
 #include "per_device.h"
@@ -43,9 +44,6 @@
 namespace qnnp {
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 
 #ifndef QNNP_STRIP_WAVES
 #define QNNP_STRIP_WAVES 16                // A/B at build time (make EXTRA=-DQNNP_STRIP_WAVES=8): sixteen waves of <= 128 registers,
@@ -70,8 +68,8 @@ struct StripParams {
   uint32_t in_pitch, hid_pitch, dw_pitch;
   uint32_t in_off, hid_off, dw_off, w2_off, b1_off, b2_off, b3_off, hid_bytes;
   uint32_t wlds, we_off, wp_off;             // 1: a chunk's expand / project fragments are staged in LDS (below), at these offsets
-  uint32_t inv_w, inv_ow;                    // magic32(W), magic32(OW): x / d == udiv(x, magic)
-  uint32_t in_piece, ppp_magic;              // bytes per input staging piece (16 / 8 / 4), magic32(cin / in_piece)
+  uint32_t inv_w, inv_ow;                    // reciprocal_floor_plus1(W), (OW), 0 for 1: x / d == div_magic(x, magic)
+  uint32_t in_piece, ppp_magic;              // bytes per input staging piece (16 / 8 / 4), the same for cin / in_piece
   uint32_t flip1, flip2, flip3, hid_pad4;
   uint32_t mode1, mode2, mode3;
   uint32_t has_expand, has_res, store_mode, hidden_pad, output_pad;
@@ -106,29 +104,7 @@ inline uint32_t stage_mode(const RequantDev& rq, bool* offset)
   return seq * 3 + clamp;
 }
 
-/* a wave-uniform pointer, in scalar registers for good (q8gemm256c.hip) */
-__device__ __forceinline__ const uint8_t* scalar_ptr(const uint8_t* ptr)
-{
-  const uint64_t v = reinterpret_cast<uint64_t>(ptr);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
-  return reinterpret_cast<const uint8_t*>((static_cast<uint64_t>(hi) << 32) | lo);
-}
-
-/* LDS-DMA of one 1 KiB weight fragment (q8gemm256c.hip): 16 bytes per lane from base + lane * 16 to dst + lane * 16,
- * as an instruction the compiler does not track -- behind the builtin it drains vmcnt(0) before EVERY later LDS access
- * of the wave, and the point of these loads is to land under the stage that runs meanwhile. The waits are explicit. */
-__device__ __forceinline__ void dma_fragment(const uint8_t* base, uint32_t lane_offset, uint8_t* dst)
-{
-  const uint32_t m0v = __builtin_amdgcn_readfirstlane(
-      static_cast<uint32_t>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint8_t*) dst)));
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               : : "v"(lane_offset), "s"(scalar_ptr(base)), "s"(m0v) : "memory");
-}
-
-/* x / d by multiplication: magic = floor(2^32 / d) + 1 is exact for x < 2^32 / d (pixel and dword indices here are
- * below 2^16); 0 stands for d == 1 */
-__device__ __forceinline__ uint32_t udiv(uint32_t x, uint32_t magic) { return magic == 0 ? x : __umulhi(x, magic); }
+/* divides by run-time values: div_magic with reciprocal_floor_plus1 (exact: pixel and dword indices here are below 2^16) */
 
 /* global -> LDS staging of `total` dwords by the whole workgroup, U loads in flight per thread before the first store
  * (a plain load-store loop is one L2 / HBM round trip per iteration: fourteen of them in front of the first MFMA of b0) */
@@ -270,15 +246,18 @@ void q8_fused_strip_kernel(const StripParams p)
   auto dma_expand = [&](uint32_t chunk) __attribute__((always_inline)) {
     const uint32_t first = chunk * p.cb, n = min(p.cb, p.nb1 - first) * KB1;
     for (uint32_t i = wave; i < n; i += kWaves) {
-      dma_fragment(reinterpret_cast<const uint8_t*>(p.w1) + (static_cast<uint64_t>(first) * KB1 + i) * 1024u, lane * 16u, we_lds + i * 1024u);
+      // one 1 KiB weight fragment, meant to land under the stage that runs meanwhile: the waits are explicit
+      const uint8_t* src = scalar_ptr(reinterpret_cast<const uint8_t*>(p.w1) + (static_cast<uint64_t>(first) * KB1 + i) * 1024u);
+      dma16_saddr_ordered(reinterpret_cast<uint64_t>(src), lane * 16u, __builtin_amdgcn_readfirstlane(lds_offset(we_lds + i * 1024u)));
     }
   };
   auto dma_project = [&](uint32_t chunk) __attribute__((always_inline)) {
     const uint32_t first = chunk * p.cb, cbn = min(p.cb, p.nb1 - first), n = p.nb3 * cbn;
     for (uint32_t i = wave; i < n; i += kWaves) {
       const uint32_t nbo = i / cbn, kbl = i - nbo * cbn;
-      dma_fragment(reinterpret_cast<const uint8_t*>(p.w3) + (static_cast<uint64_t>(nbo) * p.nb1 + first + kbl) * 1024u, lane * 16u,
-                   wp_lds + (nbo * p.cb + kbl) * 1024u);
+      const uint8_t* src = scalar_ptr(reinterpret_cast<const uint8_t*>(p.w3) + (static_cast<uint64_t>(nbo) * p.nb1 + first + kbl) * 1024u);
+      dma16_saddr_ordered(reinterpret_cast<uint64_t>(src), lane * 16u,
+                          __builtin_amdgcn_readfirstlane(lds_offset(wp_lds + (nbo * p.cb + kbl) * 1024u)));
     }
   };
   if constexpr (WLDS) {
@@ -318,17 +297,17 @@ void q8_fused_strip_kernel(const StripParams p)
     const uint32_t ipieces = (HAS_EXPAND || residual) ? nE * ppp : (HAS_EXPAND ? 0u : nE * ppp);
     const uint32_t iflip = HAS_EXPAND ? p.flip1 : p.flip2;
     auto in_dst = [&](uint32_t i) __attribute__((always_inline)) -> uint8_t* {
-      const uint32_t px = udiv(i, p.ppp_magic);
+      const uint32_t px = div_magic(i, p.ppp_magic);
       const uint32_t k = i - px * ppp;
       if constexpr (HAS_EXPAND) {
         return in_lds + px * p.in_pitch + k * p.in_piece;
       } else {                                   // the hidden tensor IS the block input: straight into the padded tile
-        const uint32_t rr = udiv(px, p.inv_w);
+        const uint32_t rr = div_magic(px, p.inv_w);
         return hid + ((prow0 + rr) * PW + (px - rr * p.W) + 1u) * p.hid_pitch + k * p.in_piece;
       }
     };
     auto in_src = [&](uint32_t i) __attribute__((always_inline)) -> const uint8_t* {
-      const uint32_t px = udiv(i, p.ppp_magic);
+      const uint32_t px = div_magic(i, p.ppp_magic);
       return strip_in + static_cast<uint64_t>(px) * p.in_stride + (i - px * ppp) * p.in_piece;
     };
     uint4 iv[kIU];
@@ -476,13 +455,13 @@ void q8_fused_strip_kernel(const StripParams p)
           for (int rg = 0; rg < 4; rg++) { pk0[rg] ^= p.flip2; if constexpr (kTwoTiles) pk1[rg] ^= p.flip2; }
           const uint4 v0 = gather16(pk0);
           if (m0 < nE) {
-            const uint32_t rr = udiv(m0, p.inv_w);
+            const uint32_t rr = div_magic(m0, p.inv_w);
             *reinterpret_cast<uint4*>(hid + ((prow0 + rr) * PW + (m0 - rr * p.W) + 1u) * p.hid_pitch + cbl * 32 + khalf * 16) = v0;
           }
           if constexpr (kTwoTiles) {
             const uint4 v1 = gather16(pk1);
             if (m1 < nE) {
-              const uint32_t rr = udiv(m1, p.inv_w);
+              const uint32_t rr = div_magic(m1, p.inv_w);
               *reinterpret_cast<uint4*>(hid + ((prow0 + rr) * PW + (m1 - rr * p.W) + 1u) * p.hid_pitch + cbl * 32 + khalf * 16) = v1;
             }
           }
@@ -517,7 +496,7 @@ void q8_fused_strip_kernel(const StripParams p)
       for (uint32_t rt = rt_first; rt < rtD; rt += kTilesPerRound * rt_step) {
         const uint32_t m0 = rt * 32u + col, m1 = (rt + rt_step) * 32u + col;
         const uint32_t mc0 = min(m0, nD - 1u), mc1 = min(m1, nD - 1u);
-        const uint32_t oy0l = udiv(mc0, p.inv_ow), oy1l = udiv(mc1, p.inv_ow);
+        const uint32_t oy0l = div_magic(mc0, p.inv_ow), oy1l = div_magic(mc1, p.inv_ow);
         const uint8_t* base0 = hid + ((oy0l * s) * PW + (mc0 - oy0l * p.OW) * s) * p.hid_pitch + cbl * 32 + khalf * 16;
         const uint8_t* base1 = hid + ((oy1l * s) * PW + (mc1 - oy1l * p.OW) * s) * p.hid_pitch + cbl * 32 + khalf * 16;
         // (the bias is re-read per tile -- four ds_read_b128 straight into the accumulator registers: held across the
@@ -594,7 +573,7 @@ void q8_fused_strip_kernel(const StripParams p)
       const uint32_t mc = m < nD ? m : nD - 1u;
       if (residual) {
         // stride 1: output pixel (oy0 + oyl, ox) is hidden / input pixel of the same coordinates
-        const uint32_t oyl = udiv(mc, p.inv_ow);
+        const uint32_t oyl = div_magic(mc, p.inv_ow);
         const uint32_t ox = mc - oyl * p.OW;
         const uint8_t* res = in_lds + ((oy0 + oyl - hy0c) * p.W + ox) * p.in_pitch;
 #pragma unroll
@@ -609,8 +588,6 @@ void q8_fused_strip_kernel(const StripParams p)
   }
   QNNP_S_STAMP(22);
 }
-
-inline uint32_t magic32(uint32_t d) { return d <= 1 ? 0u : static_cast<uint32_t>((1ull << 32) / d) + 1u; }
 
 /* strip height, chunk width and LDS layout; false when the block does not fit the kernel */
 bool plan(const qnnp_hip_fused_strip_args& a, StripParams* p, uint32_t* lds_bytes)
@@ -632,8 +609,7 @@ bool plan(const qnnp_hip_fused_strip_args& a, StripParams* p, uint32_t* lds_byte
   p->in_pitch = p->kb1 * 32u + 16u;
   const uint32_t fixed = ((9u * p->hidden_pad + 255u) & ~255u) + (2u * p->hidden_pad + p->output_pad) * 4u;
   if (9u * p->hidden_pad + (2u * p->hidden_pad + p->output_pad) * 4u > 1536u * 16u) return false;   // one staging round
-  int cus = qnnp_hip_compute_units();
-  if (cus <= 0) cus = 256;
+  const uint32_t cus = active_cu_count();
   // candidates: 1, 2, 3, ... strips of EQUAL height per image (the last one may be shorter by less than a strip count).
   // Among those that fit LDS: least (rounds of workgroups over the CUs) x (stage rounds per workgroup + 4 for its
   // staging) -- one workgroup per CU at a time. (A first version walked the height down from the whole image and
@@ -824,7 +800,7 @@ extern "C" int qnnp_hip_fused_strip_run(const struct qnnp_hip_fused_strip_args* 
   p.cin = a->input_channels; p.ch = a->hidden_channels; p.cout = a->output_channels;
   p.in_stride = a->input_stride; p.out_stride = a->output_stride; p.stride = a->stride;
   p.has_expand = a->has_expand; p.has_res = a->has_residual;
-  p.inv_w = magic32(p.W); p.inv_ow = magic32(p.OW);
+  p.inv_w = p.W <= 1 ? 0u : reciprocal_floor_plus1(p.W); p.inv_ow = p.OW <= 1 ? 0u : reciprocal_floor_plus1(p.OW);
   p.flip1 = (a->expand_flip & 0xFFu) * 0x01010101u;
   p.flip2 = (a->dw_flip & 0xFFu) * 0x01010101u;
   p.flip3 = (a->project_flip & 0xFFu) * 0x01010101u;
@@ -834,7 +810,8 @@ extern "C" int qnnp_hip_fused_strip_run(const struct qnnp_hip_fused_strip_args* 
     p.in_piece = 4;
     if (p.cin % 16 == 0 && p.in_stride % 16 == 0 && in_addr % 16 == 0) p.in_piece = 16;
     else if (p.cin % 8 == 0 && p.in_stride % 8 == 0 && in_addr % 8 == 0) p.in_piece = 8;
-    p.ppp_magic = magic32(p.cin / p.in_piece);
+    const uint32_t pieces = p.cin / p.in_piece;
+    p.ppp_magic = pieces <= 1 ? 0u : reciprocal_floor_plus1(pieces);
   }
   const uintptr_t out_addr = reinterpret_cast<uintptr_t>(a->output);
   p.store_mode = 0;
@@ -858,5 +835,5 @@ extern "C" int qnnp_hip_fused_strip_run(const struct qnnp_hip_fused_strip_args* 
   hipStream_t stream = reinterpret_cast<hipStream_t>(qnnp_hip_get_stream());
   hipLaunchKernelGGL(kernel, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), lds_bytes, stream, p);
   if (kernel_name != nullptr) *kernel_name = "q8_fused_strip";
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }

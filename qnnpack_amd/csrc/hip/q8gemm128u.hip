@@ -28,49 +28,20 @@
 
 #include <type_traits>
 
+#include "device_ops.hip.h"
 #include "igemm_params.h"
+#include "per_device.h"
 #include "requant.hip.h"
 
 namespace qnnp {
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-
 constexpr int kBM = 128;
 constexpr int kBK = 64;
 constexpr int kATile = kBM * kBK;              // 8 KiB
 constexpr int kThreads = 256;
 constexpr int kTM = 4;
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt()
-{
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ const uint8_t* scalar_ptr(const uint8_t* ptr)
-{
-  const uint64_t v = reinterpret_cast<uint64_t>(ptr);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
-  return reinterpret_cast<const uint8_t*>((static_cast<uint64_t>(hi) << 32) | lo);
-}
-
-__device__ __forceinline__ uint32_t lds_address(uint8_t* lds_ptr)
-{
-  return static_cast<uint32_t>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint8_t*) lds_ptr));
-}
-
-__device__ __forceinline__ void dma16_saddr(const uint8_t* base, uint32_t lane_offset, uint8_t* lds_wave_base)
-{
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               : : "v"(lane_offset), "s"(base), "s"(lds_address(lds_wave_base)));
-}
-
-__device__ __forceinline__ uint32_t a_swizzle(uint32_t row) { return (row & 8u) != 0 ? 3u : 0u; }
-
-#define QNNP_PIN() __builtin_amdgcn_sched_barrier(0)
 
 /* OUT: 2 = every row's channel run of the group starts dword-aligned and N % 4 == 0; 1 = the same for 2 bytes (58 / 122 channels); 0 = no
  * alignment at all. 2 and 1 transpose the requantized dwords over the four lanes of a row (v_permlane32_swap / v_permlane16_swap) so that
@@ -139,8 +110,7 @@ void q8_gemm_mfma_128xN_u16_kernel(const IgemmParams p)
   // (the extent is rounded up to whole dwords: the dword that holds the tensor's last bytes must not read as out of range -- up to three
   //  bytes past the tensor are fetched with it and masked or multiplied by zero weights)
   const uint64_t in_bytes = (static_cast<uint64_t>(p.input_end - p.input) + 3u) & ~static_cast<uint64_t>(3);
-  const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(p.input), 0, static_cast<int>(in_bytes), 0x00020000);       // (launcher: < 2^31 bytes)
+  const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.input, static_cast<int>(in_bytes));       // (launcher: < 2^31 bytes)
   const uint32_t a_byte0 = m_l * p.input_stride + g * p.kc + lhalf * 32u;            // byte offset of the piece at kt = 0
   const uint32_t a_wr = lrow * kBK + (((lhalf * 2u) ^ a_swizzle(lrow)) << 4);          // chunk 2 half; chunk 2 half + 1 sits at a_wr ^ 16
   uint32_t rs = 0;                                                                     // sum of this piece's raw bytes over all K tiles
@@ -374,7 +344,7 @@ int launch_u(const IgemmParams& p, uint32_t groups, hipStream_t stream)
   if (static_cast<uint64_t>(tiles_m) * tiles_n * tiles_n >= (1ull << 32)) return QNNP_HIP_EINVAL;
   const dim3 grid(tiles_m * tiles_n, groups, 1);
   IgemmParams pm = p;
-  pm.tiles_n_magic = tiles_n == 1 ? 0u : static_cast<uint32_t>((1ull << 32) / tiles_n) + 1u;
+  pm.tiles_n_magic = tiles_n == 1 ? 0u : reciprocal_floor_plus1(tiles_n);
   const bool dword_out = p.n % 4 == 0 && p.output_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(p.output) & 3u) == 0;
   const bool even_out = p.n % 2 == 0 && p.output_stride % 2 == 0 && (reinterpret_cast<uintptr_t>(p.output) & 1u) == 0;
   // (flat rows: dense pixels, one group, one channel tile, rows that are not whole 16-byte pieces anyway)
@@ -388,7 +358,7 @@ int launch_u(const IgemmParams& p, uint32_t groups, hipStream_t stream)
     else if (dword_out) hipLaunchKernelGGL((q8_gemm_mfma_128xN_u16_kernel<kSeq, kClamp, 2, TN>), grid, dim3(kThreads), 0, stream, pm);
     else if (even_out) hipLaunchKernelGGL((q8_gemm_mfma_128xN_u16_kernel<kSeq, kClamp, 1, TN>), grid, dim3(kThreads), 0, stream, pm);
     else hipLaunchKernelGGL((q8_gemm_mfma_128xN_u16_kernel<kSeq, kClamp, 0, TN>), grid, dim3(kThreads), 0, stream, pm);
-    rc = hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+    rc = launch_status();
   };
   using C0 = std::integral_constant<int, 0>;
   using C1 = std::integral_constant<int, 1>;

@@ -27,14 +27,14 @@
 
 #include <type_traits>
 
+#include "device_ops.hip.h"
 #include "igemm_params.h"
+#include "per_device.h"
 #include "requant.hip.h"
 
 namespace qnnp {
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr int kBM = 128;
 constexpr int kBK = 64;                        // bytes of K per tile = one 16x16x64 step
@@ -42,38 +42,6 @@ constexpr int kATile = kBM * kBK;              // 8 KiB
 constexpr int kThreads = 256;                  // 4 waves: 2 (rows) x 2 (channels), 64 rows x 16 TN channels per wave
 constexpr int kTM = 4;                         // 16-row MFMA tiles per wave
 constexpr int kRing = 4;
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt()
-{
-  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ const uint8_t* scalar_ptr(const uint8_t* ptr)
-{
-  const uint64_t v = reinterpret_cast<uint64_t>(ptr);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
-  return reinterpret_cast<const uint8_t*>((static_cast<uint64_t>(hi) << 32) | lo);
-}
-
-__device__ __forceinline__ uint32_t lds_address(uint8_t* lds_ptr)
-{
-  return static_cast<uint32_t>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint8_t*) lds_ptr));
-}
-
-/* LDS-DMA, saddr form: 16 bytes per lane from base + lane_offset to m0 + lane * 16 */
-__device__ __forceinline__ void dma16_saddr(const uint8_t* base, uint32_t lane_offset, uint8_t* lds_wave_base)
-{
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               : : "v"(lane_offset), "s"(base), "s"(lds_address(lds_wave_base)));
-}
-
-/* chunk swizzle of the activation image (q8gemm256x.hip): rows 8..15 of every 16 keep their K chunks in slots c ^ 3 */
-__device__ __forceinline__ uint32_t a_swizzle(uint32_t row) { return (row & 8u) != 0 ? 3u : 0u; }
-
-#define QNNP_PIN() __builtin_amdgcn_sched_barrier(0)
 
 /* TN: 16-channel MFMA tiles per wave: 4 = 128-channel workgroup tiles (64 KiB of LDS, two workgroups per CU), 2 = 64-channel ones
  * (48 KiB, three per CU) for channel counts that would leave most of a 128-wide tile empty (64, 96, 160, 320). */
@@ -353,12 +321,12 @@ int launch_mid(const IgemmParams& p, uint32_t groups, hipStream_t stream)
   if (static_cast<uint64_t>(tiles_m) * tiles_n * tiles_n >= (1ull << 32)) return QNNP_HIP_EINVAL;
   const dim3 grid(tiles_m * tiles_n, groups, 1);
   IgemmParams pm = p;
-  pm.tiles_n_magic = tiles_n == 1 ? 0u : static_cast<uint32_t>((1ull << 32) / tiles_n) + 1u;
+  pm.tiles_n_magic = tiles_n == 1 ? 0u : reciprocal_floor_plus1(tiles_n);
   int rc = QNNP_HIP_EINVAL;
   if (p.rq.f.shift != 0 && p.rq.f.bounded && p.rq.f.ofs_kind == 2 && !p.rq.full_range) {
     if (p.rq.zp_late == 0) hipLaunchKernelGGL((q8_gemm_mfma_128xN_c16_kernel<kRqBoundedOfs, 1, TN>), grid, dim3(kThreads), 0, stream, pm);
     else hipLaunchKernelGGL((q8_gemm_mfma_128xN_c16_kernel<kRqBoundedOfs, 2, TN>), grid, dim3(kThreads), 0, stream, pm);
-    return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+    return launch_status();
   }
   requant_dispatch_ofs(p.rq, [&](auto seq, auto full) {
     constexpr int kSeq = decltype(seq)::value;
@@ -369,7 +337,7 @@ int launch_mid(const IgemmParams& p, uint32_t groups, hipStream_t stream)
     } else {
       hipLaunchKernelGGL((q8_gemm_mfma_128xN_c16_kernel<kSeq, 2, TN>), grid, dim3(kThreads), 0, stream, pm);
     }
-    rc = hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+    rc = launch_status();
   });
   return rc;
 }

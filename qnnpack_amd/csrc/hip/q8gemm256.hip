@@ -44,73 +44,23 @@
 
 #include <type_traits>
 
+#include "device_ops.hip.h"
 #include "igemm_epilogue.hip.h"
 #include "igemm_params.h"
+#include "per_device.h"
 #include "requant.hip.h"
 
 namespace qnnp {
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
-
 constexpr int kBN = 256;
 constexpr int kBK = 64;                        // bytes of K per tile (two 32-deep MFMA sub-steps)
 constexpr int kWTile = kBN * kBK;              // 16 KiB
 constexpr uint32_t kFlip = 0x80808080u;
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt()
-{
-  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-#ifndef QNNP_DMA_AUX
-#define QNNP_DMA_AUX 0
-#endif
-__device__ __forceinline__ void dma16(const uint8_t* src, uint8_t* lds_wave_base)
-{
-  // 16 bytes per lane, LDS destination = wave-uniform base + lane * 16
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) void*) src,
-      (__attribute__((address_space(3))) void*) lds_wave_base, 16, 0, QNNP_DMA_AUX);
-}
-
-/* a wave-uniform pointer, in scalar registers for good (a uniform value the compiler happened to compute with vector
- * instructions -- a 64-bit multiply, say -- would reach an "s" asm operand as a VGPR pair: an assembler error) */
-__device__ __forceinline__ const uint8_t* scalar_ptr(const uint8_t* ptr)
-{
-  const uint64_t v = reinterpret_cast<uint64_t>(ptr);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
-  return reinterpret_cast<const uint8_t*>((static_cast<uint64_t>(hi) << 32) | lo);
-}
-
-/* The saddr form: 64-bit wave-uniform base in an SGPR pair + 32-bit lane offset. hipcc selects the VGPR-pair form for
- * the builtin whatever the shape of the address expression (one v_lshl_add_u64 per piece), hence the instruction itself;
- * m0 = LDS destination of lane 0, as the builtin sets it. (m0 is a reserved register: hipcc ignores it in a clobber list.
- * Nothing else in the lean kernels touches it -- tests/test_kernel_resources.py disassembles them and checks.) */
-__device__ __forceinline__ void dma16_saddr(const uint8_t* base, uint32_t lane_offset, uint8_t* lds_wave_base)
-{
-  const uint32_t lds_addr = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(
-      (__attribute__((address_space(3))) uint8_t*) lds_wave_base));
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               : : "v"(lane_offset), "s"(base), "s"(lds_addr));
-}
-/* The same in two halves, for the main loop: m0 is written one MFMA ahead of the load, which is the wait state the
- * pair needs (no s_nop). Nothing else in that loop touches m0. */
-__device__ __forceinline__ void dma16_set_m0(uint8_t* lds_wave_base)
-{
-  const uint32_t lds_addr = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(
-      (__attribute__((address_space(3))) uint8_t*) lds_wave_base));
-  asm volatile("s_mov_b32 m0, %0" : : "s"(lds_addr));
-}
-__device__ __forceinline__ void dma16_saddr_m0_set(const uint8_t* base, uint32_t lane_offset)
-{
-  asm volatile("global_load_lds_dwordx4 %0, %1" : : "v"(lane_offset), "s"(base));
-}
+// LDS-DMA: dma16_builtin, and in the lean flavour the saddr forms (device_ops.hip.h). Nothing else in the lean kernels
+// touches M0 -- tests/test_kernel_resources.py disassembles them and checks.
 
 constexpr int kWN = 2;                         // waves along channels (each 128 channels = 4 MFMA tiles)
 constexpr int kTN = kBN / (kWN * 32);
@@ -296,12 +246,12 @@ void q8_gemm_mfma_256x256_kernel(const IgemmParams p)
       } else {
         src = kk < p.k_total ? a_row[i] + kk : pad_k;
       }
-      dma16(src, a_dst + (i * kThreads + wave * 64) * 16);
+      dma16_builtin(src, a_dst + (i * kThreads + wave * 64) * 16);
     } else {
       const int i = piece - kAChunks;
       const uint32_t F = i * (kWM * kWN) + wave;   // fragment slot: (32-channel block, 32-deep K block)
       const uint8_t* src = w_src0[i] + static_cast<uint64_t>(kt) * w_kstep[i];   // branch-free: step 0 on the zero chunk
-      dma16(src, w_dst + F * 1024);
+      dma16_builtin(src, w_dst + F * 1024);
     }
   };
   auto stage = [&](uint32_t kt) {
@@ -466,8 +416,6 @@ void q8_gemm_mfma_256x256_kernel(const IgemmParams p)
       rs[tm] = __builtin_amdgcn_sad_u8(f.a[tm].y, 0u, rs[tm]);
     }
   };
-#define QNNP_PIN() __builtin_amdgcn_sched_barrier(0)
-
   // Counted wait: tile `kt` has landed when at most the LDS-DMA groups of the tiles issued after it
   // (kDma instructions each, completing in issue order) are still outstanding.
   auto wait_tile = [&](uint32_t later_tiles_in_flight) {
@@ -892,7 +840,7 @@ template <bool IS_CONV, int WM, int BM = 256>
 static int launch256(const IgemmParams& p, const dim3& grid, hipStream_t stream)
 {
   hipLaunchKernelGGL((q8_gemm_mfma_256x256_kernel<IS_CONV, WM, BM>), grid, dim3(WM * kWN * 64), 0, stream, p);
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 /* waves4 = false: 8 waves (two per SIMD), 64 x 128 outputs per wave -- the default;
@@ -945,7 +893,7 @@ int gemm256_launch(const IgemmParams& p, uint32_t groups, hipStream_t stream, co
     *name = conv ? "q8_gemm_mfma_256x256_pp_conv" : "q8_gemm_mfma_256x256_pp";
     if (conv) hipLaunchKernelGGL((q8_gemm_mfma_256x256_kernel<true, 4, 256, 0, true>), grid, dim3(512), 0, stream, p);
     else hipLaunchKernelGGL((q8_gemm_mfma_256x256_kernel<false, 4, 256, 0, true>), grid, dim3(512), 0, stream, p);
-    return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+    return launch_status();
   }
   if (!conv) {
     const char* env = getenv("QNNP_GFX950_ABLATE");
@@ -953,7 +901,7 @@ int gemm256_launch(const IgemmParams& p, uint32_t groups, hipStream_t stream, co
     *name = waves4 ? "q8_gemm_mfma_256x256_w4" : "q8_gemm_mfma_256x256";
 #define QNNP_ABL_CASE(V) case V: if (waves4) hipLaunchKernelGGL((q8_gemm_mfma_256x256_kernel<false, 2, 256, V>), grid, dim3(256), 0, stream, p); \
         else hipLaunchKernelGGL((q8_gemm_mfma_256x256_kernel<false, 4, 256, V>), grid, dim3(512), 0, stream, p); \
-        return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+        return launch_status();
     switch (abl) {
       case 0: break;
       QNNP_ABL_CASE(1) QNNP_ABL_CASE(2) QNNP_ABL_CASE(3) QNNP_ABL_CASE(4) QNNP_ABL_CASE(8) QNNP_ABL_CASE(16) QNNP_ABL_CASE(24) QNNP_ABL_CASE(26)
@@ -966,7 +914,7 @@ int gemm256_launch(const IgemmParams& p, uint32_t groups, hipStream_t stream, co
     if (lean != 0 && gemm256_lean_supported(p)) {
       *name = "q8_gemm_mfma_256x256_w4_lean";
       hipLaunchKernelGGL((q8_gemm_mfma_256x256_kernel<false, 2, 256, 0, false, true>), grid, dim3(256), 0, stream, p);
-      return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+      return launch_status();
     }
     if (lean > 1) return QNNP_HIP_EINVAL;
     *name = conv ? "q8_gemm_mfma_256x256_w4_conv" : "q8_gemm_mfma_256x256_w4";
@@ -976,7 +924,7 @@ int gemm256_launch(const IgemmParams& p, uint32_t groups, hipStream_t stream, co
   if (lean != 0 && gemm256_lean_supported(p)) {
     *name = "q8_gemm_mfma_256x256_lean";
     hipLaunchKernelGGL((q8_gemm_mfma_256x256_kernel<false, 4, 256, 0, false, true>), grid, dim3(512), 0, stream, p);
-    return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+    return launch_status();
   }
   if (lean > 1) return QNNP_HIP_EINVAL;        // forced and not applicable
   *name = conv ? "q8_gemm_mfma_256x256_conv" : "q8_gemm_mfma_256x256";

@@ -49,16 +49,15 @@
 
 #include <type_traits>
 
+#include "device_ops.hip.h"
 #include "igemm_epilogue.hip.h"
 #include "igemm_params.h"
+#include "per_device.h"
 #include "requant.hip.h"
 
 namespace qnnp {
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int kBM = 256;
 constexpr int kBN = 256;
@@ -76,62 +75,8 @@ constexpr int kBiasArea = kRing * kStage;      // 8 waves x 512 bytes
 constexpr uint32_t kImagePitch = kTN * 32 + 16;          // +16: the 8-lane ds_write_b128 groups hit distinct banks
 constexpr uint32_t kImageBytes = 32 * kImagePitch;       // one 32-row half of a wave's 64 x 128 output tile
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt()
-{
-  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-/* a wave-uniform pointer, in scalar registers for good (q8gemm256.hip) */
-__device__ __forceinline__ const uint8_t* scalar_ptr(const uint8_t* ptr)
-{
-  const uint64_t v = reinterpret_cast<uint64_t>(ptr);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
-  return reinterpret_cast<const uint8_t*>((static_cast<uint64_t>(hi) << 32) | lo);
-}
-
-__device__ __forceinline__ uint32_t lds_address(uint8_t* lds_ptr)
-{
-  return static_cast<uint32_t>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint8_t*) lds_ptr));
-}
-
-/* LDS-DMA, saddr form (q8gemm256.hip): 16 bytes per lane from base + lane_offset to m0 + lane * 16.
- * (Cache policy bits on these loads, measured in round 4: sc1 level, nt 10 % slower -- every line is re-read by the
- *  other CUs of the XCD; profiles/r04/gemm_centred_bias_dma_clamp_spread_policy_ab_r04d.txt.) */
-__device__ __forceinline__ void dma16_saddr(const uint8_t* base, uint32_t lane_offset, uint8_t* lds_wave_base)
-{
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               : : "v"(lane_offset), "s"(base), "s"(lds_address(lds_wave_base)));
-}
-__device__ __forceinline__ void dma16_set_m0(uint8_t* lds_wave_base)
-{
-  asm volatile("s_mov_b32 m0, %0" : : "s"(lds_address(lds_wave_base)));
-}
-__device__ __forceinline__ void dma16_saddr_m0_set(const uint8_t* base, uint32_t lane_offset)
-{
-  asm volatile("global_load_lds_dwordx4 %0, %1" : : "v"(lane_offset), "s"(base));
-}
-
-#define QNNP_PIN() __builtin_amdgcn_sched_barrier(0)
-
-// measurement builds: cycle stamps of wave 0 (item 0) and wave 4 (item 1) of every workgroup; item 3 = wall clock
-#ifdef QNNP_ENABLE_ABLATION
-#define QNNP_C_STAMP(slot)                                                                                  \
-  do {                                                                                                       \
-    if (p.trace != nullptr && lane == 0 && (wave & 3u) == 0)                                                 \
-      p.trace[(blockIdx.x * 4 + (wave >> 2)) * 8 + (slot)] = __builtin_readcyclecounter();                  \
-  } while (0)
-#define QNNP_C_STAMP_WALL(slot)                                                                             \
-  do {                                                                                                       \
-    if (p.trace != nullptr && lane == 0 && (wave & 3u) == 0)                                                 \
-      p.trace[(blockIdx.x * 4 + 2 + (wave >> 2)) * 8 + (slot)] = wall_clock64();                            \
-  } while (0)
-#else
-#define QNNP_C_STAMP(slot) do { } while (0)
-#define QNNP_C_STAMP_WALL(slot) do { } while (0)
-#endif
+// LDS-DMA: the saddr forms of device_ops.hip.h. (Cache policy bits on these loads, measured in round 4: sc1 level, nt
+// 10 % slower -- every line is re-read by the other CUs of the XCD; profiles/r04/gemm_centred_bias_dma_clamp_spread_policy_ab_r04d.txt.)
 
 /*
  * SEQ / CLAMP: rounding sequence and clamp class of the requantization (requant.hip.h), chosen by the launcher.
@@ -159,8 +104,8 @@ void q8_gemm_mfma_256x256_c_kernel(const IgemmParams p)
   const uint32_t wm = wave >> 1;       // 64-row slice
   const uint32_t wn = wave & 1u;       // 128-channel half
   const uint32_t g = blockIdx.y;
-  QNNP_C_STAMP(0);
-  QNNP_C_STAMP_WALL(0);
+  QNNP_TRACE_WAVE04(p, lane, wave, 0);
+  QNNP_TRACE_WAVE04_WALL(p, lane, wave, 0);
 
   // Workgroup -> tile (q8gemm256.hip): contiguous logical ids per XCD, bands of four row tiles.
   const uint32_t tiles_m = (p.rows + kBM - 1) / kBM;
@@ -349,7 +294,7 @@ void q8_gemm_mfma_256x256_c_kernel(const IgemmParams p)
   // ---- prologue, part 2: tile 0 and the bias line have landed (loads complete in issue order) ----
   wait_vmcnt<(RING - 1) * kDma>();
   __builtin_amdgcn_s_barrier();
-  QNNP_C_STAMP(1);
+  QNNP_TRACE_WAVE04(p, lane, wave, 1);
   Frags fa, fb;
   read_frags_slot(0, 0, fa);
   // accumulators: lane l holds, in register r of tile tn, channel (nb0 + wn * 4 + tn) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5)
@@ -479,7 +424,7 @@ void q8_gemm_mfma_256x256_c_kernel(const IgemmParams p)
 
   // (the launcher guarantees ktiles >= 2 * RING)
   iteration(F{}, T{}, T{}, Sync1{}, T{}, S0{}, 0u, 0u);   // the prologue staged pieces 2, 3 of tile RING - 1 already
-  QNNP_C_STAMP(2);
+  QNNP_TRACE_WAVE04(p, lane, wave, 2);
   auto rest = [&](auto stag_all) __attribute__((always_inline)) {
   uint32_t kt = 1;
   auto steady = [&](auto stag_c) __attribute__((always_inline)) {
@@ -496,10 +441,10 @@ void q8_gemm_mfma_256x256_c_kernel(const IgemmParams p)
     iteration(T{}, T{}, T{}, Sync1{}, T{}, S0{}, kt, 1u);
     iteration(T{}, T{}, T{}, Sync1{}, T{}, S0{}, kt + 1, 2u);
     iteration(T{}, T{}, T{}, Sync1{}, T{}, S0{}, kt + 2, 3u);
-    QNNP_C_STAMP(3);
+    QNNP_TRACE_WAVE04(p, lane, wave, 3);
     iteration(T{}, T{}, F{}, Sync1{}, T{}, S0{}, kt + 3, 0u);     // ktiles - 4: the last pieces of the last tile
     iteration(F{}, T{}, F{}, Sync2{}, T{}, S0{}, kt + 4, 1u);     // ktiles - 3: the final wait + barrier
-    QNNP_C_STAMP(4);
+    QNNP_TRACE_WAVE04(p, lane, wave, 4);
     iteration(F{}, T{}, F{}, Sync0{}, T{}, S0{}, kt + 5, 2u);     // tail: everything resident, no barriers
     iteration(F{}, F{}, F{}, Sync0{}, T{}, S0{}, kt + 6, 3u);     // last tile
   } else {
@@ -509,19 +454,19 @@ void q8_gemm_mfma_256x256_c_kernel(const IgemmParams p)
     iteration(T{}, T{}, T{}, Sync1{}, F{}, S0{}, kt, slot);
     advance();
   }
-  QNNP_C_STAMP(3);
+  QNNP_TRACE_WAVE04(p, lane, wave, 3);
   iteration(T{}, T{}, F{}, Sync1{}, F{}, S0{}, kt, slot); // kt == ktiles - RING: the last pieces of the last tile
   advance();
   iteration(F{}, T{}, F{}, Sync2{}, F{}, S0{}, kt, slot); // kt == ktiles - RING + 1: the final wait + barrier
   advance();
-  QNNP_C_STAMP(4);
+  QNNP_TRACE_WAVE04(p, lane, wave, 4);
   while (kt + 1 < ktiles) {                               // tail: everything resident, no barriers
     iteration(F{}, T{}, F{}, Sync0{}, F{}, S0{}, kt, slot);
     advance();
   }
   iteration(F{}, F{}, F{}, Sync0{}, F{}, S0{}, kt, slot); // last tile
   }
-  QNNP_C_STAMP(5);
+  QNNP_TRACE_WAVE04(p, lane, wave, 5);
 
   // ---- fused epilogue: Q31 requantize in registers -> half a wave tile at a time through LDS -> whole 128-byte lines ----
   if constexpr ((ABL & 1) != 0) {
@@ -576,13 +521,13 @@ void q8_gemm_mfma_256x256_c_kernel(const IgemmParams p)
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // read back before the other half overwrites it
-    if (tm == 0) QNNP_C_STAMP(6);
+    if (tm == 0) QNNP_TRACE_WAVE04(p, lane, wave, 6);
   }
-  QNNP_C_STAMP(7);
+  QNNP_TRACE_WAVE04(p, lane, wave, 7);
 #ifdef QNNP_ENABLE_ABLATION
   if (p.trace != nullptr) {                      // when the stores have left the wave
     wait_vmcnt<0>();
-    QNNP_C_STAMP_WALL(1);
+    QNNP_TRACE_WAVE04_WALL(p, lane, wave, 1);
   }
 #endif
   };
@@ -599,7 +544,7 @@ int launch_c(const IgemmParams& p, const dim3& grid, hipStream_t stream)
     const char* env = getenv("QNNP_GFX950_ABLATE");
     const int abl = env != nullptr ? atoi(env) : 0;
 #define QNNP_ABL_CASE(V) case V: hipLaunchKernelGGL((q8_gemm_mfma_256x256_c_kernel<kRqShift0Ofs, 1, true, 0, V>), grid, dim3(kThreads), 0, stream, p); \
-        return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+        return launch_status();
     switch (abl) {
       QNNP_ABL_CASE(1) QNNP_ABL_CASE(2) QNNP_ABL_CASE(3) QNNP_ABL_CASE(4) QNNP_ABL_CASE(8) QNNP_ABL_CASE(16) QNNP_ABL_CASE(24)
       QNNP_ABL_CASE(27) QNNP_ABL_CASE(32) QNNP_ABL_CASE(59) QNNP_ABL_CASE(31) QNNP_ABL_CASE(64)
@@ -613,7 +558,7 @@ int launch_c(const IgemmParams& p, const dim3& grid, hipStream_t stream)
     // clamp only): the bounded sequence with the clamp class picked here
     if (p.rq.zp_late == 0) hipLaunchKernelGGL((q8_gemm_mfma_256x256_c_kernel<kRqBoundedOfs, 1, ALIGNED, OPT>), grid, dim3(kThreads), 0, stream, p);
     else hipLaunchKernelGGL((q8_gemm_mfma_256x256_c_kernel<kRqBoundedOfs, 2, ALIGNED, OPT>), grid, dim3(kThreads), 0, stream, p);
-    return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+    return launch_status();
   }
   requant_dispatch_ofs(p.rq, [&](auto seq, auto full) {
     constexpr int kSeq = decltype(seq)::value;
@@ -624,7 +569,7 @@ int launch_c(const IgemmParams& p, const dim3& grid, hipStream_t stream)
     } else {
       hipLaunchKernelGGL((q8_gemm_mfma_256x256_c_kernel<kSeq, 2, ALIGNED, OPT>), grid, dim3(kThreads), 0, stream, p);
     }
-    rc = hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+    rc = launch_status();
   });
   return rc;
 }
@@ -654,7 +599,7 @@ int gemm256c_launch(const IgemmParams& p, uint32_t groups, hipStream_t stream, c
   const dim3 grid(tiles_m * tiles_n, groups, 1);
   IgemmParams pm = p;
   // x / tiles_n == hi32(x * magic) for x < 2^32 / tiles_n (the tile ids); 0 stands for tiles_n == 1
-  pm.tiles_n_magic = tiles_n == 1 ? 0u : static_cast<uint32_t>((1ull << 32) / tiles_n) + 1u;
+  pm.tiles_n_magic = tiles_n == 1 ? 0u : reciprocal_floor_plus1(tiles_n);
   const bool aligned = (p.k_pad / kBK) % kRing == 0;
   switch (opt) {
     case 0: *name = "q8_gemm_mfma_256x256_c"; return aligned ? launch_c<0, true>(pm, grid, stream) : launch_c<0, false>(pm, grid, stream);

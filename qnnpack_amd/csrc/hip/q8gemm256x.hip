@@ -46,14 +46,14 @@
 
 #include <type_traits>
 
+#include "device_ops.hip.h"
 #include "igemm_params.h"
+#include "per_device.h"
 #include "requant.hip.h"
 
 namespace qnnp {
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr int kBM = 256;
 constexpr int kBN = 256;
@@ -69,64 +69,6 @@ constexpr int kDma = 4;                        // LDS-DMA instructions per threa
 constexpr int kMma = kTM * kHalf;              // MFMAs per phase
 constexpr int kRing = 4;                       // LDS stages of 32 KiB; the remaining 32 KiB hold the waves' bias lines
 constexpr int kBiasArea = kRing * kStage;      // 8 waves x 512 bytes
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt()
-{
-  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-/* a wave-uniform pointer, in scalar registers for good */
-__device__ __forceinline__ const uint8_t* scalar_ptr(const uint8_t* ptr)
-{
-  const uint64_t v = reinterpret_cast<uint64_t>(ptr);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
-  return reinterpret_cast<const uint8_t*>((static_cast<uint64_t>(hi) << 32) | lo);
-}
-
-__device__ __forceinline__ uint32_t lds_address(uint8_t* lds_ptr)
-{
-  return static_cast<uint32_t>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint8_t*) lds_ptr));
-}
-
-/* LDS-DMA, saddr form: 16 bytes per lane from base + lane_offset to m0 + lane * 16 */
-__device__ __forceinline__ void dma16_saddr(const uint8_t* base, uint32_t lane_offset, uint8_t* lds_wave_base)
-{
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               : : "v"(lane_offset), "s"(base), "s"(lds_address(lds_wave_base)));
-}
-__device__ __forceinline__ void dma16_set_m0(uint8_t* lds_wave_base)
-{
-  asm volatile("s_mov_b32 m0, %0" : : "s"(lds_address(lds_wave_base)));
-}
-__device__ __forceinline__ void dma16_saddr_m0_set(const uint8_t* base, uint32_t lane_offset)
-{
-  asm volatile("global_load_lds_dwordx4 %0, %1" : : "v"(lane_offset), "s"(base));
-}
-
-/* chunk swizzle of the activation image: rows 8..15 of every 16 keep their K chunks in slots c ^ 3 */
-__device__ __forceinline__ uint32_t a_swizzle(uint32_t row) { return (row & 8u) != 0 ? 3u : 0u; }
-
-#define QNNP_PIN() __builtin_amdgcn_sched_barrier(0)
-
-// measurement builds: cycle stamps of wave 0 (item 0) and wave 4 (item 1) of every workgroup; items 2, 3 = wall clock
-#ifdef QNNP_ENABLE_ABLATION
-#define QNNP_X_STAMP(slot)                                                                                  \
-  do {                                                                                                       \
-    if (p.trace != nullptr && lane == 0 && (wave & 3u) == 0)                                                 \
-      p.trace[(blockIdx.x * 4 + (wave >> 2)) * 8 + (slot)] = __builtin_readcyclecounter();                  \
-  } while (0)
-#define QNNP_X_STAMP_WALL(slot)                                                                             \
-  do {                                                                                                       \
-    if (p.trace != nullptr && lane == 0 && (wave & 3u) == 0)                                                 \
-      p.trace[(blockIdx.x * 4 + 2 + (wave >> 2)) * 8 + (slot)] = wall_clock64();                            \
-  } while (0)
-#else
-#define QNNP_X_STAMP(slot) do { } while (0)
-#define QNNP_X_STAMP_WALL(slot) do { } while (0)
-#endif
 
 /*
  * SEQ / CLAMP: rounding sequence and clamp class of the requantization (requant.hip.h), chosen by the launcher.
@@ -159,8 +101,8 @@ void q8_gemm_mfma_256x256_c16_kernel(const IgemmParams p)
   const uint32_t wm = wave >> 1;       // 64-row slice
   const uint32_t wn = wave & 1u;       // 128-channel half
   const uint32_t g = blockIdx.y;
-  QNNP_X_STAMP(0);
-  QNNP_X_STAMP_WALL(0);
+  QNNP_TRACE_WAVE04(p, lane, wave, 0);
+  QNNP_TRACE_WAVE04_WALL(p, lane, wave, 0);
 
   // Workgroup -> tile (q8gemm256.hip): contiguous logical ids per XCD, bands of four row tiles -- an XCD's 32 workgroups of a
   // 16 x 16-tile launch cover 4 row tiles x 8 channel tiles, the most compact block 32 tiles allow (4 + 8 operand panels).
@@ -321,7 +263,7 @@ void q8_gemm_mfma_256x256_c16_kernel(const IgemmParams p)
   // ---- prologue, part 2: tile 0 and the bias line have landed (loads complete in issue order) ----
   wait_vmcnt<(RING - 1) * kDma>();
   __builtin_amdgcn_s_barrier();
-  QNNP_X_STAMP(1);
+  QNNP_TRACE_WAVE04(p, lane, wave, 1);
   using T = std::true_type;
   using F = std::false_type;
 #pragma unroll
@@ -433,7 +375,7 @@ void q8_gemm_mfma_256x256_c16_kernel(const IgemmParams p)
 
   // (the launcher guarantees ktiles >= 2 * RING)
   iteration(F{}, T{}, T{}, Sync1{}, T{}, 0u, 0u);   // the prologue staged pieces 2, 3 of tile RING - 1 already
-  QNNP_X_STAMP(2);
+  QNNP_TRACE_WAVE04(p, lane, wave, 2);
   uint32_t kt = 1;
   for (; kt + (RING - 1) + RING < ktiles; kt += RING) {   // steady state, ring slots as literals (kt % RING == 1 here)
     iteration(T{}, T{}, T{}, Sync1{}, T{}, kt, 1u);
@@ -446,10 +388,10 @@ void q8_gemm_mfma_256x256_c16_kernel(const IgemmParams p)
     iteration(T{}, T{}, T{}, Sync1{}, T{}, kt, 1u);
     iteration(T{}, T{}, T{}, Sync1{}, T{}, kt + 1, 2u);
     iteration(T{}, T{}, T{}, Sync1{}, T{}, kt + 2, 3u);
-    QNNP_X_STAMP(3);
+    QNNP_TRACE_WAVE04(p, lane, wave, 3);
     iteration(T{}, T{}, F{}, Sync1{}, T{}, kt + 3, 0u);     // ktiles - 4: the last pieces of the last tile
     iteration(F{}, T{}, F{}, Sync2{}, T{}, kt + 4, 1u);     // ktiles - 3: the final wait + barrier
-    QNNP_X_STAMP(4);
+    QNNP_TRACE_WAVE04(p, lane, wave, 4);
     iteration(F{}, T{}, F{}, Sync0{}, T{}, kt + 5, 2u);     // tail: everything resident, no barriers
     iteration(F{}, F{}, F{}, Sync0{}, T{}, kt + 6, 3u);     // last tile
   } else {
@@ -459,19 +401,19 @@ void q8_gemm_mfma_256x256_c16_kernel(const IgemmParams p)
       iteration(T{}, T{}, T{}, Sync1{}, F{}, kt, slot);
       advance();
     }
-    QNNP_X_STAMP(3);
+    QNNP_TRACE_WAVE04(p, lane, wave, 3);
     iteration(T{}, T{}, F{}, Sync1{}, F{}, kt, slot); // kt == ktiles - RING: the last pieces of the last tile
     advance();
     iteration(F{}, T{}, F{}, Sync2{}, F{}, kt, slot); // kt == ktiles - RING + 1: the final wait + barrier
     advance();
-    QNNP_X_STAMP(4);
+    QNNP_TRACE_WAVE04(p, lane, wave, 4);
     while (kt + 1 < ktiles) {                               // tail: everything resident, no barriers
       iteration(F{}, T{}, F{}, Sync0{}, F{}, kt, slot);
       advance();
     }
     iteration(F{}, F{}, F{}, Sync0{}, F{}, kt, slot); // last tile
   }
-  QNNP_X_STAMP(5);
+  QNNP_TRACE_WAVE04(p, lane, wave, 5);
 
   // ---- fused epilogue: Q31 requantize in registers -> lane transposes -> whole 128-byte lines, no LDS ----
   if constexpr ((ABL & 1) != 0) {
@@ -541,13 +483,13 @@ void q8_gemm_mfma_256x256_c16_kernel(const IgemmParams p)
       if (p.stream_out) asm volatile("global_store_dwordx4 %0, %1, off nt" : : "v"(dy), "v"(y) : "memory");
       else *dy = y;
     }
-    if (tm == 1) QNNP_X_STAMP(6);
+    if (tm == 1) QNNP_TRACE_WAVE04(p, lane, wave, 6);
   }
-  QNNP_X_STAMP(7);
+  QNNP_TRACE_WAVE04(p, lane, wave, 7);
 #ifdef QNNP_ENABLE_ABLATION
   if (p.trace != nullptr) {                      // when the stores have left the wave
     wait_vmcnt<0>();
-    QNNP_X_STAMP_WALL(1);
+    QNNP_TRACE_WAVE04_WALL(p, lane, wave, 1);
   }
 #endif
 }
@@ -562,7 +504,7 @@ int launch_x(const IgemmParams& p, const dim3& grid, hipStream_t stream)
     const char* env = getenv("QNNP_GFX950_ABLATE");
     const int abl = env != nullptr ? atoi(env) : 0;
 #define QNNP_ABL_CASE(V) case V: hipLaunchKernelGGL((q8_gemm_mfma_256x256_c16_kernel<kRqShift0Ofs, 1, true, V>), grid, dim3(kThreads), 0, stream, p); \
-        return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+        return launch_status();
     switch (abl) {
       QNNP_ABL_CASE(1) QNNP_ABL_CASE(2) QNNP_ABL_CASE(4) QNNP_ABL_CASE(8) QNNP_ABL_CASE(16) QNNP_ABL_CASE(24)
       QNNP_ABL_CASE(27) QNNP_ABL_CASE(32) QNNP_ABL_CASE(59) QNNP_ABL_CASE(64)
@@ -572,7 +514,7 @@ int launch_x(const IgemmParams& p, const dim3& grid, hipStream_t stream)
     const char* oenv = getenv("QNNP_C16_OPT");
     if (oenv != nullptr && atoi(oenv) == 1) {
       hipLaunchKernelGGL((q8_gemm_mfma_256x256_c16_kernel<kRqShift0Ofs, 1, true, 0, false, 1>), grid, dim3(kThreads), 0, stream, p);
-      return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+      return launch_status();
     }
   }
 #endif
@@ -580,7 +522,7 @@ int launch_x(const IgemmParams& p, const dim3& grid, hipStream_t stream)
     // bounded accumulators, shift >= 1, a clamp other than [0, 255]: the bounded sequence with the clamp class picked here
     if (p.rq.zp_late == 0) hipLaunchKernelGGL((q8_gemm_mfma_256x256_c16_kernel<kRqBoundedOfs, 1, ALIGNED, 0, ROWSUM>), grid, dim3(kThreads), 0, stream, p);
     else hipLaunchKernelGGL((q8_gemm_mfma_256x256_c16_kernel<kRqBoundedOfs, 2, ALIGNED, 0, ROWSUM>), grid, dim3(kThreads), 0, stream, p);
-    return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+    return launch_status();
   }
   requant_dispatch_ofs(p.rq, [&](auto seq, auto full) {
     constexpr int kSeq = decltype(seq)::value;
@@ -591,7 +533,7 @@ int launch_x(const IgemmParams& p, const dim3& grid, hipStream_t stream)
     } else {
       hipLaunchKernelGGL((q8_gemm_mfma_256x256_c16_kernel<kSeq, 2, ALIGNED, 0, ROWSUM>), grid, dim3(kThreads), 0, stream, p);
     }
-    rc = hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+    rc = launch_status();
   });
   return rc;
 }
@@ -608,7 +550,7 @@ int gemm256x_launch(const IgemmParams& p, uint32_t groups, hipStream_t stream, c
   const dim3 grid(tiles_m * tiles_n, groups, 1);
   IgemmParams pm = p;
   // x / tiles_n == hi32(x * magic) for x < 2^32 / tiles_n (the tile ids); 0 stands for tiles_n == 1
-  pm.tiles_n_magic = tiles_n == 1 ? 0u : static_cast<uint32_t>((1ull << 32) / tiles_n) + 1u;
+  pm.tiles_n_magic = tiles_n == 1 ? 0u : reciprocal_floor_plus1(tiles_n);
   const bool aligned = (p.k_pad / kBK) % kRing == 0;
   if (p.row_coeff != 0) {
     *name = "q8_gemm_mfma_256x256_r16";

@@ -39,18 +39,19 @@
 
 #include <stdint.h>
 
+#include "device_ops.hip.h"
 #include "igemm_epilogue.hip.h"
 #include "igemm_params.h"
+#include "per_device.h"
 #include "qnnp_hip.h"
 #include "requant.hip.h"
-
 
 namespace {
 
 using qnnp::IgemmParams;
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
+using qnnp::launch_status;
+using qnnp::v4i;
+using qnnp::v16i;
 
 constexpr int BK = 64;                       // bytes of K per main-loop step
 constexpr uint32_t kPadK = 0x80808080u;      // raw bytes whose a' = a ^ 0x80 is zero
@@ -481,7 +482,7 @@ int launch_generic(const IgemmParams& p, uint32_t groups, hipStream_t stream)
   const dim3 grid(ctas_m * tiles_n, groups, 1);     // (with a phase table `groups` is the number of phases)
   const dim3 block(WM * WN * 64, 1, 1);
   hipLaunchKernelGGL((q8_igemm_mfma_kernel<WM, WN, TM, TN, VEC, IS_CONV, PAD3>), grid, block, 0, stream, p);
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 template <int VEC, bool IS_CONV, bool PAD3 = false>
@@ -598,16 +599,13 @@ int derive(const struct qnnp_hip_igemm_args* a, IgemmSetup& s)
   //  wraps to 1 and hi32(m * 1) is 0 for every row. It takes the divide, which is m / 1.)
   p.rpi_magic = (p.offsets_dense != 0 && a->rows_per_image > 1 &&
                  static_cast<uint64_t>(a->rows) * a->rows_per_image < (UINT64_C(1) << 32))
-                    ? static_cast<uint32_t>((UINT64_C(1) << 32) / a->rows_per_image) + 1u : 0u;
+                    ? qnnp::reciprocal_floor_plus1(a->rows_per_image) : 0u;
   p.fill_table = qnnp_hip_fill_table();
   p.trace = nullptr;
 #ifdef QNNP_ENABLE_ABLATION
   p.trace = static_cast<unsigned long long*>(qnnp_hip_trace_buffer());
 #endif
-  {
-    const int cus = qnnp_hip_compute_units();
-    p.cu_count = cus > 0 ? static_cast<uint32_t>(cus) : 256u;
-  }
+  p.cu_count = qnnp::active_cu_count();
 
   // widest activation vector the actual alignment allows (a vector never straddles a tap)
   const uintptr_t in_addr = reinterpret_cast<uintptr_t>(a->input);

@@ -18,6 +18,7 @@
 
 #include "add_math.hip.h"
 #include "avgpool_math.hip.h"
+#include "per_device.h"
 #include "qnnp_hip.h"
 
 namespace qnnp {
@@ -149,12 +150,6 @@ inline uint32_t grid_for(uint64_t items, uint32_t cus)
   return static_cast<uint32_t>(blocks < cap ? (blocks ? blocks : 1) : cap);
 }
 
-inline uint32_t device_cus()
-{
-  const int cus = qnnp_hip_compute_units();   // of the active device context
-  return cus > 0 ? static_cast<uint32_t>(cus) : 256u;
-}
-
 inline bool aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
 }  // namespace
@@ -171,16 +166,16 @@ extern "C" int qnnp_hip_vadd_run(const struct qnnp_hip_vadd_args* a, const char*
   const uint64_t bytes = a->rows * a->channels;
   if (dense && bytes % 16 == 0 && aligned(a->a, 16) && aligned(a->b, 16) && aligned(a->sum, 16)) {
     const uint64_t vectors = bytes / 16;
-    hipLaunchKernelGGL(q8_vadd_flat_kernel, dim3(grid_for(vectors, device_cus())), dim3(kThreads), 0, stream,
+    hipLaunchKernelGGL(q8_vadd_flat_kernel, dim3(grid_for(vectors, active_cu_count())), dim3(kThreads), 0, stream,
                        reinterpret_cast<const uint4*>(a->a), reinterpret_cast<const uint4*>(a->b),
                        reinterpret_cast<uint4*>(a->sum), vectors, a->params,
                        a->streaming_mode == 0 ? (qnnp_hip_streaming_stores() != 0 ? 1u : 0u) : (a->streaming_mode == 2 ? 1u : 0u));
     if (kernel_name != nullptr) *kernel_name = "q8_vadd_flat";
   } else {
-    hipLaunchKernelGGL(q8_vadd_strided_kernel, dim3(grid_for(bytes, device_cus())), dim3(kThreads), 0, stream, *a);
+    hipLaunchKernelGGL(q8_vadd_strided_kernel, dim3(grid_for(bytes, active_cu_count())), dim3(kThreads), 0, stream, *a);
     if (kernel_name != nullptr) *kernel_name = "q8_vadd_strided";
   }
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 extern "C" int qnnp_hip_gavgpool_run(const struct qnnp_hip_gavgpool_args* a, const char** kernel_name)
@@ -211,5 +206,5 @@ extern "C" int qnnp_hip_gavgpool_run(const struct qnnp_hip_gavgpool_args* a, con
                        chunks, lanes_per_chunk, split);
     if (kernel_name != nullptr) *kernel_name = "q8_gavgpool_x1";
   }
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }

@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include "avgpool_math.hip.h"
+#include "per_device.h"
 #include "qnnp_hip.h"
 
 namespace qnnp {
@@ -348,7 +349,7 @@ extern "C" int qnnp_hip_maxpool_run(const struct qnnp_hip_pool_args* a, const ch
     hipLaunchKernelGGL(q8_maxpool_kernel<1>, grid, dim3(kThreads), 0, stream, *a, cvecs, rows);
     if (kernel_name != nullptr) *kernel_name = "q8_maxpool_x1";
   }
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 extern "C" int qnnp_hip_avgpool_run(const struct qnnp_hip_pool_args* a, const char** kernel_name)
@@ -371,5 +372,5 @@ extern "C" int qnnp_hip_avgpool_run(const struct qnnp_hip_pool_args* a, const ch
     hipLaunchKernelGGL(q8_avgpool_kernel<1>, grid, dim3(kThreads), 0, stream, *a, cvecs, rows);
     if (kernel_name != nullptr) *kernel_name = "q8_avgpool_x1";
   }
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }

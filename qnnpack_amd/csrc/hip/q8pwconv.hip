@@ -29,6 +29,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "device_ops.hip.h"
 #include "igemm_epilogue.hip.h"
 #include "igemm_params.h"
 #include "per_device.h"
@@ -37,9 +38,6 @@
 namespace qnnp {
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 
 /* A store of whole lines that are written exactly once (a wave's contiguous run of an output block) carries the
  * streaming hint: layer 4 (112x112x16 -> 96, 154 MB of output) 39 -> 30.5 us, layer 7 17.6 -> 13.9, same box. The hint
@@ -293,7 +291,7 @@ __device__ __forceinline__ void stream_copy_out(
     uint8_t* blk = p.output + block_ofs;
     const uint32_t pitch = 16u << log_cpr;
     for (uint32_t o = lane * 16; o < bytes; o += 1024) {
-      const uint32_t r = __umulhi(o, p.tiles_n_magic);       // o / n (launcher: magic32(n); o < 2^13)
+      const uint32_t r = __umulhi(o, p.tiles_n_magic);       // o / n (launcher: reciprocal_floor_plus1(n); o < 2^13)
       const uint32_t c = o - r * p.n;                        // multiple of 8
       const uint2 lo = *reinterpret_cast<const uint2*>(stage + r * pitch + c);
       const bool wrap = c + 8 >= p.n;                        // the second half starts the next row
@@ -760,8 +758,7 @@ void q8_pw_stream_gw_kernel(const IgemmParams p)
   const bool row_ok = m < p.rows;
   if (!row_ok) m = p.rows - 1;
   // (launcher: the input tensor is addressable with 32-bit offsets)
-  const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(p.input), 0, static_cast<int>((p.rows - 1u) * p.input_stride + p.k_total), 0x00020000);
+  const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.input, static_cast<int>((p.rows - 1u) * p.input_stride + p.k_total));
   const uint32_t row_off = m * p.input_stride;
   const int8_t* wf = p.packed_w + static_cast<uint64_t>(nb) * kblocks * 1024 + lane * 16;
   const uint32_t kbt = (p.k_total + 31u) / 32u;
@@ -861,8 +858,7 @@ void q8_pw_stream_gwk_kernel(const IgemmParams p)
   const bool row_ok = m < p.rows;
   if (!row_ok) m = p.rows - 1;
   // (launcher: the input tensor is addressable with 32-bit offsets; pieces beyond K read as zeros, see the kernel above)
-  const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(p.input), 0, static_cast<int>((p.rows - 1u) * p.input_stride + p.k_total), 0x00020000);
+  const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.input, static_cast<int>((p.rows - 1u) * p.input_stride + p.k_total));
   const uint32_t row_off = m * p.input_stride;
   const int8_t* wf = p.packed_w + static_cast<uint64_t>(nb) * kblocks * 1024 + lane * 16;
   const uint32_t kbt = (p.k_total + 31u) / 32u;
@@ -1139,10 +1135,9 @@ void q8_conv_stream_c3s_kernel(const IgemmParams p, const uint32_t log_cpr)
   const uint32_t unit_stride = gridDim.x * kWaves;
   const uint32_t raw_to_centred = 128u * 32u * KB;
   const uint32_t in_bytes = static_cast<uint32_t>(p.input_end - p.input);          // (launcher: < 2^31)
-  const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(p.input), 0, static_cast<int>(in_bytes), 0x00020000);
-  const __amdgpu_buffer_rsrc_t off_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<int32_t*>(p.offsets), 0, static_cast<int>(p.rows_per_image * p.ks * 4u + 16u), 0x00020000);   // (+16: convolution.c allocates the slack)
+  const __amdgpu_buffer_rsrc_t in_rsrc = buffer_rsrc(p.input, static_cast<int>(in_bytes));
+  const __amdgpu_buffer_rsrc_t off_rsrc = buffer_rsrc(
+      p.offsets, static_cast<int>(p.rows_per_image * p.ks * 4u + 16u));   // (+16: convolution.c allocates the slack)
   // first output row (flattened) whose window may hold the tensor's last pixel: conservatively the last image
   const uint32_t tail_first = p.rows - p.rows_per_image;
 
@@ -1282,11 +1277,8 @@ int launch_pw(const IgemmParams& p, uint32_t lds_bytes, hipStream_t stream)
   if constexpr (!RES && !D2S) {
     if (p.residual != nullptr) return launch_pw<KB, VEC, false, true>(p, lds_bytes, stream);
   }
-  auto kernel = q8_pw_stream_mfma_kernel<KB, VEC, D2S, RES>;
-  static qnnp::PerDeviceOnce attr_once;   // function attributes are per device
-  if (auto once_scope = attr_once.begin()) {
-    (void) hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
-  }
+  constexpr auto kernel = q8_pw_stream_mfma_kernel<KB, VEC, D2S, RES>;
+  allow_dynamic_lds<kernel>(kMaxLds);
   // LDS bounds the residency: kMaxLds -> 2 per CU, half of that -> 4
   uint32_t per_cu = (KB <= 5) ? 4u : 2u;
   const uint32_t by_lds = lds_bytes > 0 ? (160u * 1024u) / lds_bytes : per_cu;
@@ -1306,7 +1298,7 @@ int launch_pw(const IgemmParams& p, uint32_t lds_bytes, hipStream_t stream)
 #else
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds_bytes, stream, p);
 #endif
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 template <int VEC>
@@ -1418,11 +1410,8 @@ int launch_pw_staged_as(const IgemmParams& p, const StagedPlan& plan, hipStream_
   if constexpr (!RES && VEC == 16) {               // (a residual implies 16-byte aligned rows: q8igemm.hip)
     if (p.residual != nullptr) return launch_pw_staged_as<KB, VEC, SEQ, FULL, true>(p, plan, stream);
   }
-  auto kernel = q8_pw_stream_staged_kernel<KB, VEC, SEQ, FULL, RES>;
-  static qnnp::PerDeviceOnce attr_once;   // function attributes are per device
-  if (auto once_scope = attr_once.begin()) {
-    (void) hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
-  }
+  constexpr auto kernel = q8_pw_stream_staged_kernel<KB, VEC, SEQ, FULL, RES>;
+  allow_dynamic_lds<kernel>(kMaxLds);
   const uint32_t units = (p.rows + 31u) / 32u;
   uint32_t per_cu = plan.per_cu;
 #ifdef QNNP_ENABLE_ABLATION
@@ -1433,14 +1422,14 @@ int launch_pw_staged_as(const IgemmParams& p, const StagedPlan& plan, hipStream_
   const uint32_t needed = (units + kWaves - 1) / kWaves;
   if (gx > needed) gx = needed;
   IgemmParams pa = p;
-  pa.tiles_n_magic = static_cast<uint32_t>((1ull << 32) / p.n) + 1u;      // dense8: byte offset / n, exact below 2^32 / n
+  pa.tiles_n_magic = reciprocal_floor_plus1(p.n);      // dense8: byte offset / n, exact below 2^32 / n
   const uint32_t log_arg = plan.log_cpr | (plan.dense8 != 0 ? 0x80000000u : 0u);
 #ifdef QNNP_ENABLE_ABLATION
   pa.izp_fill = 0;
   if (const char* env = getenv("QNNP_PW_ABL")) pa.izp_fill = static_cast<uint32_t>(atoi(env));
 #endif
   hipLaunchKernelGGL(kernel, dim3(gx, plan.nsplit), dim3(kThreads), plan.lds_bytes, stream, pa, plan.nbp, log_arg);
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 template <int KB, int VEC>
@@ -1533,18 +1522,15 @@ int launch_longk_as(const IgemmParams& p, const StagedPlan& plan, hipStream_t st
       return launch_longk_as<KBMAX, SEQ, FULL, false, true>(p, plan, stream);
     }
   }
-  auto kernel = q8_pw_stream_longk_kernel<KBMAX, SEQ, FULL, RES, PF>;
-  static qnnp::PerDeviceOnce attr_once;   // function attributes are per device
-  if (auto once_scope = attr_once.begin()) {
-    (void) hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsLongK);
-  }
+  constexpr auto kernel = q8_pw_stream_longk_kernel<KBMAX, SEQ, FULL, RES, PF>;
+  allow_dynamic_lds<kernel>(kMaxLdsLongK);
   const uint32_t units = (p.rows + 31u) / 32u;
   const uint32_t per_cu_now = PF && plan.per_cu > 2u ? 2u : plan.per_cu;       // (PF: 2 waves per SIMD by its registers)
   uint32_t gx = (p.cu_count * per_cu_now + plan.nsplit - 1) / plan.nsplit;
   const uint32_t needed = (units + kWaves - 1) / kWaves;
   if (gx > needed) gx = needed;
   hipLaunchKernelGGL(kernel, dim3(gx, plan.nsplit), dim3(kThreads), plan.lds_bytes, stream, p, plan.nbp, plan.log_cpr);
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 template <int KBMAX>
@@ -1624,28 +1610,21 @@ int convstream_c3_launch(const IgemmParams& p, hipStream_t stream, const char** 
       if (grid > needed) grid = needed;
       *name = "q8_conv_stream_c3_mfma";
       requant_dispatch_ofs(p.rq, [&](auto seq, auto full) {
-        auto kernel = q8_conv_stream_c3s_kernel<decltype(seq)::value, decltype(full)::value>;
-        static qnnp::PerDeviceOnce attr_once_s;   // (one per instantiation of this lambda body)
-        if (auto once_scope = attr_once_s.begin()) {
-          (void) hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
-        }
+        constexpr auto kernel = q8_conv_stream_c3s_kernel<decltype(seq)::value, decltype(full)::value>;
+        allow_dynamic_lds<kernel>(kMaxLds);
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), staged_bytes, stream, p, log_cpr);
       });
-      return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+      return launch_status();
     }
   }
-  static qnnp::PerDeviceOnce attr_once;   // function attributes are per device
-  if (auto once_scope = attr_once.begin()) {
-    (void) hipFuncSetAttribute(reinterpret_cast<const void*>(q8_conv_stream_c3_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
-  }
+  allow_dynamic_lds<&q8_conv_stream_c3_kernel>(kMaxLds);
   const uint32_t units = (p.rows + 31u) / 32u;
   uint32_t grid = p.cu_count * 4u;
   const uint32_t needed = (units + kWaves - 1) / kWaves;
   if (grid > needed) grid = needed;
   *name = "q8_conv_stream_c3_mfma";
   hipLaunchKernelGGL(q8_conv_stream_c3_kernel, dim3(grid), dim3(kThreads), lds_bytes, stream, p);
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 /* long-K staged flavour: pointwise / fully-connected form, one group, 16-byte aligned rows both sides, 256 < K <= 1024 */
@@ -1702,7 +1681,7 @@ int pwstream_gw_launch(const IgemmParams& p, hipStream_t stream, const char** na
       if (res) hipLaunchKernelGGL((q8_pw_stream_gwk_kernel<8, true>), dim3(units), dim3(kThreads), 0, stream, p);
       else hipLaunchKernelGGL((q8_pw_stream_gwk_kernel<8, false>), dim3(units), dim3(kThreads), 0, stream, p);
     }
-    return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+    return launch_status();
   }
   *name = "q8_pw_stream_gw_mfma";
   if (p.residual != nullptr) {
@@ -1710,7 +1689,7 @@ int pwstream_gw_launch(const IgemmParams& p, hipStream_t stream, const char** na
   } else {
     hipLaunchKernelGGL(q8_pw_stream_gw_kernel<false>, dim3((units + kWaves - 1) / kWaves), dim3(kThreads), 0, stream, p);
   }
-  return hipGetLastError() == hipSuccess ? QNNP_HIP_OK : QNNP_HIP_ELAUNCH;
+  return launch_status();
 }
 
 int pwstream_launch(const IgemmParams& p0, uint32_t vec, hipStream_t stream, const char** name)
