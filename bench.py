@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the q8 conv/GEMM hot path on MI355X, one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: one rank per GPU. Under torch.distributed.run the ranks come from RANK/LOCAL_RANK/WORLD_SIZE; started
      plainly, bench.py re-launches ITSELF under torch.distributed.run with N ranks on 127.0.0.1. Fewer than N
      visible GPUs, or a WORLD_SIZE that disagrees with --gpus, is an error -- never a silent 1-GPU run.)
@@ -11,6 +11,12 @@ accumulate, fused Q31 requantize, uint8 out) through qnnp_*_fully_connected_nc_q
 whole GEMM launch. ops = 2*M*N*K, the reference's accounting (bench/q8gemm.cc:108).
 At N > 1 every rank runs its own replica of the GEMM (no batch dimension to shard: "replicas only",
 DESIGN.md) -> weak scaling, value = sum over ranks.
+
+A plain run does only what the headline needs: it sets up the GEMM, warms up, brings the chip to its sustained state,
+times the K steps, writes `--dump-outputs` if asked and prints the line (`roofline` then holds what the timed steps and
+the sustained replays measured; `cpu_baseline` is null). Everything below -- the secondary configs under "extra", the
+K separate launches beside the timed graph, the copy / bare-MFMA / vendor-GEMM yardsticks in `roofline`, the CPU
+baseline and the whole record in the --full-out file -- runs only with --full.
 
 Secondary numbers travel in the same JSON line under "extra" (not separate bench lines):
   * q8conv 3x3 56x56x64->64 batch 128 (configs[2]),
@@ -32,8 +38,8 @@ The timed region is EXACTLY K steps between barriers (wall clock, max over ranks
 launch stream by HIP events as well (-> "roofline", same launches); the K launches are captured into one hipGraph before the
 region and replayed inside it (K kernels back to back; K separate launches if capture is unavailable). It directly follows >= 1 s of the same GEMM
 replayed as a hipGraph (five batches of >= 200 ms, median reported as roofline.sustained_launch_ms), so the chip is in its
-sustained clock / power state, not in a boost burst. "cpu_baseline" times the reference's own SSE2 path (oracle/_ref, built from
-the reference sources) on this box's host cores on a bounded sample -- rank 0, N = 1 only.
+sustained clock / power state, not in a boost burst. With --full, "cpu_baseline" times the reference's own SSE2 path (oracle/_ref,
+built from the reference sources) on this box's host cores on a bounded sample (rank 0).
 Inputs are synthetic uniform-random uint8 already resident in HBM when the timed region starts, drawn from fixed seeds: with
 the same arguments every run computes the same outputs, and `--dump-outputs DIR` writes those of the last timed step (a
 seeded sample of the GEMM's rows, dump_outputs()) so that two builds can be compared output for output.
@@ -677,24 +683,28 @@ def run_stub(args, world, rank):
     barrier()
     ms_per_step = job_time_ms(local_ms, world)
     per_rank = gather_floats(local_ms, world)
-    total_batch = args.sweep_batch * world
-    start, my_batch = shard_batch(total_batch, world, rank)
-    sweep_ms = job_time_ms(0.5 * (1.0 + 0.5 * rank), world)
-    act_bytes = 1.0e7 * my_batch                           # (a stand-in for the sweep's algorithmic bytes per rank)
-    extra = {"mobilenetv2_sweep": {"images_per_s": round(total_batch / (sweep_ms * 1e-3), 1), "batch_per_gpu": my_batch,
-                                   "shard_start": start, "ms_per_batch": round(sweep_ms, 4), "timed_as": "stub",
-                                   "images_per_s_by_sum_of_layers": round(total_batch / (sweep_ms * 1e-3), 1),
-                                   "frac_of_hbm_peak": round(act_bytes / (sweep_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
-                                   "aggregate_hbm_gbs": round(world * act_bytes / (sweep_ms * 1e-3) / 1e9, 1),
-                                   "aggregate_frac_of_hbm_peak": round(act_bytes / (sweep_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)}}
     roofline = {"bound": "mfma", "kernel": "stub", "achieved": None, "peak": round(PEAK_I8_TOPS, 1), "unit": "TOP/s",
-                "frac": None, "traffic": None, "secondary": secondary_block(extra)}
-    cpu = {"value": None, "unit": "TOPS", "cores": 0, "kind": "stub", "sample": "none (harness self-test)"} if rank == 0 else None
+                "frac": None, "traffic": None}
+    extra, cpu = {}, None
+    if args.full:
+        total_batch = args.sweep_batch * world
+        start, my_batch = shard_batch(total_batch, world, rank)
+        sweep_ms = job_time_ms(0.5 * (1.0 + 0.5 * rank), world)
+        act_bytes = 1.0e7 * my_batch                           # (a stand-in for the sweep's algorithmic bytes per rank)
+        extra = {"mobilenetv2_sweep": {"images_per_s": round(total_batch / (sweep_ms * 1e-3), 1), "batch_per_gpu": my_batch,
+                                       "shard_start": start, "ms_per_batch": round(sweep_ms, 4), "timed_as": "stub",
+                                       "images_per_s_by_sum_of_layers": round(total_batch / (sweep_ms * 1e-3), 1),
+                                       "frac_of_hbm_peak": round(act_bytes / (sweep_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
+                                       "aggregate_hbm_gbs": round(world * act_bytes / (sweep_ms * 1e-3) / 1e9, 1),
+                                       "aggregate_frac_of_hbm_peak": round(act_bytes / (sweep_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)}}
+        roofline["secondary"] = secondary_block(extra)
+        if rank == 0:
+            cpu = {"value": None, "unit": "TOPS", "cores": 0, "kind": "stub", "sample": "none (harness self-test)"}
     if rank == 0:
         emit(assemble_line(world=world, steps=args.steps, warmup=args.warmup, ms_per_step=ms_per_step,
                            ev_ms_per_rank=per_rank, gemm_kernel="stub",
                            info={"arch": "stub", "compute_units": 0}, roofline=roofline, cpu=cpu,
-                           extra=extra, data="stub (no device work: harness self-test)"), args.full_out)
+                           extra=extra, data="stub (no device work: harness self-test)"), args.full_out if args.full else "")
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -726,12 +736,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline: the secondary configs under `extra`, the separate-launch, "
+                         "copy, bare-MFMA and vendor-GEMM yardsticks in `roofline`, the CPU baseline, and write the whole "
+                         "record to --full-out (a plain run does only the headline)")
     ap.add_argument("--sweep-batch", type=int, default=128, help="MobileNetV2 sweep images per GPU")
-    ap.add_argument("--no-extra", action="store_true", help="headline GEMM only")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: no secondary configs under `extra`")
     ap.add_argument("--full-out", default=os.path.join(ROOT, "gpurun_out", "bench_full.json"),
                     help="file that receives the whole record (the contract line plus `extra`: per-layer tables); '' = none")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-conv-lists", action="store_true", help="skip the ResNet-18 / ResNet-50 / ShuffleNet shape lists")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-conv-lists", action="store_true",
+                    help="with --full: skip the ResNet-18 / ResNet-50 / ShuffleNet shape lists")
     ap.add_argument("--gemm-kernel", type=int, default=0, help="0 auto, 1 generic MFMA kernel, 2 big-tile kernel")
     ap.add_argument("--dw-kernel", type=int, default=0,
                     help="measurement aid: 0 auto, 1 direct, 2 LDS-tiled, 3 register sliding window (depthwise layers)")
@@ -860,16 +875,18 @@ def main():
                 pass
         timed_graph = None
         torch.cuda.synchronize()
-    # the same K steps as K separate asynchronous launches (rounds 1-4's method; ~1 us of launch gap per step): reported beside
-    # the graph figure so the two methods can be compared round to round
-    sep0, sep1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    sep0.record(head_stream)
-    for _ in range(args.steps):
-        lib.run_operator(op)
-    sep1.record(head_stream)
-    torch.cuda.synchronize()
-    separate_ms = sep0.elapsed_time(sep1) / args.steps
+    # (--full) the same K steps as K separate asynchronous launches (rounds 1-4's method; ~1 us of launch gap per step):
+    # reported beside the graph figure so the two methods can be compared round to round
+    separate_ms = None
+    if args.full:
+        sep0, sep1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        sep0.record(head_stream)
+        for _ in range(args.steps):
+            lib.run_operator(op)
+        sep1.record(head_stream)
+        torch.cuda.synchronize()
+        separate_ms = sep0.elapsed_time(sep1) / args.steps
     stream = head_stream
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)   # (the launch stream: set_stream above)
     torch.cuda.synchronize()
@@ -913,56 +930,59 @@ def main():
                 "launch_ms": round(ev_ms, 5), "algorithmic_bytes_per_launch": 3 * M * N + 4 * N,
                 "timed_as": ("HIP events around the K timed steps (one replay of a hipGraph of K launches)"
                              if timed_graph is not None else "HIP events around the K timed steps (K separate launches)"),
-                "separate_launches_ms": round(separate_ms, 5),
                 "sustained_launch_ms": round(sustained_ms, 5),
                 "sustained_tops": round(gemm_ops / (sustained_ms * 1e-3) / 1e12, 2),
                 "sustained_as": "median of 5 x 48 replays of a 64-launch hipGraph, right before the timed steps"}
+    if separate_ms is not None:
+        roofline["separate_launches_ms"] = round(separate_ms, 5)
     copy_gbs = None
-    try:
-        # this chip's own streaming ceiling: a plain 16-byte-per-lane copy / read kernel over 1 GiB buffers
-        dbg = qnnpack_amd.load_debug()       # measurement companion library, not the product
-        # (round 4: the ceiling is the BEST streaming form -- nt loads and stores -- and the plain form is printed beside it:
-        #  the product's layer 4 had beaten the plain copy kernel, which a ceiling must not allow)
-        plain_gbs = round(dbg.copy_probe(False, 1024, 5), 1)
-        copy_gbs = max(plain_gbs, round(dbg.copy_probe(False, 1024, 5, streaming=True), 1))
-        roofline["hbm_copy_kernel_gbs"] = copy_gbs
-        roofline["hbm_copy_kernel_plain_policy_gbs"] = plain_gbs
-        roofline["hbm_read_kernel_gbs"] = round(dbg.copy_probe(True, 1024, 5), 1)
-    except Exception as exc:  # noqa: BLE001
-        print(f"# copy probe failed: {exc}", file=sys.stderr)
-    if rank == 0:
-        # the bare-MFMA rate of this very chip, measured in this process: with random operands the power
-        # management holds a lower clock, so this -- not the nominal peak -- is what a kernel can reach at best
+    if args.full:
+        # yardsticks of this chip and of the vendor library, measured after the timed steps in the same process
         try:
-            dbg = qnnpack_amd.load_debug()   # measurement companion library, not the product
-            roofline["mfma_only_random_operands"] = round(dbg.mfma_probe(True, 6400), 1)
-            roofline["mfma_only_zero_operands"] = round(dbg.mfma_probe(False, 6400), 1)
-            roofline["frac_of_mfma_only_random"] = round(achieved / roofline["mfma_only_random_operands"], 4)
+            # this chip's own streaming ceiling: a plain 16-byte-per-lane copy / read kernel over 1 GiB buffers
+            dbg = qnnpack_amd.load_debug()       # measurement companion library, not the product
+            # (round 4: the ceiling is the BEST streaming form -- nt loads and stores -- and the plain form is printed beside it:
+            #  the product's layer 4 had beaten the plain copy kernel, which a ceiling must not allow)
+            plain_gbs = round(dbg.copy_probe(False, 1024, 5), 1)
+            copy_gbs = max(plain_gbs, round(dbg.copy_probe(False, 1024, 5, streaming=True), 1))
+            roofline["hbm_copy_kernel_gbs"] = copy_gbs
+            roofline["hbm_copy_kernel_plain_policy_gbs"] = plain_gbs
+            roofline["hbm_read_kernel_gbs"] = round(dbg.copy_probe(True, 1024, 5), 1)
         except Exception as exc:  # noqa: BLE001
-            print(f"# mfma probe failed: {exc}", file=sys.stderr)
-        # the vendor library on the same problem, same box, same minute (torch._int_mm -> hipBLASLt: int8 x int8 ->
-        # int32, random operands, NO uint8 re-centring / row sums / requantization): a yardstick, not a baseline
-        try:
-            va = torch.randint(-128, 128, (M, K), dtype=torch.int8, device="cuda")
-            vb = torch.randint(-128, 128, (N, K), dtype=torch.int8, device="cuda").t()
-            for _ in range(5):
-                torch._int_mm(va, vb)
-            torch.cuda.synchronize()
-            ve0, ve1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ve0.record()
-            for _ in range(300):
-                torch._int_mm(va, vb)
-            ve1.record()
-            torch.cuda.synchronize()
-            roofline["vendor_int8_gemm_no_epilogue_tops"] = round(gemm_ops / (ve0.elapsed_time(ve1) * 1e-3 / 300) / 1e12, 1)
-            del va, vb
-        except Exception as exc:  # noqa: BLE001
-            print(f"# vendor int8 GEMM probe failed: {exc}", file=sys.stderr)
+            print(f"# copy probe failed: {exc}", file=sys.stderr)
+        if rank == 0:
+            # the bare-MFMA rate of this very chip, measured in this process: with random operands the power
+            # management holds a lower clock, so this -- not the nominal peak -- is what a kernel can reach at best
+            try:
+                dbg = qnnpack_amd.load_debug()   # measurement companion library, not the product
+                roofline["mfma_only_random_operands"] = round(dbg.mfma_probe(True, 6400), 1)
+                roofline["mfma_only_zero_operands"] = round(dbg.mfma_probe(False, 6400), 1)
+                roofline["frac_of_mfma_only_random"] = round(achieved / roofline["mfma_only_random_operands"], 4)
+            except Exception as exc:  # noqa: BLE001
+                print(f"# mfma probe failed: {exc}", file=sys.stderr)
+            # the vendor library on the same problem, same box, same minute (torch._int_mm -> hipBLASLt: int8 x int8 ->
+            # int32, random operands, NO uint8 re-centring / row sums / requantization): a yardstick, not a baseline
+            try:
+                va = torch.randint(-128, 128, (M, K), dtype=torch.int8, device="cuda")
+                vb = torch.randint(-128, 128, (N, K), dtype=torch.int8, device="cuda").t()
+                for _ in range(5):
+                    torch._int_mm(va, vb)
+                torch.cuda.synchronize()
+                ve0, ve1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ve0.record()
+                for _ in range(300):
+                    torch._int_mm(va, vb)
+                ve1.record()
+                torch.cuda.synchronize()
+                roofline["vendor_int8_gemm_no_epilogue_tops"] = round(gemm_ops / (ve0.elapsed_time(ve1) * 1e-3 / 300) / 1e12, 1)
+                del va, vb
+            except Exception as exc:  # noqa: BLE001
+                print(f"# vendor int8 GEMM probe failed: {exc}", file=sys.stderr)
     lib.delete_operator(op)
     del a, c
 
     extra = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         lib.set_async(False)
         # ---------------------------------------------------------- configs[2]: 3x3 conv 56x56x64->64, batch 128
         layer = ConvLayer(lib, torch, 128, 56, 56, 3, 3, 1, 1, 1, 64, 64, seed=3, min_bytes_between_reuse=544 << 20)
@@ -1112,7 +1132,7 @@ def main():
         roofline["secondary"] = secondary_block(extra)
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # the reference's SSE2 path on this box's host cores: the full sample at N = 1, a shorter one at N > 1 (the
         # other ranks wait at the closing barrier meanwhile) -- a SCALE line carries its baseline too
         cpu = cpu_baseline_gemm(12.0 if world == 1 else 5.0)
@@ -1126,7 +1146,7 @@ def main():
     if rank == 0:
         emit(assemble_line(world=world, steps=args.steps, warmup=args.warmup, ms_per_step=ms_per_step,
                            ev_ms_per_rank=ev_ms_per_rank, gemm_kernel=gemm_kernel, info=info,
-                           roofline=roofline, cpu=cpu, extra=extra, data="synthetic"), args.full_out)
+                           roofline=roofline, cpu=cpu, extra=extra, data="synthetic"), args.full_out if args.full else "")
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -16,7 +16,7 @@ PY
 for round in 1 2; do
   for L in $A $B; do
     cp $L qnnpack_amd/libqnnpack_gfx950.so
-    timeout 600 python bench.py --steps 20 --warmup 5 2>/dev/null | tail -n 1 > $OUT/bench_$(basename $L .so)_$round.json
+    timeout 600 python bench.py --steps 20 --warmup 5 --full --full-out $OUT/bench_$(basename $L .so)_$round.json > /dev/null 2>&1
     echo "== $L round $round"; summ $OUT/bench_$(basename $L .so)_$round.json
   done
 done

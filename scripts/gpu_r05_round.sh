@@ -8,7 +8,7 @@ tail -n 12 $OUT/pytest_gpu.log
 echo "== smoke"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -n 5 | tee $OUT/smoke.log
 echo "== bench"
-timeout 900 python bench.py --steps 20 --warmup 5 2> $OUT/bench.err | tail -n 1 > $OUT/bench.json
+timeout 900 python bench.py --steps 20 --warmup 5 --full 2> $OUT/bench.err | tail -n 1 > $OUT/bench.json
 python - <<PY
 import json
 d = json.load(open("$OUT/bench.json"))
@@ -23,7 +23,7 @@ echo "== rocprofv3 kernel stats (headline GEMM only)"
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$OUT/prof -o gemm -- python $OLDPWD/bench.py --steps 20 --warmup 5 --no-extra --no-cpu-baseline > $OLDPWD/$OUT/prof_run.log 2>&1)
 for f in $(find $OUT/prof -name "*kernel_stats*.csv" | head -1); do cut -c1-200 $f | head -n 6; cp $f $OUT/rocprof_kernel_stats_gemm.csv; done
 echo "== rocprofv3 kernel stats (whole bench)"
-(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$OUT/prof_all -o all -- python $OLDPWD/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $OLDPWD/$OUT/prof_all_run.log 2>&1)
+(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$OUT/prof_all -o all -- python $OLDPWD/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > $OLDPWD/$OUT/prof_all_run.log 2>&1)
 for f in $(find $OUT/prof_all -name "*kernel_stats*.csv" | head -1); do cut -c1-160 $f | head -n 14; cp $f $OUT/rocprof_kernel_stats_all.csv; done
 rm -rf $OUT/prof $OUT/prof_all
 echo "== PMC: fabric traffic and SQ counters of the GEMM"

@@ -7,7 +7,7 @@ timeout 300 build_tools/ubench_mfma2 2>&1 | tee $OUT/ubench_mfma2.txt
 echo "== pytest (changed files)"
 timeout 900 python -m pytest tests/test_gpu_pwstream.py tests/test_gpu_gemm256c.py -m gpu -q -p no:cacheprovider 2>&1 | tail -n 8 | tee $OUT/pytest_changed.log
 echo "== bench"
-timeout 900 python bench.py --steps 20 --warmup 5 --full-out $OUT/bench_full.json 2> $OUT/bench.err > $OUT/bench.stdout
+timeout 900 python bench.py --steps 20 --warmup 5 --full --full-out $OUT/bench_full.json 2> $OUT/bench.err > $OUT/bench.stdout
 tail -n 1 $OUT/bench.stdout > $OUT/bench.json
 wc -c $OUT/bench.json
 python - <<PY

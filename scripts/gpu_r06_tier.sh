@@ -3,7 +3,7 @@
 TAG=${1:-r06e}; OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 timeout 1800 python -m pytest tests -m gpu -q --maxfail=40 -p no:cacheprovider 2>&1 | tail -n 60 > $OUT/pytest_gpu.log
 tail -n 30 $OUT/pytest_gpu.log
-timeout 900 python bench.py --steps 20 --warmup 5 --full-out $OUT/bench_full.json 2> $OUT/bench.err | tail -n 1 > $OUT/bench.json
+timeout 900 python bench.py --steps 20 --warmup 5 --full --full-out $OUT/bench_full.json 2> $OUT/bench.err | tail -n 1 > $OUT/bench.json
 python - <<PY
 import json
 d = json.load(open("$OUT/bench.json"))

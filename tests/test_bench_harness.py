@@ -1,8 +1,9 @@
 """CPU tier: bench.py's multi-rank harness, end to end, without a GPU. QNNP_BENCH_STUB=1 replaces the device step by a
 sleep (rank r is 1 + r/2 times slower than rank 0) and RCCL by gloo; everything else is the code the driver's SCALE run
 goes through: `python bench.py --gpus N` re-launching itself under torch.distributed.run on 127.0.0.1, the WORLD_SIZE
-check, the barrier-bracketed timed region, the max-over-ranks time, the batch shards of the sweep and the one JSON line
-(whole-job value, per-rank launch times, a cpu_baseline object at N > 1 as well)."""
+check, the barrier-bracketed timed region, the max-over-ranks time and the one JSON line (whole-job value, per-rank launch
+times); with --full also the batch shards of the sweep, the whole record in the --full-out file and a cpu_baseline object at
+N > 1 as well."""
 import json
 import os
 import socket
@@ -35,7 +36,7 @@ def _line(stdout):
 def test_bench_spawns_its_ranks_and_prints_one_line(gpus, tmp_path):
     full_out = str(tmp_path / "bench_full.json")
     res = subprocess.run([sys.executable, BENCH, "--gpus", str(gpus), "--steps", "6", "--warmup", "1", "--sweep-batch", "10",
-                          "--full-out", full_out],
+                          "--full", "--full-out", full_out],
                          env=_env(), capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-2000:]
     line = _line(res.stdout)
@@ -69,6 +70,30 @@ def test_bench_spawns_its_ranks_and_prints_one_line(gpus, tmp_path):
         per_rank = line["roofline"]["per_rank_launch_ms"]
         assert len(per_rank) == gpus and per_rank == sorted(per_rank)       # rank r sleeps longer than rank r-1
         assert "one replica per GPU" in line["config"]["workload"]
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_plain_run_is_the_headline_alone(gpus, tmp_path):
+    """without --full the run times the steps and prints the line, nothing else: no `extra`, no secondary configs, no CPU
+    baseline, no full-record file (even where --full-out names one)"""
+    full_out = tmp_path / "bench_full.json"
+    res = subprocess.run([sys.executable, BENCH, "--gpus", str(gpus), "--steps", "6", "--warmup", "1",
+                          "--full-out", str(full_out)],
+                         env=_env(), capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr[-2000:]
+    assert res.stdout.rstrip().splitlines()[-1].startswith("{")
+    line = _line(res.stdout)
+    assert line["n_gpus"] == gpus and line["steps"] == 6 and line["warmup"] == 1
+    assert line["metric"] == "q8gemm_int8_tops" and line["unit"] == "TOPS" and line["higher_is_better"] is True
+    assert line["dtype"] == "u8" and line["data"].startswith("stub")
+    slowest = 2.0 * (1.0 + 0.5 * (gpus - 1))
+    assert slowest * 0.95 <= line["ms_per_step"] <= slowest * 3.0, line["ms_per_step"]
+    expected = gpus * 2.0 * 4096 ** 3 / (line["ms_per_step"] * 1e-3) / 1e12
+    assert abs(line["value"] - expected) <= 0.01 * expected
+    assert "extra" not in line and "secondary" not in line["roofline"] and line["cpu_baseline"] is None
+    assert not full_out.exists()
+    if gpus > 1:
+        assert len(line["roofline"]["per_rank_launch_ms"]) == gpus
 
 
 def test_launcher_world_size_mismatch_is_refused():
