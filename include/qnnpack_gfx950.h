@@ -90,6 +90,43 @@ enum qnnp_status qnnp_setup_max_pooling2d_nhwc_u8(
     size_t output_stride,
     pthreadpool_t threadpool);
 
+/* Channel shuffle and clamp (reference include/qnnpack.h:220-232, 257-270, prototypes unchanged). Semantics and status
+ * codes are the reference's (src/channel-shuffle.c, src/clamp.c):
+ *   channel shuffle: y[c * groups + g] = x[g * group_channels + c] for each pixel (groups >= 2, group_channels >= 1);
+ *   clamp: y = min(max(x, output_min), output_max) for each byte (channels >= 1, output_min <= output_max).
+ * Computed by HIP kernels. Clamp runs in place when input == output with equal strides. Where the reference checks
+ * nothing and would go out of range, setup answers invalid_parameter: NULL tensors, a pixel stride below the channel
+ * count (groups * group_channels), input and output byte spans that overlap (for clamp: other than exactly in place).
+ * Sizes beyond the kernels' index range (channels >= 2^31, batch >= 2^31) are unsupported_parameter. */
+enum qnnp_status qnnp_create_channel_shuffle_nc_x8(
+    size_t groups,
+    size_t group_channels,
+    uint32_t flags,
+    qnnp_operator_t* channel_shuffle);
+
+enum qnnp_status qnnp_setup_channel_shuffle_nc_x8(
+    qnnp_operator_t channel_shuffle,
+    size_t batch_size,
+    const uint8_t* input,
+    size_t input_stride,
+    uint8_t* output,
+    size_t output_stride);
+
+enum qnnp_status qnnp_create_clamp_nc_u8(
+    size_t channels,
+    uint8_t output_min,
+    uint8_t output_max,
+    uint32_t flags,
+    qnnp_operator_t* clamp);
+
+enum qnnp_status qnnp_setup_clamp_nc_u8(
+    qnnp_operator_t clamp,
+    size_t batch_size,
+    const uint8_t* input,
+    size_t input_stride,
+    uint8_t* output,
+    size_t output_stride);
+
 /* Devices. The library keeps one context (launch stream, asynchrony flag) per gfx950 GPU of the node.
  *   BEFORE qnnp_initialize: names the PRIMARY device qnnp_initialize binds (default: env QNNP_GFX950_DEVICE,
  *     else the calling thread's current HIP device).

@@ -107,6 +107,17 @@ class QnnpackLibrary:
             L.qnnp_setup_max_pooling2d_nhwc_u8.restype = c_int
             L.qnnp_setup_max_pooling2d_nhwc_u8.argtypes = [
                 c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]
+        # channel shuffle and clamp (reference include/qnnpack.h:220-232, 257-270; the product declares them in
+        # qnnpack_gfx950.h). Bound when present, as the windowed pooling entries are.
+        if hasattr(L, "qnnp_create_channel_shuffle_nc_x8") or not os.environ.get("QNNP_GFX950_LIBRARY"):
+            L.qnnp_create_channel_shuffle_nc_x8.restype = c_int
+            L.qnnp_create_channel_shuffle_nc_x8.argtypes = [c_size_t, c_size_t, c_uint32, POINTER(c_void_p)]
+            L.qnnp_setup_channel_shuffle_nc_x8.restype = c_int
+            L.qnnp_setup_channel_shuffle_nc_x8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
+            L.qnnp_create_clamp_nc_u8.restype = c_int
+            L.qnnp_create_clamp_nc_u8.argtypes = [c_size_t, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)]
+            L.qnnp_setup_clamp_nc_u8.restype = c_int
+            L.qnnp_setup_clamp_nc_u8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
         L.qnnp_run_operator.restype = c_int
         L.qnnp_run_operator.argtypes = [c_void_p, c_void_p]
         L.qnnp_delete_operator.restype = c_int
@@ -322,6 +333,46 @@ class QnnpackLibrary:
         st = self.setup_max_pooling2d_nhwc_u8_status(*args)
         if st != Status.success:
             raise QnnpackError("qnnp_setup_max_pooling2d_nhwc_u8", st)
+
+    def create_channel_shuffle_nc_x8_status(self, groups, group_channels, flags=0):
+        handle = c_void_p(None)
+        st = self.lib.qnnp_create_channel_shuffle_nc_x8(groups, group_channels, flags, ctypes.byref(handle))
+        return Status(st), handle.value
+
+    def create_channel_shuffle_nc_x8(self, *args, **kwargs) -> int:
+        st, handle = self.create_channel_shuffle_nc_x8_status(*args, **kwargs)
+        if st != Status.success:
+            raise QnnpackError("qnnp_create_channel_shuffle_nc_x8", st)
+        return handle
+
+    def setup_channel_shuffle_nc_x8_status(self, op, batch_size, input, input_stride, output, output_stride) -> Status:
+        return Status(self.lib.qnnp_setup_channel_shuffle_nc_x8(
+            op, batch_size, address_of(input), input_stride, address_of(output), output_stride))
+
+    def setup_channel_shuffle_nc_x8(self, *args) -> None:
+        st = self.setup_channel_shuffle_nc_x8_status(*args)
+        if st != Status.success:
+            raise QnnpackError("qnnp_setup_channel_shuffle_nc_x8", st)
+
+    def create_clamp_nc_u8_status(self, channels, output_min, output_max, flags=0):
+        handle = c_void_p(None)
+        st = self.lib.qnnp_create_clamp_nc_u8(channels, output_min, output_max, flags, ctypes.byref(handle))
+        return Status(st), handle.value
+
+    def create_clamp_nc_u8(self, *args, **kwargs) -> int:
+        st, handle = self.create_clamp_nc_u8_status(*args, **kwargs)
+        if st != Status.success:
+            raise QnnpackError("qnnp_create_clamp_nc_u8", st)
+        return handle
+
+    def setup_clamp_nc_u8_status(self, op, batch_size, input, input_stride, output, output_stride) -> Status:
+        return Status(self.lib.qnnp_setup_clamp_nc_u8(
+            op, batch_size, address_of(input), input_stride, address_of(output), output_stride))
+
+    def setup_clamp_nc_u8(self, *args) -> None:
+        st = self.setup_clamp_nc_u8_status(*args)
+        if st != Status.success:
+            raise QnnpackError("qnnp_setup_clamp_nc_u8", st)
 
     def run_operator_status(self, op, threadpool=None) -> Status:
         return Status(self.lib.qnnp_run_operator(op, threadpool))

@@ -33,6 +33,7 @@
 #include "avgpool_math.hip.h"
 #include "per_device.h"
 #include "qnnp_hip.h"
+#include "u8_bytewise.hip.h"
 
 namespace qnnp {
 
@@ -40,11 +41,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr uint32_t kPackedTaps = 257;   // 257 * 255 = 65535: the largest tap count a 16-bit lane can sum
-
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ u16x2 as_u16x2(uint32_t x) { return __builtin_bit_cast(u16x2, x); }
-__device__ __forceinline__ uint32_t as_u32(u16x2 x) { return __builtin_bit_cast(uint32_t, x); }
 
 /* In-image taps [a, b) of the k taps p0 + t*d (t in [0, k)) along an axis of n pixels; b >= a. The setup keeps the
  * padded extent below 2^31, so no term here overflows int32. */
@@ -90,21 +86,6 @@ __device__ __forceinline__ void load_taps(const uint8_t* px, uint32_t (&v)[VEC /
   }
 }
 
-/* running bytewise max of one dword: odd bytes in the high halves of `odd`, even bytes in the high halves of `even` */
-__device__ __forceinline__ void max_step(uint32_t& odd, uint32_t& even, uint32_t x)
-{
-  odd = as_u32(__builtin_elementwise_max(as_u16x2(odd), as_u16x2(x)));
-  even = as_u32(__builtin_elementwise_max(as_u16x2(even), as_u16x2(x) << static_cast<unsigned short>(8)));
-}
-
-/* clamp both halves' high bytes to [lo, hi] (their low bytes only break ties) and join the bytes */
-__device__ __forceinline__ uint32_t max_finish(uint32_t odd, uint32_t even, uint32_t clamp_hi, uint32_t clamp_lo)
-{
-  odd = as_u32(__builtin_elementwise_max(__builtin_elementwise_min(as_u16x2(odd), as_u16x2(clamp_hi)), as_u16x2(clamp_lo)));
-  even = as_u32(__builtin_elementwise_max(__builtin_elementwise_min(as_u16x2(even), as_u16x2(clamp_hi)), as_u16x2(clamp_lo)));
-  return __builtin_amdgcn_perm(odd, even, 0x07030501u);    // bytes: even.1, odd.1, even.3, odd.3
-}
-
 template <int VEC>
 __global__ __launch_bounds__(kThreads)
 void q8_maxpool_kernel(const qnnp_hip_pool_args p, const uint32_t cvecs, const uint32_t rows)
@@ -116,9 +97,8 @@ void q8_maxpool_kernel(const qnnp_hip_pool_args p, const uint32_t cvecs, const u
   const int32_t x0 = static_cast<int32_t>(ox * p.stride_width) - static_cast<int32_t>(p.pad_left);
   int32_t tx_begin, tx_end;
   max_taps(x0, p.kernel_width, p.dilation_width, p.input_width, tx_begin, tx_end);
-  // clamp bounds in the 16-bit-lane form of max_finish: the bound in the high byte, the low byte 0xFF / 0x00
-  const uint32_t clamp_hi = (p.output_max << 8 | 0xFFu) * 0x00010001u;
-  const uint32_t clamp_lo = (p.output_min << 8) * 0x00010001u;
+  const uint32_t clamp_hi = clamp_hi_bound(p.output_max);
+  const uint32_t clamp_lo = clamp_lo_bound(p.output_min);
 
   for (uint32_t row = blockIdx.y; row < rows; row += gridDim.y) {
     const uint32_t n = row / p.output_height;

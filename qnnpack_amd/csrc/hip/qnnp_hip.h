@@ -352,6 +352,24 @@ struct qnnp_hip_pool_args {
 int qnnp_hip_maxpool_run(const struct qnnp_hip_pool_args* args, const char** kernel_name);
 int qnnp_hip_avgpool_run(const struct qnnp_hip_pool_args* args, const char** kernel_name);
 
+/* channel shuffle and clamp (x8shuffle.hip, linked into libqnnpack_gfx950.so only -- see the Makefile): replace
+ * x8zip_x{2,3,4,m}__sse2 / u8clamp_ukernel__sse2 and the channel-shuffle / clamp cases of src/operator-run.c. For pixel
+ * p of `pixels`, each `*_stride` bytes apart:
+ *   channel shuffle: y[c * groups + g] = x[g * group_channels + c]  (g < groups, c < group_channels)
+ *   clamp:           y[c] = min(max(x[c], output_min), output_max)  (c < channels)
+ * Channel shuffle needs disjoint input and output; clamp may run in place (input == output, equal strides). */
+struct qnnp_hip_x8_args {
+  const uint8_t* input;
+  uint8_t* output;
+  uint32_t pixels;
+  uint32_t groups, group_channels;      /* channel shuffle */
+  uint32_t channels;                    /* channel shuffle: groups * group_channels */
+  uint64_t input_stride, output_stride; /* bytes between pixels */
+  uint32_t output_min, output_max;      /* clamp */
+};
+int qnnp_hip_channel_shuffle_run(const struct qnnp_hip_x8_args* args, const char** kernel_name);
+int qnnp_hip_clamp_run(const struct qnnp_hip_x8_args* args, const char** kernel_name);
+
 /* ---- fused inverted-residual block ---------------------------------------
  * [pointwise expand ->] depthwise 3x3 (pad 1, stride 1 | 2) -> pointwise project [-> + block input], one launch,
  * the expanded tensors live only in LDS (q8fused.hip). Arithmetic per stage is that of the stand-alone operators

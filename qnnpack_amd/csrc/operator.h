@@ -26,6 +26,8 @@ enum qnnp_ukernel_type {
   qnnp_ukernel_type_fused_block,
   qnnp_ukernel_type_max_pooling,        /* max-pooling.c */
   qnnp_ukernel_type_average_pooling,    /* average-pooling.c */
+  qnnp_ukernel_type_channel_shuffle,    /* channel-shuffle.c */
+  qnnp_ukernel_type_clamp,              /* clamp.c */
 };
 
 /* One output phase of a strided deconvolution (deconvolution.c): the output pixels whose (oy + pad_top) % stride_h
@@ -184,8 +186,9 @@ struct qnnp_operator {
   struct qnnp_hip_dwconv_plan dw_plan;   /* depthwise launch plan, computed at the first run after a setup */
 
   /* launch of operator types whose code is not part of every build (windowed pooling: max-pooling.c,
-   * average-pooling.c): set by their create, called by launch_kernel's default arm (operator-run.c) with device
-   * pointers. Keeps operator-run.c free of references to their kernels, so builds without them still link. */
+   * average-pooling.c; channel-shuffle.c, clamp.c): set by their create, called by launch_kernel's default arm
+   * (operator-run.c) with device pointers. Keeps operator-run.c free of references to their kernels, so builds without
+   * them still link. */
   int (*launch_hook)(struct qnnp_operator* op, const void* input, void* output);
 };
 
@@ -209,6 +212,13 @@ static inline enum qnnp_status qnnp_enter_for_update(int device, enum qnnp_statu
     return qnnp_status_invalid_parameter;
   }
   return qnnp_status_success;
+}
+
+/* whether the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte */
+static inline int qnnp_spans_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+  const uintptr_t pa = (uintptr_t) a, pb = (uintptr_t) b;
+  return pa < pb + b_bytes && pb < pa + a_bytes;
 }
 
 /* fused-block.c */
