@@ -127,6 +127,68 @@ enum qnnp_status qnnp_setup_clamp_nc_u8(
     uint8_t* output,
     size_t output_stride);
 
+/* Sigmoid and leaky ReLU (reference include/qnnpack.h:272-309, prototypes unchanged). Semantics and status codes are
+ * the reference's (src/sigmoid.c, src/leaky-relu.c): create builds a 256-byte table on the host with the reference's
+ * float arithmetic, run is y = table[x] for each byte.
+ *   sigmoid: table[i] = lrintf(clamp(256 / (1 + expf(-input_scale * (i - input_zero_point))), output_min, output_max));
+ *     the output scale must be 1/256 and the output zero point 0 (else unsupported_parameter);
+ *   leaky ReLU: x = (input_scale / output_scale) * (i - input_zero_point), y = x < 0 ? x * negative_slope : x,
+ *     table[i] = lrintf(clamp(y, output_min - output_zero_point, output_max - output_zero_point)) + output_zero_point;
+ *     0 < negative_slope <= 1, and the scale ratio must lie in [2^-8, 2^8) (else unsupported_parameter).
+ * Both need output_min < output_max (clamp allows equality). Computed by HIP kernels; they run in place when input ==
+ * output with equal strides. Where the reference checks nothing and would go out of range, setup answers
+ * invalid_parameter: NULL tensors, a pixel stride below the channel count, input and output byte spans that overlap
+ * other than exactly in place. Sizes beyond the kernels' index range (channels >= 2^31, batch >= 2^31) are
+ * unsupported_parameter.
+ * With these, softargmax (reference include/qnnpack.h:311-324) is the one reference operator this library does not
+ * have: it stays on the CPU. */
+enum qnnp_status qnnp_create_sigmoid_nc_q8(
+    size_t channels,
+    uint8_t input_zero_point,
+    float input_scale,
+    uint8_t output_zero_point,
+    float output_scale,
+    uint8_t output_min,
+    uint8_t output_max,
+    uint32_t flags,
+    qnnp_operator_t* sigmoid);
+
+enum qnnp_status qnnp_setup_sigmoid_nc_q8(
+    qnnp_operator_t sigmoid,
+    size_t batch_size,
+    const uint8_t* input,
+    size_t input_stride,
+    uint8_t* output,
+    size_t output_stride);
+
+enum qnnp_status qnnp_create_leaky_relu_nc_q8(
+    size_t channels,
+    float negative_slope,
+    uint8_t input_zero_point,
+    float input_scale,
+    uint8_t output_zero_point,
+    float output_scale,
+    uint8_t output_min,
+    uint8_t output_max,
+    uint32_t flags,
+    qnnp_operator_t* leaky_relu);
+
+enum qnnp_status qnnp_setup_leaky_relu_nc_q8(
+    qnnp_operator_t leaky_relu,
+    size_t batch_size,
+    const uint8_t* input,
+    size_t input_stride,
+    uint8_t* output,
+    size_t output_stride);
+
+/* The table operator under both, for any other uint8 -> uint8 function of one byte (tanh, hard-swish, re-quantisation
+ * between two scales, ...). No reference counterpart: the reference keeps it internal. Setup and run behave as above;
+ * create answers invalid_parameter for channels == 0 or a NULL table. */
+/* y[c] = table[x[c]] for every byte of every pixel; the 256 bytes of `table` are copied at create */
+enum qnnp_status qnnp_gfx950_create_lut_nc_x8(size_t channels, const uint8_t table[256], uint32_t flags, qnnp_operator_t* lut);
+enum qnnp_status qnnp_gfx950_setup_lut_nc_x8(qnnp_operator_t lut, size_t batch_size,
+    const uint8_t* input, size_t input_stride, uint8_t* output, size_t output_stride);
+
 /* Devices. The library keeps one context (launch stream, asynchrony flag) per gfx950 GPU of the node.
  *   BEFORE qnnp_initialize: names the PRIMARY device qnnp_initialize binds (default: env QNNP_GFX950_DEVICE,
  *     else the calling thread's current HIP device).

@@ -118,6 +118,24 @@ class QnnpackLibrary:
             L.qnnp_create_clamp_nc_u8.argtypes = [c_size_t, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)]
             L.qnnp_setup_clamp_nc_u8.restype = c_int
             L.qnnp_setup_clamp_nc_u8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
+        # sigmoid and leaky ReLU (reference include/qnnpack.h:272-309; the product declares them in qnnpack_gfx950.h).
+        # Bound when present, as above; the table operator under them exists in the product only.
+        if hasattr(L, "qnnp_create_sigmoid_nc_q8") or not os.environ.get("QNNP_GFX950_LIBRARY"):
+            L.qnnp_create_sigmoid_nc_q8.restype = c_int
+            L.qnnp_create_sigmoid_nc_q8.argtypes = [
+                c_size_t, c_uint8, c_float, c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)]
+            L.qnnp_setup_sigmoid_nc_q8.restype = c_int
+            L.qnnp_setup_sigmoid_nc_q8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
+            L.qnnp_create_leaky_relu_nc_q8.restype = c_int
+            L.qnnp_create_leaky_relu_nc_q8.argtypes = [
+                c_size_t, c_float, c_uint8, c_float, c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)]
+            L.qnnp_setup_leaky_relu_nc_q8.restype = c_int
+            L.qnnp_setup_leaky_relu_nc_q8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
+        if hasattr(L, "qnnp_gfx950_create_lut_nc_x8"):
+            L.qnnp_gfx950_create_lut_nc_x8.restype = c_int
+            L.qnnp_gfx950_create_lut_nc_x8.argtypes = [c_size_t, c_void_p, c_uint32, POINTER(c_void_p)]
+            L.qnnp_gfx950_setup_lut_nc_x8.restype = c_int
+            L.qnnp_gfx950_setup_lut_nc_x8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
         L.qnnp_run_operator.restype = c_int
         L.qnnp_run_operator.argtypes = [c_void_p, c_void_p]
         L.qnnp_delete_operator.restype = c_int
@@ -373,6 +391,75 @@ class QnnpackLibrary:
         st = self.setup_clamp_nc_u8_status(*args)
         if st != Status.success:
             raise QnnpackError("qnnp_setup_clamp_nc_u8", st)
+
+    def create_sigmoid_nc_q8_status(self, channels, input_zero_point, input_scale, output_zero_point, output_scale,
+                                    output_min, output_max, flags=0):
+        handle = c_void_p(None)
+        st = self.lib.qnnp_create_sigmoid_nc_q8(channels, input_zero_point, input_scale, output_zero_point, output_scale,
+                                                output_min, output_max, flags, ctypes.byref(handle))
+        return Status(st), handle.value
+
+    def create_sigmoid_nc_q8(self, *args, **kwargs) -> int:
+        st, handle = self.create_sigmoid_nc_q8_status(*args, **kwargs)
+        if st != Status.success:
+            raise QnnpackError("qnnp_create_sigmoid_nc_q8", st)
+        return handle
+
+    def setup_sigmoid_nc_q8_status(self, op, batch_size, input, input_stride, output, output_stride) -> Status:
+        return Status(self.lib.qnnp_setup_sigmoid_nc_q8(
+            op, batch_size, address_of(input), input_stride, address_of(output), output_stride))
+
+    def setup_sigmoid_nc_q8(self, *args) -> None:
+        st = self.setup_sigmoid_nc_q8_status(*args)
+        if st != Status.success:
+            raise QnnpackError("qnnp_setup_sigmoid_nc_q8", st)
+
+    def create_leaky_relu_nc_q8_status(self, channels, negative_slope, input_zero_point, input_scale, output_zero_point,
+                                       output_scale, output_min, output_max, flags=0):
+        handle = c_void_p(None)
+        st = self.lib.qnnp_create_leaky_relu_nc_q8(channels, negative_slope, input_zero_point, input_scale,
+                                                   output_zero_point, output_scale, output_min, output_max, flags,
+                                                   ctypes.byref(handle))
+        return Status(st), handle.value
+
+    def create_leaky_relu_nc_q8(self, *args, **kwargs) -> int:
+        st, handle = self.create_leaky_relu_nc_q8_status(*args, **kwargs)
+        if st != Status.success:
+            raise QnnpackError("qnnp_create_leaky_relu_nc_q8", st)
+        return handle
+
+    def setup_leaky_relu_nc_q8_status(self, op, batch_size, input, input_stride, output, output_stride) -> Status:
+        return Status(self.lib.qnnp_setup_leaky_relu_nc_q8(
+            op, batch_size, address_of(input), input_stride, address_of(output), output_stride))
+
+    def setup_leaky_relu_nc_q8(self, *args) -> None:
+        st = self.setup_leaky_relu_nc_q8_status(*args)
+        if st != Status.success:
+            raise QnnpackError("qnnp_setup_leaky_relu_nc_q8", st)
+
+    def create_lut_nc_x8_status(self, channels, table, flags=0):
+        """the product's table operator (qnnp_gfx950_create_lut_nc_x8); `table`: 256 uint8, or None"""
+        handle = c_void_p(None)
+        if table is not None:
+            table = np.ascontiguousarray(table, dtype=np.uint8)
+            assert table.size == 256, table.size
+        st = self.lib.qnnp_gfx950_create_lut_nc_x8(channels, address_of(table), flags, ctypes.byref(handle))
+        return Status(st), handle.value
+
+    def create_lut_nc_x8(self, *args, **kwargs) -> int:
+        st, handle = self.create_lut_nc_x8_status(*args, **kwargs)
+        if st != Status.success:
+            raise QnnpackError("qnnp_gfx950_create_lut_nc_x8", st)
+        return handle
+
+    def setup_lut_nc_x8_status(self, op, batch_size, input, input_stride, output, output_stride) -> Status:
+        return Status(self.lib.qnnp_gfx950_setup_lut_nc_x8(
+            op, batch_size, address_of(input), input_stride, address_of(output), output_stride))
+
+    def setup_lut_nc_x8(self, *args) -> None:
+        st = self.setup_lut_nc_x8_status(*args)
+        if st != Status.success:
+            raise QnnpackError("qnnp_gfx950_setup_lut_nc_x8", st)
 
     def run_operator_status(self, op, threadpool=None) -> Status:
         return Status(self.lib.qnnp_run_operator(op, threadpool))

@@ -370,6 +370,21 @@ struct qnnp_hip_x8_args {
 int qnnp_hip_channel_shuffle_run(const struct qnnp_hip_x8_args* args, const char** kernel_name);
 int qnnp_hip_clamp_run(const struct qnnp_hip_x8_args* args, const char** kernel_name);
 
+/* byte lookup table (x8lut.hip, linked into libqnnpack_gfx950.so only -- see the Makefile): replaces
+ * x8lut_ukernel__scalar and the lut case of src/operator-run.c:1017-1052, which serves sigmoid, leaky ReLU and the
+ * generic table operator. For pixel p of `pixels`, each `*_stride` bytes apart:
+ *   y[c] = table[x[c]]  (c < channels)
+ * `table` is 256 bytes of device memory, 4-byte aligned. May run in place (input == output, equal strides). */
+struct qnnp_hip_lut_args {
+  const uint8_t* input;
+  uint8_t* output;
+  const uint8_t* table;
+  uint32_t pixels;
+  uint32_t channels;
+  uint64_t input_stride, output_stride; /* bytes between pixels */
+};
+int qnnp_hip_lut_run(const struct qnnp_hip_lut_args* args, const char** kernel_name);
+
 /* ---- fused inverted-residual block ---------------------------------------
  * [pointwise expand ->] depthwise 3x3 (pad 1, stride 1 | 2) -> pointwise project [-> + block input], one launch,
  * the expanded tensors live only in LDS (q8fused.hip). Arithmetic per stage is that of the stand-alone operators

@@ -7,8 +7,8 @@
  *                  (src/operator-run.c:1054-1089): y = min(max(x, output_min), output_max) for every byte.
  *
  * Both move bytes and are bound by HBM bandwidth. Several lanes serve one pixel row when it is short, several
- * workgroups when it is long (RowMap below): a lane's row and item come from one magic-reciprocal divide of its thread
- * index, no per-element division.
+ * workgroups when it is long (RowMap, row_map.hip.h): a lane's row and item come from one magic-reciprocal divide of
+ * its thread index, no per-element division.
  *
  * Channel shuffle, three kernels:
  *   register  G = 2 or 4, gc % 4 == 0, base pointers and strides multiples of 4 bytes (16 for the x16 flavour, which
@@ -34,55 +34,17 @@
 #include "device_ops.hip.h"
 #include "per_device.h"
 #include "qnnp_hip.h"
+#include "row_map.hip.h"
 #include "u8_bytewise.hip.h"
 
 namespace qnnp {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr uint32_t kMaxGridY = 65535;
 constexpr uint32_t kLdsTile = 4096;             // bytes of staged input rows per workgroup (more rows when they fit)
 constexpr uint32_t kLdsMaxChannels = 32768;     // longest row the lds kernel stages (pitch <= 32784 bytes)
 constexpr int kLoadsInFlight = 4;               // lds kernel: staging loads per lane before it waits (four fetches)
 constexpr uint32_t kTilesPerCu = 8;             // lds kernel: smaller tiles until there are this many per CU
-
-/* `items` work items in each of `rows` rows. items <= kThreads: rows_per_block rows share a workgroup (lane ->
- * (row, item) by one magic divide); otherwise one row spans gridDim.x workgroups. Grid y walks the row groups. */
-struct RowMap {
-  uint32_t rows;
-  uint32_t items;
-  uint32_t items_inv;       // reciprocal_ceil(items) when items <= kThreads
-  uint32_t rows_per_block;
-  uint32_t groups;          // ceil(rows / rows_per_block)
-};
-
-inline RowMap row_map(uint32_t rows, uint32_t items, dim3& grid)
-{
-  RowMap m;
-  m.rows = rows;
-  m.items = items;
-  const bool shared = items <= static_cast<uint32_t>(kThreads);
-  m.items_inv = shared ? reciprocal_ceil(items) : 0u;
-  m.rows_per_block = shared ? kThreads / items : 1u;
-  m.groups = static_cast<uint32_t>((static_cast<uint64_t>(rows) + m.rows_per_block - 1) / m.rows_per_block);
-  const uint32_t gx = shared ? 1u : (items + kThreads - 1) / kThreads;
-  grid = dim3(gx, m.groups < kMaxGridY ? m.groups : kMaxGridY);
-  return m;
-}
-
-/* this lane's row within its group and item within the row; false: the lane has none */
-__device__ __forceinline__ bool row_item(const RowMap& m, uint32_t& rl, uint32_t& k)
-{
-  if (m.items <= static_cast<uint32_t>(kThreads)) {
-    rl = div_magic(threadIdx.x, m.items_inv);
-    k = threadIdx.x - rl * m.items;
-    return rl < m.rows_per_block;
-  }
-  rl = 0;
-  k = blockIdx.x * kThreads + threadIdx.x;
-  return k < m.items;
-}
 
 /* ---- channel shuffle ----------------------------------------------------------------------------------------- */
 
@@ -314,9 +276,6 @@ void u8_clamp_rows_kernel(const qnnp_hip_x8_args p, const RowMap m)
     clamp_piece<VEC>(a, a + (irow - orow), orow, orow + p.channels, p.output_min, p.output_max, clamp_hi, clamp_lo);
   }
 }
-
-inline bool aligned(uint64_t v, uint64_t a) { return v % a == 0; }
-inline uint64_t address(const void* p) { return static_cast<uint64_t>(reinterpret_cast<uintptr_t>(p)); }
 
 }  // namespace
 
