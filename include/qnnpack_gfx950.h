@@ -139,9 +139,7 @@ enum qnnp_status qnnp_setup_clamp_nc_u8(
  * output with equal strides. Where the reference checks nothing and would go out of range, setup answers
  * invalid_parameter: NULL tensors, a pixel stride below the channel count, input and output byte spans that overlap
  * other than exactly in place. Sizes beyond the kernels' index range (channels >= 2^31, batch >= 2^31) are
- * unsupported_parameter.
- * With these, softargmax (reference include/qnnpack.h:311-324) is the one reference operator this library does not
- * have: it stays on the CPU. */
+ * unsupported_parameter. */
 enum qnnp_status qnnp_create_sigmoid_nc_q8(
     size_t channels,
     uint8_t input_zero_point,
@@ -181,8 +179,39 @@ enum qnnp_status qnnp_setup_leaky_relu_nc_q8(
     uint8_t* output,
     size_t output_stride);
 
-/* The table operator under both, for any other uint8 -> uint8 function of one byte (tanh, hard-swish, re-quantisation
- * between two scales, ...). No reference counterpart: the reference keeps it internal. Setup and run behave as above;
+/* Softargmax (reference include/qnnpack.h:311-324, prototypes unchanged; note: no input zero point). With it every operator
+ * of the reference's qnnpack.h runs as a HIP kernel. Semantics and status codes are the reference's (src/softargmax.c,
+ * src/operator-run.c:625-637, src/u8lut32norm/scalar.c): create builds a table of 256 uint32_t on the host with the
+ * reference's double arithmetic,
+ *   table[i] = lrint(fmin((2^32 - 1) / channels, 8388607) * exp((i - 255) * input_scale)),
+ * the output scale must be 1/256 and the output zero point 0 (else unsupported_parameter), and run computes for each of
+ * batch_size rows of `channels` bytes, all in uint32_t:
+ *   m = max_c x[c];  t_c = table[x[c] + 255 - m];  vsum = sum_c t_c;  y[c] = min(((t_c << 8) + (vsum >> 1)) / vsum, 255).
+ * The sum WRAPS modulo 2^32, as the reference's does (rows of more than 512 channels whose bytes all sit near the row's
+ * maximum), and the division is exact. Where vsum is 0 modulo 2^32 -- a constant row of 1024, 4096 or 65536 channels,
+ * say -- the reference divides by zero and dies; here that row's output is all 0: the sum can only be 0 modulo 2^32 by
+ * being at least 2^32, and every t_c << 8 is below 2^31. Runs in place when input == output with equal strides. Setup
+ * answers as the table activations' above: invalid_parameter for NULL tensors, a row stride below the channel count, and
+ * input and output byte spans that overlap other than exactly in place; unsupported_parameter for sizes beyond the
+ * kernels' index range (channels >= 2^31 at create, batch >= 2^31). */
+enum qnnp_status qnnp_create_softargmax_nc_q8(
+    size_t channels,
+    float input_scale,
+    uint8_t output_zero_point,
+    float output_scale,
+    uint32_t flags,
+    qnnp_operator_t* softargmax);
+
+enum qnnp_status qnnp_setup_softargmax_nc_q8(
+    qnnp_operator_t softargmax,
+    size_t batch_size,
+    const uint8_t* input,
+    size_t input_stride,
+    uint8_t* output,
+    size_t output_stride);
+
+/* The table operator under sigmoid and leaky ReLU, for any other uint8 -> uint8 function of one byte (tanh, hard-swish,
+ * re-quantisation between two scales, ...). No reference counterpart: the reference keeps it internal. Setup and run behave as theirs;
  * create answers invalid_parameter for channels == 0 or a NULL table. */
 /* y[c] = table[x[c]] for every byte of every pixel; the 256 bytes of `table` are copied at create */
 enum qnnp_status qnnp_gfx950_create_lut_nc_x8(size_t channels, const uint8_t table[256], uint32_t flags, qnnp_operator_t* lut);

@@ -131,6 +131,13 @@ class QnnpackLibrary:
                 c_size_t, c_float, c_uint8, c_float, c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)]
             L.qnnp_setup_leaky_relu_nc_q8.restype = c_int
             L.qnnp_setup_leaky_relu_nc_q8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
+        # softargmax (reference include/qnnpack.h:311-324; the product declares it in qnnpack_gfx950.h). Bound when
+        # present, as above.
+        if hasattr(L, "qnnp_create_softargmax_nc_q8") or not os.environ.get("QNNP_GFX950_LIBRARY"):
+            L.qnnp_create_softargmax_nc_q8.restype = c_int
+            L.qnnp_create_softargmax_nc_q8.argtypes = [c_size_t, c_float, c_uint8, c_float, c_uint32, POINTER(c_void_p)]
+            L.qnnp_setup_softargmax_nc_q8.restype = c_int
+            L.qnnp_setup_softargmax_nc_q8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
         if hasattr(L, "qnnp_gfx950_create_lut_nc_x8"):
             L.qnnp_gfx950_create_lut_nc_x8.restype = c_int
             L.qnnp_gfx950_create_lut_nc_x8.argtypes = [c_size_t, c_void_p, c_uint32, POINTER(c_void_p)]
@@ -436,6 +443,27 @@ class QnnpackLibrary:
         st = self.setup_leaky_relu_nc_q8_status(*args)
         if st != Status.success:
             raise QnnpackError("qnnp_setup_leaky_relu_nc_q8", st)
+
+    def create_softargmax_nc_q8_status(self, channels, input_scale, output_zero_point, output_scale, flags=0):
+        handle = c_void_p(None)
+        st = self.lib.qnnp_create_softargmax_nc_q8(channels, input_scale, output_zero_point, output_scale, flags,
+                                                   ctypes.byref(handle))
+        return Status(st), handle.value
+
+    def create_softargmax_nc_q8(self, *args, **kwargs) -> int:
+        st, handle = self.create_softargmax_nc_q8_status(*args, **kwargs)
+        if st != Status.success:
+            raise QnnpackError("qnnp_create_softargmax_nc_q8", st)
+        return handle
+
+    def setup_softargmax_nc_q8_status(self, op, batch_size, input, input_stride, output, output_stride) -> Status:
+        return Status(self.lib.qnnp_setup_softargmax_nc_q8(
+            op, batch_size, address_of(input), input_stride, address_of(output), output_stride))
+
+    def setup_softargmax_nc_q8(self, *args) -> None:
+        st = self.setup_softargmax_nc_q8_status(*args)
+        if st != Status.success:
+            raise QnnpackError("qnnp_setup_softargmax_nc_q8", st)
 
     def create_lut_nc_x8_status(self, channels, table, flags=0):
         """the product's table operator (qnnp_gfx950_create_lut_nc_x8); `table`: 256 uint8, or None"""

@@ -385,6 +385,22 @@ struct qnnp_hip_lut_args {
 };
 int qnnp_hip_lut_run(const struct qnnp_hip_lut_args* args, const char** kernel_name);
 
+/* softargmax (q8softargmax.hip, linked into libqnnpack_gfx950.so only -- see the Makefile): replaces u8rmax_ukernel__sse2,
+ * u8lut32norm_ukernel__scalar and the softargmax case of src/operator-run.c:625-637, 1091-1108. For each of `rows` rows
+ * of `channels` bytes, each `*_stride` bytes apart, all in uint32_t:
+ *   m = max_c x[c];  t_c = table[x[c] + 255 - m];  vsum = sum_c t_c (mod 2^32);
+ *   y[c] = min(((t_c << 8) + (vsum >> 1)) / vsum, 255),  or 0 for every c where vsum == 0
+ * `table` is 256 uint32_t of device memory, 4-byte aligned. May run in place (input == output, equal strides). */
+struct qnnp_hip_softargmax_args {
+  const uint8_t* input;
+  uint8_t* output;
+  const uint32_t* table;
+  uint32_t rows;
+  uint32_t channels;
+  uint64_t input_stride, output_stride; /* bytes between rows */
+};
+int qnnp_hip_softargmax_run(const struct qnnp_hip_softargmax_args* args, const char** kernel_name);
+
 /* ---- fused inverted-residual block ---------------------------------------
  * [pointwise expand ->] depthwise 3x3 (pad 1, stride 1 | 2) -> pointwise project [-> + block input], one launch,
  * the expanded tensors live only in LDS (q8fused.hip). Arithmetic per stage is that of the stand-alone operators

@@ -29,6 +29,7 @@ enum qnnp_ukernel_type {
   qnnp_ukernel_type_channel_shuffle,    /* channel-shuffle.c */
   qnnp_ukernel_type_clamp,              /* clamp.c */
   qnnp_ukernel_type_lut,                /* lut.c, sigmoid.c, leaky-relu.c */
+  qnnp_ukernel_type_softargmax,         /* softargmax.c */
 };
 
 /* One output phase of a strided deconvolution (deconvolution.c): the output pixels whose (oy + pad_top) % stride_h
@@ -128,7 +129,7 @@ struct qnnp_operator {
   enum qnnp_ukernel_type ukernel_type;
 
   /* ---- device-side state owned by the operator ---- */
-  void* d_weights;        /* igemm: int8 fragment panels; dwconv: int16 [taps][c_pad]; lut: the 256-byte table */
+  void* d_weights;        /* igemm: int8 fragment panels; dwconv: int16 [taps][c_pad]; lut: the 256-byte table; softargmax: 256 uint32_t */
   void* d_weights_rows16; /* igemm, 3-channel first layers: the [ky][16-byte row slot] fragment image (pack.h), or NULL */
   /* grouped 1x1 convolutions (ukernel gemm, groups > 1): the same operator as ONE dense GEMM -- the groups' weight blocks on the diagonal of
    * a [groups * output channels][groups * input channels] matrix whose other elements are the kernel zero point (w - kzp = 0: bit for
@@ -187,7 +188,7 @@ struct qnnp_operator {
   struct qnnp_hip_dwconv_plan dw_plan;   /* depthwise launch plan, computed at the first run after a setup */
 
   /* launch of operator types whose code is not part of every build (windowed pooling: max-pooling.c,
-   * average-pooling.c; channel-shuffle.c, clamp.c; lut.c): set by their create, called by launch_kernel's default arm
+   * average-pooling.c; channel-shuffle.c, clamp.c; lut.c; softargmax.c): set by their create, called by launch_kernel's default arm
    * (operator-run.c) with device pointers. Keeps operator-run.c free of references to their kernels, so builds without
    * them still link. */
   int (*launch_hook)(struct qnnp_operator* op, const void* input, void* output);
