@@ -210,13 +210,91 @@ enum qnnp_status qnnp_setup_softargmax_nc_q8(
     uint8_t* output,
     size_t output_stride);
 
-/* The table operator under sigmoid and leaky ReLU, for any other uint8 -> uint8 function of one byte (tanh, hard-swish,
- * re-quantisation between two scales, ...). No reference counterpart: the reference keeps it internal. Setup and run behave as theirs;
+/* The table operator under sigmoid, leaky ReLU, hardswish and hardsigmoid, for any other uint8 -> uint8 function of one
+ * byte (tanh, re-quantisation between two scales, ...). No reference counterpart: the reference keeps it internal. Setup and run behave as theirs;
  * create answers invalid_parameter for channels == 0 or a NULL table. */
 /* y[c] = table[x[c]] for every byte of every pixel; the 256 bytes of `table` are copied at create */
 enum qnnp_status qnnp_gfx950_create_lut_nc_x8(size_t channels, const uint8_t table[256], uint32_t flags, qnnp_operator_t* lut);
 enum qnnp_status qnnp_gfx950_setup_lut_nc_x8(qnnp_operator_t lut, size_t batch_size,
     const uint8_t* input, size_t input_stride, uint8_t* output, size_t output_stride);
+
+/* Hardswish and hardsigmoid, MobileNetV3's two activations, as table operators. No reference counterpart. Create builds
+ * the 256-byte table on the host in float32, every operation rounded once (no fused multiply-add), lrintf rounding to
+ * nearest even:
+ *   x = input_scale * (float) (i - input_zero_point);   h = min(max(x + 3.0f, 0.0f), 6.0f);
+ *   hardswish:   table[i] = lrintf(min(max((1.0f / output_scale) * ((x * h) / 6.0f) + (float) output_zero_point,
+ *                                          (float) output_min), (float) output_max));
+ *   hardsigmoid: table[i] = lrintf(min(max(256.0f * (h / 6.0f), (float) output_min), (float) output_max));
+ *     the output scale must be 1/256 and the output zero point 0, as sigmoid's (else unsupported_parameter).
+ * Status codes as qnnp_create_sigmoid_nc_q8, in its order: uninitialized; invalid_parameter for channels == 0, a scale
+ * that is not a normal number above zero, output_min >= output_max; unsupported_parameter for channels >= 2^31.
+ * Setup, run and delete are the table operator's: qnnp_gfx950_setup_lut_nc_x8 (in place when input == output with equal
+ * strides), qnnp_run_operator, qnnp_delete_operator. */
+enum qnnp_status qnnp_gfx950_create_hardswish_nc_q8(
+    size_t channels,
+    uint8_t input_zero_point,
+    float input_scale,
+    uint8_t output_zero_point,
+    float output_scale,
+    uint8_t output_min,
+    uint8_t output_max,
+    uint32_t flags,
+    qnnp_operator_t* hardswish);
+
+enum qnnp_status qnnp_gfx950_create_hardsigmoid_nc_q8(
+    size_t channels,
+    uint8_t input_zero_point,
+    float input_scale,
+    uint8_t output_zero_point,
+    float output_scale,
+    uint8_t output_min,
+    uint8_t output_max,
+    uint32_t flags,
+    qnnp_operator_t* hardsigmoid);
+
+/* Quantized multiply, element-wise or with the second operand broadcast over groups of rows. No reference counterpart.
+ * `a` and `product` have b_rows * a_rows_per_b_row rows of `channels` bytes, `b` has b_rows rows; strides are bytes
+ * between rows. Row r of `a` meets row r / a_rows_per_b_row of `b`: a_rows_per_b_row == 1 is the plain element-wise
+ * product, a_rows_per_b_row == the pixels of an image is the scale x * s that ends a squeeze-and-excite block (s: one
+ * row per image). For each byte, bit-exact:
+ *   acc     = ((int32) a - a_zero_point) * ((int32) b - b_zero_point)                 |acc| <= 65025
+ *   product = qnnp_q31_requantize(acc, ratio, product_zero_point, product_min, product_max)
+ *   ratio   = a_scale * b_scale / product_scale      in float32, left to right: one rounding after *, one after /
+ * with the reference's scalar qnnp_q31_requantize, the one the convolutions fuse. `flags` is accepted and ignored.
+ * Create, in this order: uninitialized; invalid_parameter for channels == 0, for any of the three scales not a normal
+ * number above zero, for product_min >= product_max; unsupported_parameter for channels >= 2^31 and for a ratio outside
+ * [2^-32, 1), the domain of the Q31 down-convert -- with |acc| up to 65025, a ratio of 1 or more would saturate nearly
+ * every output anyway.
+ * Setup: b_rows == 0 or a_rows_per_b_row == 0 succeeds and run then does nothing. invalid_parameter: a NULL tensor; a
+ * stride below `channels`; byte spans that overlap other than the permitted in-place forms -- product == a with equal
+ * strides always, product == b with equal strides only when a_rows_per_b_row == 1; a and b are only read and may
+ * overlap freely (a == b is the square); memory of another GPU. unsupported_parameter: b_rows * a_rows_per_b_row >=
+ * 2^31. A setup refused by these checks leaves the previous valid setup runnable. Tensors are host or device memory;
+ * the operator records into a hipGraph capture with device pointers, runs in async mode, and honours
+ * qnnp_gfx950_operator_set_streaming_stores where the product is not in place (kernel q8_mul_x16). */
+enum qnnp_status qnnp_gfx950_create_multiply_nc_q8(
+    size_t channels,
+    uint8_t a_zero_point,
+    float a_scale,
+    uint8_t b_zero_point,
+    float b_scale,
+    uint8_t product_zero_point,
+    float product_scale,
+    uint8_t product_min,
+    uint8_t product_max,
+    uint32_t flags,
+    qnnp_operator_t* multiply);
+
+enum qnnp_status qnnp_gfx950_setup_multiply_nc_q8(
+    qnnp_operator_t multiply,
+    size_t b_rows,
+    size_t a_rows_per_b_row,
+    const uint8_t* a,
+    size_t a_stride,
+    const uint8_t* b,
+    size_t b_stride,
+    uint8_t* product,
+    size_t product_stride);
 
 /* Devices. The library keeps one context (launch stream, asynchrony flag) per gfx950 GPU of the node.
  *   BEFORE qnnp_initialize: names the PRIMARY device qnnp_initialize binds (default: env QNNP_GFX950_DEVICE,
@@ -345,7 +423,8 @@ enum qnnp_status qnnp_gfx950_set_option(const char* key, int value);
  * once (a chained network) wants 0; an operator on its own, as the reference bench runs them, 1 -- both kinds can live
  * in one process, and no launch of another thread is affected.
  * Honoured by every kernel that has a streaming form: convolution / fully connected / depthwise operators, the
- * element-wise add, and deconvolutions that run as GEMMs (kernel == stride, and the per-phase GEMMs). Kernels WITHOUT a
+ * element-wise add, the multiply (16-byte pieces, product not in place), and deconvolutions that run as GEMMs (kernel ==
+ * stride, and the per-phase GEMMs). Kernels WITHOUT a
  * streaming form write plain stores whatever the setting, and the call still answers success for them: the stride-2
  * 3x3 / 4x4 deconvolution stream kernel, global average pooling (its output is a few KB) and fused blocks (their output
  * feeds the next block). */

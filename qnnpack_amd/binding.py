@@ -143,6 +143,18 @@ class QnnpackLibrary:
             L.qnnp_gfx950_create_lut_nc_x8.argtypes = [c_size_t, c_void_p, c_uint32, POINTER(c_void_p)]
             L.qnnp_gfx950_setup_lut_nc_x8.restype = c_int
             L.qnnp_gfx950_setup_lut_nc_x8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
+        # multiply, hardswish and hardsigmoid exist in the product only (include/qnnpack_gfx950.h). Bound when present.
+        if hasattr(L, "qnnp_gfx950_create_multiply_nc_q8"):
+            L.qnnp_gfx950_create_multiply_nc_q8.restype = c_int
+            L.qnnp_gfx950_create_multiply_nc_q8.argtypes = [
+                c_size_t, c_uint8, c_float, c_uint8, c_float, c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)]
+            L.qnnp_gfx950_setup_multiply_nc_q8.restype = c_int
+            L.qnnp_gfx950_setup_multiply_nc_q8.argtypes = [
+                c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
+            for name in ("qnnp_gfx950_create_hardswish_nc_q8", "qnnp_gfx950_create_hardsigmoid_nc_q8"):
+                getattr(L, name).restype = c_int
+                getattr(L, name).argtypes = [
+                    c_size_t, c_uint8, c_float, c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)]
         L.qnnp_run_operator.restype = c_int
         L.qnnp_run_operator.argtypes = [c_void_p, c_void_p]
         L.qnnp_delete_operator.restype = c_int
@@ -488,6 +500,60 @@ class QnnpackLibrary:
         st = self.setup_lut_nc_x8_status(*args)
         if st != Status.success:
             raise QnnpackError("qnnp_gfx950_setup_lut_nc_x8", st)
+
+    def create_multiply_nc_q8_status(self, channels, a_zero_point, a_scale, b_zero_point, b_scale,
+                                     product_zero_point, product_scale, product_min, product_max, flags=0):
+        """the product's multiply operator (qnnp_gfx950_create_multiply_nc_q8)"""
+        handle = c_void_p(None)
+        st = self.lib.qnnp_gfx950_create_multiply_nc_q8(
+            channels, a_zero_point, a_scale, b_zero_point, b_scale, product_zero_point, product_scale,
+            product_min, product_max, flags, ctypes.byref(handle))
+        return Status(st), handle.value
+
+    def create_multiply_nc_q8(self, *args, **kwargs) -> int:
+        st, handle = self.create_multiply_nc_q8_status(*args, **kwargs)
+        if st != Status.success:
+            raise QnnpackError("qnnp_gfx950_create_multiply_nc_q8", st)
+        return handle
+
+    def setup_multiply_nc_q8_status(self, op, b_rows, a_rows_per_b_row, a, a_stride, b, b_stride,
+                                    product, product_stride) -> Status:
+        return Status(self.lib.qnnp_gfx950_setup_multiply_nc_q8(
+            op, b_rows, a_rows_per_b_row, address_of(a), a_stride, address_of(b), b_stride,
+            address_of(product), product_stride))
+
+    def setup_multiply_nc_q8(self, *args) -> None:
+        st = self.setup_multiply_nc_q8_status(*args)
+        if st != Status.success:
+            raise QnnpackError("qnnp_gfx950_setup_multiply_nc_q8", st)
+
+    def create_hardswish_nc_q8_status(self, channels, input_zero_point, input_scale, output_zero_point, output_scale,
+                                      output_min, output_max, flags=0):
+        """a table operator: set it up with setup_lut_nc_x8"""
+        handle = c_void_p(None)
+        st = self.lib.qnnp_gfx950_create_hardswish_nc_q8(channels, input_zero_point, input_scale, output_zero_point,
+                                                         output_scale, output_min, output_max, flags, ctypes.byref(handle))
+        return Status(st), handle.value
+
+    def create_hardswish_nc_q8(self, *args, **kwargs) -> int:
+        st, handle = self.create_hardswish_nc_q8_status(*args, **kwargs)
+        if st != Status.success:
+            raise QnnpackError("qnnp_gfx950_create_hardswish_nc_q8", st)
+        return handle
+
+    def create_hardsigmoid_nc_q8_status(self, channels, input_zero_point, input_scale, output_zero_point, output_scale,
+                                        output_min, output_max, flags=0):
+        """a table operator: set it up with setup_lut_nc_x8"""
+        handle = c_void_p(None)
+        st = self.lib.qnnp_gfx950_create_hardsigmoid_nc_q8(channels, input_zero_point, input_scale, output_zero_point,
+                                                           output_scale, output_min, output_max, flags, ctypes.byref(handle))
+        return Status(st), handle.value
+
+    def create_hardsigmoid_nc_q8(self, *args, **kwargs) -> int:
+        st, handle = self.create_hardsigmoid_nc_q8_status(*args, **kwargs)
+        if st != Status.success:
+            raise QnnpackError("qnnp_gfx950_create_hardsigmoid_nc_q8", st)
+        return handle
 
     def run_operator_status(self, op, threadpool=None) -> Status:
         return Status(self.lib.qnnp_run_operator(op, threadpool))

@@ -385,6 +385,27 @@ struct qnnp_hip_lut_args {
 };
 int qnnp_hip_lut_run(const struct qnnp_hip_lut_args* args, const char** kernel_name);
 
+/* element-wise / broadcast multiply (q8mul.hip, linked into libqnnpack_gfx950.so only -- see the Makefile). No reference
+ * counterpart. `a` and `product` have b_rows * a_rows_per_b_row rows of `channels` bytes, `b` has b_rows rows, each
+ * `*_stride` bytes apart; row r of `a` meets row r / a_rows_per_b_row of `b`:
+ *   acc     = ((int32) a[c] - a_zero_point) * ((int32) b[c] - b_zero_point)      |acc| <= 65025 < 2^16
+ *   product = qnnp_q31_requantize(acc) with `rq`                                  (requant.hip.h)
+ * May run in place on `a` (product == a, equal strides) and, when a_rows_per_b_row == 1, on `b`; `a` and `b` may be
+ * the same tensor. b_rows * a_rows_per_b_row and channels must be below 2^31. */
+struct qnnp_hip_mul_args {
+  const uint8_t* a;
+  const uint8_t* b;
+  uint8_t* product;
+  uint32_t b_rows;
+  uint32_t a_rows_per_b_row;
+  uint32_t channels;
+  uint64_t a_stride, b_stride, product_stride;   /* bytes between rows */
+  int32_t a_zero_point, b_zero_point;
+  struct qnnp_hip_requant rq;
+  uint32_t streaming_mode;    /* as qnnp_hip_igemm_args: 0 = process default, 1 = off, 2 = on */
+};
+int qnnp_hip_mul_run(const struct qnnp_hip_mul_args* args, const char** kernel_name);
+
 /* softargmax (q8softargmax.hip, linked into libqnnpack_gfx950.so only -- see the Makefile): replaces u8rmax_ukernel__sse2,
  * u8lut32norm_ukernel__scalar and the softargmax case of src/operator-run.c:625-637, 1091-1108. For each of `rows` rows
  * of `channels` bytes, each `*_stride` bytes apart, all in uint32_t:

@@ -30,6 +30,7 @@ enum qnnp_ukernel_type {
   qnnp_ukernel_type_clamp,              /* clamp.c */
   qnnp_ukernel_type_lut,                /* lut.c, sigmoid.c, leaky-relu.c */
   qnnp_ukernel_type_softargmax,         /* softargmax.c */
+  qnnp_ukernel_type_multiply,           /* multiply.c */
 };
 
 /* One output phase of a strided deconvolution (deconvolution.c): the output pixels whose (oy + pad_top) % stride_h
@@ -122,6 +123,12 @@ struct qnnp_operator {
   float output_scale;
   struct qnnp_hip_add_params add_params;
   struct qnnp_hip_avgpool_params avgpool_params;
+  /* multiply (multiply.c): batch_size = mul_b_rows * mul_a_rows_per_b_row rows of `a` and of the product; `b` is input2;
+   * the zero points of a and b; the requantization is `requant` below */
+  size_t mul_b_rows;
+  size_t mul_a_rows_per_b_row;
+  uint8_t mul_a_zero_point;
+  uint8_t mul_b_zero_point;
 
   uint8_t input_zero_point;
   uint8_t kernel_zero_point;
@@ -171,7 +178,7 @@ struct qnnp_operator {
   size_t stage_in_capacity;
   void* d_stage_out;
   size_t stage_out_capacity;
-  int input2_on_device;   /* add: the second operand */
+  int input2_on_device;   /* add, multiply: the second operand */
   void* d_stage_in2;
   size_t stage_in2_capacity;
   size_t input2_span;
@@ -188,7 +195,7 @@ struct qnnp_operator {
   struct qnnp_hip_dwconv_plan dw_plan;   /* depthwise launch plan, computed at the first run after a setup */
 
   /* launch of operator types whose code is not part of every build (windowed pooling: max-pooling.c,
-   * average-pooling.c; channel-shuffle.c, clamp.c; lut.c; softargmax.c): set by their create, called by launch_kernel's default arm
+   * average-pooling.c; channel-shuffle.c, clamp.c; lut.c; softargmax.c; multiply.c): set by their create, called by launch_kernel's default arm
    * (operator-run.c) with device pointers. Keeps operator-run.c free of references to their kernels, so builds without
    * them still link. */
   int (*launch_hook)(struct qnnp_operator* op, const void* input, void* output);
