@@ -37,7 +37,7 @@ extern "C" {
  *                    workgroups per CU; tile width by the channel count), 25 / 26 = the same with 64- / 128-channel tiles,
  *                    27 = the 32x32x32 weight-stationary 3x3 convolution kernel for 64 input channels with a centred image (auto
  *                    takes its 16x16x64 flavour since round 6), 28 = the 16x16x64 GEMM with kernel-zero-point row sums (any kernel
- *                    zero point; what auto picks where 15 ran before),
+ *                    zero point but 128, which has no row term and is 23's; what auto picks where 15 ran before),
  *                    29 = the 128-row GEMM for 1x1 / fully-connected shapes with NO alignment (hip/q8gemm128u.hip: grouped, odd channel
  *                    counts, unaligned pixels; what auto picks where 1 ran for them),
  *                    30 = the LDS-staged flavour of the 7x7 / 5x5 first-layer kernel (hip/q8convc3.hip; 14 keeps the register-path one),

@@ -765,6 +765,8 @@ int make_plan(const IgemmSetup& s, const struct qnnp_hip_igemm_args* a, IgemmPla
     *plan = forced_plan(a->variant, wave_image);
     // 14 / 30: the 32-byte-slot flavour for 5- and 7-row windows (ResNet's 7x7 entry layer) where the 16-byte one refuses
     if (plan->kernel == Kernel::Rows16 && !supported(s, a, Kernel::Rows16)) plan->kernel = Kernel::Rows32;
+    // 28: kernel zero point 128 has no row term -- gemm256x_launch would run (and report) the centred flavour, which is 23's
+    if (plan->image == Image::Rowsum && s.p.row_coeff == 0) return QNNP_HIP_EINVAL;
     return supported(s, a, plan->kernel, plan->image) ? QNNP_HIP_OK : QNNP_HIP_EINVAL;
   }
   auto pick = [plan](Kernel k, Image image = Image::Standard, uint32_t option = 0u) { *plan = IgemmPlan{k, image, option}; return QNNP_HIP_OK; };

@@ -231,8 +231,12 @@ QNNP_HD struct qnnp_requant_lane qnnp_requant_lane_init(const struct qnnp_requan
   l.kind = 0;
   l.konst = 0;
   /* both kinds need a = n - rowterm inside int32 (u is a + 2^31 reduced mod 2^32): guaranteed when the operator's
-   * accumulators are bounded at create time (|n| < 2^30 with the reduction length that bound implies, K < 2^14, so
-   * |rowterm| <= 128 * 255 * K < 2^15 * 2^14 = 2^29, so |a| <= |n| + |rowterm| < 2^30 + 2^29 < 2^31); without a bound the caller keeps the forms that only need n itself */
+   * accumulators are bounded at create time. |n| < 2^30 comes from max|bias| + 65025 * K < 2^30 (qnnp_accumulator_bits),
+   * which admits reduction lengths up to K = 16512 (65025 * 16512 = 1073692800 < 2^30 = 1073741824 < 65025 * 16513).
+   * rowterm = (128 - kzp) * sum_k (a ^ 0x80) with |128 - kzp| <= 128 and |a ^ 0x80| <= 128 as int8, so
+   * |rowterm| <= 128 * 128 * 16512 = 270532608 < 2^29 and |a| <= |n| + |rowterm| < 2^30 + 2^29 < 2^31 (the packed tail's
+   * |rowterm| <= 2^30 holds as well). tests/test_worstcase_host.py forms both from extreme operands at K = 16512;
+   * without a bound the caller keeps the forms that only need n itself */
   const int bounded_acc = accumulator_bits >= 1 && accumulator_bits <= 30;
   if (f.shift == 0 && zero_point_folded && bounded_acc) {
     l.kind = 1;
