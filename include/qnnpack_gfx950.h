@@ -296,6 +296,61 @@ enum qnnp_status qnnp_gfx950_setup_multiply_nc_q8(
     uint8_t* product,
     size_t product_stride);
 
+/* Bilinear resize of a uint8 NHWC tensor to another height and width: the upsampling that ends a segmentation head, the
+ * resize of a decoded image in front of a network's first convolution. No reference counterpart. Quantization is
+ * unchanged (the same scale and zero point in and out, as max pooling's), so there are no scale arguments. Pixels are
+ * `channels` bytes, `*_pixel_stride` bytes apart; an image is height * width pixels, images follow each other.
+ *
+ * The definition is integers only, so the result is bit-exact by construction. For each axis take the input size n_in,
+ * the output size n_out and the output index o; all arithmetic in uint64_t, divisions round down:
+ *   default (half-pixel centres, PyTorch's align_corners=False):
+ *     num = max((2 * o + 1) * n_in - n_out, 0)   [the signed value, clamped];   f = (4096 * num + 2 * n_out) / (4 * n_out)
+ *   with QNNP_GFX950_RESIZE_ALIGN_CORNERS:
+ *     f = 0 if n_out == 1, else (4096 * o * (n_in - 1) + (n_out - 1)) / (2 * (n_out - 1))
+ *   f is the source coordinate in Q11, rounded to nearest. Then
+ *     i0 = min(f >> 11, n_in - 1),   i1 = min(i0 + 1, n_in - 1),   w = (i0 == i1) ? 0 : (f & 2047)
+ * With (y0, y1, wy) from the rows and (x0, x1, wx) from the columns, every channel c of output pixel (oy, ox) of every
+ * image is, in uint32_t:
+ *     top = x[y0][x0][c] * (2048 - wx) + x[y0][x1][c] * wx
+ *     bot = x[y1][x0][c] * (2048 - wx) + x[y1][x1][c] * wx
+ *     y   = (top * (2048 - wy) + bot * wy + 2^21) >> 22                        (<= 255 * 2^22 + 2^21 < 2^31)
+ * Equal sizes give the identity; the result is within 0.63 of the real-valued bilinear value (0.5 from the last
+ * rounding, 255 * 2 * 2^-12 from the two Q11 weights), hence within 1 of its rounding.
+ *
+ * Create, in this order: uninitialized; invalid_parameter for channels == 0 and for a flag bit other than
+ * QNNP_GFX950_RESIZE_ALIGN_CORNERS (flags carry meaning here and are not ignored); unsupported_parameter for channels >=
+ * 2^31.
+ * Setup: batch_size == 0 succeeds and run then does nothing. Then, in this order: invalid_parameter for any of the four
+ * sizes 0, a NULL tensor, a pixel stride below `channels`; unsupported_parameter for any of the four sizes >= 2^24 (which
+ * keeps the table arithmetic inside 64 bits) and for batch_size * output_height * output_width >= 2^31 or batch_size *
+ * input_height * input_width >= 2^31; invalid_parameter for input and output byte spans that share a byte -- there is
+ * no in-place form: every output pixel reads up to four input pixels that other lanes' stores could hit -- and for memory
+ * of another GPU; out_of_memory for the tables (setup builds one table per axis on the host and keeps both in one
+ * grow-only device allocation of the operator). A setup refused by these checks leaves the previous valid setup runnable.
+ * Inside a graph capture create and setup answer invalid_parameter. Tensors are host or device memory; the operator
+ * records into a hipGraph capture with device pointers, runs in async mode, and honours
+ * qnnp_gfx950_operator_set_streaming_stores on its 16-byte kernel (u8_resize_x16: channels, base addresses and pixel
+ * strides multiples of 16; u8_resize_x4 serves every other tensor of 4 channels and more at any alignment, u8_resize_x1
+ * fewer channels). Run and delete are qnnp_run_operator / qnnp_delete_operator. */
+#define QNNP_GFX950_RESIZE_ALIGN_CORNERS 0x00000001u
+
+enum qnnp_status qnnp_gfx950_create_resize_bilinear2d_nhwc_u8(
+    size_t channels,
+    uint32_t flags,
+    qnnp_operator_t* resize);
+
+enum qnnp_status qnnp_gfx950_setup_resize_bilinear2d_nhwc_u8(
+    qnnp_operator_t resize,
+    size_t batch_size,
+    size_t input_height,
+    size_t input_width,
+    size_t output_height,
+    size_t output_width,
+    const uint8_t* input,
+    size_t input_pixel_stride,
+    uint8_t* output,
+    size_t output_pixel_stride);
+
 /* Devices. The library keeps one context (launch stream, asynchrony flag) per gfx950 GPU of the node.
  *   BEFORE qnnp_initialize: names the PRIMARY device qnnp_initialize binds (default: env QNNP_GFX950_DEVICE,
  *     else the calling thread's current HIP device).
@@ -423,7 +478,8 @@ enum qnnp_status qnnp_gfx950_set_option(const char* key, int value);
  * once (a chained network) wants 0; an operator on its own, as the reference bench runs them, 1 -- both kinds can live
  * in one process, and no launch of another thread is affected.
  * Honoured by every kernel that has a streaming form: convolution / fully connected / depthwise operators, the
- * element-wise add, the multiply (16-byte pieces, product not in place), and deconvolutions that run as GEMMs (kernel ==
+ * element-wise add, the multiply (16-byte pieces, product not in place), the bilinear resize (u8_resize_x16: the store
+ * only, its loads are re-read by neighbouring output pixels), and deconvolutions that run as GEMMs (kernel ==
  * stride, and the per-phase GEMMs). Kernels WITHOUT a
  * streaming form write plain stores whatever the setting, and the call still answers success for them: the stride-2
  * 3x3 / 4x4 deconvolution stream kernel, global average pooling (its output is a few KB) and fused blocks (their output

@@ -53,6 +53,8 @@ def address_of(buf) -> Optional[int]:
 class QnnpackLibrary:
     """The C API of include/qnnpack.h bound over ``path``."""
 
+    RESIZE_ALIGN_CORNERS = 0x00000001   # QNNP_GFX950_RESIZE_ALIGN_CORNERS (include/qnnpack_gfx950.h)
+
     def __init__(self, path: str):
         self.path = path
         self.lib = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
@@ -155,6 +157,13 @@ class QnnpackLibrary:
                 getattr(L, name).restype = c_int
                 getattr(L, name).argtypes = [
                     c_size_t, c_uint8, c_float, c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)]
+        # bilinear resize exists in the product only (include/qnnpack_gfx950.h). Bound when present.
+        if hasattr(L, "qnnp_gfx950_create_resize_bilinear2d_nhwc_u8"):
+            L.qnnp_gfx950_create_resize_bilinear2d_nhwc_u8.restype = c_int
+            L.qnnp_gfx950_create_resize_bilinear2d_nhwc_u8.argtypes = [c_size_t, c_uint32, POINTER(c_void_p)]
+            L.qnnp_gfx950_setup_resize_bilinear2d_nhwc_u8.restype = c_int
+            L.qnnp_gfx950_setup_resize_bilinear2d_nhwc_u8.argtypes = [
+                c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
         L.qnnp_run_operator.restype = c_int
         L.qnnp_run_operator.argtypes = [c_void_p, c_void_p]
         L.qnnp_delete_operator.restype = c_int
@@ -526,6 +535,30 @@ class QnnpackLibrary:
         st = self.setup_multiply_nc_q8_status(*args)
         if st != Status.success:
             raise QnnpackError("qnnp_gfx950_setup_multiply_nc_q8", st)
+
+    def create_resize_bilinear2d_nhwc_u8_status(self, channels, flags=0):
+        """the product's bilinear resize operator (qnnp_gfx950_create_resize_bilinear2d_nhwc_u8); flags: RESIZE_ALIGN_CORNERS"""
+        handle = c_void_p(None)
+        st = self.lib.qnnp_gfx950_create_resize_bilinear2d_nhwc_u8(channels, flags, ctypes.byref(handle))
+        return Status(st), handle.value
+
+    def create_resize_bilinear2d_nhwc_u8(self, *args, **kwargs) -> int:
+        st, handle = self.create_resize_bilinear2d_nhwc_u8_status(*args, **kwargs)
+        if st != Status.success:
+            raise QnnpackError("qnnp_gfx950_create_resize_bilinear2d_nhwc_u8", st)
+        return handle
+
+    def setup_resize_bilinear2d_nhwc_u8_status(self, op, batch_size, input_height, input_width, output_height,
+                                               output_width, input, input_pixel_stride, output,
+                                               output_pixel_stride) -> Status:
+        return Status(self.lib.qnnp_gfx950_setup_resize_bilinear2d_nhwc_u8(
+            op, batch_size, input_height, input_width, output_height, output_width, address_of(input),
+            input_pixel_stride, address_of(output), output_pixel_stride))
+
+    def setup_resize_bilinear2d_nhwc_u8(self, *args) -> None:
+        st = self.setup_resize_bilinear2d_nhwc_u8_status(*args)
+        if st != Status.success:
+            raise QnnpackError("qnnp_gfx950_setup_resize_bilinear2d_nhwc_u8", st)
 
     def create_hardswish_nc_q8_status(self, channels, input_zero_point, input_scale, output_zero_point, output_scale,
                                       output_min, output_max, flags=0):

@@ -16,6 +16,7 @@
 #include "operator.h"
 #include "pack.h"
 #include "requantization.h"
+#include "resize-table.h"
 #include "hip/requant_math.h"
 
 void qnnp_debug_pack_igemm_w(
@@ -225,4 +226,15 @@ void qnnp_debug_strip_depthwise_images(
     int offset_form, int8_t* w2, int32_t* biasc)
 {
   qnnp_strip_depthwise_images(wadj, bias1, c_pad, ch, hidden_pad, izp, kzp, offset_form, w2, biasc);
+}
+
+/* one axis table of the bilinear resize (resize-table.h), unpacked: out_i0 / out_i1 / out_w hold n_out entries each */
+void qnnp_debug_resize_axis_table(size_t n_in, size_t n_out, int align_corners, uint32_t* out_i0, uint32_t* out_i1, uint32_t* out_w)
+{
+  for (size_t o = 0; o < n_out; o++) {
+    const struct qnnp_resize_entry e = qnnp_resize_axis_entry(n_in, n_out, align_corners, o);
+    out_i0[o] = e.i0;
+    out_i1[o] = e.i0 + (e.w_step >> 11);
+    out_w[o] = e.w_step & 2047u;
+  }
 }

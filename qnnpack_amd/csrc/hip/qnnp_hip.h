@@ -406,6 +406,28 @@ struct qnnp_hip_mul_args {
 };
 int qnnp_hip_mul_run(const struct qnnp_hip_mul_args* args, const char** kernel_name);
 
+/* bilinear resize of uint8 NHWC tensors (u8resize.hip, linked into libqnnpack_gfx950.so only -- see the Makefile). No
+ * reference counterpart. `table` is device memory, 8-byte aligned: output_height row entries, then output_width column
+ * entries, each {uint32_t i0; uint32_t w | step << 11} as resize-table.h builds them (i0 + step < the input size). With
+ * (y0, y1 = y0 + step, wy) of output row oy and (x0, x1, wx) of output column ox, every channel c of every image, in
+ * uint32_t:
+ *   top = x[y0][x0][c] * (2048 - wx) + x[y0][x1][c] * wx;   bot = x[y1][x0][c] * (2048 - wx) + x[y1][x1][c] * wx
+ *   y[oy][ox][c] = (top * (2048 - wy) + bot * wy + 2^21) >> 22
+ * Pixels are `*_stride` bytes apart, images input_height * input_width (output_height * output_width) pixels. Input and
+ * output must not overlap. The four sizes are below 2^24, batch * input pixels and batch * output pixels below 2^31. */
+struct qnnp_hip_resize_args {
+  const uint8_t* input;
+  uint8_t* output;
+  const void* table;
+  uint32_t batch;
+  uint32_t input_height, input_width;
+  uint32_t output_height, output_width;
+  uint32_t channels;
+  uint64_t input_stride, output_stride;   /* bytes between pixels */
+  uint32_t streaming_mode;    /* as qnnp_hip_igemm_args: 0 = process default, 1 = off, 2 = on */
+};
+int qnnp_hip_resize_run(const struct qnnp_hip_resize_args* args, const char** kernel_name);
+
 /* softargmax (q8softargmax.hip, linked into libqnnpack_gfx950.so only -- see the Makefile): replaces u8rmax_ukernel__sse2,
  * u8lut32norm_ukernel__scalar and the softargmax case of src/operator-run.c:625-637, 1091-1108. For each of `rows` rows
  * of `channels` bytes, each `*_stride` bytes apart, all in uint32_t:

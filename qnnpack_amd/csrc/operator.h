@@ -31,6 +31,7 @@ enum qnnp_ukernel_type {
   qnnp_ukernel_type_lut,                /* lut.c, sigmoid.c, leaky-relu.c */
   qnnp_ukernel_type_softargmax,         /* softargmax.c */
   qnnp_ukernel_type_multiply,           /* multiply.c */
+  qnnp_ukernel_type_resize_bilinear,    /* resize-bilinear.c */
 };
 
 /* One output phase of a strided deconvolution (deconvolution.c): the output pixels whose (oy + pad_top) % stride_h
@@ -129,6 +130,12 @@ struct qnnp_operator {
   size_t mul_a_rows_per_b_row;
   uint8_t mul_a_zero_point;
   uint8_t mul_b_zero_point;
+  /* bilinear resize (resize-bilinear.c): input_height / input_width / output_height / output_width above are its four
+   * sizes; the flag and the axis tables of the last setup -- ONE grow-only device allocation, owned: output_height row
+   * entries, then output_width column entries (resize-table.h) */
+  int resize_align_corners;
+  void* d_resize_table;
+  size_t resize_table_capacity;   /* in entries */
 
   uint8_t input_zero_point;
   uint8_t kernel_zero_point;
@@ -195,7 +202,7 @@ struct qnnp_operator {
   struct qnnp_hip_dwconv_plan dw_plan;   /* depthwise launch plan, computed at the first run after a setup */
 
   /* launch of operator types whose code is not part of every build (windowed pooling: max-pooling.c,
-   * average-pooling.c; channel-shuffle.c, clamp.c; lut.c; softargmax.c; multiply.c): set by their create, called by launch_kernel's default arm
+   * average-pooling.c; channel-shuffle.c, clamp.c; lut.c; softargmax.c; multiply.c; resize-bilinear.c): set by their create, called by launch_kernel's default arm
    * (operator-run.c) with device pointers. Keeps operator-run.c free of references to their kernels, so builds without
    * them still link. */
   int (*launch_hook)(struct qnnp_operator* op, const void* input, void* output);
