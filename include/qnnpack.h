@@ -139,7 +139,10 @@ enum qnnp_status qnnp_setup_global_average_pooling_nwc_q8(
     qnnp_operator_t global_average_pooling, size_t batch_size, size_t width,
     const uint8_t* input, size_t input_stride, uint8_t* output, size_t output_stride);
 
-/* reference include/qnnpack.h:234-245. Quantized element-wise sum of two [batch][channels] tensors. */
+/* reference include/qnnpack.h:234-245. Quantized element-wise sum of two [batch][channels] tensors. a_scale / sum_scale
+ * and b_scale / sum_scale must each lie in [2^-14, 2^8), as in the reference. Where both are below 2^-10 the
+ * reference's result is undefined (a 32-bit shift by 32 ... 35); here it is defined: neither input can move the sum by
+ * half a step, so every output is sum_zero_point clamped to [sum_min, sum_max], the correctly rounded sum. */
 enum qnnp_status qnnp_create_add_nc_q8(
     size_t channels, uint8_t a_zero_point, float a_scale, uint8_t b_zero_point, float b_scale,
     uint8_t sum_zero_point, float sum_scale, uint8_t sum_min, uint8_t sum_max,

@@ -287,10 +287,19 @@ int oracle_add_q8(
   /* src/qnnpack/requantization.h:341-359 */
   const float max_output_scale = a_output_scale > b_output_scale ? a_output_scale : b_output_scale;
   const int32_t max_scale_exponent = (int32_t) (f32_bits(max_output_scale) >> 23) - 127;
-  const uint32_t shift = (uint32_t) (21 - max_scale_exponent);
-  const float scale_multiplier = f32_from_bits((uint32_t) (21 - max_scale_exponent + 127) << 23);
-  const uint32_t a_multiplier = (uint32_t) (int32_t) lrintf(a_output_scale * scale_multiplier);
-  const uint32_t b_multiplier = (uint32_t) (int32_t) lrintf(b_output_scale * scale_multiplier);
+  uint32_t shift = (uint32_t) (21 - max_scale_exponent);            /* in [14, 35] */
+  uint32_t a_multiplier = 0, b_multiplier = 0;
+  if (shift <= 31) {
+    const float scale_multiplier = f32_from_bits((uint32_t) (21 - max_scale_exponent + 127) << 23);
+    a_multiplier = (uint32_t) (int32_t) lrintf(a_output_scale * scale_multiplier);
+    b_multiplier = (uint32_t) (int32_t) lrintf(b_output_scale * scale_multiplier);
+  } else {
+    /* both ratios below 2^-10: the reference is undefined here (its asserts and its "[13, 31]" comment, :336-347,
+     * contradict each other; a 32-bit shift by 32 ... 35 is no C). |acc| < 2^31 <= 2^(shift - 1), so the correctly
+     * rounded quotient is 0 for every input and every output is clamp(y_zero_point): multipliers 0 state that with a
+     * shift C can express. */
+    shift = 31;
+  }
   /* :400-413 (scalar member) */
   const uint32_t remainder_mask = (UINT32_C(1) << shift) - UINT32_C(1);
   const uint32_t remainder_threshold = remainder_mask >> 1;

@@ -120,7 +120,9 @@ int oracle_convolution2d_q8(
 /* Quantized element-wise add, the whole operator. Parameters: the scalar member of
  * qnnp_compute_add_quantization_params (src/qnnpack/requantization.h:327-360, :400-413); arithmetic:
  * qnnp_add_quantize (:500-522), which test/vadd-microkernel-tester.h:180,194 asserts every microkernel equals.
- * Validation as src/add.c:73-89. Returns 0, or -1 when a scale ratio is outside [2^-14, 2^8). */
+ * Validation as src/add.c:73-89. Returns 0, or -1 when a scale ratio is outside [2^-14, 2^8). Where both ratios are
+ * below 2^-10 the reference's shift would be 32 ... 35 and its result is undefined; the oracle then writes
+ * clamp(y_zero_point) everywhere, the correctly rounded sum (tests/test_pointwise_range_host.py holds it to that). */
 int oracle_add_q8(
     size_t batch, size_t channels,
     uint8_t a_zero_point, float a_scale, uint8_t b_zero_point, float b_scale,

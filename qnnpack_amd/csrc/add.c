@@ -4,7 +4,9 @@
  *
  * Replaces reference src/add.c:20-116 (create) and :118-149 (setup): same validation order and status
  * codes; the quantization parameters are the scalar member of qnnp_compute_add_quantization_params
- * (reference src/qnnpack/requantization.h:327-360, :400-413), consumed on the device by q8pointwise.hip.
+ * (reference src/qnnpack/requantization.h:327-360, :400-413), built by qnnp_compute_add_params (requantization.h) and
+ * consumed on the device by q8pointwise.hip. Where both scale ratios are below 2^-10 the reference's parameters are
+ * undefined; here every output is then clamp(sum_zero_point), the correctly rounded sum (requantization.h).
  */
 #include <math.h>
 #include <stdbool.h>
@@ -18,43 +20,12 @@
 #include "hip/qnnp_hip.h"
 #include "log.h"
 #include "operator.h"
+#include "requantization.h"
 #include "state.h"
 
 static inline bool scale_is_valid(float scale)
 {
   return scale > 0.0f && isnormal(scale);
-}
-
-/* reference requantization.h:327-360 + scalar members :400-413 */
-static struct qnnp_hip_add_params compute_add_params(
-    uint8_t a_zero_point, uint8_t b_zero_point, uint8_t output_zero_point,
-    float a_output_scale, float b_output_scale, uint8_t output_min, uint8_t output_max)
-{
-  const float max_output_scale = a_output_scale > b_output_scale ? a_output_scale : b_output_scale;
-  uint32_t max_scale_bits;
-  memcpy(&max_scale_bits, &max_output_scale, sizeof(max_scale_bits));
-  const int32_t max_scale_exponent = (int32_t) (max_scale_bits >> 23) - 127;
-  const uint32_t shift = (uint32_t) (21 - max_scale_exponent);          /* in [13, 31] */
-  const uint32_t multiplier_bits = (uint32_t) (21 - max_scale_exponent + 127) << 23;
-  float scale_multiplier;
-  memcpy(&scale_multiplier, &multiplier_bits, sizeof(scale_multiplier));
-  /* multipliers in [0, 2^22), the larger one in [2^21, 2^22); lrintf = round to nearest even */
-  const uint32_t a_multiplier = (uint32_t) (int32_t) lrintf(a_output_scale * scale_multiplier);
-  const uint32_t b_multiplier = (uint32_t) (int32_t) lrintf(b_output_scale * scale_multiplier);
-  const uint32_t remainder_mask = (UINT32_C(1) << shift) - UINT32_C(1);
-
-  struct qnnp_hip_add_params p;
-  p.a_multiplier = a_multiplier;
-  p.b_multiplier = b_multiplier;
-  p.zero_point_product =
-      (int32_t) -(a_multiplier * (uint32_t) a_zero_point + b_multiplier * (uint32_t) b_zero_point);
-  p.shift = shift;
-  p.remainder_mask = (int32_t) remainder_mask;
-  p.remainder_threshold = (int32_t) (remainder_mask >> 1);
-  p.y_zero_point = (int32_t) (uint32_t) output_zero_point;
-  p.y_min = (int32_t) (uint32_t) output_min;
-  p.y_max = (int32_t) (uint32_t) output_max;
-  return p;
 }
 
 static enum qnnp_status qnnp_create_add_nc_q8_impl(
@@ -123,7 +94,7 @@ static enum qnnp_status qnnp_create_add_nc_q8_impl(
     return qnnp_status_out_of_memory;
   }
   op->channels = channels;
-  op->add_params = compute_add_params(a_zero_point, b_zero_point, sum_zero_point,
+  op->add_params = qnnp_compute_add_params(a_zero_point, b_zero_point, sum_zero_point,
       a_output_scale, b_output_scale, sum_min, sum_max);
   op->ukernel_type = qnnp_ukernel_type_add;
   *add_out = op;

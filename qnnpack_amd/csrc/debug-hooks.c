@@ -99,6 +99,15 @@ void qnnp_debug_compute_requant(
   *out = qnnp_compute_requant(scale, zero_point, qmin, qmax);
 }
 
+/* the add's parameters as qnnp_create_add_nc_q8 builds them from the two float32 scale ratios it forms (add.c) */
+void qnnp_debug_add_params(
+    uint8_t a_zero_point, uint8_t b_zero_point, uint8_t output_zero_point, float a_output_scale, float b_output_scale,
+    uint8_t output_min, uint8_t output_max, struct qnnp_hip_add_params* out)
+{
+  *out = qnnp_compute_add_params(a_zero_point, b_zero_point, output_zero_point, a_output_scale, b_output_scale,
+      output_min, output_max);
+}
+
 /* the device requantization arithmetic (hip/requant_math.h) evaluated on the host: scale, clamp, add zero point */
 void qnnp_debug_requant_fast_bits(
     size_t count, const int32_t* acc, float scale, uint8_t zero_point, uint8_t qmin, uint8_t qmax,

@@ -10,6 +10,7 @@
  */
 #pragma once
 
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
@@ -76,5 +77,55 @@ static inline struct qnnp_hip_avgpool_params qnnp_compute_avgpool_params(
   p.output_min_less_zero_point = (int32_t) (uint32_t) output_min - (int32_t) (uint32_t) output_zero_point;
   p.output_max_less_zero_point = (int32_t) (uint32_t) output_max - (int32_t) (uint32_t) output_zero_point;
   p.output_zero_point = (int32_t) (uint32_t) output_zero_point;
+  return p;
+}
+
+/*
+ * Scalar member of qnnp_compute_add_quantization_params (reference src/qnnpack/requantization.h:327-360, :400-413):
+ * the two input-to-output scale ratios, each in [2^-14, 2^8), become multipliers in [0, 2^22] -- the larger one in
+ * [2^21, 2^22] -- and a right shift of 21 - exponent(larger ratio). Consumed by add_quantize (hip/add_math.hip.h): the
+ * stand-alone add, the residual add folded into a convolution (residual.c) and the fused block (fused-block.c).
+ *
+ * The shift is in [14, 31] while the larger ratio is at least 2^-10. Below that it would be 32 ... 35, which neither a
+ * 32-bit shift nor the 32-bit remainder mask can express (the reference is undefined there: its asserts and its
+ * comment contradict each other, requantization.h:336-347). The accumulator a * a_multiplier + b * b_multiplier +
+ * zero_point_product is below 2^31 in magnitude, that is below half of 2^shift, so the correctly rounded quotient is 0
+ * for every input: both multipliers and the zero-point product are 0 there and the shift is 31, and every output is
+ * clamp(output_zero_point).
+ */
+static inline struct qnnp_hip_add_params qnnp_compute_add_params(
+    uint8_t a_zero_point, uint8_t b_zero_point, uint8_t output_zero_point,
+    float a_output_scale, float b_output_scale, uint8_t output_min, uint8_t output_max)
+{
+  const float max_output_scale = a_output_scale > b_output_scale ? a_output_scale : b_output_scale;
+  uint32_t max_scale_bits;
+  memcpy(&max_scale_bits, &max_output_scale, sizeof(max_scale_bits));
+  const int32_t max_scale_exponent = (int32_t) (max_scale_bits >> 23) - 127;
+  uint32_t shift = (uint32_t) (21 - max_scale_exponent);                /* in [14, 35] */
+  uint32_t a_multiplier = 0, b_multiplier = 0;
+  if (shift <= 31) {
+    const uint32_t multiplier_bits = (uint32_t) (21 - max_scale_exponent + 127) << 23;
+    float scale_multiplier;
+    memcpy(&scale_multiplier, &multiplier_bits, sizeof(scale_multiplier));
+    /* multipliers in [0, 2^22], the larger one in [2^21, 2^22] (2^22: a mantissa of 24 ones, rounded to 22 bits);
+     * lrintf = round to nearest even */
+    a_multiplier = (uint32_t) (int32_t) lrintf(a_output_scale * scale_multiplier);
+    b_multiplier = (uint32_t) (int32_t) lrintf(b_output_scale * scale_multiplier);
+  } else {
+    shift = 31;                                                         /* the quotient is 0 for every input */
+  }
+  const uint32_t remainder_mask = (UINT32_C(1) << shift) - UINT32_C(1);
+
+  struct qnnp_hip_add_params p;
+  p.a_multiplier = a_multiplier;
+  p.b_multiplier = b_multiplier;
+  p.zero_point_product =
+      (int32_t) -(a_multiplier * (uint32_t) a_zero_point + b_multiplier * (uint32_t) b_zero_point);
+  p.shift = shift;                                                      /* in [14, 31] */
+  p.remainder_mask = (int32_t) remainder_mask;
+  p.remainder_threshold = (int32_t) (remainder_mask >> 1);
+  p.y_zero_point = (int32_t) (uint32_t) output_zero_point;
+  p.y_min = (int32_t) (uint32_t) output_min;
+  p.y_max = (int32_t) (uint32_t) output_max;
   return p;
 }

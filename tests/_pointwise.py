@@ -7,6 +7,13 @@ mr = 7: channels 8..24 x width 1..7 and 7..28, channels 1..7 x width 1..16, stri
 zero points step 51, min / max 128; defaults of test/global-average-pooling-operator-tester.h:221-226).
 The reference testers compare against a float model with a 0.5-0.6 LSB tolerance; here the scalar oracle
 (qnnp_add_quantize / qnnp_avgpool_quantize restated) is the bit-exact expectation.
+
+The oracle restates the integer algorithm, so it cannot notice a defect of the algorithm itself. The second half of
+this file holds it to real arithmetic: float64 models of both operators and lists of parameter sets at the edges of
+the accepted scale ratios ([2^-14, 2^8) for add, [2^-8, 2^8) for the pooling). Those lists are kept apart from
+add_cases() / gap_cases(): these also run against the compiled reference, which is undefined at some of the edges.
+tests/test_pointwise_range_host.py checks the oracle against the models, tests/test_pointwise_range_gpu.py the
+kernels against the oracle.
 """
 from __future__ import annotations
 
@@ -226,3 +233,180 @@ def gap_run(lib, case: GapCase, inp, to_device=None, from_device=None):
     finally:
         lib.delete_operator(op)
     return out, kname
+
+
+# ---- the whole accepted range, held to real arithmetic ---------------------------------------------------------------
+def f32(x: float) -> float:
+    return float(np.float32(x))
+
+
+def f32_below(x: float) -> float:
+    """the float32 just below x"""
+    return float(np.nextafter(np.float32(x), np.float32(0.0)))
+
+
+# Below this larger ratio the reference's right shift would be 32 ... 35 (21 - exponent): the reference is undefined,
+# the product and the oracle answer clamp(sum zero point) (qnnp_compute_add_params, requantization.h of the product).
+ADD_SEAM = 2.0 ** -10
+
+# a_scale / sum_scale and b_scale / sum_scale, each in [2^-14, 2^8): both ends, both sides of the seam, and values
+# with full mantissas in between and at 1
+ADD_RANGE_RATIOS = [f32(v) for v in (
+    2.0 ** -14, 1.37 * 2.0 ** -14, f32_below(2.0 ** -10), 2.0 ** -10, 1.5 * 2.0 ** -10, 1.11 * 2.0 ** -7, 1.37 * 2.0 ** -3,
+    0.75, 1.0, 1.25, 1.11 * 2.0 ** 3, 1.37 * 2.0 ** 7, f32_below(2.0 ** 8))]
+ADD_RANGE_ZERO_POINTS = [(0, 0, 0), (255, 255, 255), (0, 255, 128), (255, 0, 0)]
+ADD_RANGE_CLAMPS = [(0, 255), (128, 255), (0, 128), (100, 101)]
+
+# |y - clip(real)| <= ADD_TOL, derived (not measured). With M_a = round(r_a * 2^shift), M_b likewise, the kernel forms
+# acc = (a - a_zp) * M_a + (b - b_zp) * M_b exactly (|acc| <= 2 * 255 * 2^22 < 2^31: no wrap) and rounds acc * 2^-shift
+# to the nearest integer: 0.5. Each multiplier is off by at most half a unit, |M * 2^-shift - r| <= 2^-(shift + 1), and
+# |a - a_zp|, |b - b_zp| <= 255, so acc * 2^-shift is within 2 * 255 * 2^-(shift + 1) = 255 * 2^-shift of the real
+# sum; shift = 21 - exponent(larger ratio) >= 14 because the ratios are below 2^8. Clamping moves y and the real value
+# towards each other. Below the seam y = clamp(y_zp) and |real - y_zp| <= 2 * 255 * ADD_SEAM < 0.4981.
+ADD_TOL = 0.5 + 255 * 2.0 ** -14
+
+
+@dataclass(frozen=True)
+class AddRangeSet:
+    name: str
+    a_scale: float
+    b_scale: float
+    y_scale: float = 1.0
+    a_zp: int = 121
+    b_zp: int = 127
+    y_zp: int = 133
+    qmin: int = 0
+    qmax: int = 255
+
+    @property
+    def ratios(self):
+        """the two float32 quotients as qnnp_create_add_nc_q8 forms them (add.c)"""
+        return (np.float32(self.a_scale) / np.float32(self.y_scale), np.float32(self.b_scale) / np.float32(self.y_scale))
+
+    @property
+    def below_seam(self) -> bool:
+        return float(max(self.ratios)) < ADD_SEAM
+
+    @property
+    def band(self) -> str:
+        """by the larger ratio; the GPU tier runs one test id per kernel and band"""
+        top = float(max(self.ratios))
+        return "below_seam" if top < ADD_SEAM else "low" if top < 0.5 else "mid" if top < 2.0 else "high"
+
+
+ADD_RANGE_BANDS = ("below_seam", "low", "mid", "high")
+
+
+def add_range_sets() -> List[AddRangeSet]:
+    r = ADD_RANGE_RATIOS
+    out = [AddRangeSet(f"r{i}_r{j}", r[i], r[j]) for i in range(len(r)) for j in range(len(r))]
+    last = len(r) - 1
+    for i, j in [(k, k) for k in range(len(r))] + [(0, last), (last, 0)]:
+        for zps in ADD_RANGE_ZERO_POINTS:
+            for qmin, qmax in ADD_RANGE_CLAMPS:
+                out.append(AddRangeSet(f"r{i}_r{j}_zp{zps[0]}_{zps[1]}_{zps[2]}_q{qmin}_{qmax}", r[i], r[j], 1.0,
+                                       zps[0], zps[1], zps[2], qmin, qmax))
+    # a sum scale that is no power of two: the ratios are rounded float32 quotients (one third, two thirds, ...)
+    out += [
+        AddRangeSet("third_two_thirds", 1.0, 2.0, 3.0),
+        AddRangeSet("y3_mid", 0.75, 1.25, 3.0),
+        AddRangeSet("y3_lowest", 3.0 * 2.0 ** -14, 3.0 * 2.0 ** -14, 3.0),          # both quotients exactly 2^-14
+        AddRangeSet("y3_below_seam", 2.9 * 2.0 ** -10, 1.0 * 2.0 ** -12, 3.0),
+        AddRangeSet("y3_high_low", 700.0, 3.0 * 2.0 ** -14, 3.0, 0, 255, 128, 0, 255),
+    ]
+    return out
+
+
+def add_range_inputs():
+    """a[r][c] = r, b[r][c] = c: every (a, b) byte pair once, as [256][256] tensors"""
+    a = np.repeat(np.arange(256, dtype=np.uint8)[:, None], 256, axis=1).copy()
+    return a, np.ascontiguousarray(a.T)
+
+
+def add_real(s: AddRangeSet, a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """the sum in real arithmetic (float64), unclamped"""
+    ra, rb = (float(v) for v in s.ratios)
+    return (a.astype(np.float64) - s.a_zp) * ra + (b.astype(np.float64) - s.b_zp) * rb + s.y_zp
+
+
+_ADD_RANGE_EXPECTED = {}
+
+
+def add_range_expected(s: AddRangeSet) -> np.ndarray:
+    """the oracle's [256][256] bytes for the inputs of add_range_inputs(); computed once per set, read-only"""
+    if s not in _ADD_RANGE_EXPECTED:
+        a, b = add_range_inputs()
+        y = np.full(65536, FILL, dtype=np.uint8)
+        o1.add_q8(256, 256, s.a_zp, s.a_scale, s.b_zp, s.b_scale, s.y_zp, s.y_scale, s.qmin, s.qmax,
+                  a.reshape(-1), 256, b.reshape(-1), 256, y, 256)
+        y = y.reshape(256, 256)
+        y.setflags(write=False)
+        _ADD_RANGE_EXPECTED[s] = y
+    return _ADD_RANGE_EXPECTED[s]
+
+
+def worst_distance(y: np.ndarray, real: np.ndarray, qmin: int, qmax: int) -> float:
+    """max |y - clip(real, qmin, qmax)| over every output, clamped or not"""
+    return float(np.max(np.abs(y.astype(np.float64) - np.clip(real, qmin, qmax))))
+
+
+# Average pooling, global and windowed: input_scale / output_scale in [2^-8, 2^8)
+POOL_RANGE_RATIOS = [f32(v) for v in (2.0 ** -8, 1.37 * 2.0 ** -8, 1.0, 1.11 * 2.0 ** 7, f32_below(2.0 ** 8))]
+POOL_RANGE_ZERO_POINTS = [(0, 0), (255, 255), (0, 255), (255, 0), (121, 133)]      # (input, output)
+POOL_RANGE_CLAMPS = [(0, 255), (100, 101)]
+
+# |y - clip(real)| <= POOL_TOL, derived (not measured). With N pixels in the divisor and n = sum - N * in_zp
+# (|n| <= 255 * N), the kernels round n * s to the nearest integer exactly (64-bit product of n and the 24-bit mantissa
+# of s): 0.5. s = fl(in_scale / fl(out_scale * N)) is the float32 that create / setup form: two roundings, so
+# |s - ratio / N| <= (ratio / N) * (2^-23 + 2^-48) and n * s is within 255 * ratio * (2^-23 + 2^-48) of the real value,
+# which is below 255 * 2^8 * 2^-23 for every float32 ratio below 2^8. The lists here have out_scale = 1, so the ratio
+# itself is exact (another output scale would add a third rounding).
+POOL_TOL = 0.5 + 255 * 2.0 ** 8 * 2.0 ** -23
+
+GAP_RANGE_WIDTHS = (1, 2, 7, 49, 300)
+GAP_RANGE_CHANNELS = 256
+
+
+def gap_range_cases(channels: int = GAP_RANGE_CHANNELS, in_stride: int = 0) -> List[GapCase]:
+    """batch 4 (the four images of gap_range_pixels) x widths x ratios x zero-point corners x clamps"""
+    out = []
+    for width in GAP_RANGE_WIDTHS:
+        for k, ratio in enumerate(POOL_RANGE_RATIOS):
+            for in_zp, out_zp in POOL_RANGE_ZERO_POINTS:
+                for qmin, qmax in POOL_RANGE_CLAMPS:
+                    out.append(GapCase(f"gr_c{channels}_s{in_stride}_w{width}_r{k}_zp{in_zp}_{out_zp}_q{qmin}_{qmax}", 4, width,
+                                       channels, in_stride=in_stride, in_scale=ratio, out_scale=1.0, in_zp=in_zp,
+                                       out_zp=out_zp, qmin=qmin, qmax=qmax))
+    return out
+
+
+def gap_range_pixels(width: int, channels: int = GAP_RANGE_CHANNELS) -> np.ndarray:
+    """[4][width][channels]: channel c holds byte c at every pixel (the mean is exactly c); random; all 0; all 255"""
+    rng = np.random.default_rng(_seed(f"gap_range_w{width}"))
+    px = np.empty((4, width, GAP_RANGE_CHANNELS), np.uint8)
+    px[0] = np.arange(GAP_RANGE_CHANNELS, dtype=np.uint8)[None, :]
+    px[1] = rng.integers(0, 256, size=(width, GAP_RANGE_CHANNELS), dtype=np.uint8)
+    px[2] = 0
+    px[3] = 255
+    return np.ascontiguousarray(px[:, :, :channels])
+
+
+def gap_range_input(case: GapCase, pixels: np.ndarray) -> np.ndarray:
+    """`pixels` laid out with the case's input stride (the bytes between pixels are 0x5A)"""
+    si, _ = case.strides
+    rows = case.batch * case.width
+    flat = np.full((rows - 1) * si + case.channels, 0x5A, dtype=np.uint8)
+    idx = np.arange(rows, dtype=np.int64)[:, None] * si + np.arange(case.channels)[None, :]
+    flat[idx] = pixels.reshape(rows, case.channels)
+    return flat
+
+
+def pool_ratio(in_scale: float, out_scale: float) -> float:
+    """the float32 quotient input_scale / output_scale as the creates form it, as a float64"""
+    return float(np.float32(in_scale) / np.float32(out_scale))
+
+
+def gap_real(case: GapCase, pixels: np.ndarray) -> np.ndarray:
+    """[batch][channels] in real arithmetic (float64), unclamped: (mean - in_zp) * ratio + out_zp"""
+    mean = pixels.astype(np.int64).sum(axis=1) / float(case.width)
+    return (mean - case.in_zp) * pool_ratio(case.in_scale, case.out_scale) + case.out_zp

@@ -827,6 +827,78 @@ def expected(case: PoolCase, x: np.ndarray) -> List[np.ndarray]:
     return outs
 
 
+# ---- average pooling over its whole range of scale ratios, held to real arithmetic ---------------------------------
+# The numpy model above restates the integer algorithm, so it cannot notice a defect of the algorithm itself. These
+# cases sit at the edges of the accepted input-to-output scale ratios, [2^-8, 2^8), and at the zero-point corners, and
+# avg_real() is the operator in float64. A list of its own: all_cases() also runs against the compiled reference.
+# tests/test_pointwise_range_host.py checks the model against avg_real(), tests/test_pointwise_range_gpu.py the kernels
+# against the model.
+def _f32_below(x: float) -> float:
+    return float(np.nextafter(np.float32(x), np.float32(0.0)))
+
+
+RANGE_RATIOS = [float(np.float32(v)) for v in (2.0 ** -8, 1.37 * 2.0 ** -8, 1.0, 1.11 * 2.0 ** 7, _f32_below(2.0 ** 8))]
+RANGE_ZERO_POINTS = [(0, 0), (255, 255), (0, 255), (255, 0), (121, 133)]      # (input, output)
+RANGE_CLAMPS = [(0, 255), (100, 101)]
+# (tag, image side, window, padding, stride)
+RANGE_GEOMETRIES = [("2x2s2", 6, 2, 0, 2), ("3x3s1p1", 5, 3, 1, 1), ("7x7_whole_image", 7, 7, 0, 1)]
+
+# |y - clip(real)| <= RANGE_TOL, derived (not measured). With N taps in the window (the divisor, padded taps included)
+# and n = the sum of (x - in_zp) over the taps inside the image (|n| <= 255 * N), the kernel rounds n * s to the nearest
+# integer exactly: 0.5. s = fl(in_scale / fl(out_scale * N)) is the float32 that create forms: two roundings, so n * s
+# is within 255 * ratio * (2^-23 + 2^-48) < 255 * 2^8 * 2^-23 of the real value for every float32 ratio below 2^8. The
+# list has out_scale = 1, so the ratio itself is exact.
+RANGE_TOL = 0.5 + 255 * 2.0 ** 8 * 2.0 ** -23
+
+
+def range_cases() -> List[PoolCase]:
+    """batch 2 (the two images of range_input): geometries x {16, 19} channels x ratios x zero-point corners x clamps"""
+    out = []
+    for tag, side, window, pad, stride in RANGE_GEOMETRIES:
+        for channels in (16, 19):
+            for k, ratio in enumerate(RANGE_RATIOS):
+                for in_zp, out_zp in RANGE_ZERO_POINTS:
+                    for qmin, qmax in RANGE_CLAMPS:
+                        out.append(PoolCase("avg", f"avg/range/{tag}_c{channels}_r{k}_zp{in_zp}_{out_zp}_q{qmin}_{qmax}", 2, side,
+                                            side, channels, window, window, pad, pad, pad, pad, stride, stride, qmin=qmin,
+                                            qmax=qmax, in_scale=ratio, out_scale=1.0, in_zp=in_zp, out_zp=out_zp))
+    return out
+
+
+def range_input(case: PoolCase) -> np.ndarray:
+    """image 0: channel c holds one byte at every pixel, 0 in the first channel and 255 in the last; image 1: random.
+    Laid out with the case's input stride (the bytes between pixels are 0x5A)."""
+    n, h, w = case.batch, case.input_height, case.input_width
+    assert n == 2
+    rng = np.random.default_rng(_seed(f"range/{h}x{w}x{case.channels}"))
+    img = np.empty((2, h, w, case.channels), np.uint8)
+    img[0] = (np.arange(case.channels) * 255 // (case.channels - 1)).astype(np.uint8)[None, None, :]
+    img[1] = rng.integers(0, 256, size=(h, w, case.channels), dtype=np.uint8)
+    si, _ = case.strides
+    rows = n * h * w
+    flat = np.full((rows - 1) * si + case.channels, 0x5A, dtype=np.uint8)
+    idx = np.arange(rows, dtype=np.int64)[:, None] * si + np.arange(case.channels)[None, :]
+    flat[idx] = img.reshape(rows, case.channels)
+    return flat
+
+
+def avg_real(case: PoolCase, x: np.ndarray) -> np.ndarray:
+    """[n][oh][ow][c] in real arithmetic (float64), unclamped: (mean - in_zp) * ratio + out_zp, where a padded tap of
+    the window counts as in_zp and the divisor is the whole window"""
+    n, h, w = case.batch, case.input_height, case.input_width
+    img = _pixels(case, x, n, h, w).astype(np.float64) - case.in_zp
+    padded = np.zeros((n, h + case.pad_top + case.pad_bottom, w + case.pad_left + case.pad_right, case.channels))
+    padded[:, case.pad_top:case.pad_top + h, case.pad_left:case.pad_left + w] = img
+    oh, ow = case.output_size(h, w)
+    total = np.zeros((n, oh, ow, case.channels))
+    for ky in range(case.pooling_height):
+        for kx in range(case.pooling_width):
+            total += padded[:, ky:ky + (oh - 1) * case.stride_height + 1:case.stride_height,
+                            kx:kx + (ow - 1) * case.stride_width + 1:case.stride_width]
+    ratio = float(np.float32(case.in_scale) / np.float32(case.out_scale))
+    return total / float(case.pooling_height * case.pooling_width) * ratio + case.out_zp
+
+
 # ---- drivers ----------------------------------------------------------------------------------------------------
 def create(lib, case: PoolCase):
     if case.kind == "max":

@@ -6,6 +6,7 @@
  * Any heap overflow, use-after-free, leak or undefined arithmetic in the packers, offset tables, phase splitting,
  * staging logic or error paths aborts the program. Prints "host-sanitizers-ok" on success.
  */
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -390,6 +391,53 @@ int main(void)
     CHECK(qnnp_run_operator(op, NULL) == qnnp_status_success);
     free(x); free(y);
     CHECK(qnnp_delete_operator(op) == qnnp_status_success);
+  }
+
+  /* the same three parameter builders over their whole accepted ranges (requantization.h): an add at one ratio pair per
+   * exponent of the larger ratio, -14 ... 7 (its right shift is 21 - exponent: beyond 31 below 2^-10), and the two
+   * average poolings at both ends of [2^-8, 2^8) */
+  {
+    uint8_t* a = random_bytes(9 * 31), * b = random_bytes(9 * 29), * s = random_bytes(9 * 24);
+    for (int e = -14; e <= 7; e++) {
+      const float larger = ldexpf(1.37f, e);
+      const float smaller = e > -14 ? ldexpf(1.0f, -14) : larger;
+      for (int swap = 0; swap < 2; swap++) {
+        CHECK(qnnp_create_add_nc_q8(24, 121, swap ? smaller : larger, 127, swap ? larger : smaller, 133, 1.0f, 0, 255, 0, &op) == qnnp_status_success);
+        CHECK(qnnp_setup_add_nc_q8(op, 9, a, 31, b, 29, s, 24) == qnnp_status_success);
+        CHECK(qnnp_run_operator(op, NULL) == qnnp_status_success);
+        CHECK(qnnp_delete_operator(op) == qnnp_status_success);
+      }
+    }
+    CHECK(qnnp_create_add_nc_q8(24, 121, 1.0f, 127, 1.0f, 133, 4096.0f, 0, 255, 0, &op) == qnnp_status_success);   /* 2^-12 both */
+    CHECK(qnnp_delete_operator(op) == qnnp_status_success);
+    CHECK(qnnp_create_add_nc_q8(24, 121, nextafterf(256.0f, 0.0f), 127, ldexpf(1.0f, -14), 133, 1.0f, 0, 255, 0, &op) == qnnp_status_success);
+    CHECK(qnnp_delete_operator(op) == qnnp_status_success);
+    CHECK(qnnp_create_add_nc_q8(24, 121, 1.0f, 127, 1.0f, 133, 32768.0f, 0, 255, 0, &op) == qnnp_status_unsupported_parameter);   /* 2^-15 */
+    CHECK(qnnp_create_add_nc_q8(24, 121, 256.0f, 127, 1.0f, 133, 1.0f, 0, 255, 0, &op) == qnnp_status_unsupported_parameter);
+    free(a); free(b); free(s);
+
+    const float ends[2] = {ldexpf(1.0f, -8), nextafterf(256.0f, 0.0f)};
+    uint8_t* x = random_bytes(2 * 300 * 19), * y = random_bytes(2 * 7 * 7 * 19);
+    for (int i = 0; i < 2; i++) {
+      CHECK(qnnp_create_global_average_pooling_nwc_q8(19, 0, ends[i], 255, 1.0f, 0, 255, 0, &op) == qnnp_status_success);
+      for (size_t width = 1; width <= 300; width *= 300) {
+        CHECK(qnnp_setup_global_average_pooling_nwc_q8(op, 2, width, x, 19, y, 19) == qnnp_status_success);
+        CHECK(qnnp_run_operator(op, NULL) == qnnp_status_success);
+      }
+      CHECK(qnnp_delete_operator(op) == qnnp_status_success);
+      /* 2x2 stride 2, then 7x7 over a 7x7 image with padding 1 */
+      CHECK(qnnp_create_average_pooling2d_nhwc_q8(0, 0, 0, 0, 2, 2, 2, 2, 19, 255, ends[i], 0, 1.0f, 0, 255, 0, &op) == qnnp_status_success);
+      CHECK(qnnp_setup_average_pooling2d_nhwc_q8(op, 2, 6, 6, x, 19, y, 19, NULL) == qnnp_status_success);
+      CHECK(qnnp_run_operator(op, NULL) == qnnp_status_success);
+      CHECK(qnnp_delete_operator(op) == qnnp_status_success);
+      CHECK(qnnp_create_average_pooling2d_nhwc_q8(1, 1, 1, 1, 7, 7, 1, 1, 19, 0, ends[i], 255, 1.0f, 100, 101, 0, &op) == qnnp_status_success);
+      CHECK(qnnp_setup_average_pooling2d_nhwc_q8(op, 2, 7, 7, x, 19, y, 19, NULL) == qnnp_status_success);
+      CHECK(qnnp_run_operator(op, NULL) == qnnp_status_success);
+      CHECK(qnnp_delete_operator(op) == qnnp_status_success);
+    }
+    CHECK(qnnp_create_global_average_pooling_nwc_q8(19, 0, 256.0f, 255, 1.0f, 0, 255, 0, &op) == qnnp_status_unsupported_parameter);
+    CHECK(qnnp_create_average_pooling2d_nhwc_q8(0, 0, 0, 0, 2, 2, 2, 2, 19, 0, ldexpf(1.0f, -9), 0, 1.0f, 0, 255, 0, &op) == qnnp_status_unsupported_parameter);
+    free(x); free(y);
   }
 
   /* fused block built from stand-alone operators */

@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 ADD_Q = dict(a_zp=121, a_scale=0.75, b_scale=1.25, y_zp=133, y_scale=0.96875, y_min=3, y_max=250)
 
 
-def _oracle(batch, hw, cin, cout, k, groups, x, kernel, bias, izp, kzp, res, res_stride, out_stride):
+def _oracle(batch, hw, cin, cout, k, groups, x, kernel, bias, izp, kzp, res, res_stride, out_stride, add_q=ADD_Q):
     pad = k // 2
     shape = o1.conv_shape(batch, hw, hw, (pad,) * 4, (k, k), (1, 1), (1, 1), groups, cin // groups, cout // groups)
     acc = o1.conv2d_acc(shape, x, kernel, bias, izp, kzp)
@@ -32,13 +32,14 @@ def _oracle(batch, hw, cin, cout, k, groups, x, kernel, bias, izp, kzp, res, res
     rows = batch * hw * hw
     conv = o1.requantize_rows(acc.reshape(-1, cout), np.float32(1.0) / oscale, ozp, 0, 255)
     y = np.full(rows * out_stride, 0xA5, np.uint8)
-    o1.add_q8(rows, cout, ADD_Q["a_zp"], ADD_Q["a_scale"], ozp, ADD_Q["b_scale"], ADD_Q["y_zp"], ADD_Q["y_scale"],
-              ADD_Q["y_min"], ADD_Q["y_max"], res, res_stride, np.ascontiguousarray(conv).reshape(-1), cout, y, out_stride)
+    o1.add_q8(rows, cout, add_q["a_zp"], add_q["a_scale"], ozp, add_q["b_scale"], add_q["y_zp"], add_q["y_scale"],
+              add_q["y_min"], add_q["y_max"], res, res_stride, np.ascontiguousarray(conv).reshape(-1), cout, y, out_stride)
     return y, float(oscale), int(ozp)
 
 
 def _run_case(qnnp, batch, hw, cin, cout, k=1, groups=1, variant=0, res_stride=None, out_stride=None, res_misalign=0,
-              seed=0):
+              seed=0, add_q=ADD_Q):
+    """`add_q`: the add's parameters (the convolution output's zero point is its b zero point), ADD_Q by default"""
     rng = np.random.default_rng(seed + 7 * hw + cin + cout)
     res_stride = res_stride or cout
     out_stride = out_stride or cout
@@ -49,7 +50,8 @@ def _run_case(qnnp, batch, hw, cin, cout, k=1, groups=1, variant=0, res_stride=N
     kernel = rng.integers(0, 256, (groups, goc, k, k, gic), dtype=np.uint8)
     bias = rng.integers(-5000, 5000, cout).astype(np.int32)
     res = rng.integers(0, 256, rows * res_stride, dtype=np.uint8)
-    expected, oscale, ozp = _oracle(batch, hw, cin, cout, k, groups, x, kernel, bias, izp, kzp, res, res_stride, out_stride)
+    expected, oscale, ozp = _oracle(batch, hw, cin, cout, k, groups, x, kernel, bias, izp, kzp, res, res_stride, out_stride,
+                                    add_q)
 
     d_x, d_res = to_device(x), to_device(res, misalign=res_misalign)
     d_out = to_device(np.full(rows * out_stride, 0xA5, np.uint8))
@@ -58,8 +60,8 @@ def _run_case(qnnp, batch, hw, cin, cout, k=1, groups=1, variant=0, res_stride=N
     pad = k // 2
     conv = qnnp.create_convolution2d_nhwc_q8(pad, pad, pad, pad, k, k, 1, 1, 1, 1, groups, gic, goc, izp, 1.0, kzp, 1.0,
                                              kernel, bias, ozp, oscale, 0, 255, 0)
-    add = qnnp.create_add_nc_q8(cout, ADD_Q["a_zp"], ADD_Q["a_scale"], ozp, ADD_Q["b_scale"], ADD_Q["y_zp"],
-                                ADD_Q["y_scale"], ADD_Q["y_min"], ADD_Q["y_max"], 0)
+    add = qnnp.create_add_nc_q8(cout, add_q["a_zp"], add_q["a_scale"], ozp, add_q["b_scale"], add_q["y_zp"],
+                                add_q["y_scale"], add_q["y_min"], add_q["y_max"], 0)
     try:
         qnnp.set_option("gemm_kernel", variant)
         # the reference's form: convolution, then add(a = residual, b = convolution output)
