@@ -12,16 +12,15 @@
 #include <stdbool.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <qnnpack.h>
 
 #include "hip/qnnp_hip.h"
+#include "lifecycle.h"
 #include "log.h"
 #include "operator.h"
 #include "requantization.h"
-#include "state.h"
 
 static inline bool scale_is_valid(float scale)
 {
@@ -42,11 +41,6 @@ static enum qnnp_status qnnp_create_add_nc_q8_impl(
     qnnp_operator_t* add_out)
 {
   (void) flags;
-  /* reference add.c:36-39 */
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_create_add_nc_q8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
-  }
   /* reference add.c:41-71 */
   if (channels == 0) {
     qnnp_log_error("cannot create add operator with %zu channels: number of channels may not be zero", channels);
@@ -87,16 +81,13 @@ static enum qnnp_status qnnp_create_add_nc_q8_impl(
     return qnnp_status_unsupported_parameter;
   }
 
-  qnnp_operator_t op = calloc(1, sizeof(struct qnnp_operator));
-  if (op != NULL) op->device = qnnp_hip_device();   /* the context this create runs in (entry point below) */
+  qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_add, NULL);
   if (op == NULL) {
-    qnnp_log_error("out of host memory: %zu bytes for qnnp_operator structure", sizeof(struct qnnp_operator));
     return qnnp_status_out_of_memory;
   }
   op->channels = channels;
   op->add_params = qnnp_compute_add_params(a_zero_point, b_zero_point, sum_zero_point,
       a_output_scale, b_output_scale, sum_min, sum_max);
-  op->ukernel_type = qnnp_ukernel_type_add;
   *add_out = op;
   return qnnp_status_success;
 }
@@ -111,12 +102,7 @@ static enum qnnp_status qnnp_setup_add_nc_q8_impl(
     uint8_t* sum,
     size_t sum_stride)
 {
-  /* reference add.c:128-131 */
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_setup_add_nc_q8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
-  }
-  if (op == NULL || op->ukernel_type != qnnp_ukernel_type_add) {
+  if (op->ukernel_type != qnnp_ukernel_type_add) {
     return qnnp_status_invalid_parameter;
   }
   /* reference add.c:133-136 */
@@ -143,23 +129,10 @@ static enum qnnp_status qnnp_setup_add_nc_q8_impl(
   op->input_span = (batch_size - 1) * a_stride + channels;
   op->input2_span = (batch_size - 1) * b_stride + channels;
   op->output_span = (batch_size - 1) * sum_stride + channels;
-  {
-    enum qnnp_status bound = qnnp_status_success;
-    if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(a, op->input_span, &op->input_on_device, &op->d_stage_in, &op->stage_in_capacity);
-    if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(b, op->input2_span, &op->input2_on_device, &op->d_stage_in2, &op->stage_in2_capacity);
-    if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(sum, op->output_span, &op->output_on_device, &op->d_stage_out, &op->stage_out_capacity);
-    if (bound != qnnp_status_success) {
-      qnnp_log_error("failed to bind the tensors: device staging for host memory could not be allocated, or a tensor "
-          "lives on a different device than the operator");
-      return bound;
-    }
-  }
-  return qnnp_status_success;
+  return qnnp_bind_tensors(op, "qnnp_setup_add_nc_q8");
 }
 
-/* ---- public entry points: run the implementation inside the right device context ------------------
- * create: the calling thread's selected device (qnnp_gfx950_set_device, default = the primary one) becomes the
- * operator's device; setup: the operator's device. The previous HIP device of the thread is restored on return. */
+/* ---- public entry points: the implementations above inside the device guards of lifecycle.h ---- */
 
 enum qnnp_status qnnp_create_add_nc_q8(
     size_t channels,
@@ -174,17 +147,14 @@ enum qnnp_status qnnp_create_add_nc_q8(
     uint32_t flags,
     qnnp_operator_t* add_out)
 {
-  if (!qnnp_state.initialized) {
-    return qnnp_create_add_nc_q8_impl(channels, a_zero_point, a_scale, b_zero_point, b_scale, sum_zero_point, sum_scale, sum_min, sum_max, flags, add_out);   /* logs and answers qnnp_status_uninitialized */
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
+  const enum qnnp_status status = qnnp_enter_create("qnnp_create_add_nc_q8", &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = qnnp_create_add_nc_q8_impl(channels, a_zero_point, a_scale, b_zero_point, b_scale, sum_zero_point, sum_scale, sum_min, sum_max, flags, add_out);
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_create(token,
+      qnnp_create_add_nc_q8_impl(channels, a_zero_point, a_scale, b_zero_point, b_scale, sum_zero_point, sum_scale,
+          sum_min, sum_max, flags, add_out));
 }
 
 enum qnnp_status qnnp_setup_add_nc_q8(
@@ -197,20 +167,11 @@ enum qnnp_status qnnp_setup_add_nc_q8(
     uint8_t* sum,
     size_t sum_stride)
 {
-  if (!qnnp_state.initialized || op == NULL) {
-    return qnnp_setup_add_nc_q8_impl(op, batch_size, a, a_stride, b, b_stride, sum, sum_stride);   /* answers qnnp_status_uninitialized / invalid_parameter */
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(op->device, qnnp_status_invalid_parameter, &token);
+  const enum qnnp_status status = qnnp_enter_setup("qnnp_setup_add_nc_q8", op, &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = qnnp_setup_add_nc_q8_impl(op, batch_size, a, a_stride, b, b_stride, sum, sum_stride);
-  /* the implementation cleared setup_valid where it began to change the operator: a failed setup leaves it
-   * unrunnable instead of half updated (run answers invalid_parameter) */
-  if (status == qnnp_status_success) {
-    op->setup_valid = 1;
-  }
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_setup(op, token,
+      qnnp_setup_add_nc_q8_impl(op, batch_size, a, a_stride, b, b_stride, sum, sum_stride));
 }

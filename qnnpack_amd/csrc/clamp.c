@@ -15,15 +15,14 @@
 #include <inttypes.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <qnnpack.h>
 #include <qnnpack_gfx950.h>
 
 #include "hip/qnnp_hip.h"
+#include "lifecycle.h"
 #include "log.h"
 #include "operator.h"
-#include "state.h"
 
 static int launch_clamp(struct qnnp_operator* op, const void* input, void* output)
 {
@@ -41,19 +40,12 @@ static int launch_clamp(struct qnnp_operator* op, const void* input, void* outpu
   return qnnp_hip_clamp_run(&args, &op->kernel_name);
 }
 
-static enum qnnp_status qnnp_create_clamp_nc_u8_impl(
+static enum qnnp_status create_clamp(
     size_t channels,
     uint8_t output_min,
     uint8_t output_max,
-    uint32_t flags,
     qnnp_operator_t* clamp_out)
 {
-  (void) flags;
-  /* reference clamp.c:30-33 */
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_create_clamp_nc_u8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
-  }
   /* reference clamp.c:35-48 */
   if (channels == 0) {
     qnnp_log_error("cannot create clamp operator with %zu channels: number of channels must be non-zero", channels);
@@ -69,77 +61,16 @@ static enum qnnp_status qnnp_create_clamp_nc_u8_impl(
     return qnnp_status_unsupported_parameter;
   }
 
-  qnnp_operator_t op = calloc(1, sizeof(struct qnnp_operator));
+  qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_clamp, launch_clamp);
   if (op == NULL) {
-    qnnp_log_error("out of host memory: %zu bytes for qnnp_operator structure", sizeof(struct qnnp_operator));
     return qnnp_status_out_of_memory;
   }
-  op->device = qnnp_hip_device();   /* the context this create runs in (entry point below) */
   op->channels = channels;
   op->output_min = output_min;
   op->output_max = output_max;
-  op->ukernel_type = qnnp_ukernel_type_clamp;
-  op->launch_hook = launch_clamp;
   *clamp_out = op;
   return qnnp_status_success;
 }
-
-static enum qnnp_status qnnp_setup_clamp_nc_u8_impl(
-    qnnp_operator_t op,
-    size_t batch_size,
-    const uint8_t* input,
-    size_t input_stride,
-    uint8_t* output,
-    size_t output_stride)
-{
-  /* reference clamp.c:80-83 */
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_setup_clamp_nc_u8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
-  }
-  if (op == NULL || op->ukernel_type != qnnp_ukernel_type_clamp) {
-    return qnnp_status_invalid_parameter;
-  }
-  /* reference clamp.c:85-88 */
-  if (batch_size == 0) {
-    op->batch_size = 0;
-    return qnnp_status_success;
-  }
-  const size_t channels = op->channels;
-  if (input == NULL || output == NULL || input_stride < channels || output_stride < channels) {
-    qnnp_log_error("cannot set up clamp operator: NULL tensor or pixel stride smaller than the channel count");
-    return qnnp_status_invalid_parameter;
-  }
-  if (batch_size > (size_t) INT32_MAX) {
-    qnnp_log_error("cannot set up clamp operator with batch %zu: outside the device kernel's index range", batch_size);
-    return qnnp_status_unsupported_parameter;
-  }
-  const size_t input_span = (batch_size - 1) * input_stride + channels;
-  const size_t output_span = (batch_size - 1) * output_stride + channels;
-  const int in_place = (const void*) input == (const void*) output && input_stride == output_stride;
-  if (!in_place && qnnp_spans_overlap(input, input_span, output, output_span)) {
-    qnnp_log_error("cannot set up clamp operator: the input and output tensors overlap without being the same tensor");
-    return qnnp_status_invalid_parameter;
-  }
-
-  op->setup_valid = 0;   /* until every check, allocation and upload below has succeeded */
-  op->batch_size = batch_size;
-  op->input = input;
-  op->input_pixel_stride = input_stride;
-  op->output = output;
-  op->output_pixel_stride = output_stride;
-  op->input_span = input_span;
-  op->output_span = output_span;
-  enum qnnp_status bound = qnnp_bind_endpoint(input, op->input_span, &op->input_on_device, &op->d_stage_in, &op->stage_in_capacity);
-  if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(output, op->output_span, &op->output_on_device, &op->d_stage_out, &op->stage_out_capacity);
-  if (bound != qnnp_status_success) {
-    qnnp_log_error("failed to bind the tensors: device staging for host memory could not be allocated, or a tensor "
-        "lives on a different device than the operator");
-  }
-  return bound;
-}
-
-/* ---- public entry points: run the implementation inside the right device context (as max-pooling.c) ---- */
 
 enum qnnp_status qnnp_create_clamp_nc_u8(
     size_t channels,
@@ -148,18 +79,14 @@ enum qnnp_status qnnp_create_clamp_nc_u8(
     uint32_t flags,
     qnnp_operator_t* clamp)
 {
-  if (!qnnp_state.initialized) {
-    /* logs and answers qnnp_status_uninitialized */
-    return qnnp_create_clamp_nc_u8_impl(channels, output_min, output_max, flags, clamp);
-  }
+  (void) flags;
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
+  /* reference clamp.c:30-33 */
+  const enum qnnp_status status = qnnp_enter_create("qnnp_create_clamp_nc_u8", &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = qnnp_create_clamp_nc_u8_impl(channels, output_min, output_max, flags, clamp);
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_create(token, create_clamp(channels, output_min, output_max, clamp));
 }
 
 enum qnnp_status qnnp_setup_clamp_nc_u8(
@@ -170,20 +97,14 @@ enum qnnp_status qnnp_setup_clamp_nc_u8(
     uint8_t* output,
     size_t output_stride)
 {
-  if (!qnnp_state.initialized || clamp == NULL) {
-    /* answers qnnp_status_uninitialized / invalid_parameter */
-    return qnnp_setup_clamp_nc_u8_impl(clamp, batch_size, input, input_stride, output, output_stride);
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(clamp->device, qnnp_status_invalid_parameter, &token);
+  /* reference clamp.c:80-83 */
+  enum qnnp_status status = qnnp_enter_setup("qnnp_setup_clamp_nc_u8", clamp, &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = qnnp_setup_clamp_nc_u8_impl(clamp, batch_size, input, input_stride, output, output_stride);
-  /* a failed setup leaves the operator unrunnable instead of half updated (run answers invalid_parameter) */
-  if (status == qnnp_status_success) {
-    clamp->setup_valid = 1;
-  }
-  qnnp_hip_leave(token);
-  return status;
+  /* reference clamp.c:85-97 */
+  status = clamp->ukernel_type != qnnp_ukernel_type_clamp ? qnnp_status_invalid_parameter :
+      qnnp_setup_nc(clamp, "qnnp_setup_clamp_nc_u8", 1, batch_size, input, input_stride, output, output_stride);
+  return qnnp_leave_setup(clamp, token, status);
 }

@@ -25,6 +25,7 @@
 
 #include "hip/qnnp_hip.h"
 #include "indirection.h"
+#include "lifecycle.h"
 #include "log.h"
 #include "operator.h"
 #include "bias-pair.h"
@@ -328,16 +329,9 @@ static enum qnnp_status qnnp_create_convolution2d_nhwc_q8_impl(
 {
   (void) flags; /* accepted and ignored, as in the reference (convolution.c:63) */
   qnnp_operator_t op = NULL;
-  enum qnnp_status status = qnnp_status_uninitialized;
 
-  /* 1. validate. reference convolution.c:69-72 */
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_create_convolution2d_nhwc_q8 called before qnnp_initialize succeeded");
-    goto error;
-  }
-
-  /* reference convolution.c:74-115 */
-  status = qnnp_status_invalid_parameter;
+  /* 1. validate. reference convolution.c:74-115 (:69-72, the initialization, is the entry point's guard) */
+  enum qnnp_status status = qnnp_status_invalid_parameter;
   if (kernel_width == 0 || kernel_height == 0) {
     qnnp_log_error("cannot create convolution with %" PRIu32 "x%" PRIu32 " kernel: kernel dimensions may not be zero",
         kernel_width, kernel_height);
@@ -392,13 +386,27 @@ static enum qnnp_status qnnp_create_convolution2d_nhwc_q8_impl(
     goto error;
   }
 
+  /*
+   * 2. Operator-type selection. Reference convolution.c:180-189 sends 3x3 / 5x5
+   * depthwise to dwconv, unpadded stride-1 1x1 to gemm and the rest to conv.
+   * The device depthwise kernel is not limited to 9 or 25 taps, so every
+   * depthwise convolution (one input and one output channel per group) takes
+   * it; results are identical, only the kernel differs.
+   */
+  const bool any_padding =
+      (input_padding_left | input_padding_top | input_padding_right | input_padding_bottom) != 0;
+  enum qnnp_ukernel_type ukernel_type = qnnp_ukernel_type_conv;
+  if (group_input_channels == 1 && group_output_channels == 1 && groups > 1) {
+    ukernel_type = qnnp_ukernel_type_dwconv;
+  } else if (kernel_size == 1 && subsampling_height == 1 && subsampling_width == 1 && !any_padding) {
+    ukernel_type = qnnp_ukernel_type_gemm;
+  }
+
   status = qnnp_status_out_of_memory;
-  op = calloc(1, sizeof(struct qnnp_operator));
+  op = qnnp_allocate_operator(ukernel_type, NULL);
   if (op == NULL) {
-    qnnp_log_error("out of host memory: %zu bytes for qnnp_operator structure", sizeof(struct qnnp_operator));
     goto error;
   }
-  op->device = qnnp_hip_device();   /* the context this create runs in (entry point below) */
   op->input_padding_top = input_padding_top;
   op->input_padding_right = input_padding_right;
   op->input_padding_bottom = input_padding_bottom;
@@ -418,25 +426,8 @@ static enum qnnp_status qnnp_create_convolution2d_nhwc_q8_impl(
   op->requant.accumulator_bits = qnnp_accumulator_bits(bias, (size_t) groups * group_output_channels,
       kernel_size * group_input_channels);
 
-  /*
-   * 2. Operator-type selection. Reference convolution.c:180-189 sends 3x3 / 5x5
-   * depthwise to dwconv, unpadded stride-1 1x1 to gemm and the rest to conv.
-   * The device depthwise kernel is not limited to 9 or 25 taps, so every
-   * depthwise convolution (one input and one output channel per group) takes
-   * it; results are identical, only the kernel differs.
-   */
-  const bool any_padding =
-      (input_padding_left | input_padding_top | input_padding_right | input_padding_bottom) != 0;
-  if (group_input_channels == 1 && group_output_channels == 1 && groups > 1) {
-    op->ukernel_type = qnnp_ukernel_type_dwconv;
-  } else if (kernel_size == 1 && subsampling_height == 1 && subsampling_width == 1 && !any_padding) {
-    op->ukernel_type = qnnp_ukernel_type_gemm;
-  } else {
-    op->ukernel_type = qnnp_ukernel_type_conv;
-  }
-
   /* 3. / 4. the device images */
-  status = op->ukernel_type == qnnp_ukernel_type_dwconv ? pack_depthwise(op, kernel, bias) : pack_gemm(op, kernel, bias);
+  status = ukernel_type == qnnp_ukernel_type_dwconv ? pack_depthwise(op, kernel, bias) : pack_gemm(op, kernel, bias);
   if (status != qnnp_status_success) {
     goto error;
   }
@@ -463,12 +454,7 @@ static enum qnnp_status qnnp_setup_convolution2d_nhwc_q8_impl(
 {
   (void) threadpool; /* unused by the reference's setup too (convolution.c:389) */
 
-  /* reference convolution.c:391-394 */
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_setup_convolution2d_nhwc_q8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
-  }
-  if (op == NULL || op->transposed || op->kernel_height == 0 ||
+  if (op->transposed || op->kernel_height == 0 ||
       (op->ukernel_type != qnnp_ukernel_type_conv && op->ukernel_type != qnnp_ukernel_type_dwconv &&
        op->ukernel_type != qnnp_ukernel_type_gemm)) {
     return qnnp_status_invalid_parameter;   /* not a handle from qnnp_create_convolution2d_nhwc_q8 */
@@ -529,15 +515,9 @@ static enum qnnp_status qnnp_setup_convolution2d_nhwc_q8_impl(
 
   op->input_span = (batch_size * input_size - 1) * input_pixel_stride + in_channels;
   op->output_span = (batch_size * output_size - 1) * output_pixel_stride + out_channels;
-  {
-    enum qnnp_status bound = qnnp_status_success;
-    if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(input, op->input_span, &op->input_on_device, &op->d_stage_in, &op->stage_in_capacity);
-    if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(output, op->output_span, &op->output_on_device, &op->d_stage_out, &op->stage_out_capacity);
-    if (bound != qnnp_status_success) {
-      qnnp_log_error("failed to bind the tensors: device staging for host memory could not be allocated, or a tensor "
-          "lives on a different device than the operator");
-      return bound;
-    }
+  const enum qnnp_status bound = qnnp_bind_tensors(op, "qnnp_setup_convolution2d_nhwc_q8");
+  if (bound != qnnp_status_success) {
+    return bound;
   }
 
   switch (op->ukernel_type) {
@@ -590,9 +570,7 @@ static enum qnnp_status qnnp_setup_convolution2d_nhwc_q8_impl(
   }
 }
 
-/* ---- public entry points: run the implementation inside the right device context ------------------
- * create: the calling thread's selected device (qnnp_gfx950_set_device, default = the primary one) becomes the
- * operator's device; setup: the operator's device. The previous HIP device of the thread is restored on return. */
+/* ---- public entry points: the implementations above inside the device guards of lifecycle.h ---- */
 
 enum qnnp_status qnnp_create_convolution2d_nhwc_q8(
     uint32_t input_padding_top,
@@ -621,17 +599,17 @@ enum qnnp_status qnnp_create_convolution2d_nhwc_q8(
     uint32_t flags,
     qnnp_operator_t* convolution_out)
 {
-  if (!qnnp_state.initialized) {
-    return qnnp_create_convolution2d_nhwc_q8_impl(input_padding_top, input_padding_right, input_padding_bottom, input_padding_left, kernel_height, kernel_width, subsampling_height, subsampling_width, dilation_height, dilation_width, groups, group_input_channels, group_output_channels, input_zero_point, input_scale, kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max, flags, convolution_out);   /* logs and answers qnnp_status_uninitialized */
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
+  const enum qnnp_status status = qnnp_enter_create("qnnp_create_convolution2d_nhwc_q8", &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = qnnp_create_convolution2d_nhwc_q8_impl(input_padding_top, input_padding_right, input_padding_bottom, input_padding_left, kernel_height, kernel_width, subsampling_height, subsampling_width, dilation_height, dilation_width, groups, group_input_channels, group_output_channels, input_zero_point, input_scale, kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max, flags, convolution_out);
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_create(token,
+      qnnp_create_convolution2d_nhwc_q8_impl(input_padding_top, input_padding_right, input_padding_bottom,
+          input_padding_left, kernel_height, kernel_width, subsampling_height, subsampling_width, dilation_height,
+          dilation_width, groups, group_input_channels, group_output_channels, input_zero_point, input_scale,
+          kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max,
+          flags, convolution_out));
 }
 
 enum qnnp_status qnnp_setup_convolution2d_nhwc_q8(
@@ -645,20 +623,12 @@ enum qnnp_status qnnp_setup_convolution2d_nhwc_q8(
     size_t output_pixel_stride,
     pthreadpool_t threadpool)
 {
-  if (!qnnp_state.initialized || op == NULL) {
-    return qnnp_setup_convolution2d_nhwc_q8_impl(op, batch_size, input_height, input_width, input, input_pixel_stride, output, output_pixel_stride, threadpool);   /* answers qnnp_status_uninitialized / invalid_parameter */
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(op->device, qnnp_status_invalid_parameter, &token);
+  const enum qnnp_status status = qnnp_enter_setup("qnnp_setup_convolution2d_nhwc_q8", op, &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = qnnp_setup_convolution2d_nhwc_q8_impl(op, batch_size, input_height, input_width, input, input_pixel_stride, output, output_pixel_stride, threadpool);
-  /* the implementation cleared setup_valid where it began to change the operator: a failed setup leaves it
-   * unrunnable instead of half updated (run answers invalid_parameter) */
-  if (status == qnnp_status_success) {
-    op->setup_valid = 1;
-  }
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_setup(op, token,
+      qnnp_setup_convolution2d_nhwc_q8_impl(op, batch_size, input_height, input_width, input, input_pixel_stride,
+          output, output_pixel_stride, threadpool));
 }

@@ -34,6 +34,7 @@
 
 #include "hip/qnnp_hip.h"
 #include "indirection.h"
+#include "lifecycle.h"
 #include "log.h"
 #include "operator.h"
 #include "bias-pair.h"
@@ -279,16 +280,9 @@ static enum qnnp_status qnnp_create_deconvolution2d_nhwc_q8_impl(
 {
   (void) flags;
   qnnp_operator_t op = NULL;
-  enum qnnp_status status = qnnp_status_uninitialized;
 
-  /* reference deconvolution.c:69-72 */
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_create_deconvolution2d_nhwc_q8 called before qnnp_initialize succeeded");
-    goto error;
-  }
-
-  /* reference deconvolution.c:74-116 */
-  status = qnnp_status_invalid_parameter;
+  /* reference deconvolution.c:74-116 (:69-72, the initialization, is the entry point's guard) */
+  enum qnnp_status status = qnnp_status_invalid_parameter;
   if (kernel_width == 0 || kernel_height == 0) {
     qnnp_log_error("cannot create deconvolution with %" PRIu32 "x%" PRIu32 " kernel: kernel dimensions may not be zero",
         kernel_width, kernel_height);
@@ -343,12 +337,10 @@ static enum qnnp_status qnnp_create_deconvolution2d_nhwc_q8_impl(
   }
 
   status = qnnp_status_out_of_memory;
-  op = calloc(1, sizeof(struct qnnp_operator));
+  op = qnnp_allocate_operator(qnnp_ukernel_type_conv, NULL);   /* reference deconvolution.c:203 */
   if (op == NULL) {
-    qnnp_log_error("out of host memory: %zu bytes for qnnp_operator structure", sizeof(struct qnnp_operator));
     goto error;
   }
-  op->device = qnnp_hip_device();   /* the context this create runs in (entry point below) */
   op->input_padding_top = input_padding_top;
   op->input_padding_right = input_padding_right;
   op->input_padding_bottom = input_padding_bottom;
@@ -369,7 +361,6 @@ static enum qnnp_status qnnp_create_deconvolution2d_nhwc_q8_impl(
   op->requant = qnnp_compute_requant(deconvolution_scale, output_zero_point, output_min, output_max);
   op->requant.accumulator_bits = qnnp_accumulator_bits(bias, (size_t) groups * group_output_channels,
       kernel_size * group_input_channels);
-  op->ukernel_type = qnnp_ukernel_type_conv;   /* reference deconvolution.c:203 */
   op->transposed = 1;
 
   status = pack_deconvolution(op, kernel, bias);
@@ -502,12 +493,7 @@ static enum qnnp_status qnnp_setup_deconvolution2d_nhwc_q8_impl(
 {
   (void) threadpool;
 
-  /* reference deconvolution.c:225-228 */
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_setup_deconvolution2d_nhwc_q8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
-  }
-  if (op == NULL || !op->transposed) {
+  if (!op->transposed) {
     return qnnp_status_invalid_parameter;
   }
 
@@ -563,15 +549,9 @@ static enum qnnp_status qnnp_setup_deconvolution2d_nhwc_q8_impl(
 
   op->input_span = (batch_size * input_size - 1) * input_pixel_stride + in_channels;
   op->output_span = (batch_size * output_size - 1) * output_pixel_stride + out_channels;
-  {
-    enum qnnp_status bound = qnnp_status_success;
-    if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(input, op->input_span, &op->input_on_device, &op->d_stage_in, &op->stage_in_capacity);
-    if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(output, op->output_span, &op->output_on_device, &op->d_stage_out, &op->stage_out_capacity);
-    if (bound != qnnp_status_success) {
-      qnnp_log_error("failed to bind the tensors: device staging for host memory could not be allocated, or a tensor "
-          "lives on a different device than the operator");
-      return bound;
-    }
+  const enum qnnp_status bound = qnnp_bind_tensors(op, "qnnp_setup_deconvolution2d_nhwc_q8");
+  if (bound != qnnp_status_success) {
+    return bound;
   }
 
   op->variant = 1;   /* the offset-table kernel: the table, not the geometry, defines this operator */
@@ -619,9 +599,7 @@ static enum qnnp_status qnnp_setup_deconvolution2d_nhwc_q8_impl(
   return qnnp_status_success;
 }
 
-/* ---- public entry points: run the implementation inside the right device context ------------------
- * create: the calling thread's selected device (qnnp_gfx950_set_device, default = the primary one) becomes the
- * operator's device; setup: the operator's device. The previous HIP device of the thread is restored on return. */
+/* ---- public entry points: the implementations above inside the device guards of lifecycle.h ---- */
 
 enum qnnp_status qnnp_create_deconvolution2d_nhwc_q8(
     uint32_t input_padding_top,
@@ -652,17 +630,17 @@ enum qnnp_status qnnp_create_deconvolution2d_nhwc_q8(
     uint32_t flags,
     qnnp_operator_t* deconvolution_out)
 {
-  if (!qnnp_state.initialized) {
-    return qnnp_create_deconvolution2d_nhwc_q8_impl(input_padding_top, input_padding_right, input_padding_bottom, input_padding_left, adjustment_height, adjustment_width, kernel_height, kernel_width, stride_height, stride_width, dilation_height, dilation_width, groups, group_input_channels, group_output_channels, input_zero_point, input_scale, kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max, flags, deconvolution_out);   /* logs and answers qnnp_status_uninitialized */
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
+  const enum qnnp_status status = qnnp_enter_create("qnnp_create_deconvolution2d_nhwc_q8", &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = qnnp_create_deconvolution2d_nhwc_q8_impl(input_padding_top, input_padding_right, input_padding_bottom, input_padding_left, adjustment_height, adjustment_width, kernel_height, kernel_width, stride_height, stride_width, dilation_height, dilation_width, groups, group_input_channels, group_output_channels, input_zero_point, input_scale, kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max, flags, deconvolution_out);
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_create(token,
+      qnnp_create_deconvolution2d_nhwc_q8_impl(input_padding_top, input_padding_right, input_padding_bottom,
+          input_padding_left, adjustment_height, adjustment_width, kernel_height, kernel_width, stride_height,
+          stride_width, dilation_height, dilation_width, groups, group_input_channels, group_output_channels,
+          input_zero_point, input_scale, kernel_zero_point, kernel_scale, kernel, bias, output_zero_point,
+          output_scale, output_min, output_max, flags, deconvolution_out));
 }
 
 enum qnnp_status qnnp_setup_deconvolution2d_nhwc_q8(
@@ -676,20 +654,12 @@ enum qnnp_status qnnp_setup_deconvolution2d_nhwc_q8(
     size_t output_pixel_stride,
     pthreadpool_t threadpool)
 {
-  if (!qnnp_state.initialized || op == NULL) {
-    return qnnp_setup_deconvolution2d_nhwc_q8_impl(op, batch_size, input_height, input_width, input, input_pixel_stride, output, output_pixel_stride, threadpool);   /* answers qnnp_status_uninitialized / invalid_parameter */
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(op->device, qnnp_status_invalid_parameter, &token);
+  const enum qnnp_status status = qnnp_enter_setup("qnnp_setup_deconvolution2d_nhwc_q8", op, &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = qnnp_setup_deconvolution2d_nhwc_q8_impl(op, batch_size, input_height, input_width, input, input_pixel_stride, output, output_pixel_stride, threadpool);
-  /* the implementation cleared setup_valid where it began to change the operator: a failed setup leaves it
-   * unrunnable instead of half updated (run answers invalid_parameter) */
-  if (status == qnnp_status_success) {
-    op->setup_valid = 1;
-  }
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_setup(op, token,
+      qnnp_setup_deconvolution2d_nhwc_q8_impl(op, batch_size, input_height, input_width, input, input_pixel_stride,
+          output, output_pixel_stride, threadpool));
 }

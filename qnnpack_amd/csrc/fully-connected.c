@@ -16,6 +16,7 @@
 #include <qnnpack.h>
 
 #include "hip/qnnp_hip.h"
+#include "lifecycle.h"
 #include "log.h"
 #include "operator.h"
 #include "bias-pair.h"
@@ -48,16 +49,9 @@ static enum qnnp_status qnnp_create_fully_connected_nc_q8_impl(
   qnnp_operator_t op = NULL;
   int8_t* host_weights = NULL;
   int32_t* host_bias = NULL;
-  enum qnnp_status status = qnnp_status_uninitialized;
 
-  /* reference fully-connected.c:44-47 */
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_create_fully_connected_nc_q8 called before qnnp_initialize succeeded");
-    goto error;
-  }
-
-  /* reference fully-connected.c:49-67 */
-  status = qnnp_status_invalid_parameter;
+  /* reference fully-connected.c:49-67 (:44-47, the initialization, is the entry point's guard) */
+  enum qnnp_status status = qnnp_status_invalid_parameter;
   if (!scale_is_valid(input_scale)) {
     qnnp_log_error("cannot create fully connected operator with %.7g input scale: a scale has to be a finite number above zero", input_scale);
     goto error;
@@ -95,10 +89,8 @@ static enum qnnp_status qnnp_create_fully_connected_nc_q8_impl(
   }
 
   status = qnnp_status_out_of_memory;
-  op = calloc(1, sizeof(struct qnnp_operator));
-  if (op != NULL) op->device = qnnp_hip_device();   /* the context this create runs in (entry point below) */
+  op = qnnp_allocate_operator(qnnp_ukernel_type_gemm, NULL);
   if (op == NULL) {
-    qnnp_log_error("out of host memory: %zu bytes for qnnp_operator structure", sizeof(struct qnnp_operator));
     goto error;
   }
 
@@ -166,7 +158,6 @@ static enum qnnp_status qnnp_create_fully_connected_nc_q8_impl(
   op->kernel_zero_point = kernel_zero_point;
   op->requant = qnnp_compute_requant(requantization_scale, output_zero_point, output_min, output_max);
   op->requant.accumulator_bits = qnnp_accumulator_bits(bias, output_channels, input_channels);
-  op->ukernel_type = qnnp_ukernel_type_gemm;
 
   *fully_connected_out = op;
   return qnnp_status_success;
@@ -186,12 +177,7 @@ static enum qnnp_status qnnp_setup_fully_connected_nc_q8_impl(
     uint8_t* output,
     size_t output_stride)
 {
-  /* reference fully-connected.c:139-142 */
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_setup_fully_connected_nc_q8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
-  }
-  if (op == NULL || op->ukernel_type != qnnp_ukernel_type_gemm || op->transposed || op->group_input_channels == 0) {
+  if (op->ukernel_type != qnnp_ukernel_type_gemm || op->transposed || op->group_input_channels == 0) {
     return qnnp_status_invalid_parameter;   /* not a handle from a fully connected / 1x1 create */
   }
 
@@ -226,22 +212,15 @@ static enum qnnp_status qnnp_setup_fully_connected_nc_q8_impl(
 
   op->input_span = (batch_size - 1) * input_stride + op->group_input_channels;
   op->output_span = (batch_size - 1) * output_stride + op->group_output_channels;
-  {
-    enum qnnp_status bound = qnnp_bind_endpoint(input, op->input_span, &op->input_on_device, &op->d_stage_in, &op->stage_in_capacity);
-    if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(output, op->output_span, &op->output_on_device, &op->d_stage_out, &op->stage_out_capacity);
-    if (bound != qnnp_status_success) {
-      qnnp_log_error("failed to bind the tensors: device staging for host memory could not be allocated, or a tensor "
-          "lives on a different device than the operator");
-      return bound;
-    }
+  const enum qnnp_status bound = qnnp_bind_tensors(op, "qnnp_setup_fully_connected_nc_q8");
+  if (bound != qnnp_status_success) {
+    return bound;
   }
   op->variant = qnnp_state.opt_gemm_kernel;
   return qnnp_status_success;
 }
 
-/* ---- public entry points: run the implementation inside the right device context ------------------
- * create: the calling thread's selected device (qnnp_gfx950_set_device, default = the primary one) becomes the
- * operator's device; setup: the operator's device. The previous HIP device of the thread is restored on return. */
+/* ---- public entry points: the implementations above inside the device guards of lifecycle.h ---- */
 
 enum qnnp_status qnnp_create_fully_connected_nc_q8(
     size_t input_channels,
@@ -259,17 +238,15 @@ enum qnnp_status qnnp_create_fully_connected_nc_q8(
     uint32_t flags,
     qnnp_operator_t* fully_connected_out)
 {
-  if (!qnnp_state.initialized) {
-    return qnnp_create_fully_connected_nc_q8_impl(input_channels, output_channels, input_zero_point, input_scale, kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max, flags, fully_connected_out);   /* logs and answers qnnp_status_uninitialized */
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
+  const enum qnnp_status status = qnnp_enter_create("qnnp_create_fully_connected_nc_q8", &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = qnnp_create_fully_connected_nc_q8_impl(input_channels, output_channels, input_zero_point, input_scale, kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max, flags, fully_connected_out);
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_create(token,
+      qnnp_create_fully_connected_nc_q8_impl(input_channels, output_channels, input_zero_point, input_scale,
+          kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max,
+          flags, fully_connected_out));
 }
 
 enum qnnp_status qnnp_setup_fully_connected_nc_q8(
@@ -280,20 +257,11 @@ enum qnnp_status qnnp_setup_fully_connected_nc_q8(
     uint8_t* output,
     size_t output_stride)
 {
-  if (!qnnp_state.initialized || op == NULL) {
-    return qnnp_setup_fully_connected_nc_q8_impl(op, batch_size, input, input_stride, output, output_stride);   /* answers qnnp_status_uninitialized / invalid_parameter */
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(op->device, qnnp_status_invalid_parameter, &token);
+  const enum qnnp_status status = qnnp_enter_setup("qnnp_setup_fully_connected_nc_q8", op, &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = qnnp_setup_fully_connected_nc_q8_impl(op, batch_size, input, input_stride, output, output_stride);
-  /* the implementation cleared setup_valid where it began to change the operator: a failed setup leaves it
-   * unrunnable instead of half updated (run answers invalid_parameter) */
-  if (status == qnnp_status_success) {
-    op->setup_valid = 1;
-  }
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_setup(op, token,
+      qnnp_setup_fully_connected_nc_q8_impl(op, batch_size, input, input_stride, output, output_stride));
 }

@@ -19,6 +19,7 @@
 #include <qnnpack_gfx950.h>
 
 #include "hip/qnnp_hip.h"
+#include "lifecycle.h"
 #include "log.h"
 #include "operator.h"
 #include "pack.h"
@@ -218,10 +219,6 @@ static enum qnnp_status qnnp_gfx950_create_fused_block_impl(
     qnnp_operator_t expand, qnnp_operator_t depthwise, qnnp_operator_t project, qnnp_operator_t residual_add,
     qnnp_operator_t* fused_out)
 {
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_gfx950_create_fused_block called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
-  }
   if (depthwise == NULL || project == NULL || fused_out == NULL) {
     return qnnp_status_invalid_parameter;
   }
@@ -249,18 +246,16 @@ static enum qnnp_status qnnp_gfx950_create_fused_block_impl(
     qnnp_log_error("cannot create fused block: the operators live on different devices");
     return qnnp_status_invalid_parameter;
   }
-  qnnp_operator_t op = calloc(1, sizeof(struct qnnp_operator));
-  if (op != NULL) op->device = depthwise->device;   /* it borrows their device images */
+  qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_fused_block, NULL);
   if (op == NULL) {
-    qnnp_log_error("out of host memory: %zu bytes for qnnp_operator structure", sizeof(struct qnnp_operator));
     return qnnp_status_out_of_memory;
   }
+  op->device = depthwise->device;   /* not the calling thread's: it borrows their device images */
   op->fused_expand = expand;
   op->fused_depthwise = depthwise;
   op->fused_project = project;
   op->fused_add = residual_add;
   op->channels = project->group_output_channels;
-  op->ukernel_type = qnnp_ukernel_type_fused_block;
   build_strip_images(op);                       /* (optional: without them the tile kernel is all the block has) */
   *fused_out = op;
   return qnnp_status_success;
@@ -270,10 +265,7 @@ static enum qnnp_status qnnp_gfx950_setup_fused_block_impl(
     qnnp_operator_t op, size_t batch_size, size_t input_height, size_t input_width,
     const uint8_t* input, size_t input_stride, uint8_t* output, size_t output_stride)
 {
-  if (!qnnp_state.initialized) {
-    return qnnp_status_uninitialized;
-  }
-  if (op == NULL || op->ukernel_type != qnnp_ukernel_type_fused_block) {
+  if (op->ukernel_type != qnnp_ukernel_type_fused_block) {
     return qnnp_status_invalid_parameter;
   }
   if (batch_size == 0) {
@@ -306,15 +298,9 @@ static enum qnnp_status qnnp_gfx950_setup_fused_block_impl(
   }
   op->input_span = (in_pixels - 1) * input_stride + cin;
   op->output_span = (out_pixels - 1) * output_stride + cout;
-  {
-    enum qnnp_status bound = qnnp_status_success;
-    if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(input, op->input_span, &op->input_on_device, &op->d_stage_in, &op->stage_in_capacity);
-    if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(output, op->output_span, &op->output_on_device, &op->d_stage_out, &op->stage_out_capacity);
-    if (bound != qnnp_status_success) {
-      qnnp_log_error("failed to bind the tensors: device staging for host memory could not be allocated, or a tensor "
-          "lives on a different device than the operator");
-      return bound;
-    }
+  const enum qnnp_status bound = qnnp_bind_tensors(op, "qnnp_gfx950_setup_fused_block");
+  if (bound != qnnp_status_success) {
+    return bound;
   }
   /* does a kernel take this block (LDS plan, channel multiples, alignment)? The strip kernel first. */
   const void* in_dev = op->input_on_device ? input : op->d_stage_in;
@@ -348,50 +334,40 @@ int qnnp_fused_block_launch(struct qnnp_operator* op, const void* input, void* o
   return qnnp_hip_fused_block_run(&args, &op->kernel_name);
 }
 
-/* ---- public entry points: run the implementation inside the right device context ------------------
- * create: the device of the member operators (the block's own device images live beside theirs, whatever device the
- * calling thread has selected); setup: the operator's device. The previous HIP device of the thread is restored on return. */
+/* ---- public entry points: the implementations above inside the device guards of lifecycle.h ---- */
 
 enum qnnp_status qnnp_gfx950_create_fused_block(
     qnnp_operator_t expand, qnnp_operator_t depthwise, qnnp_operator_t project, qnnp_operator_t residual_add,
     qnnp_operator_t* fused_out)
 {
-  if (!qnnp_state.initialized) {
-    return qnnp_gfx950_create_fused_block_impl(expand, depthwise, project, residual_add, fused_out);   /* logs and answers qnnp_status_uninitialized */
+  enum qnnp_status status = qnnp_check_initialized("qnnp_gfx950_create_fused_block");
+  if (status != qnnp_status_success) {
+    return status;
   }
   /* The block borrows its members' device images and adds its own (build_strip_images: alloc + upload), so everything
    * device-side must happen on THEIR device -- not on whichever one the calling thread has selected. Members on
    * different devices are refused by the implementation; a NULL depthwise as well. */
   int token;
-  enum qnnp_status status = depthwise != NULL ?
+  status = depthwise != NULL ?
       qnnp_enter_for_update(depthwise->device, qnnp_status_invalid_parameter, &token) :
       qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = qnnp_gfx950_create_fused_block_impl(expand, depthwise, project, residual_add, fused_out);
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_create(token,
+      qnnp_gfx950_create_fused_block_impl(expand, depthwise, project, residual_add, fused_out));
 }
 
 enum qnnp_status qnnp_gfx950_setup_fused_block(
     qnnp_operator_t op, size_t batch_size, size_t input_height, size_t input_width,
     const uint8_t* input, size_t input_stride, uint8_t* output, size_t output_stride)
 {
-  if (!qnnp_state.initialized || op == NULL) {
-    return qnnp_gfx950_setup_fused_block_impl(op, batch_size, input_height, input_width, input, input_stride, output, output_stride);   /* answers qnnp_status_uninitialized / invalid_parameter */
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(op->device, qnnp_status_invalid_parameter, &token);
+  const enum qnnp_status status = qnnp_enter_setup("qnnp_gfx950_setup_fused_block", op, &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = qnnp_gfx950_setup_fused_block_impl(op, batch_size, input_height, input_width, input, input_stride, output, output_stride);
-  /* the implementation cleared setup_valid where it began to change the operator: a failed setup leaves it
-   * unrunnable instead of half updated (run answers invalid_parameter) */
-  if (status == qnnp_status_success) {
-    op->setup_valid = 1;
-  }
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_setup(op, token,
+      qnnp_gfx950_setup_fused_block_impl(op, batch_size, input_height, input_width, input, input_stride, output,
+          output_stride));
 }

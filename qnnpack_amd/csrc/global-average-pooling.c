@@ -13,16 +13,15 @@
 #include <stdbool.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <qnnpack.h>
 
 #include "hip/qnnp_hip.h"
+#include "lifecycle.h"
 #include "log.h"
 #include "operator.h"
 #include "requantization.h"
-#include "state.h"
 
 static inline bool scale_is_valid(float scale)
 {
@@ -41,11 +40,6 @@ static enum qnnp_status qnnp_create_global_average_pooling_nwc_q8_impl(
     qnnp_operator_t* global_average_pooling_out)
 {
   (void) flags;
-  /* reference global-average-pooling.c:34-37 */
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_create_global_average_pooling_nwc_q8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
-  }
   /* reference global-average-pooling.c:39-59 */
   if (channels == 0) {
     qnnp_log_error("cannot create global average pooling operator with %zu channels: number of channels may not be zero",
@@ -75,10 +69,8 @@ static enum qnnp_status qnnp_create_global_average_pooling_nwc_q8_impl(
     return qnnp_status_unsupported_parameter;
   }
 
-  qnnp_operator_t op = calloc(1, sizeof(struct qnnp_operator));
-  if (op != NULL) op->device = qnnp_hip_device();   /* the context this create runs in (entry point below) */
+  qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_global_average_pooling, NULL);
   if (op == NULL) {
-    qnnp_log_error("out of host memory: %zu bytes for qnnp_operator structure", sizeof(struct qnnp_operator));
     return qnnp_status_out_of_memory;
   }
   op->channels = channels;
@@ -88,7 +80,6 @@ static enum qnnp_status qnnp_create_global_average_pooling_nwc_q8_impl(
   op->output_scale = output_scale;
   op->output_min = output_min;
   op->output_max = output_max;
-  op->ukernel_type = qnnp_ukernel_type_global_average_pooling;
   *global_average_pooling_out = op;
   return qnnp_status_success;
 }
@@ -102,12 +93,7 @@ static enum qnnp_status qnnp_setup_global_average_pooling_nwc_q8_impl(
     uint8_t* output,
     size_t output_stride)
 {
-  /* reference global-average-pooling.c:118-121 */
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_setup_global_average_pooling_nwc_q8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
-  }
-  if (op == NULL || op->ukernel_type != qnnp_ukernel_type_global_average_pooling) {
+  if (op->ukernel_type != qnnp_ukernel_type_global_average_pooling) {
     return qnnp_status_invalid_parameter;
   }
   /* reference global-average-pooling.c:123-126 */
@@ -147,22 +133,10 @@ static enum qnnp_status qnnp_setup_global_average_pooling_nwc_q8_impl(
 
   op->input_span = (batch_size * width - 1) * input_stride + channels;
   op->output_span = (batch_size - 1) * output_stride + channels;
-  {
-    enum qnnp_status bound = qnnp_status_success;
-    if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(input, op->input_span, &op->input_on_device, &op->d_stage_in, &op->stage_in_capacity);
-    if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(output, op->output_span, &op->output_on_device, &op->d_stage_out, &op->stage_out_capacity);
-    if (bound != qnnp_status_success) {
-      qnnp_log_error("failed to bind the tensors: device staging for host memory could not be allocated, or a tensor "
-          "lives on a different device than the operator");
-      return bound;
-    }
-  }
-  return qnnp_status_success;
+  return qnnp_bind_tensors(op, "qnnp_setup_global_average_pooling_nwc_q8");
 }
 
-/* ---- public entry points: run the implementation inside the right device context ------------------
- * create: the calling thread's selected device (qnnp_gfx950_set_device, default = the primary one) becomes the
- * operator's device; setup: the operator's device. The previous HIP device of the thread is restored on return. */
+/* ---- public entry points: the implementations above inside the device guards of lifecycle.h ---- */
 
 enum qnnp_status qnnp_create_global_average_pooling_nwc_q8(
     size_t channels,
@@ -175,17 +149,14 @@ enum qnnp_status qnnp_create_global_average_pooling_nwc_q8(
     uint32_t flags,
     qnnp_operator_t* global_average_pooling_out)
 {
-  if (!qnnp_state.initialized) {
-    return qnnp_create_global_average_pooling_nwc_q8_impl(channels, input_zero_point, input_scale, output_zero_point, output_scale, output_min, output_max, flags, global_average_pooling_out);   /* logs and answers qnnp_status_uninitialized */
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
+  const enum qnnp_status status = qnnp_enter_create("qnnp_create_global_average_pooling_nwc_q8", &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = qnnp_create_global_average_pooling_nwc_q8_impl(channels, input_zero_point, input_scale, output_zero_point, output_scale, output_min, output_max, flags, global_average_pooling_out);
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_create(token,
+      qnnp_create_global_average_pooling_nwc_q8_impl(channels, input_zero_point, input_scale, output_zero_point,
+          output_scale, output_min, output_max, flags, global_average_pooling_out));
 }
 
 enum qnnp_status qnnp_setup_global_average_pooling_nwc_q8(
@@ -197,20 +168,12 @@ enum qnnp_status qnnp_setup_global_average_pooling_nwc_q8(
     uint8_t* output,
     size_t output_stride)
 {
-  if (!qnnp_state.initialized || op == NULL) {
-    return qnnp_setup_global_average_pooling_nwc_q8_impl(op, batch_size, width, input, input_stride, output, output_stride);   /* answers qnnp_status_uninitialized / invalid_parameter */
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(op->device, qnnp_status_invalid_parameter, &token);
+  const enum qnnp_status status = qnnp_enter_setup("qnnp_setup_global_average_pooling_nwc_q8", op, &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = qnnp_setup_global_average_pooling_nwc_q8_impl(op, batch_size, width, input, input_stride, output, output_stride);
-  /* the implementation cleared setup_valid where it began to change the operator: a failed setup leaves it
-   * unrunnable instead of half updated (run answers invalid_parameter) */
-  if (status == qnnp_status_success) {
-    op->setup_valid = 1;
-  }
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_setup(op, token,
+      qnnp_setup_global_average_pooling_nwc_q8_impl(op, batch_size, width, input, input_stride, output,
+          output_stride));
 }

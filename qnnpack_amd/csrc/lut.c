@@ -24,10 +24,10 @@
 #include <qnnpack_gfx950.h>
 
 #include "hip/qnnp_hip.h"
+#include "lifecycle.h"
 #include "log.h"
 #include "lut.h"
 #include "operator.h"
-#include "state.h"
 #include "upload.h"
 
 static int launch_lut(struct qnnp_operator* op, const void* input, void* output)
@@ -58,91 +58,34 @@ enum qnnp_status qnnp_create_lut_operator(const char* what, size_t channels, con
     return status;
   }
   status = qnnp_status_out_of_memory;
-  qnnp_operator_t op = calloc(1, sizeof(struct qnnp_operator));
-  if (op == NULL) {
-    qnnp_log_error("out of host memory: %zu bytes for qnnp_operator structure", sizeof(struct qnnp_operator));
-  } else {
-    op->device = qnnp_hip_device();   /* the context this create runs in */
+  qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_lut, launch_lut);
+  if (op != NULL) {
     op->d_weights = qnnp_upload(table, 256);
     if (op->d_weights == NULL) {
       qnnp_log_error("failed to place the 256-byte table of the %s operator on the device", what);
       free(op);
     } else {
       op->channels = channels;
-      op->ukernel_type = qnnp_ukernel_type_lut;
-      op->launch_hook = launch_lut;
       *lut_out = op;
       status = qnnp_status_success;
     }
   }
-  qnnp_hip_leave(token);
-  return status;
-}
-
-static enum qnnp_status setup_lut(const char* what, qnnp_operator_t op, size_t batch_size, const uint8_t* input,
-                                  size_t input_stride, uint8_t* output, size_t output_stride)
-{
-  /* reference sigmoid.c:138-141, leaky-relu.c:145-148 */
-  if (batch_size == 0) {
-    op->batch_size = 0;
-    return qnnp_status_success;
-  }
-  const size_t channels = op->channels;
-  if (input == NULL || output == NULL || input_stride < channels || output_stride < channels) {
-    qnnp_log_error("%s: NULL tensor or pixel stride smaller than the channel count", what);
-    return qnnp_status_invalid_parameter;
-  }
-  if (batch_size > (size_t) INT32_MAX) {
-    qnnp_log_error("%s with batch %zu: outside the device kernel's index range", what, batch_size);
-    return qnnp_status_unsupported_parameter;
-  }
-  const size_t input_span = (batch_size - 1) * input_stride + channels;
-  const size_t output_span = (batch_size - 1) * output_stride + channels;
-  const int in_place = (const void*) input == (const void*) output && input_stride == output_stride;
-  if (!in_place && qnnp_spans_overlap(input, input_span, output, output_span)) {
-    qnnp_log_error("%s: the input and output tensors overlap without being the same tensor", what);
-    return qnnp_status_invalid_parameter;
-  }
-
-  op->setup_valid = 0;   /* until every check and allocation below has succeeded */
-  op->batch_size = batch_size;
-  op->input = input;
-  op->input_pixel_stride = input_stride;
-  op->output = output;
-  op->output_pixel_stride = output_stride;
-  op->input_span = input_span;
-  op->output_span = output_span;
-  enum qnnp_status bound = qnnp_bind_endpoint(input, op->input_span, &op->input_on_device, &op->d_stage_in, &op->stage_in_capacity);
-  if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(output, op->output_span, &op->output_on_device, &op->d_stage_out, &op->stage_out_capacity);
-  if (bound != qnnp_status_success) {
-    qnnp_log_error("%s: failed to bind the tensors: device staging for host memory could not be allocated, or a tensor "
-        "lives on a different device than the operator", what);
-  }
-  return bound;
+  return qnnp_leave_create(token, status);
 }
 
 enum qnnp_status qnnp_setup_lut_operator(const char* what, qnnp_operator_t lut, size_t batch_size, const uint8_t* input,
                                          size_t input_stride, uint8_t* output, size_t output_stride)
 {
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("%s called before qnnp_initialize succeeded", what);
-    return qnnp_status_uninitialized;
-  }
-  if (lut == NULL || lut->ukernel_type != qnnp_ukernel_type_lut) {
-    return qnnp_status_invalid_parameter;
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(lut->device, qnnp_status_invalid_parameter, &token);
+  /* reference sigmoid.c:133-136, leaky-relu.c:140-143 */
+  enum qnnp_status status = qnnp_enter_setup(what, lut, &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = setup_lut(what, lut, batch_size, input, input_stride, output, output_stride);
-  /* a failed setup leaves the operator unrunnable instead of half updated (run answers invalid_parameter) */
-  if (status == qnnp_status_success) {
-    lut->setup_valid = 1;
-  }
-  qnnp_hip_leave(token);
-  return status;
+  /* reference sigmoid.c:138-150, leaky-relu.c:145-157 */
+  status = lut->ukernel_type != qnnp_ukernel_type_lut ? qnnp_status_invalid_parameter :
+      qnnp_setup_nc(lut, what, 1, batch_size, input, input_stride, output, output_stride);
+  return qnnp_leave_setup(lut, token, status);
 }
 
 /* ---- the generic operator: any 256-byte table ---- */
@@ -150,9 +93,9 @@ enum qnnp_status qnnp_setup_lut_operator(const char* what, qnnp_operator_t lut, 
 enum qnnp_status qnnp_gfx950_create_lut_nc_x8(size_t channels, const uint8_t table[256], uint32_t flags, qnnp_operator_t* lut)
 {
   (void) flags;
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_gfx950_create_lut_nc_x8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
+  const enum qnnp_status status = qnnp_check_initialized("qnnp_gfx950_create_lut_nc_x8");
+  if (status != qnnp_status_success) {
+    return status;
   }
   if (channels == 0) {
     qnnp_log_error("cannot create lookup table operator with %zu channels: number of channels must be non-zero", channels);

@@ -17,14 +17,13 @@
 #include <inttypes.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <qnnpack.h>
 
 #include "hip/qnnp_hip.h"
+#include "lifecycle.h"
 #include "log.h"
 #include "operator.h"
-#include "state.h"
 
 static int launch_max_pooling(struct qnnp_operator* op, const void* input, void* output)
 {
@@ -72,11 +71,6 @@ static enum qnnp_status qnnp_create_max_pooling2d_nhwc_u8_impl(
     qnnp_operator_t* max_pooling_out)
 {
   (void) flags;
-  /* reference max-pooling.c:56-59 */
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_create_max_pooling2d_nhwc_u8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
-  }
   /* reference max-pooling.c:61-103 (the pooling size is a 32-bit product there too) */
   const uint32_t pooling_size = pooling_height * pooling_width;
   if (pooling_size == 0) {
@@ -108,12 +102,10 @@ static enum qnnp_status qnnp_create_max_pooling2d_nhwc_u8_impl(
     return qnnp_status_unsupported_parameter;
   }
 
-  qnnp_operator_t op = calloc(1, sizeof(struct qnnp_operator));
+  qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_max_pooling, launch_max_pooling);
   if (op == NULL) {
-    qnnp_log_error("out of host memory: %zu bytes for qnnp_operator structure", sizeof(struct qnnp_operator));
     return qnnp_status_out_of_memory;
   }
-  op->device = qnnp_hip_device();   /* the context this create runs in (entry point below) */
   op->input_padding_top = input_padding_top;
   op->input_padding_right = input_padding_right;
   op->input_padding_bottom = input_padding_bottom;
@@ -127,8 +119,6 @@ static enum qnnp_status qnnp_create_max_pooling2d_nhwc_u8_impl(
   op->channels = channels;
   op->output_min = output_min;
   op->output_max = output_max;
-  op->ukernel_type = qnnp_ukernel_type_max_pooling;
-  op->launch_hook = launch_max_pooling;
   *max_pooling_out = op;
   return qnnp_status_success;
 }
@@ -143,12 +133,7 @@ static enum qnnp_status qnnp_setup_max_pooling2d_nhwc_u8_impl(
     uint8_t* output,
     size_t output_pixel_stride)
 {
-  /* reference max-pooling.c:148-151 */
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_setup_max_pooling2d_nhwc_u8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
-  }
-  if (op == NULL || op->ukernel_type != qnnp_ukernel_type_max_pooling) {
+  if (op->ukernel_type != qnnp_ukernel_type_max_pooling) {
     return qnnp_status_invalid_parameter;
   }
   /* reference max-pooling.c:153-156 */
@@ -200,16 +185,10 @@ static enum qnnp_status qnnp_setup_max_pooling2d_nhwc_u8_impl(
 
   op->input_span = (batch_size * input_height * input_width - 1) * input_pixel_stride + channels;
   op->output_span = (batch_size * op->output_height * op->output_width - 1) * output_pixel_stride + channels;
-  enum qnnp_status bound = qnnp_bind_endpoint(input, op->input_span, &op->input_on_device, &op->d_stage_in, &op->stage_in_capacity);
-  if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(output, op->output_span, &op->output_on_device, &op->d_stage_out, &op->stage_out_capacity);
-  if (bound != qnnp_status_success) {
-    qnnp_log_error("failed to bind the tensors: device staging for host memory could not be allocated, or a tensor "
-        "lives on a different device than the operator");
-  }
-  return bound;
+  return qnnp_bind_tensors(op, "qnnp_setup_max_pooling2d_nhwc_u8");
 }
 
-/* ---- public entry points: run the implementation inside the right device context (as global-average-pooling.c) ---- */
+/* ---- public entry points: the implementations above inside the device guards of lifecycle.h ---- */
 
 enum qnnp_status qnnp_create_max_pooling2d_nhwc_u8(
     uint32_t input_padding_top,
@@ -228,21 +207,15 @@ enum qnnp_status qnnp_create_max_pooling2d_nhwc_u8(
     uint32_t flags,
     qnnp_operator_t* max_pooling)
 {
-  if (!qnnp_state.initialized) {
-    return qnnp_create_max_pooling2d_nhwc_u8_impl(input_padding_top, input_padding_right, input_padding_bottom,
-        input_padding_left, pooling_height, pooling_width, stride_height, stride_width, dilation_height, dilation_width,
-        channels, output_min, output_max, flags, max_pooling);   /* logs and answers qnnp_status_uninitialized */
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
+  const enum qnnp_status status = qnnp_enter_create("qnnp_create_max_pooling2d_nhwc_u8", &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = qnnp_create_max_pooling2d_nhwc_u8_impl(input_padding_top, input_padding_right,
-      input_padding_bottom, input_padding_left, pooling_height, pooling_width, stride_height, stride_width,
-      dilation_height, dilation_width, channels, output_min, output_max, flags, max_pooling);
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_create(token,
+      qnnp_create_max_pooling2d_nhwc_u8_impl(input_padding_top, input_padding_right, input_padding_bottom,
+          input_padding_left, pooling_height, pooling_width, stride_height, stride_width, dilation_height,
+          dilation_width, channels, output_min, output_max, flags, max_pooling));
 }
 
 enum qnnp_status qnnp_setup_max_pooling2d_nhwc_u8(
@@ -257,21 +230,12 @@ enum qnnp_status qnnp_setup_max_pooling2d_nhwc_u8(
     pthreadpool_t threadpool)
 {
   (void) threadpool;
-  if (!qnnp_state.initialized || max_pooling == NULL) {
-    return qnnp_setup_max_pooling2d_nhwc_u8_impl(max_pooling, batch_size, input_height, input_width, input, input_stride,
-        output, output_stride);   /* answers qnnp_status_uninitialized / invalid_parameter */
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(max_pooling->device, qnnp_status_invalid_parameter, &token);
+  const enum qnnp_status status = qnnp_enter_setup("qnnp_setup_max_pooling2d_nhwc_u8", max_pooling, &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = qnnp_setup_max_pooling2d_nhwc_u8_impl(max_pooling, batch_size, input_height,
-      input_width, input, input_stride, output, output_stride);
-  /* a failed setup leaves the operator unrunnable instead of half updated (run answers invalid_parameter) */
-  if (status == qnnp_status_success) {
-    max_pooling->setup_valid = 1;
-  }
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_setup(max_pooling, token,
+      qnnp_setup_max_pooling2d_nhwc_u8_impl(max_pooling, batch_size, input_height, input_width, input, input_stride,
+          output, output_stride));
 }

@@ -19,16 +19,15 @@
 #include <stdbool.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <qnnpack.h>
 #include <qnnpack_gfx950.h>
 
 #include "hip/qnnp_hip.h"
+#include "lifecycle.h"
 #include "log.h"
 #include "operator.h"
 #include "requantization.h"
-#include "state.h"
 
 static inline bool scale_is_valid(float scale)
 {
@@ -69,9 +68,9 @@ enum qnnp_status qnnp_gfx950_create_multiply_nc_q8(
     qnnp_operator_t* multiply)
 {
   (void) flags;
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_gfx950_create_multiply_nc_q8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
+  enum qnnp_status status = qnnp_check_initialized("qnnp_gfx950_create_multiply_nc_q8");
+  if (status != qnnp_status_success) {
+    return status;
   }
   if (channels == 0) {
     qnnp_log_error("cannot create multiply operator with %zu channels: number of channels may not be zero", channels);
@@ -109,34 +108,32 @@ enum qnnp_status qnnp_gfx950_create_multiply_nc_q8(
   }
 
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
+  status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  qnnp_operator_t op = calloc(1, sizeof(struct qnnp_operator));
+  qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_multiply, launch_multiply);
   if (op == NULL) {
-    qnnp_log_error("out of host memory: %zu bytes for qnnp_operator structure", sizeof(struct qnnp_operator));
     status = qnnp_status_out_of_memory;
   } else {
-    op->device = qnnp_hip_device();   /* the context this create runs in */
     op->channels = channels;
     op->mul_a_zero_point = a_zero_point;
     op->mul_b_zero_point = b_zero_point;
     op->requant = qnnp_compute_requant(ratio, product_zero_point, product_min, product_max);
     /* one product, no bias: |acc| <= 65025 < 2^16 */
     op->requant.accumulator_bits = qnnp_accumulator_bits(NULL, 0, 1);
-    op->ukernel_type = qnnp_ukernel_type_multiply;
-    op->launch_hook = launch_multiply;
     *multiply = op;
   }
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_create(token, status);
 }
 
 static enum qnnp_status setup_multiply(
     qnnp_operator_t op, size_t b_rows, size_t a_rows_per_b_row, const uint8_t* a, size_t a_stride,
     const uint8_t* b, size_t b_stride, uint8_t* product, size_t product_stride)
 {
+  if (op->ukernel_type != qnnp_ukernel_type_multiply) {
+    return qnnp_status_invalid_parameter;
+  }
   if (b_rows == 0 || a_rows_per_b_row == 0) {
     op->batch_size = 0;
     return qnnp_status_success;
@@ -184,14 +181,7 @@ static enum qnnp_status setup_multiply(
   op->input_span = a_span;
   op->input2_span = b_span;
   op->output_span = product_span;
-  enum qnnp_status bound = qnnp_bind_endpoint(a, a_span, &op->input_on_device, &op->d_stage_in, &op->stage_in_capacity);
-  if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(b, b_span, &op->input2_on_device, &op->d_stage_in2, &op->stage_in2_capacity);
-  if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(product, product_span, &op->output_on_device, &op->d_stage_out, &op->stage_out_capacity);
-  if (bound != qnnp_status_success) {
-    qnnp_log_error("cannot set up multiply operator: failed to bind the tensors: device staging for host memory could "
-        "not be allocated, or a tensor lives on a different device than the operator");
-  }
-  return bound;
+  return qnnp_bind_tensors(op, "qnnp_gfx950_setup_multiply_nc_q8");
 }
 
 enum qnnp_status qnnp_gfx950_setup_multiply_nc_q8(
@@ -205,23 +195,11 @@ enum qnnp_status qnnp_gfx950_setup_multiply_nc_q8(
     uint8_t* product,
     size_t product_stride)
 {
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_gfx950_setup_multiply_nc_q8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
-  }
-  if (multiply == NULL || multiply->ukernel_type != qnnp_ukernel_type_multiply) {
-    return qnnp_status_invalid_parameter;
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(multiply->device, qnnp_status_invalid_parameter, &token);
+  const enum qnnp_status status = qnnp_enter_setup("qnnp_gfx950_setup_multiply_nc_q8", multiply, &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = setup_multiply(multiply, b_rows, a_rows_per_b_row, a, a_stride, b, b_stride, product, product_stride);
-  /* a failed setup leaves the operator unrunnable instead of half updated (run answers invalid_parameter) */
-  if (status == qnnp_status_success) {
-    multiply->setup_valid = 1;
-  }
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_setup(multiply, token,
+      setup_multiply(multiply, b_rows, a_rows_per_b_row, a, a_stride, b, b_stride, product, product_stride));
 }

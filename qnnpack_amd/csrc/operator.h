@@ -201,34 +201,14 @@ struct qnnp_operator {
                            * failed setup cannot be run against half-updated geometry / tables */
   struct qnnp_hip_dwconv_plan dw_plan;   /* depthwise launch plan, computed at the first run after a setup */
 
-  /* launch of operator types whose code is not part of every build (windowed pooling: max-pooling.c,
-   * average-pooling.c; channel-shuffle.c, clamp.c; lut.c; softargmax.c; multiply.c; resize-bilinear.c): set by their create, called by launch_kernel's default arm
-   * (operator-run.c) with device pointers. Keeps operator-run.c free of references to their kernels, so builds without
-   * them still link. */
+  /* the launch of the operator types that operator-run.c does not launch itself (lifecycle.h qnnp_allocate_operator) */
   int (*launch_hook)(struct qnnp_operator* op, const void* input, void* output);
 };
 
 /* Decide where a caller pointer lives and (re)size the device staging buffer a host pointer needs:
  * success; out_of_memory (staging); invalid_parameter (device memory of a GPU other than the operator's).
- * (operator-run.c) */
+ * (operator-run.c; setups call it through lifecycle.h's qnnp_bind_tensors) */
 enum qnnp_status qnnp_bind_endpoint(const void* ptr, size_t span, int* on_device, void** stage, size_t* capacity);
-
-/* The device guard of the public create / setup entry points: enters `device` (qnnp_hip_leave(*token) undoes it) and
- * answers success, or `no_device` when that device cannot be entered, or invalid_parameter inside a graph capture on it
- * (qnnp_gfx950_graph_begin ... graph_end: only operator launches are recordable there -- an upload would become a graph
- * node reading host memory that is freed right after the call). Nothing is left entered on a refusal. */
-static inline enum qnnp_status qnnp_enter_for_update(int device, enum qnnp_status no_device, int* token)
-{
-  *token = qnnp_hip_enter(device);
-  if (*token < 0) {
-    return no_device;
-  }
-  if (qnnp_hip_graph_capturing()) {
-    qnnp_hip_leave(*token);
-    return qnnp_status_invalid_parameter;
-  }
-  return qnnp_status_success;
-}
 
 /* whether the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte */
 static inline int qnnp_spans_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)

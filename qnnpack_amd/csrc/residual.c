@@ -17,16 +17,18 @@
 #include <qnnpack_gfx950.h>
 
 #include "hip/qnnp_hip.h"
+#include "lifecycle.h"
 #include "log.h"
 #include "operator.h"
-#include "state.h"
 
 enum qnnp_status qnnp_gfx950_attach_residual_add(
     qnnp_operator_t convolution, qnnp_operator_t add, const uint8_t* residual, size_t residual_stride)
 {
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_gfx950_attach_residual_add called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
+  /* Like a setup that validates first: every check that needs no device comes before the device is entered, so inside
+   * a graph capture they still answer with their own status. */
+  enum qnnp_status status = qnnp_check_initialized("qnnp_gfx950_attach_residual_add");
+  if (status != qnnp_status_success) {
+    return status;
   }
   if (convolution == NULL || add == NULL) {
     return qnnp_status_invalid_parameter;
@@ -63,7 +65,7 @@ enum qnnp_status qnnp_gfx950_attach_residual_add(
     return qnnp_status_unsupported_parameter;
   }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(convolution->device, qnnp_status_invalid_parameter, &token);
+  status = qnnp_enter_for_update(convolution->device, qnnp_status_invalid_parameter, &token);
   if (status != qnnp_status_success) {
     return status;
   }

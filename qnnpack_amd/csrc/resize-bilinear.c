@@ -22,10 +22,10 @@
 #include <qnnpack_gfx950.h>
 
 #include "hip/qnnp_hip.h"
+#include "lifecycle.h"
 #include "log.h"
 #include "operator.h"
 #include "resize-table.h"
-#include "state.h"
 #include "upload.h"
 
 static int launch_resize(struct qnnp_operator* op, const void* input, void* output)
@@ -49,9 +49,9 @@ static int launch_resize(struct qnnp_operator* op, const void* input, void* outp
 
 enum qnnp_status qnnp_gfx950_create_resize_bilinear2d_nhwc_u8(size_t channels, uint32_t flags, qnnp_operator_t* resize)
 {
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_gfx950_create_resize_bilinear2d_nhwc_u8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
+  enum qnnp_status status = qnnp_check_initialized("qnnp_gfx950_create_resize_bilinear2d_nhwc_u8");
+  if (status != qnnp_status_success) {
+    return status;
   }
   if (channels == 0) {
     qnnp_log_error("cannot create resize operator with %zu channels: number of channels may not be zero", channels);
@@ -67,30 +67,28 @@ enum qnnp_status qnnp_gfx950_create_resize_bilinear2d_nhwc_u8(size_t channels, u
   }
 
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
+  status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  qnnp_operator_t op = calloc(1, sizeof(struct qnnp_operator));
+  qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_resize_bilinear, launch_resize);
   if (op == NULL) {
-    qnnp_log_error("out of host memory: %zu bytes for qnnp_operator structure", sizeof(struct qnnp_operator));
     status = qnnp_status_out_of_memory;
   } else {
-    op->device = qnnp_hip_device();   /* the context this create runs in */
     op->channels = channels;
     op->resize_align_corners = (flags & QNNP_GFX950_RESIZE_ALIGN_CORNERS) != 0;
-    op->ukernel_type = qnnp_ukernel_type_resize_bilinear;
-    op->launch_hook = launch_resize;
     *resize = op;
   }
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_create(token, status);
 }
 
 static enum qnnp_status setup_resize(
     qnnp_operator_t op, size_t batch_size, size_t input_height, size_t input_width, size_t output_height,
     size_t output_width, const uint8_t* input, size_t input_stride, uint8_t* output, size_t output_stride)
 {
+  if (op->ukernel_type != qnnp_ukernel_type_resize_bilinear) {
+    return qnnp_status_invalid_parameter;
+  }
   if (batch_size == 0) {
     op->batch_size = 0;
     return qnnp_status_success;
@@ -162,12 +160,7 @@ static enum qnnp_status setup_resize(
   op->output_pixel_stride = output_stride;
   op->input_span = input_span;
   op->output_span = output_span;
-  enum qnnp_status bound = qnnp_bind_endpoint(input, input_span, &op->input_on_device, &op->d_stage_in, &op->stage_in_capacity);
-  if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(output, output_span, &op->output_on_device, &op->d_stage_out, &op->stage_out_capacity);
-  if (bound != qnnp_status_success) {
-    qnnp_log_error("cannot set up resize operator: device staging for host memory could not be allocated");
-  }
-  return bound;
+  return qnnp_bind_tensors(op, "qnnp_gfx950_setup_resize_bilinear2d_nhwc_u8");
 }
 
 enum qnnp_status qnnp_gfx950_setup_resize_bilinear2d_nhwc_u8(
@@ -182,24 +175,11 @@ enum qnnp_status qnnp_gfx950_setup_resize_bilinear2d_nhwc_u8(
     uint8_t* output,
     size_t output_pixel_stride)
 {
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_gfx950_setup_resize_bilinear2d_nhwc_u8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
-  }
-  if (resize == NULL || resize->ukernel_type != qnnp_ukernel_type_resize_bilinear) {
-    return qnnp_status_invalid_parameter;
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(resize->device, qnnp_status_invalid_parameter, &token);
+  const enum qnnp_status status = qnnp_enter_setup("qnnp_gfx950_setup_resize_bilinear2d_nhwc_u8", resize, &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = setup_resize(resize, batch_size, input_height, input_width, output_height, output_width, input,
-      input_pixel_stride, output, output_pixel_stride);
-  /* a failed setup leaves the operator unrunnable instead of half updated (run answers invalid_parameter) */
-  if (status == qnnp_status_success) {
-    resize->setup_valid = 1;
-  }
-  qnnp_hip_leave(token);
-  return status;
+  return qnnp_leave_setup(resize, token, setup_resize(resize, batch_size, input_height, input_width, output_height,
+      output_width, input, input_pixel_stride, output, output_pixel_stride));
 }

@@ -26,9 +26,9 @@
 #include <qnnpack_gfx950.h>
 
 #include "hip/qnnp_hip.h"
+#include "lifecycle.h"
 #include "log.h"
 #include "operator.h"
-#include "state.h"
 #include "upload.h"
 
 static int launch_softargmax(struct qnnp_operator* op, const void* input, void* output)
@@ -56,9 +56,9 @@ enum qnnp_status qnnp_create_softargmax_nc_q8(
 {
   (void) flags;
   /* reference softargmax.c:31-34 */
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_create_softargmax_nc_q8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
+  const enum qnnp_status initialized = qnnp_check_initialized("qnnp_create_softargmax_nc_q8");
+  if (initialized != qnnp_status_success) {
+    return initialized;
   }
   /* reference softargmax.c:36-54: invalid_parameter */
   if (channels == 0) {
@@ -104,11 +104,8 @@ enum qnnp_status qnnp_create_softargmax_nc_q8(
     return status;
   }
   status = qnnp_status_out_of_memory;
-  qnnp_operator_t op = calloc(1, sizeof(struct qnnp_operator));
-  if (op == NULL) {
-    qnnp_log_error("out of host memory: %zu bytes for qnnp_operator structure", sizeof(struct qnnp_operator));
-  } else {
-    op->device = qnnp_hip_device();   /* the context this create runs in */
+  qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_softargmax, launch_softargmax);
+  if (op != NULL) {
     op->d_weights = qnnp_upload(table, sizeof(table));
     if (op->d_weights == NULL) {
       qnnp_log_error("failed to place the %zu-byte table of the softargmax operator on the device", sizeof(table));
@@ -116,56 +113,11 @@ enum qnnp_status qnnp_create_softargmax_nc_q8(
     } else {
       op->channels = channels;
       op->input_scale = input_scale;
-      op->ukernel_type = qnnp_ukernel_type_softargmax;
-      op->launch_hook = launch_softargmax;
       *softargmax = op;
       status = qnnp_status_success;
     }
   }
-  qnnp_hip_leave(token);
-  return status;
-}
-
-static enum qnnp_status setup_softargmax(qnnp_operator_t op, size_t batch_size, const uint8_t* input, size_t input_stride,
-                                         uint8_t* output, size_t output_stride)
-{
-  /* reference softargmax.c:119-122 */
-  if (batch_size == 0) {
-    op->batch_size = 0;
-    return qnnp_status_success;
-  }
-  const size_t channels = op->channels;
-  if (input == NULL || output == NULL || input_stride < channels || output_stride < channels) {
-    qnnp_log_error("qnnp_setup_softargmax_nc_q8: NULL tensor or row stride smaller than the channel count");
-    return qnnp_status_invalid_parameter;
-  }
-  if (batch_size > (size_t) INT32_MAX) {
-    qnnp_log_error("qnnp_setup_softargmax_nc_q8 with batch %zu: outside the device kernel's index range", batch_size);
-    return qnnp_status_unsupported_parameter;
-  }
-  const size_t input_span = (batch_size - 1) * input_stride + channels;
-  const size_t output_span = (batch_size - 1) * output_stride + channels;
-  const int in_place = (const void*) input == (const void*) output && input_stride == output_stride;
-  if (!in_place && qnnp_spans_overlap(input, input_span, output, output_span)) {
-    qnnp_log_error("qnnp_setup_softargmax_nc_q8: the input and output tensors overlap without being the same tensor");
-    return qnnp_status_invalid_parameter;
-  }
-
-  op->setup_valid = 0;   /* until every check and allocation below has succeeded */
-  op->batch_size = batch_size;
-  op->input = input;
-  op->input_pixel_stride = input_stride;
-  op->output = output;
-  op->output_pixel_stride = output_stride;
-  op->input_span = input_span;
-  op->output_span = output_span;
-  enum qnnp_status bound = qnnp_bind_endpoint(input, op->input_span, &op->input_on_device, &op->d_stage_in, &op->stage_in_capacity);
-  if (bound == qnnp_status_success) bound = qnnp_bind_endpoint(output, op->output_span, &op->output_on_device, &op->d_stage_out, &op->stage_out_capacity);
-  if (bound != qnnp_status_success) {
-    qnnp_log_error("qnnp_setup_softargmax_nc_q8: failed to bind the tensors: device staging for host memory could not be "
-        "allocated, or a tensor lives on a different device than the operator");
-  }
-  return bound;
+  return qnnp_leave_create(token, status);
 }
 
 enum qnnp_status qnnp_setup_softargmax_nc_q8(
@@ -176,23 +128,14 @@ enum qnnp_status qnnp_setup_softargmax_nc_q8(
     uint8_t* output,
     size_t output_stride)
 {
-  if (!qnnp_state.initialized) {
-    qnnp_log_error("qnnp_setup_softargmax_nc_q8 called before qnnp_initialize succeeded");
-    return qnnp_status_uninitialized;
-  }
-  if (softargmax == NULL || softargmax->ukernel_type != qnnp_ukernel_type_softargmax) {
-    return qnnp_status_invalid_parameter;
-  }
   int token;
-  enum qnnp_status status = qnnp_enter_for_update(softargmax->device, qnnp_status_invalid_parameter, &token);
+  /* reference softargmax.c:114-117 */
+  enum qnnp_status status = qnnp_enter_setup("qnnp_setup_softargmax_nc_q8", softargmax, &token);
   if (status != qnnp_status_success) {
     return status;
   }
-  status = setup_softargmax(softargmax, batch_size, input, input_stride, output, output_stride);
-  /* a failed setup leaves the operator unrunnable instead of half updated (run answers invalid_parameter) */
-  if (status == qnnp_status_success) {
-    softargmax->setup_valid = 1;
-  }
-  qnnp_hip_leave(token);
-  return status;
+  /* reference softargmax.c:119-131 */
+  status = softargmax->ukernel_type != qnnp_ukernel_type_softargmax ? qnnp_status_invalid_parameter :
+      qnnp_setup_nc(softargmax, "qnnp_setup_softargmax_nc_q8", 1, batch_size, input, input_stride, output, output_stride);
+  return qnnp_leave_setup(softargmax, token, status);
 }
