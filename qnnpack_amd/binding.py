@@ -8,14 +8,19 @@ That both load through the same signatures IS the drop-in claim.
 Reference interface mirrored: include/qnnpack.h:24-76, 118-140, 327-332.
 Pointers are passed as raw addresses (``int``), numpy arrays (host memory) or
 anything with a ``data_ptr()`` method (e.g. a torch tensor on the bound GPU).
+
+Every C function is described once, in the two tables below; ``argtypes`` / ``restype`` and the operators' methods are
+made from them, and tests/test_binding_signatures.py holds the tables to the prototypes of the public headers.
 """
 from __future__ import annotations
 
+import ast
 import ctypes
+import inspect
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_size_t, c_uint8, c_uint32, c_void_p
+from ctypes import POINTER, c_char_p, c_float, c_int, c_size_t, c_uint8, c_uint32, c_void_p
 from enum import IntEnum
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -50,627 +55,269 @@ def address_of(buf) -> Optional[int]:
     raise TypeError(f"cannot take the address of {type(buf)!r}")
 
 
+# ---- the description of the C API ----
+# A parameter is "<kind> <name>" or "<kind> <name>=<default>"; the kind gives its ctype and what a generated method does
+# with the caller's value.
+_CTYPES = {
+    "size_t": c_size_t, "u32": c_uint32, "u8": c_uint8, "f32": c_float, "int": c_int, "str": c_char_p,
+    "ptr": c_void_p,        # passed as it is: an operator handle (named `op` where it is the function's own), stream, graph
+    "tensor": c_void_p,     # through address_of
+    "u8[]": c_void_p, "i32[]": c_void_p, "u8[256]": c_void_p,   # host array of that dtype (and size), None -> NULL
+    "out": POINTER(c_void_p),   # a create's trailing handle: not a Python parameter, returned
+    "null": c_void_p,           # the setups' threadpool: not a Python parameter, always NULL
+    "ptr*": POINTER(c_void_p), "f32*": POINTER(c_float), "int*": POINTER(c_int), "size_t*": POINTER(c_size_t),
+}
+_HOST_ARRAYS = {"u8[]": (np.uint8, None), "i32[]": (np.int32, None), "u8[256]": (np.uint8, 256)}
+
+# When a symbol is bound at load. QNNP_GFX950_LIBRARY may name an OLDER build for a same-box A/B: entry points younger
+# than it are then simply not bound; the product library must have them all (tests/test_abi.py).
+ALWAYS = "always"               # a missing symbol is an AttributeError at load
+UNLESS_OLDER = "unless_older"   # the same, unless QNNP_GFX950_LIBRARY is set and the symbol is missing
+IF_PRESENT = "if_present"       # the product's own operators, which the compiled reference does not have
+
+
+class Param(NamedTuple):
+    kind: str
+    name: str
+    default: object = inspect.Parameter.empty
+
+
+class Function(NamedTuple):
+    symbol: str
+    params: tuple
+    bound: str
+    restype: object
+    methods: bool       # whether <name>_status and <name> are generated, <name> the symbol without qnnp_ / gfx950_
+    doc: Optional[str]
+
+    @property
+    def argtypes(self) -> list:
+        return [_CTYPES[p.kind] for p in self.params]
+
+
+def _fn(symbol, spec="", bound=ALWAYS, restype=c_int, methods=False, doc=None) -> Function:
+    params = []
+    for item in filter(None, (s.strip() for s in spec.split(","))):
+        kind, _, name = item.partition(" ")
+        name, has_default, default = name.partition("=")
+        params.append(Param(kind, name, ast.literal_eval(default) if has_default else inspect.Parameter.empty))
+    return Function(symbol, tuple(params), bound, restype, methods, doc)
+
+
+def _op(symbol, spec="", bound=ALWAYS, doc=None) -> Function:
+    return _fn(symbol, spec, bound, methods=True, doc=doc)
+
+
+# parameter runs that several prototypes share (the headers call the four paddings input_padding_*)
+_PADDING = "u32 pad_top, u32 pad_right, u32 pad_bottom, u32 pad_left, "
+_IN_Q = "u8 input_zero_point, f32 input_scale, "
+_OUT_Q = "u8 output_zero_point, f32 output_scale, u8 output_min, u8 output_max, u32 flags=0, out "
+_WEIGHTS_Q = _IN_Q + "u8 kernel_zero_point, f32 kernel_scale, u8[] kernel, i32[] bias, " + _OUT_Q
+_GROUPS = "u32 groups, size_t group_input_channels, size_t group_output_channels, "
+_POOLING = "u32 pooling_height, u32 pooling_width, u32 stride_height, u32 stride_width, "
+_BINARY_Q = ("size_t channels, u8 a_zero_point, f32 a_scale, u8 b_zero_point, f32 b_scale, "
+             "u8 {0}_zero_point, f32 {0}_scale, u8 {0}_min, u8 {0}_max, u32 flags=0, out ")
+_SETUP_NHWC = ("ptr op, size_t batch_size, size_t input_height, size_t input_width, "
+               "tensor input, size_t input_stride, tensor output, size_t output_stride")
+_SETUP_NC = "ptr op, size_t batch_size, tensor input, size_t input_stride, tensor output, size_t output_stride"
+_LUT_DOC = "a table operator: set it up with setup_lut_nc_x8"
+
+# include/qnnpack.h, then the operators that the product declares in include/qnnpack_gfx950.h
+QNNPACK_API = (
+    _op("qnnp_initialize"),
+    _fn("qnnp_deinitialize"),
+    _op("qnnp_create_convolution2d_nhwc_q8",
+        _PADDING + "u32 kernel_height, u32 kernel_width, u32 subsampling_height, u32 subsampling_width, "
+        "u32 dilation_height, u32 dilation_width, " + _GROUPS + _WEIGHTS_Q + "convolution"),
+    _op("qnnp_setup_convolution2d_nhwc_q8", _SETUP_NHWC + ", null threadpool"),
+    _op("qnnp_create_deconvolution2d_nhwc_q8",
+        _PADDING + "u32 adjustment_height, u32 adjustment_width, u32 kernel_height, u32 kernel_width, "
+        "u32 stride_height, u32 stride_width, u32 dilation_height, u32 dilation_width, "
+        + _GROUPS + _WEIGHTS_Q + "deconvolution",
+        doc="kernel: [groups][group_input_channels][kh][kw][group_output_channels] (reference include/qnnpack.h:78-105)."),
+    _op("qnnp_setup_deconvolution2d_nhwc_q8", _SETUP_NHWC + ", null threadpool"),
+    _op("qnnp_create_fully_connected_nc_q8", "size_t input_channels, size_t output_channels, " + _WEIGHTS_Q + "fully_connected"),
+    _op("qnnp_setup_fully_connected_nc_q8", _SETUP_NC),
+    _op("qnnp_create_global_average_pooling_nwc_q8", "size_t channels, " + _IN_Q + _OUT_Q + "global_average_pooling"),
+    _op("qnnp_setup_global_average_pooling_nwc_q8",
+        "ptr op, size_t batch_size, size_t width, tensor input, size_t input_stride, tensor output, size_t output_stride"),
+    _op("qnnp_create_add_nc_q8", _BINARY_Q.format("sum") + "add"),
+    _op("qnnp_setup_add_nc_q8",
+        "ptr op, size_t batch_size, tensor a, size_t a_stride, tensor b, size_t b_stride, tensor sum, size_t sum_stride"),
+    _op("qnnp_run_operator", "ptr op, ptr threadpool=None"),
+    _op("qnnp_delete_operator", "ptr op"),
+    # the rest of the reference's include/qnnpack.h (162-232, 257-324)
+    _op("qnnp_create_average_pooling2d_nhwc_q8",
+        _PADDING + _POOLING + "size_t channels, " + _IN_Q + _OUT_Q + "average_pooling", UNLESS_OLDER),
+    _op("qnnp_setup_average_pooling2d_nhwc_q8", _SETUP_NHWC + ", null threadpool", UNLESS_OLDER),
+    _op("qnnp_create_max_pooling2d_nhwc_u8",
+        _PADDING + _POOLING + "u32 dilation_height, u32 dilation_width, size_t channels, "
+        "u8 output_min, u8 output_max, u32 flags=0, out max_pooling", UNLESS_OLDER),
+    _op("qnnp_setup_max_pooling2d_nhwc_u8", _SETUP_NHWC + ", null threadpool", UNLESS_OLDER),
+    _op("qnnp_create_channel_shuffle_nc_x8", "size_t groups, size_t group_channels, u32 flags=0, out channel_shuffle", UNLESS_OLDER),
+    _op("qnnp_setup_channel_shuffle_nc_x8", _SETUP_NC, UNLESS_OLDER),
+    _op("qnnp_create_clamp_nc_u8", "size_t channels, u8 output_min, u8 output_max, u32 flags=0, out clamp", UNLESS_OLDER),
+    _op("qnnp_setup_clamp_nc_u8", _SETUP_NC, UNLESS_OLDER),
+    _op("qnnp_create_sigmoid_nc_q8", "size_t channels, " + _IN_Q + _OUT_Q + "sigmoid", UNLESS_OLDER),
+    _op("qnnp_setup_sigmoid_nc_q8", _SETUP_NC, UNLESS_OLDER),
+    _op("qnnp_create_leaky_relu_nc_q8", "size_t channels, f32 negative_slope, " + _IN_Q + _OUT_Q + "leaky_relu", UNLESS_OLDER),
+    _op("qnnp_setup_leaky_relu_nc_q8", _SETUP_NC, UNLESS_OLDER),
+    _op("qnnp_create_softargmax_nc_q8",
+        "size_t channels, f32 input_scale, u8 output_zero_point, f32 output_scale, u32 flags=0, out softargmax", UNLESS_OLDER),
+    _op("qnnp_setup_softargmax_nc_q8", _SETUP_NC, UNLESS_OLDER),
+    # operators of the product only
+    _op("qnnp_gfx950_create_lut_nc_x8", "size_t channels, u8[256] table, u32 flags=0, out lut", IF_PRESENT,
+        doc="the product's table operator (qnnp_gfx950_create_lut_nc_x8); `table`: 256 uint8, or None"),
+    _op("qnnp_gfx950_setup_lut_nc_x8", _SETUP_NC, IF_PRESENT),
+    _op("qnnp_gfx950_create_hardswish_nc_q8", "size_t channels, " + _IN_Q + _OUT_Q + "hardswish", IF_PRESENT, doc=_LUT_DOC),
+    _op("qnnp_gfx950_create_hardsigmoid_nc_q8", "size_t channels, " + _IN_Q + _OUT_Q + "hardsigmoid", IF_PRESENT, doc=_LUT_DOC),
+    _op("qnnp_gfx950_create_multiply_nc_q8", _BINARY_Q.format("product") + "multiply", IF_PRESENT,
+        doc="the product's multiply operator (qnnp_gfx950_create_multiply_nc_q8)"),
+    _op("qnnp_gfx950_setup_multiply_nc_q8",
+        "ptr op, size_t b_rows, size_t a_rows_per_b_row, tensor a, size_t a_stride, tensor b, size_t b_stride, "
+        "tensor product, size_t product_stride", IF_PRESENT),
+    _op("qnnp_gfx950_create_resize_bilinear2d_nhwc_u8", "size_t channels, u32 flags=0, out resize", IF_PRESENT,
+        doc="the product's bilinear resize operator (qnnp_gfx950_create_resize_bilinear2d_nhwc_u8); flags: RESIZE_ALIGN_CORNERS"),
+    _op("qnnp_gfx950_setup_resize_bilinear2d_nhwc_u8",
+        "ptr op, size_t batch_size, size_t input_height, size_t input_width, size_t output_height, size_t output_width, "
+        "tensor input, size_t input_pixel_stride, tensor output, size_t output_pixel_stride", IF_PRESENT),
+)
+
+# the rest of include/qnnpack_gfx950.h and include/qnnpack_gfx950_test.h: Gfx950Library's own methods call these
+GFX950_API = (
+    _fn("qnnp_gfx950_set_device", "int device"),
+    _fn("qnnp_gfx950_get_device"),
+    _fn("qnnp_gfx950_device_count"),
+    _fn("qnnp_gfx950_set_stream", "ptr hip_stream"),
+    _fn("qnnp_gfx950_set_async", "int async"),
+    _fn("qnnp_gfx950_synchronize"),
+    _fn("qnnp_gfx950_malloc", "size_t bytes", restype=c_void_p),
+    _fn("qnnp_gfx950_free", "ptr device_ptr", restype=None),
+    _fn("qnnp_gfx950_memcpy_h2d", "ptr dst_device, ptr src_host, size_t bytes"),
+    _fn("qnnp_gfx950_memcpy_d2h", "ptr dst_host, ptr src_device, size_t bytes"),
+    _fn("qnnp_gfx950_memset", "ptr dst_device, int value, size_t bytes"),
+    _fn("qnnp_gfx950_time_operator", "ptr op, int warmup, int iters, f32* avg_ms_out"),
+    _fn("qnnp_gfx950_time_operator_rotating",
+        "ptr op, size_t nsets, ptr* inputs, ptr* outputs, int warmup, int iters, f32* avg_ms_out"),
+    _fn("qnnp_gfx950_graph_begin"),
+    _fn("qnnp_gfx950_graph_end", "ptr* graph_out"),
+    _fn("qnnp_gfx950_graph_launch", "ptr graph"),
+    _fn("qnnp_gfx950_graph_synchronize", "ptr graph"),
+    _fn("qnnp_gfx950_graph_time", "ptr graph, int warmup, int iters, f32* avg_ms_out"),
+    _fn("qnnp_gfx950_graph_destroy", "ptr graph", restype=None),
+    _op("qnnp_gfx950_create_fused_block", "ptr expand, ptr depthwise, ptr project, ptr residual_add=None, out fused"),
+    _op("qnnp_gfx950_setup_fused_block", _SETUP_NHWC),
+    _op("qnnp_gfx950_attach_residual_add", "ptr convolution, ptr add, tensor residual, size_t residual_stride", UNLESS_OLDER),
+    _fn("qnnp_gfx950_operator_residual_folded", "ptr op", UNLESS_OLDER),
+    _fn("qnnp_gfx950_set_option", "str key, int value"),
+    _fn("qnnp_gfx950_test_force_kernel", "str family, int code"),
+    _fn("qnnp_gfx950_test_operator_ran_dense", "ptr op"),
+    _fn("qnnp_gfx950_operator_set_streaming_stores", "ptr op, int value"),
+    _fn("qnnp_gfx950_operator_kernel", "ptr op", restype=c_char_p),
+    _fn("qnnp_gfx950_device_info", "str arch, size_t arch_len, int* compute_units, int* clock_khz, size_t* hbm_bytes"),
+)
+
+API = {f.symbol: f for f in QNNPACK_API + GFX950_API}
+
+
+def _bind(lib, table) -> None:
+    """Set argtypes / restype of the table's symbols on a loaded library."""
+    older = bool(os.environ.get("QNNP_GFX950_LIBRARY"))
+    for f in table:
+        if (f.bound == IF_PRESENT or (f.bound == UNLESS_OLDER and older)) and not hasattr(lib, f.symbol):
+            continue
+        c_function = getattr(lib, f.symbol)
+        c_function.restype = f.restype
+        c_function.argtypes = f.argtypes
+
+
+def _method_pair(f: Function):
+    """<name>_status, which returns the Status (and the new handle, where the function creates one), and <name>, which
+    raises QnnpackError for any status but success."""
+    name = f.symbol.replace("qnnp_", "", 1).replace("gfx950_", "", 1)
+    creates = bool(f.params) and f.params[-1].kind == "out"
+    signature = inspect.Signature(
+        [inspect.Parameter("self", inspect.Parameter.POSITIONAL_OR_KEYWORD)]
+        + [inspect.Parameter(p.name, inspect.Parameter.POSITIONAL_OR_KEYWORD, default=p.default)
+           for p in f.params if p.kind not in ("out", "null")])
+
+    def status(self, *args, **kwargs):
+        given = signature.bind(self, *args, **kwargs)
+        given.apply_defaults()
+        handle = c_void_p(None)
+        host_arrays = []        # alive until the call has returned
+        c_args = []
+        for p in f.params:
+            if p.kind == "out":
+                c_args.append(ctypes.byref(handle))
+                continue
+            value = None if p.kind == "null" else given.arguments[p.name]
+            if p.kind in _HOST_ARRAYS and value is not None:
+                dtype, size = _HOST_ARRAYS[p.kind]
+                value = np.ascontiguousarray(value, dtype=dtype)
+                assert size is None or value.size == size, value.size
+                host_arrays.append(value)
+            c_args.append(address_of(value) if p.kind == "tensor" or p.kind in _HOST_ARRAYS else value)
+        st = Status(getattr(self.lib, f.symbol)(*c_args))
+        return (st, handle.value) if creates else st
+
+    def checked(self, *args, **kwargs):
+        result = getattr(self, status.__name__)(*args, **kwargs)
+        st, handle = result if creates else (result, None)
+        if st != Status.success:
+            raise QnnpackError(f.symbol, st)
+        return handle
+
+    status.__name__, checked.__name__ = name + "_status", name
+    status.__signature__ = checked.__signature__ = signature
+    status.__doc__ = checked.__doc__ = f.doc
+    return status, checked
+
+
+def _with_methods_of(table):
+    """Class decorator: the generated methods of the table's operator functions become attributes of the class."""
+    def install(cls):
+        for f in table:
+            if f.methods:
+                for method in _method_pair(f):
+                    method.__qualname__ = f"{cls.__qualname__}.{method.__name__}"
+                    method.__module__ = cls.__module__
+                    setattr(cls, method.__name__, method)
+        return cls
+    return install
+
+
+@_with_methods_of(QNNPACK_API)
 class QnnpackLibrary:
-    """The C API of include/qnnpack.h bound over ``path``."""
+    """The C API of include/qnnpack.h bound over ``path``.
+
+    Every operator function of QNNPACK_API is two methods, e.g. create_add_nc_q8_status(...) -> (Status, handle or None)
+    and create_add_nc_q8(...) -> handle, setup_add_nc_q8_status(op, ...) -> Status and setup_add_nc_q8(op, ...) -> None;
+    tests of error behaviour use the _status forms, the others raise QnnpackError.
+    """
 
     RESIZE_ALIGN_CORNERS = 0x00000001   # QNNP_GFX950_RESIZE_ALIGN_CORNERS (include/qnnpack_gfx950.h)
 
     def __init__(self, path: str):
         self.path = path
         self.lib = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
-        L = self.lib
-        L.qnnp_initialize.restype = c_int
-        L.qnnp_initialize.argtypes = []
-        L.qnnp_deinitialize.restype = c_int
-        L.qnnp_deinitialize.argtypes = []
-        L.qnnp_create_convolution2d_nhwc_q8.restype = c_int
-        L.qnnp_create_convolution2d_nhwc_q8.argtypes = (
-            [c_uint32] * 11 + [c_size_t, c_size_t, c_uint8, c_float, c_uint8, c_float, c_void_p, c_void_p,
-                               c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)])
-        L.qnnp_setup_convolution2d_nhwc_q8.restype = c_int
-        L.qnnp_setup_convolution2d_nhwc_q8.argtypes = [
-            c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]
-        L.qnnp_create_deconvolution2d_nhwc_q8.restype = c_int
-        L.qnnp_create_deconvolution2d_nhwc_q8.argtypes = (
-            [c_uint32] * 13 + [c_size_t, c_size_t, c_uint8, c_float, c_uint8, c_float, c_void_p, c_void_p,
-                               c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)])
-        L.qnnp_setup_deconvolution2d_nhwc_q8.restype = c_int
-        L.qnnp_setup_deconvolution2d_nhwc_q8.argtypes = [
-            c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]
-        L.qnnp_create_global_average_pooling_nwc_q8.restype = c_int
-        L.qnnp_create_global_average_pooling_nwc_q8.argtypes = [
-            c_size_t, c_uint8, c_float, c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)]
-        L.qnnp_setup_global_average_pooling_nwc_q8.restype = c_int
-        L.qnnp_setup_global_average_pooling_nwc_q8.argtypes = [
-            c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
-        L.qnnp_create_add_nc_q8.restype = c_int
-        L.qnnp_create_add_nc_q8.argtypes = [
-            c_size_t, c_uint8, c_float, c_uint8, c_float, c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)]
-        L.qnnp_setup_add_nc_q8.restype = c_int
-        L.qnnp_setup_add_nc_q8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
-        L.qnnp_create_fully_connected_nc_q8.restype = c_int
-        L.qnnp_create_fully_connected_nc_q8.argtypes = [
-            c_size_t, c_size_t, c_uint8, c_float, c_uint8, c_float, c_void_p, c_void_p,
-            c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)]
-        L.qnnp_setup_fully_connected_nc_q8.restype = c_int
-        L.qnnp_setup_fully_connected_nc_q8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
-        # windowed pooling (reference include/qnnpack.h:162-218; the product declares them in qnnpack_gfx950.h). Bound when
-        # present: an older product build named by QNNP_GFX950_LIBRARY may predate them.
-        if hasattr(L, "qnnp_create_max_pooling2d_nhwc_u8") or not os.environ.get("QNNP_GFX950_LIBRARY"):
-            L.qnnp_create_average_pooling2d_nhwc_q8.restype = c_int
-            L.qnnp_create_average_pooling2d_nhwc_q8.argtypes = (
-                [c_uint32] * 8 + [c_size_t, c_uint8, c_float, c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)])
-            L.qnnp_setup_average_pooling2d_nhwc_q8.restype = c_int
-            L.qnnp_setup_average_pooling2d_nhwc_q8.argtypes = [
-                c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]
-            L.qnnp_create_max_pooling2d_nhwc_u8.restype = c_int
-            L.qnnp_create_max_pooling2d_nhwc_u8.argtypes = (
-                [c_uint32] * 10 + [c_size_t, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)])
-            L.qnnp_setup_max_pooling2d_nhwc_u8.restype = c_int
-            L.qnnp_setup_max_pooling2d_nhwc_u8.argtypes = [
-                c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]
-        # channel shuffle and clamp (reference include/qnnpack.h:220-232, 257-270; the product declares them in
-        # qnnpack_gfx950.h). Bound when present, as the windowed pooling entries are.
-        if hasattr(L, "qnnp_create_channel_shuffle_nc_x8") or not os.environ.get("QNNP_GFX950_LIBRARY"):
-            L.qnnp_create_channel_shuffle_nc_x8.restype = c_int
-            L.qnnp_create_channel_shuffle_nc_x8.argtypes = [c_size_t, c_size_t, c_uint32, POINTER(c_void_p)]
-            L.qnnp_setup_channel_shuffle_nc_x8.restype = c_int
-            L.qnnp_setup_channel_shuffle_nc_x8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
-            L.qnnp_create_clamp_nc_u8.restype = c_int
-            L.qnnp_create_clamp_nc_u8.argtypes = [c_size_t, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)]
-            L.qnnp_setup_clamp_nc_u8.restype = c_int
-            L.qnnp_setup_clamp_nc_u8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
-        # sigmoid and leaky ReLU (reference include/qnnpack.h:272-309; the product declares them in qnnpack_gfx950.h).
-        # Bound when present, as above; the table operator under them exists in the product only.
-        if hasattr(L, "qnnp_create_sigmoid_nc_q8") or not os.environ.get("QNNP_GFX950_LIBRARY"):
-            L.qnnp_create_sigmoid_nc_q8.restype = c_int
-            L.qnnp_create_sigmoid_nc_q8.argtypes = [
-                c_size_t, c_uint8, c_float, c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)]
-            L.qnnp_setup_sigmoid_nc_q8.restype = c_int
-            L.qnnp_setup_sigmoid_nc_q8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
-            L.qnnp_create_leaky_relu_nc_q8.restype = c_int
-            L.qnnp_create_leaky_relu_nc_q8.argtypes = [
-                c_size_t, c_float, c_uint8, c_float, c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)]
-            L.qnnp_setup_leaky_relu_nc_q8.restype = c_int
-            L.qnnp_setup_leaky_relu_nc_q8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
-        # softargmax (reference include/qnnpack.h:311-324; the product declares it in qnnpack_gfx950.h). Bound when
-        # present, as above.
-        if hasattr(L, "qnnp_create_softargmax_nc_q8") or not os.environ.get("QNNP_GFX950_LIBRARY"):
-            L.qnnp_create_softargmax_nc_q8.restype = c_int
-            L.qnnp_create_softargmax_nc_q8.argtypes = [c_size_t, c_float, c_uint8, c_float, c_uint32, POINTER(c_void_p)]
-            L.qnnp_setup_softargmax_nc_q8.restype = c_int
-            L.qnnp_setup_softargmax_nc_q8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
-        if hasattr(L, "qnnp_gfx950_create_lut_nc_x8"):
-            L.qnnp_gfx950_create_lut_nc_x8.restype = c_int
-            L.qnnp_gfx950_create_lut_nc_x8.argtypes = [c_size_t, c_void_p, c_uint32, POINTER(c_void_p)]
-            L.qnnp_gfx950_setup_lut_nc_x8.restype = c_int
-            L.qnnp_gfx950_setup_lut_nc_x8.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
-        # multiply, hardswish and hardsigmoid exist in the product only (include/qnnpack_gfx950.h). Bound when present.
-        if hasattr(L, "qnnp_gfx950_create_multiply_nc_q8"):
-            L.qnnp_gfx950_create_multiply_nc_q8.restype = c_int
-            L.qnnp_gfx950_create_multiply_nc_q8.argtypes = [
-                c_size_t, c_uint8, c_float, c_uint8, c_float, c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)]
-            L.qnnp_gfx950_setup_multiply_nc_q8.restype = c_int
-            L.qnnp_gfx950_setup_multiply_nc_q8.argtypes = [
-                c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
-            for name in ("qnnp_gfx950_create_hardswish_nc_q8", "qnnp_gfx950_create_hardsigmoid_nc_q8"):
-                getattr(L, name).restype = c_int
-                getattr(L, name).argtypes = [
-                    c_size_t, c_uint8, c_float, c_uint8, c_float, c_uint8, c_uint8, c_uint32, POINTER(c_void_p)]
-        # bilinear resize exists in the product only (include/qnnpack_gfx950.h). Bound when present.
-        if hasattr(L, "qnnp_gfx950_create_resize_bilinear2d_nhwc_u8"):
-            L.qnnp_gfx950_create_resize_bilinear2d_nhwc_u8.restype = c_int
-            L.qnnp_gfx950_create_resize_bilinear2d_nhwc_u8.argtypes = [c_size_t, c_uint32, POINTER(c_void_p)]
-            L.qnnp_gfx950_setup_resize_bilinear2d_nhwc_u8.restype = c_int
-            L.qnnp_gfx950_setup_resize_bilinear2d_nhwc_u8.argtypes = [
-                c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
-        L.qnnp_run_operator.restype = c_int
-        L.qnnp_run_operator.argtypes = [c_void_p, c_void_p]
-        L.qnnp_delete_operator.restype = c_int
-        L.qnnp_delete_operator.argtypes = [c_void_p]
-
-    # -- status-returning raw calls (tests of error behaviour use these) ----
-    def initialize_status(self) -> Status:
-        return Status(self.lib.qnnp_initialize())
-
-    def initialize(self) -> None:
-        st = self.lib.qnnp_initialize()
-        if st != 0:
-            raise QnnpackError("qnnp_initialize", st)
+        _bind(self.lib, QNNPACK_API)
 
     def deinitialize(self) -> Status:
         return Status(self.lib.qnnp_deinitialize())
 
-    def create_convolution2d_nhwc_q8_status(
-            self, pad_top, pad_right, pad_bottom, pad_left, kernel_height, kernel_width,
-            subsampling_height, subsampling_width, dilation_height, dilation_width,
-            groups, group_input_channels, group_output_channels,
-            input_zero_point, input_scale, kernel_zero_point, kernel_scale,
-            kernel, bias, output_zero_point, output_scale, output_min, output_max, flags=0):
-        kernel = None if kernel is None else np.ascontiguousarray(kernel, dtype=np.uint8)
-        bias = None if bias is None else np.ascontiguousarray(bias, dtype=np.int32)
-        handle = c_void_p(None)
-        st = self.lib.qnnp_create_convolution2d_nhwc_q8(
-            pad_top, pad_right, pad_bottom, pad_left, kernel_height, kernel_width,
-            subsampling_height, subsampling_width, dilation_height, dilation_width,
-            groups, group_input_channels, group_output_channels,
-            input_zero_point, input_scale, kernel_zero_point, kernel_scale,
-            address_of(kernel), address_of(bias),
-            output_zero_point, output_scale, output_min, output_max, flags, ctypes.byref(handle))
-        return Status(st), handle.value
 
-    def create_convolution2d_nhwc_q8(self, *args, **kwargs) -> int:
-        st, handle = self.create_convolution2d_nhwc_q8_status(*args, **kwargs)
-        if st != Status.success:
-            raise QnnpackError("qnnp_create_convolution2d_nhwc_q8", st)
-        return handle
-
-    def setup_convolution2d_nhwc_q8_status(
-            self, op, batch_size, input_height, input_width, input, input_stride, output, output_stride) -> Status:
-        return Status(self.lib.qnnp_setup_convolution2d_nhwc_q8(
-            op, batch_size, input_height, input_width, address_of(input), input_stride,
-            address_of(output), output_stride, None))
-
-    def setup_convolution2d_nhwc_q8(self, *args) -> None:
-        st = self.setup_convolution2d_nhwc_q8_status(*args)
-        if st != Status.success:
-            raise QnnpackError("qnnp_setup_convolution2d_nhwc_q8", st)
-
-    def create_deconvolution2d_nhwc_q8_status(
-            self, pad_top, pad_right, pad_bottom, pad_left, adjustment_height, adjustment_width,
-            kernel_height, kernel_width, stride_height, stride_width, dilation_height, dilation_width,
-            groups, group_input_channels, group_output_channels,
-            input_zero_point, input_scale, kernel_zero_point, kernel_scale,
-            kernel, bias, output_zero_point, output_scale, output_min, output_max, flags=0):
-        """kernel: [groups][group_input_channels][kh][kw][group_output_channels] (reference include/qnnpack.h:78-105)."""
-        kernel = None if kernel is None else np.ascontiguousarray(kernel, dtype=np.uint8)
-        bias = None if bias is None else np.ascontiguousarray(bias, dtype=np.int32)
-        handle = c_void_p(None)
-        st = self.lib.qnnp_create_deconvolution2d_nhwc_q8(
-            pad_top, pad_right, pad_bottom, pad_left, adjustment_height, adjustment_width,
-            kernel_height, kernel_width, stride_height, stride_width, dilation_height, dilation_width,
-            groups, group_input_channels, group_output_channels,
-            input_zero_point, input_scale, kernel_zero_point, kernel_scale,
-            address_of(kernel), address_of(bias),
-            output_zero_point, output_scale, output_min, output_max, flags, ctypes.byref(handle))
-        return Status(st), handle.value
-
-    def create_deconvolution2d_nhwc_q8(self, *args, **kwargs) -> int:
-        st, handle = self.create_deconvolution2d_nhwc_q8_status(*args, **kwargs)
-        if st != Status.success:
-            raise QnnpackError("qnnp_create_deconvolution2d_nhwc_q8", st)
-        return handle
-
-    def setup_deconvolution2d_nhwc_q8_status(
-            self, op, batch_size, input_height, input_width, input, input_stride, output, output_stride) -> Status:
-        return Status(self.lib.qnnp_setup_deconvolution2d_nhwc_q8(
-            op, batch_size, input_height, input_width, address_of(input), input_stride,
-            address_of(output), output_stride, None))
-
-    def setup_deconvolution2d_nhwc_q8(self, *args) -> None:
-        st = self.setup_deconvolution2d_nhwc_q8_status(*args)
-        if st != Status.success:
-            raise QnnpackError("qnnp_setup_deconvolution2d_nhwc_q8", st)
-
-    def create_global_average_pooling_nwc_q8_status(
-            self, channels, input_zero_point, input_scale, output_zero_point, output_scale,
-            output_min, output_max, flags=0):
-        handle = c_void_p(None)
-        st = self.lib.qnnp_create_global_average_pooling_nwc_q8(
-            channels, input_zero_point, input_scale, output_zero_point, output_scale, output_min, output_max, flags,
-            ctypes.byref(handle))
-        return Status(st), handle.value
-
-    def create_global_average_pooling_nwc_q8(self, *args, **kwargs) -> int:
-        st, handle = self.create_global_average_pooling_nwc_q8_status(*args, **kwargs)
-        if st != Status.success:
-            raise QnnpackError("qnnp_create_global_average_pooling_nwc_q8", st)
-        return handle
-
-    def setup_global_average_pooling_nwc_q8_status(self, op, batch_size, width, input, input_stride,
-                                                   output, output_stride) -> Status:
-        return Status(self.lib.qnnp_setup_global_average_pooling_nwc_q8(
-            op, batch_size, width, address_of(input), input_stride, address_of(output), output_stride))
-
-    def setup_global_average_pooling_nwc_q8(self, *args) -> None:
-        st = self.setup_global_average_pooling_nwc_q8_status(*args)
-        if st != Status.success:
-            raise QnnpackError("qnnp_setup_global_average_pooling_nwc_q8", st)
-
-    def create_add_nc_q8_status(self, channels, a_zero_point, a_scale, b_zero_point, b_scale,
-                                sum_zero_point, sum_scale, sum_min, sum_max, flags=0):
-        handle = c_void_p(None)
-        st = self.lib.qnnp_create_add_nc_q8(channels, a_zero_point, a_scale, b_zero_point, b_scale,
-                                            sum_zero_point, sum_scale, sum_min, sum_max, flags, ctypes.byref(handle))
-        return Status(st), handle.value
-
-    def create_add_nc_q8(self, *args, **kwargs) -> int:
-        st, handle = self.create_add_nc_q8_status(*args, **kwargs)
-        if st != Status.success:
-            raise QnnpackError("qnnp_create_add_nc_q8", st)
-        return handle
-
-    def setup_add_nc_q8_status(self, op, batch_size, a, a_stride, b, b_stride, sum, sum_stride) -> Status:
-        return Status(self.lib.qnnp_setup_add_nc_q8(
-            op, batch_size, address_of(a), a_stride, address_of(b), b_stride, address_of(sum), sum_stride))
-
-    def setup_add_nc_q8(self, *args) -> None:
-        st = self.setup_add_nc_q8_status(*args)
-        if st != Status.success:
-            raise QnnpackError("qnnp_setup_add_nc_q8", st)
-
-    def create_fully_connected_nc_q8_status(
-            self, input_channels, output_channels, input_zero_point, input_scale,
-            kernel_zero_point, kernel_scale, kernel, bias,
-            output_zero_point, output_scale, output_min, output_max, flags=0):
-        kernel = None if kernel is None else np.ascontiguousarray(kernel, dtype=np.uint8)
-        bias = None if bias is None else np.ascontiguousarray(bias, dtype=np.int32)
-        handle = c_void_p(None)
-        st = self.lib.qnnp_create_fully_connected_nc_q8(
-            input_channels, output_channels, input_zero_point, input_scale,
-            kernel_zero_point, kernel_scale, address_of(kernel), address_of(bias),
-            output_zero_point, output_scale, output_min, output_max, flags, ctypes.byref(handle))
-        return Status(st), handle.value
-
-    def create_fully_connected_nc_q8(self, *args, **kwargs) -> int:
-        st, handle = self.create_fully_connected_nc_q8_status(*args, **kwargs)
-        if st != Status.success:
-            raise QnnpackError("qnnp_create_fully_connected_nc_q8", st)
-        return handle
-
-    def setup_fully_connected_nc_q8_status(self, op, batch_size, input, input_stride, output, output_stride) -> Status:
-        return Status(self.lib.qnnp_setup_fully_connected_nc_q8(
-            op, batch_size, address_of(input), input_stride, address_of(output), output_stride))
-
-    def setup_fully_connected_nc_q8(self, *args) -> None:
-        st = self.setup_fully_connected_nc_q8_status(*args)
-        if st != Status.success:
-            raise QnnpackError("qnnp_setup_fully_connected_nc_q8", st)
-
-    def create_average_pooling2d_nhwc_q8_status(
-            self, pad_top, pad_right, pad_bottom, pad_left, pooling_height, pooling_width, stride_height, stride_width,
-            channels, input_zero_point, input_scale, output_zero_point, output_scale, output_min, output_max, flags=0):
-        handle = c_void_p(None)
-        st = self.lib.qnnp_create_average_pooling2d_nhwc_q8(
-            pad_top, pad_right, pad_bottom, pad_left, pooling_height, pooling_width, stride_height, stride_width,
-            channels, input_zero_point, input_scale, output_zero_point, output_scale, output_min, output_max, flags,
-            ctypes.byref(handle))
-        return Status(st), handle.value
-
-    def create_average_pooling2d_nhwc_q8(self, *args, **kwargs) -> int:
-        st, handle = self.create_average_pooling2d_nhwc_q8_status(*args, **kwargs)
-        if st != Status.success:
-            raise QnnpackError("qnnp_create_average_pooling2d_nhwc_q8", st)
-        return handle
-
-    def setup_average_pooling2d_nhwc_q8_status(
-            self, op, batch_size, input_height, input_width, input, input_stride, output, output_stride) -> Status:
-        return Status(self.lib.qnnp_setup_average_pooling2d_nhwc_q8(
-            op, batch_size, input_height, input_width, address_of(input), input_stride,
-            address_of(output), output_stride, None))
-
-    def setup_average_pooling2d_nhwc_q8(self, *args) -> None:
-        st = self.setup_average_pooling2d_nhwc_q8_status(*args)
-        if st != Status.success:
-            raise QnnpackError("qnnp_setup_average_pooling2d_nhwc_q8", st)
-
-    def create_max_pooling2d_nhwc_u8_status(
-            self, pad_top, pad_right, pad_bottom, pad_left, pooling_height, pooling_width, stride_height, stride_width,
-            dilation_height, dilation_width, channels, output_min, output_max, flags=0):
-        handle = c_void_p(None)
-        st = self.lib.qnnp_create_max_pooling2d_nhwc_u8(
-            pad_top, pad_right, pad_bottom, pad_left, pooling_height, pooling_width, stride_height, stride_width,
-            dilation_height, dilation_width, channels, output_min, output_max, flags, ctypes.byref(handle))
-        return Status(st), handle.value
-
-    def create_max_pooling2d_nhwc_u8(self, *args, **kwargs) -> int:
-        st, handle = self.create_max_pooling2d_nhwc_u8_status(*args, **kwargs)
-        if st != Status.success:
-            raise QnnpackError("qnnp_create_max_pooling2d_nhwc_u8", st)
-        return handle
-
-    def setup_max_pooling2d_nhwc_u8_status(
-            self, op, batch_size, input_height, input_width, input, input_stride, output, output_stride) -> Status:
-        return Status(self.lib.qnnp_setup_max_pooling2d_nhwc_u8(
-            op, batch_size, input_height, input_width, address_of(input), input_stride,
-            address_of(output), output_stride, None))
-
-    def setup_max_pooling2d_nhwc_u8(self, *args) -> None:
-        st = self.setup_max_pooling2d_nhwc_u8_status(*args)
-        if st != Status.success:
-            raise QnnpackError("qnnp_setup_max_pooling2d_nhwc_u8", st)
-
-    def create_channel_shuffle_nc_x8_status(self, groups, group_channels, flags=0):
-        handle = c_void_p(None)
-        st = self.lib.qnnp_create_channel_shuffle_nc_x8(groups, group_channels, flags, ctypes.byref(handle))
-        return Status(st), handle.value
-
-    def create_channel_shuffle_nc_x8(self, *args, **kwargs) -> int:
-        st, handle = self.create_channel_shuffle_nc_x8_status(*args, **kwargs)
-        if st != Status.success:
-            raise QnnpackError("qnnp_create_channel_shuffle_nc_x8", st)
-        return handle
-
-    def setup_channel_shuffle_nc_x8_status(self, op, batch_size, input, input_stride, output, output_stride) -> Status:
-        return Status(self.lib.qnnp_setup_channel_shuffle_nc_x8(
-            op, batch_size, address_of(input), input_stride, address_of(output), output_stride))
-
-    def setup_channel_shuffle_nc_x8(self, *args) -> None:
-        st = self.setup_channel_shuffle_nc_x8_status(*args)
-        if st != Status.success:
-            raise QnnpackError("qnnp_setup_channel_shuffle_nc_x8", st)
-
-    def create_clamp_nc_u8_status(self, channels, output_min, output_max, flags=0):
-        handle = c_void_p(None)
-        st = self.lib.qnnp_create_clamp_nc_u8(channels, output_min, output_max, flags, ctypes.byref(handle))
-        return Status(st), handle.value
-
-    def create_clamp_nc_u8(self, *args, **kwargs) -> int:
-        st, handle = self.create_clamp_nc_u8_status(*args, **kwargs)
-        if st != Status.success:
-            raise QnnpackError("qnnp_create_clamp_nc_u8", st)
-        return handle
-
-    def setup_clamp_nc_u8_status(self, op, batch_size, input, input_stride, output, output_stride) -> Status:
-        return Status(self.lib.qnnp_setup_clamp_nc_u8(
-            op, batch_size, address_of(input), input_stride, address_of(output), output_stride))
-
-    def setup_clamp_nc_u8(self, *args) -> None:
-        st = self.setup_clamp_nc_u8_status(*args)
-        if st != Status.success:
-            raise QnnpackError("qnnp_setup_clamp_nc_u8", st)
-
-    def create_sigmoid_nc_q8_status(self, channels, input_zero_point, input_scale, output_zero_point, output_scale,
-                                    output_min, output_max, flags=0):
-        handle = c_void_p(None)
-        st = self.lib.qnnp_create_sigmoid_nc_q8(channels, input_zero_point, input_scale, output_zero_point, output_scale,
-                                                output_min, output_max, flags, ctypes.byref(handle))
-        return Status(st), handle.value
-
-    def create_sigmoid_nc_q8(self, *args, **kwargs) -> int:
-        st, handle = self.create_sigmoid_nc_q8_status(*args, **kwargs)
-        if st != Status.success:
-            raise QnnpackError("qnnp_create_sigmoid_nc_q8", st)
-        return handle
-
-    def setup_sigmoid_nc_q8_status(self, op, batch_size, input, input_stride, output, output_stride) -> Status:
-        return Status(self.lib.qnnp_setup_sigmoid_nc_q8(
-            op, batch_size, address_of(input), input_stride, address_of(output), output_stride))
-
-    def setup_sigmoid_nc_q8(self, *args) -> None:
-        st = self.setup_sigmoid_nc_q8_status(*args)
-        if st != Status.success:
-            raise QnnpackError("qnnp_setup_sigmoid_nc_q8", st)
-
-    def create_leaky_relu_nc_q8_status(self, channels, negative_slope, input_zero_point, input_scale, output_zero_point,
-                                       output_scale, output_min, output_max, flags=0):
-        handle = c_void_p(None)
-        st = self.lib.qnnp_create_leaky_relu_nc_q8(channels, negative_slope, input_zero_point, input_scale,
-                                                   output_zero_point, output_scale, output_min, output_max, flags,
-                                                   ctypes.byref(handle))
-        return Status(st), handle.value
-
-    def create_leaky_relu_nc_q8(self, *args, **kwargs) -> int:
-        st, handle = self.create_leaky_relu_nc_q8_status(*args, **kwargs)
-        if st != Status.success:
-            raise QnnpackError("qnnp_create_leaky_relu_nc_q8", st)
-        return handle
-
-    def setup_leaky_relu_nc_q8_status(self, op, batch_size, input, input_stride, output, output_stride) -> Status:
-        return Status(self.lib.qnnp_setup_leaky_relu_nc_q8(
-            op, batch_size, address_of(input), input_stride, address_of(output), output_stride))
-
-    def setup_leaky_relu_nc_q8(self, *args) -> None:
-        st = self.setup_leaky_relu_nc_q8_status(*args)
-        if st != Status.success:
-            raise QnnpackError("qnnp_setup_leaky_relu_nc_q8", st)
-
-    def create_softargmax_nc_q8_status(self, channels, input_scale, output_zero_point, output_scale, flags=0):
-        handle = c_void_p(None)
-        st = self.lib.qnnp_create_softargmax_nc_q8(channels, input_scale, output_zero_point, output_scale, flags,
-                                                   ctypes.byref(handle))
-        return Status(st), handle.value
-
-    def create_softargmax_nc_q8(self, *args, **kwargs) -> int:
-        st, handle = self.create_softargmax_nc_q8_status(*args, **kwargs)
-        if st != Status.success:
-            raise QnnpackError("qnnp_create_softargmax_nc_q8", st)
-        return handle
-
-    def setup_softargmax_nc_q8_status(self, op, batch_size, input, input_stride, output, output_stride) -> Status:
-        return Status(self.lib.qnnp_setup_softargmax_nc_q8(
-            op, batch_size, address_of(input), input_stride, address_of(output), output_stride))
-
-    def setup_softargmax_nc_q8(self, *args) -> None:
-        st = self.setup_softargmax_nc_q8_status(*args)
-        if st != Status.success:
-            raise QnnpackError("qnnp_setup_softargmax_nc_q8", st)
-
-    def create_lut_nc_x8_status(self, channels, table, flags=0):
-        """the product's table operator (qnnp_gfx950_create_lut_nc_x8); `table`: 256 uint8, or None"""
-        handle = c_void_p(None)
-        if table is not None:
-            table = np.ascontiguousarray(table, dtype=np.uint8)
-            assert table.size == 256, table.size
-        st = self.lib.qnnp_gfx950_create_lut_nc_x8(channels, address_of(table), flags, ctypes.byref(handle))
-        return Status(st), handle.value
-
-    def create_lut_nc_x8(self, *args, **kwargs) -> int:
-        st, handle = self.create_lut_nc_x8_status(*args, **kwargs)
-        if st != Status.success:
-            raise QnnpackError("qnnp_gfx950_create_lut_nc_x8", st)
-        return handle
-
-    def setup_lut_nc_x8_status(self, op, batch_size, input, input_stride, output, output_stride) -> Status:
-        return Status(self.lib.qnnp_gfx950_setup_lut_nc_x8(
-            op, batch_size, address_of(input), input_stride, address_of(output), output_stride))
-
-    def setup_lut_nc_x8(self, *args) -> None:
-        st = self.setup_lut_nc_x8_status(*args)
-        if st != Status.success:
-            raise QnnpackError("qnnp_gfx950_setup_lut_nc_x8", st)
-
-    def create_multiply_nc_q8_status(self, channels, a_zero_point, a_scale, b_zero_point, b_scale,
-                                     product_zero_point, product_scale, product_min, product_max, flags=0):
-        """the product's multiply operator (qnnp_gfx950_create_multiply_nc_q8)"""
-        handle = c_void_p(None)
-        st = self.lib.qnnp_gfx950_create_multiply_nc_q8(
-            channels, a_zero_point, a_scale, b_zero_point, b_scale, product_zero_point, product_scale,
-            product_min, product_max, flags, ctypes.byref(handle))
-        return Status(st), handle.value
-
-    def create_multiply_nc_q8(self, *args, **kwargs) -> int:
-        st, handle = self.create_multiply_nc_q8_status(*args, **kwargs)
-        if st != Status.success:
-            raise QnnpackError("qnnp_gfx950_create_multiply_nc_q8", st)
-        return handle
-
-    def setup_multiply_nc_q8_status(self, op, b_rows, a_rows_per_b_row, a, a_stride, b, b_stride,
-                                    product, product_stride) -> Status:
-        return Status(self.lib.qnnp_gfx950_setup_multiply_nc_q8(
-            op, b_rows, a_rows_per_b_row, address_of(a), a_stride, address_of(b), b_stride,
-            address_of(product), product_stride))
-
-    def setup_multiply_nc_q8(self, *args) -> None:
-        st = self.setup_multiply_nc_q8_status(*args)
-        if st != Status.success:
-            raise QnnpackError("qnnp_gfx950_setup_multiply_nc_q8", st)
-
-    def create_resize_bilinear2d_nhwc_u8_status(self, channels, flags=0):
-        """the product's bilinear resize operator (qnnp_gfx950_create_resize_bilinear2d_nhwc_u8); flags: RESIZE_ALIGN_CORNERS"""
-        handle = c_void_p(None)
-        st = self.lib.qnnp_gfx950_create_resize_bilinear2d_nhwc_u8(channels, flags, ctypes.byref(handle))
-        return Status(st), handle.value
-
-    def create_resize_bilinear2d_nhwc_u8(self, *args, **kwargs) -> int:
-        st, handle = self.create_resize_bilinear2d_nhwc_u8_status(*args, **kwargs)
-        if st != Status.success:
-            raise QnnpackError("qnnp_gfx950_create_resize_bilinear2d_nhwc_u8", st)
-        return handle
-
-    def setup_resize_bilinear2d_nhwc_u8_status(self, op, batch_size, input_height, input_width, output_height,
-                                               output_width, input, input_pixel_stride, output,
-                                               output_pixel_stride) -> Status:
-        return Status(self.lib.qnnp_gfx950_setup_resize_bilinear2d_nhwc_u8(
-            op, batch_size, input_height, input_width, output_height, output_width, address_of(input),
-            input_pixel_stride, address_of(output), output_pixel_stride))
-
-    def setup_resize_bilinear2d_nhwc_u8(self, *args) -> None:
-        st = self.setup_resize_bilinear2d_nhwc_u8_status(*args)
-        if st != Status.success:
-            raise QnnpackError("qnnp_gfx950_setup_resize_bilinear2d_nhwc_u8", st)
-
-    def create_hardswish_nc_q8_status(self, channels, input_zero_point, input_scale, output_zero_point, output_scale,
-                                      output_min, output_max, flags=0):
-        """a table operator: set it up with setup_lut_nc_x8"""
-        handle = c_void_p(None)
-        st = self.lib.qnnp_gfx950_create_hardswish_nc_q8(channels, input_zero_point, input_scale, output_zero_point,
-                                                         output_scale, output_min, output_max, flags, ctypes.byref(handle))
-        return Status(st), handle.value
-
-    def create_hardswish_nc_q8(self, *args, **kwargs) -> int:
-        st, handle = self.create_hardswish_nc_q8_status(*args, **kwargs)
-        if st != Status.success:
-            raise QnnpackError("qnnp_gfx950_create_hardswish_nc_q8", st)
-        return handle
-
-    def create_hardsigmoid_nc_q8_status(self, channels, input_zero_point, input_scale, output_zero_point, output_scale,
-                                        output_min, output_max, flags=0):
-        """a table operator: set it up with setup_lut_nc_x8"""
-        handle = c_void_p(None)
-        st = self.lib.qnnp_gfx950_create_hardsigmoid_nc_q8(channels, input_zero_point, input_scale, output_zero_point,
-                                                           output_scale, output_min, output_max, flags, ctypes.byref(handle))
-        return Status(st), handle.value
-
-    def create_hardsigmoid_nc_q8(self, *args, **kwargs) -> int:
-        st, handle = self.create_hardsigmoid_nc_q8_status(*args, **kwargs)
-        if st != Status.success:
-            raise QnnpackError("qnnp_gfx950_create_hardsigmoid_nc_q8", st)
-        return handle
-
-    def run_operator_status(self, op, threadpool=None) -> Status:
-        return Status(self.lib.qnnp_run_operator(op, threadpool))
-
-    def run_operator(self, op, threadpool=None) -> None:
-        st = self.lib.qnnp_run_operator(op, threadpool)
-        if st != 0:
-            raise QnnpackError("qnnp_run_operator", st)
-
-    def delete_operator_status(self, op) -> Status:
-        return Status(self.lib.qnnp_delete_operator(op))
-
-    def delete_operator(self, op) -> None:
-        st = self.lib.qnnp_delete_operator(op)
-        if st != 0:
-            raise QnnpackError("qnnp_delete_operator", st)
-
-
+@_with_methods_of(GFX950_API)
 class Gfx950Library(QnnpackLibrary):
-    """Product library: qnnpack.h plus the extensions of include/qnnpack_gfx950.h."""
+    """Product library: qnnpack.h plus the extensions of include/qnnpack_gfx950.h (GFX950_API).
+
+    Generated as above: the fused inverted-residual block ([create|setup]_fused_block[_status]) and the residual add
+    folded into a convolution (attach_residual_add[_status]).
+    """
 
     def __init__(self, path: str):
         super().__init__(path)
-        L = self.lib
-        L.qnnp_gfx950_set_device.restype = c_int
-        L.qnnp_gfx950_set_device.argtypes = [c_int]
-        L.qnnp_gfx950_get_device.restype = c_int
-        L.qnnp_gfx950_device_count.restype = c_int
-        L.qnnp_gfx950_device_count.argtypes = []
-        L.qnnp_gfx950_set_stream.restype = c_int
-        L.qnnp_gfx950_set_stream.argtypes = [c_void_p]
-        L.qnnp_gfx950_set_async.restype = c_int
-        L.qnnp_gfx950_set_async.argtypes = [c_int]
-        L.qnnp_gfx950_synchronize.restype = c_int
-        L.qnnp_gfx950_malloc.restype = c_void_p
-        L.qnnp_gfx950_malloc.argtypes = [c_size_t]
-        L.qnnp_gfx950_free.restype = None
-        L.qnnp_gfx950_free.argtypes = [c_void_p]
-        for name in ("qnnp_gfx950_memcpy_h2d", "qnnp_gfx950_memcpy_d2h"):
-            getattr(L, name).restype = c_int
-            getattr(L, name).argtypes = [c_void_p, c_void_p, c_size_t]
-        L.qnnp_gfx950_memset.restype = c_int
-        L.qnnp_gfx950_memset.argtypes = [c_void_p, c_int, c_size_t]
-        L.qnnp_gfx950_time_operator.restype = c_int
-        L.qnnp_gfx950_time_operator.argtypes = [c_void_p, c_int, c_int, POINTER(c_float)]
-        L.qnnp_gfx950_time_operator_rotating.restype = c_int
-        L.qnnp_gfx950_time_operator_rotating.argtypes = [
-            c_void_p, c_size_t, POINTER(c_void_p), POINTER(c_void_p), c_int, c_int, POINTER(c_float)]
-        L.qnnp_gfx950_graph_begin.restype = c_int
-        L.qnnp_gfx950_graph_begin.argtypes = []
-        L.qnnp_gfx950_graph_end.restype = c_int
-        L.qnnp_gfx950_graph_end.argtypes = [POINTER(c_void_p)]
-        L.qnnp_gfx950_graph_launch.restype = c_int
-        L.qnnp_gfx950_graph_launch.argtypes = [c_void_p]
-        L.qnnp_gfx950_graph_synchronize.restype = c_int
-        L.qnnp_gfx950_graph_synchronize.argtypes = [c_void_p]
-        L.qnnp_gfx950_graph_time.restype = c_int
-        L.qnnp_gfx950_graph_time.argtypes = [c_void_p, c_int, c_int, POINTER(c_float)]
-        L.qnnp_gfx950_graph_destroy.restype = None
-        L.qnnp_gfx950_graph_destroy.argtypes = [c_void_p]
-        L.qnnp_gfx950_create_fused_block.restype = c_int
-        L.qnnp_gfx950_create_fused_block.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]
-        L.qnnp_gfx950_setup_fused_block.restype = c_int
-        L.qnnp_gfx950_setup_fused_block.argtypes = [c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
-        # (QNNP_GFX950_LIBRARY may point at an OLDER build for a same-box A/B: entry points younger than it are then
-        #  simply not bound; the product library must have them all -- tests/test_abi.py)
-        if hasattr(L, "qnnp_gfx950_attach_residual_add") or not os.environ.get("QNNP_GFX950_LIBRARY"):
-            L.qnnp_gfx950_attach_residual_add.restype = c_int
-            L.qnnp_gfx950_attach_residual_add.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t]
-            L.qnnp_gfx950_operator_residual_folded.restype = c_int
-            L.qnnp_gfx950_operator_residual_folded.argtypes = [c_void_p]
-        L.qnnp_gfx950_set_option.restype = c_int
-        L.qnnp_gfx950_set_option.argtypes = [c_char_p, c_int]
-        L.qnnp_gfx950_test_force_kernel.restype = c_int           # include/qnnpack_gfx950_test.h
-        L.qnnp_gfx950_test_force_kernel.argtypes = [c_char_p, c_int]
-        L.qnnp_gfx950_test_operator_ran_dense.restype = c_int
-        L.qnnp_gfx950_test_operator_ran_dense.argtypes = [c_void_p]
-        L.qnnp_gfx950_operator_set_streaming_stores.restype = c_int
-        L.qnnp_gfx950_operator_set_streaming_stores.argtypes = [c_void_p, c_int]
-        L.qnnp_gfx950_operator_kernel.restype = c_char_p
-        L.qnnp_gfx950_operator_kernel.argtypes = [c_void_p]
-        L.qnnp_gfx950_device_info.restype = c_int
-        L.qnnp_gfx950_device_info.argtypes = [
-            ctypes.c_char_p, c_size_t, POINTER(c_int), POINTER(c_int), POINTER(c_size_t)]
+        _bind(self.lib, GFX950_API)
 
     def _check(self, call: str, st: int) -> None:
         if st != 0:
@@ -729,37 +376,6 @@ class Gfx950Library(QnnpackLibrary):
         self._check("qnnp_gfx950_time_operator_rotating",
                     self.lib.qnnp_gfx950_time_operator_rotating(op, n, ins, outs, warmup, iters, ctypes.byref(ms)))
         return float(ms.value)
-
-    # ---- fused inverted-residual block (qnnpack_gfx950.h) ----
-    def create_fused_block_status(self, expand, depthwise, project, residual_add=None):
-        handle = c_void_p(None)
-        st = self.lib.qnnp_gfx950_create_fused_block(expand, depthwise, project, residual_add, ctypes.byref(handle))
-        return Status(st), handle.value
-
-    def create_fused_block(self, expand, depthwise, project, residual_add=None) -> int:
-        st, handle = self.create_fused_block_status(expand, depthwise, project, residual_add)
-        if st != Status.success:
-            raise QnnpackError("qnnp_gfx950_create_fused_block", st)
-        return handle
-
-    def setup_fused_block_status(self, op, batch_size, input_height, input_width, input, input_stride,
-                                 output, output_stride) -> Status:
-        return Status(self.lib.qnnp_gfx950_setup_fused_block(
-            op, batch_size, input_height, input_width, address_of(input), input_stride, address_of(output), output_stride))
-
-    def setup_fused_block(self, *args) -> None:
-        st = self.setup_fused_block_status(*args)
-        if st != Status.success:
-            raise QnnpackError("qnnp_gfx950_setup_fused_block", st)
-
-    # ---- residual add folded into a convolution (qnnpack_gfx950.h) ----
-    def attach_residual_add_status(self, convolution, add, residual, residual_stride) -> Status:
-        return Status(self.lib.qnnp_gfx950_attach_residual_add(convolution, add, address_of(residual), residual_stride))
-
-    def attach_residual_add(self, convolution, add, residual, residual_stride) -> None:
-        st = self.attach_residual_add_status(convolution, add, residual, residual_stride)
-        if st != Status.success:
-            raise QnnpackError("qnnp_gfx950_attach_residual_add", st)
 
     def operator_residual_folded(self, op) -> int:
         """After a run: 1 = the add rode in the convolution kernel's epilogue, 0 = separate launch, -1 = none attached."""

@@ -2,7 +2,6 @@
 declare, and fails LOUDLY (no CPU fallback) when no gfx950 device is present."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -10,13 +9,9 @@ import pytest
 import qnnpack_amd
 from qnnpack_amd import Status
 
+from _headers import declared_functions
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared_functions(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(qnnp_[a-z0-9_]+)\s*\(", text)))
 
 
 def test_headers_declare_the_reference_entry_points():
