@@ -9,7 +9,7 @@ Reference interface mirrored: include/qnnpack.h:24-76, 118-140, 327-332.
 Pointers are passed as raw addresses (``int``), numpy arrays (host memory) or
 anything with a ``data_ptr()`` method (e.g. a torch tensor on the bound GPU).
 
-Every C function is described once, in the two tables below; ``argtypes`` / ``restype`` and the operators' methods are
+Every C function is described once, in the tables below; ``argtypes`` / ``restype`` and the operators' methods are
 made from them, and tests/test_binding_signatures.py holds the tables to the prototypes of the public headers.
 """
 from __future__ import annotations
@@ -219,6 +219,26 @@ GFX950_API = (
 
 API = {f.symbol: f for f in QNNPACK_API + GFX950_API}
 
+# include/qnnpack_gfx950_float.h: float32 <-> uint8 at the two ends of a network. A table of its own, bound and installed
+# on Gfx950Library only: API above stays the image of the three headers it is checked against. Float strides count
+# elements, byte strides bytes.
+FLOAT_API = (
+    _op("qnnp_gfx950_create_quantize_nc_f32_q8",
+        "size_t channels, u8 output_zero_point, f32 output_scale, u8 output_min, u8 output_max, u32 flags=0, out quantize",
+        IF_PRESENT, doc="the product's quantize operator: set it up with setup_quantize_nc_f32_q8 (rows) or "
+                        "setup_quantize_nchw_f32_nhwc_q8 (planar float in, NHWC uint8 out)"),
+    _op("qnnp_gfx950_setup_quantize_nc_f32_q8", _SETUP_NC, IF_PRESENT),
+    _op("qnnp_gfx950_setup_quantize_nchw_f32_nhwc_q8",
+        "ptr op, size_t batch_size, size_t pixels, tensor input, tensor output, size_t output_pixel_stride", IF_PRESENT),
+    _op("qnnp_gfx950_create_dequantize_nc_q8_f32",
+        "size_t channels, u8 input_zero_point, f32 input_scale, u32 flags=0, out dequantize",
+        IF_PRESENT, doc="the product's dequantize operator: set it up with setup_dequantize_nc_q8_f32 (rows) or "
+                        "setup_dequantize_nhwc_q8_nchw_f32 (NHWC uint8 in, planar float out)"),
+    _op("qnnp_gfx950_setup_dequantize_nc_q8_f32", _SETUP_NC, IF_PRESENT),
+    _op("qnnp_gfx950_setup_dequantize_nhwc_q8_nchw_f32",
+        "ptr op, size_t batch_size, size_t pixels, tensor input, size_t input_pixel_stride, tensor output", IF_PRESENT),
+)
+
 
 def _bind(lib, table) -> None:
     """Set argtypes / restype of the table's symbols on a loaded library."""
@@ -307,17 +327,19 @@ class QnnpackLibrary:
         return Status(self.lib.qnnp_deinitialize())
 
 
-@_with_methods_of(GFX950_API)
+@_with_methods_of(GFX950_API + FLOAT_API)
 class Gfx950Library(QnnpackLibrary):
-    """Product library: qnnpack.h plus the extensions of include/qnnpack_gfx950.h (GFX950_API).
+    """Product library: qnnpack.h plus the extensions of include/qnnpack_gfx950.h (GFX950_API) and the float32 <-> uint8
+    operators of include/qnnpack_gfx950_float.h (FLOAT_API).
 
-    Generated as above: the fused inverted-residual block ([create|setup]_fused_block[_status]) and the residual add
-    folded into a convolution (attach_residual_add[_status]).
+    Generated as above: the fused inverted-residual block ([create|setup]_fused_block[_status]), the residual add
+    folded into a convolution (attach_residual_add[_status]), and quantize / dequantize with their two setups each.
     """
 
     def __init__(self, path: str):
         super().__init__(path)
         _bind(self.lib, GFX950_API)
+        _bind(self.lib, FLOAT_API)
 
     def _check(self, call: str, st: int) -> None:
         if st != 0:

@@ -428,6 +428,47 @@ struct qnnp_hip_resize_args {
 };
 int qnnp_hip_resize_run(const struct qnnp_hip_resize_args* args, const char** kernel_name);
 
+/* float32 -> uint8 and back (f32q8.hip, linked into libqnnpack_gfx950.so only -- see the Makefile). No reference
+ * counterpart. Every float operation is rounded once (no fused multiply-add):
+ *   quantize:    t = x * inv_scale;  t = isnan(t) ? 0 : t;  t = min(max(t, clamp_lo), clamp_hi);
+ *                y = (uint8) ((int32) rintf(t) + zero_point)                 clamp_* = (float) (output_min|max - zero_point)
+ *   dequantize:  y = (float) ((int32) x - zero_point) * scale
+ * Rows (planar == 0): `rows` rows of `channels` elements; the float stride is in ELEMENTS, the byte stride in bytes.
+ * Planar (planar == 1): the float tensor is dense NCHW -- element (n, c, p) at float index (n * channels + c) * pixels + p
+ * -- and the byte tensor NHWC, pixel (n, p) at byte (n * pixels + p) * byte stride; `rows` is the batch. Input and
+ * output must not overlap. rows, channels, rows * pixels and channels * pixels are below 2^31; float pointers are 4-byte
+ * aligned. */
+struct qnnp_hip_quantize_args {
+  const float* input;
+  uint8_t* output;
+  uint32_t planar;
+  uint32_t rows;
+  uint32_t pixels;            /* planar only */
+  uint32_t channels;
+  uint64_t input_stride;      /* rows: float elements between rows */
+  uint64_t output_stride;     /* rows: bytes between rows; planar: bytes between pixels */
+  float inv_scale;
+  float clamp_lo, clamp_hi;
+  int32_t zero_point;
+  uint32_t streaming_mode;    /* as qnnp_hip_igemm_args: 0 = process default, 1 = off, 2 = on */
+};
+int qnnp_hip_quantize_run(const struct qnnp_hip_quantize_args* args, const char** kernel_name);
+
+struct qnnp_hip_dequantize_args {
+  const uint8_t* input;
+  float* output;
+  uint32_t planar;
+  uint32_t rows;
+  uint32_t pixels;            /* planar only */
+  uint32_t channels;
+  uint64_t input_stride;      /* rows: bytes between rows; planar: bytes between pixels */
+  uint64_t output_stride;     /* rows: float elements between rows */
+  float scale;
+  int32_t zero_point;
+  uint32_t streaming_mode;    /* as qnnp_hip_igemm_args: 0 = process default, 1 = off, 2 = on */
+};
+int qnnp_hip_dequantize_run(const struct qnnp_hip_dequantize_args* args, const char** kernel_name);
+
 /* softargmax (q8softargmax.hip, linked into libqnnpack_gfx950.so only -- see the Makefile): replaces u8rmax_ukernel__sse2,
  * u8lut32norm_ukernel__scalar and the softargmax case of src/operator-run.c:625-637, 1091-1108. For each of `rows` rows
  * of `channels` bytes, each `*_stride` bytes apart, all in uint32_t:

@@ -32,6 +32,8 @@ enum qnnp_ukernel_type {
   qnnp_ukernel_type_softargmax,         /* softargmax.c */
   qnnp_ukernel_type_multiply,           /* multiply.c */
   qnnp_ukernel_type_resize_bilinear,    /* resize-bilinear.c */
+  qnnp_ukernel_type_quantize,           /* quantize.c */
+  qnnp_ukernel_type_dequantize,         /* dequantize.c */
 };
 
 /* One output phase of a strided deconvolution (deconvolution.c): the output pixels whose (oy + pad_top) % stride_h
@@ -136,6 +138,12 @@ struct qnnp_operator {
   int resize_align_corners;
   void* d_resize_table;
   size_t resize_table_capacity;   /* in entries */
+  /* quantize / dequantize (quantize.c, dequantize.c): which setup was the last -- 0 rows (NC; the float tensor's
+   * *_pixel_stride is in elements), 1 planar (dense NCHW float, NHWC bytes; f32_pixels = height * width) -- and
+   * quantize's 1 / output_scale */
+  int f32_planar;
+  size_t f32_pixels;
+  float f32_inv_scale;
 
   uint8_t input_zero_point;
   uint8_t kernel_zero_point;
