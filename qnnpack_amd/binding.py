@@ -62,12 +62,12 @@ _CTYPES = {
     "size_t": c_size_t, "u32": c_uint32, "u8": c_uint8, "f32": c_float, "int": c_int, "str": c_char_p,
     "ptr": c_void_p,        # passed as it is: an operator handle (named `op` where it is the function's own), stream, graph
     "tensor": c_void_p,     # through address_of
-    "u8[]": c_void_p, "i32[]": c_void_p, "u8[256]": c_void_p,   # host array of that dtype (and size), None -> NULL
+    "u8[]": c_void_p, "i32[]": c_void_p, "f32[]": c_void_p, "u8[256]": c_void_p,   # host array of that dtype (and size), None -> NULL
     "out": POINTER(c_void_p),   # a create's trailing handle: not a Python parameter, returned
     "null": c_void_p,           # the setups' threadpool: not a Python parameter, always NULL
     "ptr*": POINTER(c_void_p), "f32*": POINTER(c_float), "int*": POINTER(c_int), "size_t*": POINTER(c_size_t),
 }
-_HOST_ARRAYS = {"u8[]": (np.uint8, None), "i32[]": (np.int32, None), "u8[256]": (np.uint8, 256)}
+_HOST_ARRAYS = {"u8[]": (np.uint8, None), "i32[]": (np.int32, None), "f32[]": (np.float32, None), "u8[256]": (np.uint8, 256)}
 
 # When a symbol is bound at load. QNNP_GFX950_LIBRARY may name an OLDER build for a same-box A/B: entry points younger
 # than it are then simply not bound; the product library must have them all (tests/test_abi.py).
@@ -240,6 +240,23 @@ FLOAT_API = (
 )
 
 
+# include/qnnpack_gfx950_perchannel.h: convolution and fully connected with one weight scale per output channel. A table
+# of its own like FLOAT_API, for the same reason. `kernel_scales`: groups * group_output_channels (output_channels) floats;
+# setup, run and delete are the per-tensor operators' (setup_convolution2d_nhwc_q8, setup_fully_connected_nc_q8, ...).
+_WEIGHTS_Q_PER_CHANNEL = _IN_Q + "u8 kernel_zero_point, f32[] kernel_scales, u8[] kernel, i32[] bias, " + _OUT_Q
+PERCHANNEL_API = (
+    _op("qnnp_gfx950_create_convolution2d_nhwc_q8_per_channel",
+        _PADDING + "u32 kernel_height, u32 kernel_width, u32 subsampling_height, u32 subsampling_width, "
+        "u32 dilation_height, u32 dilation_width, " + _GROUPS + _WEIGHTS_Q_PER_CHANNEL + "convolution", IF_PRESENT,
+        doc="qnnp_create_convolution2d_nhwc_q8 with one kernel scale per output channel (all groups); set it up with "
+            "setup_convolution2d_nhwc_q8"),
+    _op("qnnp_gfx950_create_fully_connected_nc_q8_per_channel",
+        "size_t input_channels, size_t output_channels, " + _WEIGHTS_Q_PER_CHANNEL + "fully_connected", IF_PRESENT,
+        doc="qnnp_create_fully_connected_nc_q8 with one kernel scale per output channel; set it up with "
+            "setup_fully_connected_nc_q8"),
+)
+
+
 def _bind(lib, table) -> None:
     """Set argtypes / restype of the table's symbols on a loaded library."""
     older = bool(os.environ.get("QNNP_GFX950_LIBRARY"))
@@ -327,19 +344,22 @@ class QnnpackLibrary:
         return Status(self.lib.qnnp_deinitialize())
 
 
-@_with_methods_of(GFX950_API + FLOAT_API)
+@_with_methods_of(GFX950_API + FLOAT_API + PERCHANNEL_API)
 class Gfx950Library(QnnpackLibrary):
-    """Product library: qnnpack.h plus the extensions of include/qnnpack_gfx950.h (GFX950_API) and the float32 <-> uint8
-    operators of include/qnnpack_gfx950_float.h (FLOAT_API).
+    """Product library: qnnpack.h plus the extensions of include/qnnpack_gfx950.h (GFX950_API), the float32 <-> uint8
+    operators of include/qnnpack_gfx950_float.h (FLOAT_API) and the per-channel creates of
+    include/qnnpack_gfx950_perchannel.h (PERCHANNEL_API).
 
     Generated as above: the fused inverted-residual block ([create|setup]_fused_block[_status]), the residual add
-    folded into a convolution (attach_residual_add[_status]), and quantize / dequantize with their two setups each.
+    folded into a convolution (attach_residual_add[_status]), quantize / dequantize with their two setups each, and
+    create_convolution2d_nhwc_q8_per_channel / create_fully_connected_nc_q8_per_channel.
     """
 
     def __init__(self, path: str):
         super().__init__(path)
         _bind(self.lib, GFX950_API)
         _bind(self.lib, FLOAT_API)
+        _bind(self.lib, PERCHANNEL_API)
 
     def _check(self, call: str, st: int) -> None:
         if st != 0:

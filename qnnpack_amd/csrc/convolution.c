@@ -22,6 +22,7 @@
 #include <string.h>
 
 #include <qnnpack.h>
+#include <qnnpack_gfx950_perchannel.h>
 
 #include "hip/qnnp_hip.h"
 #include "indirection.h"
@@ -30,6 +31,7 @@
 #include "operator.h"
 #include "bias-pair.h"
 #include "pack.h"
+#include "per-channel.h"
 #include "requantization.h"
 #include "state.h"
 #include "upload.h"
@@ -71,6 +73,11 @@ static enum qnnp_status pack_depthwise(struct qnnp_operator* op, const uint8_t* 
   op->d_bias = (int32_t*) qnnp_upload(host_bias, b_bytes);
   if (op->d_weights == NULL || op->d_bias == NULL) {
     qnnp_log_error("device allocation or upload failed: %zu bytes of packed depthwise weights on the device", w_bytes + b_bytes);
+    goto done;
+  }
+  if (op->per_channel) {
+    /* the kernels of hip/q8dwconv_pc.hip read these two images and the table: nothing below has a reader */
+    status = qnnp_status_success;
     goto done;
   }
   /* 3x3 with weights in int8 range: the register image of the int8 dot-product walk (pack.h); 5x5 likewise: eight rows
@@ -275,6 +282,11 @@ static enum qnnp_status pack_gemm(struct qnnp_operator* op, const uint8_t* kerne
     qnnp_log_error("device allocation or upload failed: %zu bytes of packed weights on the device", w_bytes + 2 * b_bytes);
     return qnnp_status_out_of_memory;
   }
+  if (op->per_channel) {
+    /* the per-channel flavour of the generic kernel reads this image and the table: never the grouped-as-dense image,
+     * the centred one or the row slots */
+    return qnnp_status_success;
+  }
   if (op->ukernel_type == qnnp_ukernel_type_gemm && groups > 1 && groups * gic <= 1024 && groups * goc <= 1024) {
     pack_dense_optional(op, kernel, bias);
   }
@@ -300,7 +312,12 @@ static enum qnnp_status pack_gemm(struct qnnp_operator* op, const uint8_t* kerne
   return pack_rows(op, kernel, bias);
 }
 
+/* kernel_scales == NULL: the per-tensor create with `kernel_scale`. Else the per-channel one: `per_channel` is set,
+ * `kernel_scale` is unused and kernel_scales holds groups * group_output_channels floats. (per_channel with a NULL array
+ * is the refusal the per-channel entry point owes its caller.) */
 static enum qnnp_status qnnp_create_convolution2d_nhwc_q8_impl(
+    int per_channel,
+    const float* kernel_scales,
     uint32_t input_padding_top,
     uint32_t input_padding_right,
     uint32_t input_padding_bottom,
@@ -351,8 +368,12 @@ static enum qnnp_status qnnp_create_convolution2d_nhwc_q8_impl(
     qnnp_log_error("cannot create convolution with %.7g input scale: a scale has to be a finite number above zero", input_scale);
     goto error;
   }
-  if (!scale_is_valid(kernel_scale)) {
-    qnnp_log_error("cannot create convolution with %.7g kernel scale: a scale has to be a finite number above zero", kernel_scale);
+  if (per_channel ? kernel_scales == NULL : !scale_is_valid(kernel_scale)) {
+    if (per_channel) {
+      qnnp_log_error("cannot create convolution: the array of kernel scales may not be NULL");
+    } else {
+      qnnp_log_error("cannot create convolution with %.7g kernel scale: a scale has to be a finite number above zero", kernel_scale);
+    }
     goto error;
   }
   if (!scale_is_valid(output_scale)) {
@@ -363,10 +384,37 @@ static enum qnnp_status qnnp_create_convolution2d_nhwc_q8_impl(
     qnnp_log_error("cannot create convolution: groups, channel counts, kernel and bias may not be zero");
     goto error;
   }
+  const size_t output_channels = (size_t) groups * group_output_channels;
+  if (per_channel) {
+    const size_t bad = qnnp_per_channel_first_invalid(kernel_scales, output_channels);
+    if (bad != output_channels) {
+      qnnp_log_error("cannot create convolution with %.7g kernel scale of channel %zu: a scale has to be a finite number above zero",
+          kernel_scales[bad], bad);
+      goto error;
+    }
+  }
 
   /* reference convolution.c:117-168 (the "inefficiency" notes are informational there) */
   status = qnnp_status_unsupported_parameter;
-  const float convolution_scale = input_scale * kernel_scale / output_scale;
+  float convolution_scale = 0.0f;
+  if (per_channel) {
+    const size_t bad = qnnp_per_channel_first_unsupported(input_scale, kernel_scales, output_scale, output_channels);
+    if (bad != output_channels) {
+      qnnp_log_error(
+          "cannot create convolution with %.7g input scale, %.7g kernel scale of channel %zu, and %.7g output scale: "
+          "convolution scale %.7g is outside [2**-32, 1.0)",
+          input_scale, kernel_scales[bad], bad, output_scale,
+          qnnp_per_channel_scale(input_scale, kernel_scales[bad], output_scale));
+      goto error;
+    }
+    /* (what op->requant carries beside the zero point and the clamp: the largest channel scale) */
+    for (size_t c = 0; c < output_channels; c++) {
+      const float scale = qnnp_per_channel_scale(input_scale, kernel_scales[c], output_scale);
+      if (scale > convolution_scale) convolution_scale = scale;
+    }
+  } else {
+    convolution_scale = input_scale * kernel_scale / output_scale;
+  }
   if (convolution_scale >= 1.0f) {
     qnnp_log_error(
         "cannot create convolution with %.7g input scale, %.7g kernel scale, and %.7g output scale: "
@@ -422,6 +470,7 @@ static enum qnnp_status qnnp_create_convolution2d_nhwc_q8_impl(
   op->group_output_channels = group_output_channels;
   op->input_zero_point = input_zero_point;
   op->kernel_zero_point = kernel_zero_point;
+  op->per_channel = per_channel;
   op->requant = qnnp_compute_requant(convolution_scale, output_zero_point, output_min, output_max);
   op->requant.accumulator_bits = qnnp_accumulator_bits(bias, (size_t) groups * group_output_channels,
       kernel_size * group_input_channels);
@@ -430,6 +479,17 @@ static enum qnnp_status qnnp_create_convolution2d_nhwc_q8_impl(
   status = ukernel_type == qnnp_ukernel_type_dwconv ? pack_depthwise(op, kernel, bias) : pack_gemm(op, kernel, bias);
   if (status != qnnp_status_success) {
     goto error;
+  }
+  if (per_channel) {
+    /* one entry per output channel, padded to the kernels' channel pad: c_pad for depthwise (its "groups" are channels of
+     * one run), n_pad per group for the GEMM image */
+    op->d_requant_pc = ukernel_type == qnnp_ukernel_type_dwconv
+        ? qnnp_per_channel_upload_table(1, groups, op->c_pad, input_scale, kernel_scales, output_scale)
+        : qnnp_per_channel_upload_table(groups, group_output_channels, op->n_pad, input_scale, kernel_scales, output_scale);
+    if (op->d_requant_pc == NULL) {
+      status = qnnp_status_out_of_memory;
+      goto error;
+    }
   }
 
   /* reference convolution.c:372: the handle is written only on success */
@@ -605,10 +665,50 @@ enum qnnp_status qnnp_create_convolution2d_nhwc_q8(
     return status;
   }
   return qnnp_leave_create(token,
-      qnnp_create_convolution2d_nhwc_q8_impl(input_padding_top, input_padding_right, input_padding_bottom,
+      qnnp_create_convolution2d_nhwc_q8_impl(0, NULL, input_padding_top, input_padding_right, input_padding_bottom,
           input_padding_left, kernel_height, kernel_width, subsampling_height, subsampling_width, dilation_height,
           dilation_width, groups, group_input_channels, group_output_channels, input_zero_point, input_scale,
           kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max,
+          flags, convolution_out));
+}
+
+enum qnnp_status qnnp_gfx950_create_convolution2d_nhwc_q8_per_channel(
+    uint32_t input_padding_top,
+    uint32_t input_padding_right,
+    uint32_t input_padding_bottom,
+    uint32_t input_padding_left,
+    uint32_t kernel_height,
+    uint32_t kernel_width,
+    uint32_t subsampling_height,
+    uint32_t subsampling_width,
+    uint32_t dilation_height,
+    uint32_t dilation_width,
+    uint32_t groups,
+    size_t group_input_channels,
+    size_t group_output_channels,
+    uint8_t input_zero_point,
+    float input_scale,
+    uint8_t kernel_zero_point,
+    const float* kernel_scales,
+    const uint8_t* kernel,
+    const int32_t* bias,
+    uint8_t output_zero_point,
+    float output_scale,
+    uint8_t output_min,
+    uint8_t output_max,
+    uint32_t flags,
+    qnnp_operator_t* convolution_out)
+{
+  int token;
+  const enum qnnp_status status = qnnp_enter_create("qnnp_gfx950_create_convolution2d_nhwc_q8_per_channel", &token);
+  if (status != qnnp_status_success) {
+    return status;
+  }
+  return qnnp_leave_create(token,
+      qnnp_create_convolution2d_nhwc_q8_impl(1, kernel_scales, input_padding_top, input_padding_right,
+          input_padding_bottom, input_padding_left, kernel_height, kernel_width, subsampling_height, subsampling_width,
+          dilation_height, dilation_width, groups, group_input_channels, group_output_channels, input_zero_point,
+          input_scale, kernel_zero_point, 0.0f, kernel, bias, output_zero_point, output_scale, output_min, output_max,
           flags, convolution_out));
 }
 

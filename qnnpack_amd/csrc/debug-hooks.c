@@ -18,6 +18,8 @@
 #include "requantization.h"
 #include "resize-table.h"
 #include "hip/requant_math.h"
+#include "hip/requant_pc.h"
+#include "per-channel.h"
 
 void qnnp_debug_pack_igemm_w(
     uint32_t groups, uint32_t n, uint32_t k_total, uint32_t n_pad, uint32_t k_pad,
@@ -206,6 +208,27 @@ void qnnp_debug_requant_lane(
     if (y > hi) y = hi;
     out[i] = (uint8_t) (y + zp_late);
   }
+}
+
+/* the per-channel kernels' requantization (hip/requant_pc.h) on the host, with the multiplier and shift that
+ * qnnp_compute_requant derives from `scale` */
+void qnnp_debug_requant_pc(
+    size_t count, const int32_t* acc, float scale, uint8_t zero_point, uint8_t qmin, uint8_t qmax, uint8_t* out)
+{
+  const struct qnnp_hip_requant rq = qnnp_compute_requant(scale, zero_point, qmin, qmax);
+  for (size_t i = 0; i < count; i++) {
+    out[i] = (uint8_t) qnnp_requant_pc(acc[i], rq.multiplier, rq.shift, rq.output_min_less_zero_point,
+        rq.output_max_less_zero_point, rq.output_zero_point);
+  }
+}
+
+/* the table a per-channel create uploads (per-channel.h): `table` holds groups * group_pad {multiplier, shift} pairs */
+void qnnp_debug_per_channel_table(
+    uint32_t groups, size_t group_channels, uint32_t group_pad, float input_scale, const float* kernel_scales,
+    float output_scale, int32_t* table)
+{
+  qnnp_per_channel_fill_table((struct qnnp_requant_pc_entry*) table, groups, group_channels, group_pad, input_scale,
+      kernel_scales, output_scale);
 }
 
 void qnnp_debug_pack_igemm_w_slots(

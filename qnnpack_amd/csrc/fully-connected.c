@@ -14,6 +14,7 @@
 #include <stdlib.h>
 
 #include <qnnpack.h>
+#include <qnnpack_gfx950_perchannel.h>
 
 #include "hip/qnnp_hip.h"
 #include "lifecycle.h"
@@ -21,6 +22,7 @@
 #include "operator.h"
 #include "bias-pair.h"
 #include "pack.h"
+#include "per-channel.h"
 #include "requantization.h"
 #include "state.h"
 
@@ -29,7 +31,11 @@ static inline bool scale_is_valid(float scale)
   return scale > 0.0f && isnormal(scale);
 }
 
+/* kernel_scales == NULL: the per-tensor create with `kernel_scale`. Else the per-channel one: `per_channel` is set,
+ * `kernel_scale` is unused and kernel_scales holds output_channels floats (convolution.c has the same pair). */
 static enum qnnp_status qnnp_create_fully_connected_nc_q8_impl(
+    int per_channel,
+    const float* kernel_scales,
     size_t input_channels,
     size_t output_channels,
     uint8_t input_zero_point,
@@ -56,8 +62,12 @@ static enum qnnp_status qnnp_create_fully_connected_nc_q8_impl(
     qnnp_log_error("cannot create fully connected operator with %.7g input scale: a scale has to be a finite number above zero", input_scale);
     goto error;
   }
-  if (!scale_is_valid(kernel_scale)) {
-    qnnp_log_error("cannot create fully connected operator with %.7g kernel scale: a scale has to be a finite number above zero", kernel_scale);
+  if (per_channel ? kernel_scales == NULL : !scale_is_valid(kernel_scale)) {
+    if (per_channel) {
+      qnnp_log_error("cannot create fully connected operator: the array of kernel scales may not be NULL");
+    } else {
+      qnnp_log_error("cannot create fully connected operator with %.7g kernel scale: a scale has to be a finite number above zero", kernel_scale);
+    }
     goto error;
   }
   if (!scale_is_valid(output_scale)) {
@@ -68,10 +78,36 @@ static enum qnnp_status qnnp_create_fully_connected_nc_q8_impl(
     qnnp_log_error("cannot create fully connected operator: channel counts, kernel and bias may not be zero");
     goto error;
   }
+  if (per_channel) {
+    const size_t bad = qnnp_per_channel_first_invalid(kernel_scales, output_channels);
+    if (bad != output_channels) {
+      qnnp_log_error("cannot create fully connected operator with %.7g kernel scale of channel %zu: a scale has to be a "
+          "finite number above zero", kernel_scales[bad], bad);
+      goto error;
+    }
+  }
 
   /* reference fully-connected.c:69-78 */
   status = qnnp_status_unsupported_parameter;
-  const float requantization_scale = input_scale * kernel_scale / output_scale;
+  float requantization_scale = 0.0f;
+  if (per_channel) {
+    const size_t bad = qnnp_per_channel_first_unsupported(input_scale, kernel_scales, output_scale, output_channels);
+    if (bad != output_channels) {
+      qnnp_log_error(
+          "cannot create fully connected operator with %.7g input scale, %.7g kernel scale of channel %zu, and %.7g output "
+          "scale: requantization scale %.7g is outside [2**-32, 1.0)",
+          input_scale, kernel_scales[bad], bad, output_scale,
+          qnnp_per_channel_scale(input_scale, kernel_scales[bad], output_scale));
+      goto error;
+    }
+    /* (what op->requant carries beside the zero point and the clamp: the largest channel scale) */
+    for (size_t c = 0; c < output_channels; c++) {
+      const float scale = qnnp_per_channel_scale(input_scale, kernel_scales[c], output_scale);
+      if (scale > requantization_scale) requantization_scale = scale;
+    }
+  } else {
+    requantization_scale = input_scale * kernel_scale / output_scale;
+  }
   if (requantization_scale >= 1.0f) {
     qnnp_log_error(
         "cannot create fully connected operator with %.7g input scale, %.7g kernel scale, and %.7g output scale: "
@@ -118,7 +154,14 @@ static enum qnnp_status qnnp_create_fully_connected_nc_q8_impl(
   /* The big GEMM kernel's zero-point-centred image (pack.h, hip/q8gemm256c.hip): kernel zero point 128 IS the
    * standard image; 127 (the reference benchmarks' value, bench/q8gemm.cc:60-64) gets its own, for the shapes that
    * kernel takes (no K padding, channel blocks of 256, MFMA-bound sizes). */
-  if (kernel_zero_point == 128) {
+  if (per_channel) {
+    /* the per-channel flavour of the generic kernel reads the standard image and this table, nothing else */
+    op->per_channel = 1;
+    op->d_requant_pc = qnnp_per_channel_upload_table(1, output_channels, n_pad, input_scale, kernel_scales, output_scale);
+    if (op->d_requant_pc == NULL) {
+      goto error;
+    }
+  } else if (kernel_zero_point == 128) {
     op->centre_flip = 0x80;
   } else if (kernel_zero_point == 127 && k_pad == input_channels &&
              /* (the 256-wide tiling's shapes, or the 128-wide one's: hip/q8gemm128x.hip takes any K % 64 == 0) */
@@ -244,8 +287,35 @@ enum qnnp_status qnnp_create_fully_connected_nc_q8(
     return status;
   }
   return qnnp_leave_create(token,
-      qnnp_create_fully_connected_nc_q8_impl(input_channels, output_channels, input_zero_point, input_scale,
+      qnnp_create_fully_connected_nc_q8_impl(0, NULL, input_channels, output_channels, input_zero_point, input_scale,
           kernel_zero_point, kernel_scale, kernel, bias, output_zero_point, output_scale, output_min, output_max,
+          flags, fully_connected_out));
+}
+
+enum qnnp_status qnnp_gfx950_create_fully_connected_nc_q8_per_channel(
+    size_t input_channels,
+    size_t output_channels,
+    uint8_t input_zero_point,
+    float input_scale,
+    uint8_t kernel_zero_point,
+    const float* kernel_scales,
+    const uint8_t* kernel,
+    const int32_t* bias,
+    uint8_t output_zero_point,
+    float output_scale,
+    uint8_t output_min,
+    uint8_t output_max,
+    uint32_t flags,
+    qnnp_operator_t* fully_connected_out)
+{
+  int token;
+  const enum qnnp_status status = qnnp_enter_create("qnnp_gfx950_create_fully_connected_nc_q8_per_channel", &token);
+  if (status != qnnp_status_success) {
+    return status;
+  }
+  return qnnp_leave_create(token,
+      qnnp_create_fully_connected_nc_q8_impl(1, kernel_scales, input_channels, output_channels, input_zero_point,
+          input_scale, kernel_zero_point, 0.0f, kernel, bias, output_zero_point, output_scale, output_min, output_max,
           flags, fully_connected_out));
 }
 

@@ -222,6 +222,11 @@ static enum qnnp_status qnnp_gfx950_create_fused_block_impl(
   if (depthwise == NULL || project == NULL || fused_out == NULL) {
     return qnnp_status_invalid_parameter;
   }
+  /* the fused kernels requantize per tensor (qnnpack_gfx950_perchannel.h): a per-channel member keeps the block unfused */
+  if (depthwise->per_channel || project->per_channel || (expand != NULL && expand->per_channel)) {
+    qnnp_log_error("cannot create fused block: a member has per-channel weight scales");
+    return qnnp_status_unsupported_parameter;
+  }
   /* the shapes the fused kernel is written for; anything else stays with the stand-alone operators */
   if (depthwise->ukernel_type != qnnp_ukernel_type_dwconv ||
       depthwise->kernel_height != 3 || depthwise->kernel_width != 3 ||

@@ -130,6 +130,45 @@ __device__ __forceinline__ void igemm_store_pk4(
   }
 }
 
+/* Per-channel requantization (requant_pc.h) of one 32 x 32 tile: `table` points at the entry of the tile's first channel
+ * (table + group * n_pad + ncol0; 32 entries follow, pad entries valid). The lane's register run rg is the four
+ * consecutive channels 8 rg + 4 khalf ...: their entries are two 16-byte loads (L1 / L2 resident) inside the loop, not
+ * sixteen entries held across the tile -- the 128 x 128 flavour is at the register limit. Plain C++ on the accumulators:
+ * the compiler pads the MFMA-result hazard itself (requant.hip.h says what happened when inline asm read them).
+ * Both store paths: STAGED writes the lane's 16 bytes into the LDS image (`dst` = LDS row, `col0` = the tile's first
+ * column in the workgroup tile; all 64 lanes take part in the exchange), else `dst` is the output row and the stores
+ * are those of igemm_store_pk4. */
+template <bool STAGED>
+__device__ __forceinline__ void igemm_tile_pc(
+    const v16i& acc, const int4 (&bias)[4], int32_t rowterm, const qnnp_requant_pc_entry* table,
+    uint8_t* dst, uint32_t col0, uint32_t khalf, bool row_ok, const IgemmParams& p)
+{
+  uint32_t pk[4];
+#pragma unroll
+  for (int rg = 0; rg < 4; rg++) {
+    const int4* e = reinterpret_cast<const int4*>(table + rg * 8 + khalf * 4);
+    const int4 e01 = e[0], e23 = e[1];       // {m0, s0, m1, s1}, {m2, s2, m3, s3}
+    const int32_t v0 = add_wrap(acc[rg * 4 + 0], rowterm, bias[rg].x);
+    const int32_t v1 = add_wrap(acc[rg * 4 + 1], rowterm, bias[rg].y);
+    const int32_t v2 = add_wrap(acc[rg * 4 + 2], rowterm, bias[rg].z);
+    const int32_t v3 = add_wrap(acc[rg * 4 + 3], rowterm, bias[rg].w);
+    const uint32_t y0 = static_cast<uint32_t>(qnnp_requant_pc(v0, e01.x, static_cast<uint32_t>(e01.y), p.pc_lo, p.pc_hi, p.pc_zp));
+    const uint32_t y1 = static_cast<uint32_t>(qnnp_requant_pc(v1, e01.z, static_cast<uint32_t>(e01.w), p.pc_lo, p.pc_hi, p.pc_zp));
+    const uint32_t y2 = static_cast<uint32_t>(qnnp_requant_pc(v2, e23.x, static_cast<uint32_t>(e23.y), p.pc_lo, p.pc_hi, p.pc_zp));
+    const uint32_t y3 = static_cast<uint32_t>(qnnp_requant_pc(v3, e23.z, static_cast<uint32_t>(e23.w), p.pc_lo, p.pc_hi, p.pc_zp));
+    pk[rg] = y0 | (y1 << 8) | (y2 << 16) | (y3 << 24);
+  }
+  if constexpr (STAGED) {
+    const auto s02 = __builtin_amdgcn_permlane32_swap(pk[0], pk[2], false, false);
+    const auto s13 = __builtin_amdgcn_permlane32_swap(pk[1], pk[3], false, false);
+    if (row_ok) {
+      *reinterpret_cast<uint4*>(dst + col0 + khalf * 16) = make_uint4(s02[0], s02[1], s13[0], s13[1]);
+    }
+  } else {
+    igemm_store_pk4(pk, dst, col0, khalf, row_ok, p);
+  }
+}
+
 /* The same for the lane forms of the requantization (requant.hip.h): the accumulators started from the bias table
  * that carries 2^31, `addend` = lane_addend(row term of this lane's row). */
 template <int SEQ, bool FULL_RANGE, bool RESIDUAL = false>

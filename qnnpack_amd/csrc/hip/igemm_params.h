@@ -10,6 +10,7 @@
 
 #include "qnnp_hip.h"
 #include "requant.hip.h"
+#include "requant_pc.h"
 
 namespace qnnp {
 
@@ -104,6 +105,11 @@ struct IgemmParams {
   // m / rows_per_image == hi32(m * magic)), else 0 = divide. offsets_dense == 0: the kernel never looks at `offsets`.
   uint32_t offsets_dense;
   uint32_t rpi_magic;
+  // per-channel requantization (the PC flavour of the generic kernel only; behind everything else, as above, so that the
+  // kernels that never look at it keep their argument offsets): table [groups][n_pad] of (multiplier, shift), pad entries
+  // valid, and the operator's clamp (less the zero point) and zero point. nullptr: `rq` is the whole requantization.
+  const qnnp_requant_pc_entry* rq_pc;
+  int32_t pc_lo, pc_hi, pc_zp;
 };
 
 /* convolution geometry for the LDS-tiled direct-convolution kernel */

@@ -46,6 +46,10 @@
 
 extern "C" void* qnnp_hip_get_stream(void);
 
+/* q8dwconv_pc.hip: operators with per-channel requantization. Weak: that file is linked into libqnnpack_gfx950.so only
+ * (see the Makefile), and a library without it refuses such an operator at run. */
+extern "C" int qnnp_hip_dwconv_pc_run(const struct qnnp_hip_dwconv_args* a, const char** kernel_name) __attribute__((weak));
+
 namespace {
 
 using qnnp::buffer_rsrc;
@@ -2648,6 +2652,13 @@ int make_plan(DwParams& p, const struct qnnp_hip_dwconv_args* a, uintptr_t in_ad
 extern "C" int qnnp_hip_dwconv_run(const struct qnnp_hip_dwconv_args* a, const char** kernel_name)
 {
   if (a == nullptr || a->batch == 0 || a->channels == 0) return QNNP_HIP_EINVAL;
+  // Per-channel operators (a table of multipliers and shifts): the kernels of q8dwconv_pc.hip and nothing else -- no kernel
+  // of this file reads the table, so a forced one is refused, never run per tensor.
+  if (a->rq_pc != nullptr) {
+    if (a->variant != 0) return QNNP_HIP_EINVAL;
+    if (qnnp_hip_dwconv_pc_run == nullptr) return QNNP_HIP_EINVAL;
+    return qnnp_hip_dwconv_pc_run(a, kernel_name);
+  }
   DwParams p;
   p.input = a->input;
   p.output = a->output;

@@ -102,7 +102,9 @@ __device__ __forceinline__ void fill_vec(uint32_t fill, uint32_t (&w)[4], int j)
  * next row tile are issued before the epilogue of the current one, so the (latency-bound) global reads
  * overlap the (VALU-bound) requantization instead of alternating with it.
  */
-template <int WM, int WN, int TM, int TN, int VEC, bool IS_CONV, bool PAD3 = false>
+// PC: per-channel requantization (igemm_tile_pc, igemm_epilogue.hip.h) in place of the per-operator sequences; the main
+// loop is the same code. The `false` instantiations are the kernels of every per-tensor operator.
+template <int WM, int WN, int TM, int TN, int VEC, bool IS_CONV, bool PAD3 = false, bool PC = false>
 __global__ __launch_bounds__(WM * WN * 64, (TM * TN >= 4) ? 2 : 3)
 void q8_igemm_mfma_kernel(const IgemmParams p_in)
 {
@@ -405,7 +407,45 @@ void q8_igemm_mfma_kernel(const IgemmParams p_in)
     __syncthreads();
 
     // ---- fused epilogue (igemm_epilogue.hip.h); the requantization flavour is chosen once per tile ----
-    if (p.store_mode == 2 && p.out_rows == nullptr) {
+    if constexpr (PC) {
+      const qnnp_requant_pc_entry* table = p.rq_pc + static_cast<uint64_t>(g) * p.n_pad;
+      const bool staged = p.store_mode == 2 && p.out_rows == nullptr;
+#pragma unroll
+      for (int tm = 0; tm < TM; tm++) {
+        const uint32_t row = frag_row0 + tm * 32;
+        const uint32_t m = m_tile * BM + row;
+        const int32_t rowterm = p.row_coeff * lds_rowsum[row];
+        uint64_t out_pixel = m;
+        if (p.out_rows != nullptr && m < p.rows) {
+          const uint32_t img_m = m / p.rows_per_image;
+          out_pixel = static_cast<uint64_t>(img_m) * p.out_image_rows +
+                      static_cast<uint32_t>(p.out_rows[m - img_m * p.rows_per_image]);
+        }
+        uint8_t* out_row = p.output + out_pixel * p.output_stride + static_cast<uint64_t>(g) * p.n;
+#pragma unroll
+        for (int tn = 0; tn < TN; tn++) {
+          const uint32_t nb = nb0 + tn;
+          if (nb >= nblocks) continue;       // wave-uniform
+          if (staged) {
+            qnnp::igemm_tile_pc<true>(acc[tm][tn], bias4[tn], rowterm, table + nb * 32, lds_out + row * OUT_PITCH,
+                                      (wn * TN + tn) * 32, frag_khalf, true, p);
+          } else {
+            qnnp::igemm_tile_pc<false>(acc[tm][tn], bias4[tn], rowterm, table + nb * 32, out_row, nb * 32, frag_khalf, m < p.rows, p);
+          }
+        }
+      }
+      if (staged) {
+        __syncthreads();
+        const uint32_t m0 = m_tile * BM;
+        const uint32_t n0 = n_tile * BN;
+        const uint32_t rows_valid = min(static_cast<uint32_t>(BM), p.rows - m0);
+        const uint32_t n_valid = min(static_cast<uint32_t>(BN), p.n - n0);
+        qnnp::igemm_copy_out<NT>(
+            lds_out, OUT_PITCH, rows_valid, n_valid,
+            p.output + static_cast<uint64_t>(m0) * p.output_stride + static_cast<uint64_t>(g) * p.n + n0,
+            p.output_stride, tid);
+      }
+    } else if (p.store_mode == 2 && p.out_rows == nullptr) {
       // staged: requantized tile -> LDS (row-major image of the output) -> line-sized coalesced stores
       qnnp::requant_dispatch_ofs(p.rq, [&](auto shift0, auto full) {
 #pragma unroll
@@ -456,7 +496,7 @@ void q8_igemm_mfma_kernel(const IgemmParams p_in)
   }
 }
 
-template <int WM, int WN, int TM, int TN, int VEC, bool IS_CONV, bool PAD3 = false>
+template <int WM, int WN, int TM, int TN, int VEC, bool IS_CONV, bool PAD3 = false, bool PC = false>
 int launch_generic(const IgemmParams& p, uint32_t groups, hipStream_t stream)
 {
   constexpr int BM = WM * TM * 32;
@@ -469,7 +509,7 @@ int launch_generic(const IgemmParams& p, uint32_t groups, hipStream_t stream)
   if (blocks_per_cu == 0) {
     int nb = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &nb, q8_igemm_mfma_kernel<WM, WN, TM, TN, VEC, IS_CONV, PAD3>, WM * WN * 64, 0) != hipSuccess || nb < 1) {
+            &nb, q8_igemm_mfma_kernel<WM, WN, TM, TN, VEC, IS_CONV, PAD3, PC>, WM * WN * 64, 0) != hipSuccess || nb < 1) {
       (void) hipGetLastError();
       nb = 2;
     }
@@ -481,33 +521,36 @@ int launch_generic(const IgemmParams& p, uint32_t groups, hipStream_t stream)
   if (ctas_m > tiles_m) ctas_m = tiles_m;
   const dim3 grid(ctas_m * tiles_n, groups, 1);     // (with a phase table `groups` is the number of phases)
   const dim3 block(WM * WN * 64, 1, 1);
-  hipLaunchKernelGGL((q8_igemm_mfma_kernel<WM, WN, TM, TN, VEC, IS_CONV, PAD3>), grid, block, 0, stream, p);
+  hipLaunchKernelGGL((q8_igemm_mfma_kernel<WM, WN, TM, TN, VEC, IS_CONV, PAD3, PC>), grid, block, 0, stream, p);
   return launch_status();
 }
 
-template <int VEC, bool IS_CONV, bool PAD3 = false>
+template <int VEC, bool IS_CONV, bool PAD3 = false, bool PC = false>
 int dispatch_tile(const IgemmParams& p, uint32_t groups, hipStream_t stream, const char** name)
 {
   if (p.n_pad <= 32) {
-    *name = PAD3 ? "q8_igemm_mfma_128x32_c3" : "q8_igemm_mfma_128x32";
-    return launch_generic<4, 1, 1, 1, VEC, IS_CONV, PAD3>(p, groups, stream);
+    *name = PC ? (PAD3 ? "q8_igemm_pc_mfma_128x32_c3" : "q8_igemm_pc_mfma_128x32")
+               : (PAD3 ? "q8_igemm_mfma_128x32_c3" : "q8_igemm_mfma_128x32");
+    return launch_generic<4, 1, 1, 1, VEC, IS_CONV, PAD3, PC>(p, groups, stream);
   }
   if (p.n_pad <= 64) {
-    *name = PAD3 ? "q8_igemm_mfma_128x64_c3" : "q8_igemm_mfma_128x64";
-    return launch_generic<4, 1, 1, 2, VEC, IS_CONV, PAD3>(p, groups, stream);
+    *name = PC ? (PAD3 ? "q8_igemm_pc_mfma_128x64_c3" : "q8_igemm_pc_mfma_128x64")
+               : (PAD3 ? "q8_igemm_mfma_128x64_c3" : "q8_igemm_mfma_128x64");
+    return launch_generic<4, 1, 1, 2, VEC, IS_CONV, PAD3, PC>(p, groups, stream);
   }
-  *name = PAD3 ? "q8_igemm_mfma_128x128_c3" : "q8_igemm_mfma_128x128";
-  return launch_generic<2, 2, 2, 2, VEC, IS_CONV, PAD3>(p, groups, stream);
+  *name = PC ? (PAD3 ? "q8_igemm_pc_mfma_128x128_c3" : "q8_igemm_pc_mfma_128x128")
+             : (PAD3 ? "q8_igemm_mfma_128x128_c3" : "q8_igemm_mfma_128x128");
+  return launch_generic<2, 2, 2, 2, VEC, IS_CONV, PAD3, PC>(p, groups, stream);
 }
 
-template <bool IS_CONV>
+template <bool IS_CONV, bool PC = false>
 int dispatch_vec(const IgemmParams& p, uint32_t groups, uint32_t vec, hipStream_t stream, const char** name)
 {
   switch (vec) {
-    case 16: return dispatch_tile<16, IS_CONV>(p, groups, stream, name);
-    case 8: return dispatch_tile<8, IS_CONV>(p, groups, stream, name);
-    case 4: return dispatch_tile<4, IS_CONV>(p, groups, stream, name);
-    default: return dispatch_tile<1, IS_CONV>(p, groups, stream, name);
+    case 16: return dispatch_tile<16, IS_CONV, false, PC>(p, groups, stream, name);
+    case 8: return dispatch_tile<8, IS_CONV, false, PC>(p, groups, stream, name);
+    case 4: return dispatch_tile<4, IS_CONV, false, PC>(p, groups, stream, name);
+    default: return dispatch_tile<1, IS_CONV, false, PC>(p, groups, stream, name);
   }
 }
 
@@ -589,6 +632,11 @@ int derive(const struct qnnp_hip_igemm_args* a, IgemmSetup& s)
   if (p.bias2u == nullptr) p.lane.kind = 0;      // no table to start from: the offset forms
   p.stream_out = a->streaming_mode == 0 ? (qnnp_hip_streaming_stores() != 0 ? 1u : 0u) : (a->streaming_mode == 2 ? 1u : 0u);
   p.a_flip = 0;
+  // per-channel requantization: the table, and the operator's clamp and zero point as the definition takes them
+  p.rq_pc = a->rq_pc;
+  p.pc_lo = a->rq.output_min_less_zero_point;
+  p.pc_hi = a->rq.output_max_less_zero_point;
+  p.pc_zp = a->rq.output_zero_point;
   // a table row per output pixel with its one tap inside the image: a strided 1x1 convolution without padding taps
   p.offsets_dense = (a->offsets != nullptr && a->ks == 1 && a->kernel_height == 1 && a->kernel_width == 1 && a->groups == 1 &&
                      a->pad_top == 0 && a->pad_left == 0 && a->rows_per_image > 0 && a->output_height > 0 && a->output_width > 0 &&
@@ -760,6 +808,13 @@ bool supported(const IgemmSetup& s, const struct qnnp_hip_igemm_args* a, Kernel 
 int make_plan(const IgemmSetup& s, const struct qnnp_hip_igemm_args* a, IgemmPlan* plan)
 {
   const Image wave_image = s.centred && a->groups == 1 ? Image::Centred : Image::Standard;
+  // Per-channel operators: the per-channel flavour of the generic kernel, before any other rule. It is the only kernel that
+  // reads the table, so a forced code other than the generic kernel's is refused, never run per tensor.
+  if (a->rq_pc != nullptr) {
+    if ((a->variant != 0 && a->variant != 1) || s.p.d2s_sh != 0 || a->residual != nullptr) return QNNP_HIP_EINVAL;
+    *plan = IgemmPlan{Kernel::Generic, Image::Standard, 0u};
+    return QNNP_HIP_OK;
+  }
   if (s.p.d2s_sh != 0 && a->variant != kCodePw) return QNNP_HIP_EINVAL;   // depth-to-space exists in the streaming kernel only
   if (a->variant != 0) {
     *plan = forced_plan(a->variant, wave_image);
@@ -905,6 +960,12 @@ int launch(const IgemmSetup& s, const struct qnnp_hip_igemm_args* a, const Igemm
     case Kernel::BigC: rc = qnnp::gemm256c_launch(q, a->groups, stream, &name, plan.option); break;
     case Kernel::BigX: rc = qnnp::gemm256x_launch(q, a->groups, stream, &name); break;
     case Kernel::Generic:
+      if (a->rq_pc != nullptr) {
+        if (s.pad3) rc = dispatch_tile<4, true, true, true>(p, a->groups, stream, &name);
+        else if (a->offsets != nullptr) rc = dispatch_vec<true, true>(p, a->phases != nullptr ? a->nphases * a->groups : a->groups, s.vec, stream, &name);
+        else rc = dispatch_vec<false, true>(p, a->groups, s.vec, stream, &name);
+        break;
+      }
       if (s.pad3) rc = dispatch_tile<4, true, true>(p, a->groups, stream, &name);
       else if (a->offsets != nullptr) rc = dispatch_vec<true>(p, a->phases != nullptr ? a->nphases * a->groups : a->groups, s.vec, stream, &name);
       else rc = dispatch_vec<false>(p, a->groups, s.vec, stream, &name);

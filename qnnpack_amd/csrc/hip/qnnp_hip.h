@@ -131,6 +131,7 @@ struct qnnp_hip_igemm_phase {
 };
 
 struct qnnp_hip_add_params;
+struct qnnp_requant_pc_entry;   /* requant_pc.h */
 struct qnnp_hip_igemm_args {
   const uint8_t* input;
   uint8_t* output;
@@ -196,6 +197,12 @@ struct qnnp_hip_igemm_args {
   /* the streaming-store hint of THIS launch (qnnp_gfx950_operator_set_streaming_stores): 0 = the process default
    * ("streaming_stores" option), 1 = off, 2 = on */
   uint32_t streaming_mode;
+  /* optional per-channel requantization (include/qnnpack_gfx950_perchannel.h; convolution.c / fully-connected.c): device
+   * table [groups][n_pad] of (multiplier, shift), entry g * n_pad + c for output channel c of group g, pad entries valid;
+   * `rq` then supplies the zero point and the clamp only. NULL: `rq` is the whole requantization. The operator runs on
+   * the per-channel flavour of the generic kernel (variant 0 or 1; any other code: QNNP_HIP_EINVAL). (Behind everything
+   * else, like `residual` in IgemmParams: nothing that was here moves.) */
+  const struct qnnp_requant_pc_entry* rq_pc;
 };
 int qnnp_hip_igemm_run(const struct qnnp_hip_igemm_args* args, const char** kernel_name);
 
@@ -265,8 +272,14 @@ struct qnnp_hip_dwconv_args {
   int variant;                /* 0 auto, 1 generic direct, 2 LDS-tiled, 3 register sliding window (3x3), 4 matrix-core (gather), 5 matrix-core (LDS band), 6 column-sliding window (3x3) */
   struct qnnp_hip_dwconv_plan* plan;   /* optional plan cache owned by the caller (NULL: plan on every call) */
   uint32_t streaming_mode;    /* as qnnp_hip_igemm_args: 0 = process default, 1 = off, 2 = on */
+  /* optional per-channel requantization, as in qnnp_hip_igemm_args: device table [c_pad], pad entries valid. The operator
+   * runs on the kernels of q8dwconv_pc.hip (variant 0 only; any other code: QNNP_HIP_EINVAL). */
+  const struct qnnp_requant_pc_entry* rq_pc;
 };
 int qnnp_hip_dwconv_run(const struct qnnp_hip_dwconv_args* args, const char** kernel_name);
+/* the same for arguments with a per-channel table (q8dwconv_pc.hip, linked into libqnnpack_gfx950.so only -- see the
+ * Makefile); qnnp_hip_dwconv_run hands such arguments over, the host code calls only that */
+int qnnp_hip_dwconv_pc_run(const struct qnnp_hip_dwconv_args* args, const char** kernel_name);
 
 /* ---- q8 element-wise add and global average pooling ("next" row 4) --------------
  * HBM-bound byte kernels (q8pointwise.hip).

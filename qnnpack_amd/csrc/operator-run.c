@@ -99,6 +99,7 @@ static int launch_kernel(struct qnnp_operator* op, const void* input, const void
         .rq = op->requant,
         .variant = op->variant,
         .plan = &op->dw_plan,
+        .rq_pc = (const struct qnnp_requant_pc_entry*) op->d_requant_pc,
       };
       return qnnp_hip_dwconv_run(&args, &op->kernel_name);
     }
@@ -271,6 +272,7 @@ static int launch_kernel(struct qnnp_operator* op, const void* input, const void
         .bias2_centred = op->d_bias_centred != NULL ? op->d_bias_centred : op->d_bias,
         .centre_flip = op->centre_flip,
         .streaming_mode = op->streaming_mode,
+        .rq_pc = (const struct qnnp_requant_pc_entry*) op->d_requant_pc,
       };
       /* grouped 1x1 with a dense image (convolution.c): many rows -> the dense GEMM; "gemm_kernel" 31 forces it, any other
        * forced kernel keeps the grouped image */

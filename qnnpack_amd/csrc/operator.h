@@ -149,6 +149,12 @@ struct qnnp_operator {
   uint8_t kernel_zero_point;
   struct qnnp_hip_requant requant;
   enum qnnp_ukernel_type ukernel_type;
+  /* per-channel weight scales (include/qnnpack_gfx950_perchannel.h): the operator keeps its ukernel_type; `requant` holds
+   * the zero point and the clamp (its multiplier and shift are those of the largest channel scale and reach no kernel), and
+   * the (multiplier, shift) of every output channel are in d_requant_pc -- owned; conv / gemm: [groups][n_pad], dwconv:
+   * [c_pad], pad entries valid (per-channel.h) */
+  int per_channel;
+  void* d_requant_pc;
 
   /* ---- device-side state owned by the operator ---- */
   void* d_weights;        /* igemm: int8 fragment panels; dwconv: int16 [taps][c_pad]; lut: the 256-byte table; softargmax: 256 uint32_t */

@@ -39,6 +39,11 @@ enum qnnp_status qnnp_gfx950_attach_residual_add(
     qnnp_log_error("failed to attach residual add: needs a convolution / fully connected operator and an add operator");
     return qnnp_status_invalid_parameter;
   }
+  if (convolution->per_channel) {
+    /* no kernel folds an add behind per-channel requantization (qnnpack_gfx950_perchannel.h): keep the add operator */
+    qnnp_log_error("failed to attach residual add: the convolution has per-channel weight scales");
+    return qnnp_status_unsupported_parameter;
+  }
   if (convolution->device != add->device) {
     qnnp_log_error("failed to attach residual add: the operators belong to different devices");
     return qnnp_status_invalid_parameter;
