@@ -27,6 +27,14 @@ static inline bool scale_is_valid(float scale)
   return scale > 0.0f && isnormal(scale);
 }
 
+/* reference operator-run.c, case qnnp_ukernel_type_add (q8vadd over rows of `channels` bytes) */
+static int launch_add(struct qnnp_operator* op, const void* input, const void* input2, void* output)
+{
+  const struct qnnp_hip_vadd_args args = qnnp_vadd_args(op, input, op->input_pixel_stride, input2, op->input2_pixel_stride,
+      output, op->output_pixel_stride, op->batch_size, op->channels, &op->add_params);
+  return qnnp_hip_vadd_run(&args, &op->kernel_name);
+}
+
 static enum qnnp_status qnnp_create_add_nc_q8_impl(
     size_t channels,
     uint8_t a_zero_point,
@@ -81,7 +89,7 @@ static enum qnnp_status qnnp_create_add_nc_q8_impl(
     return qnnp_status_unsupported_parameter;
   }
 
-  qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_add, NULL);
+  qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_add, launch_add);
   if (op == NULL) {
     return qnnp_status_out_of_memory;
   }

@@ -33,8 +33,9 @@
 #include "operator.h"
 #include "requantization.h"
 
-static int launch_average_pooling(struct qnnp_operator* op, const void* input, void* output)
+static int launch_average_pooling(struct qnnp_operator* op, const void* input, const void* input2, void* output)
 {
+  (void) input2;
   /* reference operator-run.c:845-898 */
   const struct qnnp_hip_pool_args args = {
     .input = (const uint8_t*) input,

@@ -2,7 +2,7 @@
  * channel-shuffle.c -- qnnp_create_channel_shuffle_nc_x8 / qnnp_setup_channel_shuffle_nc_x8 for the gfx950 build.
  *
  * Replaces reference src/channel-shuffle.c:21-71 (create) and :73-98 (setup): same checks in the same order, same
- * status codes. The run is the kernel of hip/x8shuffle.hip, reached through op->launch_hook.
+ * status codes. The run is the kernel of hip/x8shuffle.hip, reached through op->launch.
  *
  * Where the reference checks nothing and would go out of range, this build answers instead:
  *   - invalid_parameter: NULL tensors, pixel strides below groups * group_channels, and input and output byte spans
@@ -22,8 +22,9 @@
 #include "log.h"
 #include "operator.h"
 
-static int launch_channel_shuffle(struct qnnp_operator* op, const void* input, void* output)
+static int launch_channel_shuffle(struct qnnp_operator* op, const void* input, const void* input2, void* output)
 {
+  (void) input2;
   /* reference operator-run.c:1109-1147 */
   const struct qnnp_hip_x8_args args = {
     .input = (const uint8_t*) input,

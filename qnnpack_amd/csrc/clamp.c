@@ -3,7 +3,7 @@
  *
  * Replaces reference src/clamp.c:20-70 (create) and :72-97 (setup): same checks in the same order, same status codes.
  * The reference's clamping parameters (qnnp_compute_u8_clamping_params) reduce to the two bounds kept in
- * op->output_min / op->output_max. The run is the kernel of hip/x8shuffle.hip, reached through op->launch_hook.
+ * op->output_min / op->output_max. The run is the kernel of hip/x8shuffle.hip, reached through op->launch.
  *
  * Where the reference checks nothing and would go out of range, this build answers instead:
  *   - invalid_parameter: NULL tensors, pixel strides below the channel count, and input and output byte spans that
@@ -24,8 +24,9 @@
 #include "log.h"
 #include "operator.h"
 
-static int launch_clamp(struct qnnp_operator* op, const void* input, void* output)
+static int launch_clamp(struct qnnp_operator* op, const void* input, const void* input2, void* output)
 {
+  (void) input2;
   /* reference operator-run.c:1054-1089 */
   const struct qnnp_hip_x8_args args = {
     .input = (const uint8_t*) input,

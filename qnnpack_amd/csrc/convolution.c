@@ -133,7 +133,7 @@ done:
  * ((w - kzp) = 0: the grouped result bit for bit) reads every input byte once and writes whole pixels, at `groups` times the
  * multiplies -- which these layers do not notice: ShuffleNet v1's 28x28 layers at batch 128 run 15 ... 59 us grouped and 12 ... 27
  * dense (profiles/r06/grouped_1x1_dense_equivalents_r06v.txt); from 14x14 down the two are level or the grouped form leads, so
- * operator-run.c takes this image from 65536 rows up. Built for up to 1024 channels on either side (<= 1 MiB of weights).
+ * the launch takes this image from 65536 rows up. Built for up to 1024 channels on either side (<= 1 MiB of weights).
  * Optional: without it the operator keeps its grouped image. */
 static void pack_dense_optional(struct qnnp_operator* op, const uint8_t* kernel, const int32_t* bias)
 {
@@ -312,6 +312,134 @@ static enum qnnp_status pack_gemm(struct qnnp_operator* op, const uint8_t* kerne
   return pack_rows(op, kernel, bias);
 }
 
+/* ---- launches: one call through the C-ABI HIP shim (hip/qnnp_hip.h) per operator ------------------------------------ */
+
+/* `rc` is what the operator's own kernel answered. An attached residual add (residual.c) that the kernel did not carry
+ * follows as the add kernel, in place on the output. */
+static int finish_residual_add(struct qnnp_operator* op, void* output, int rc)
+{
+  if (rc != QNNP_HIP_OK || op->residual == NULL || op->residual_folded) return rc;
+  const struct qnnp_hip_vadd_args args = qnnp_vadd_args(op, op->residual, op->residual_pixel_stride,
+      output, op->output_pixel_stride, output, op->output_pixel_stride,
+      op->batch_size * op->output_height * op->output_width, (size_t) op->groups * op->group_output_channels,
+      &op->residual_params);
+  const char* add_kernel = NULL;
+  return qnnp_hip_vadd_run(&args, &add_kernel);
+}
+
+static int launch_dwconv(struct qnnp_operator* op, const void* input, const void* input2, void* output)
+{
+  (void) input2;
+  /* reference operator-run.c:647-710 (context) + :238-284 (trampolines) */
+  const struct qnnp_hip_dwconv_args args = {
+    .input = (const uint8_t*) input,
+    .output = (uint8_t*) output,
+    .streaming_mode = op->streaming_mode,
+    .wadj = (const int16_t*) op->d_weights,
+    .bias1 = op->d_bias,
+    .dwm_x = (const int8_t*) op->d_dwm_x,
+    .dwm_bias = op->d_dwm_bias,
+    .dwm_parts = op->dwm_parts,
+    .w_range = op->dw_wrange,
+    .dot4 = (const uint32_t*) op->d_dw_dot4,
+    .c_pad32 = op->c_pad32,
+    .batch = (uint32_t) op->batch_size,
+    .input_height = (uint32_t) op->input_height,
+    .input_width = (uint32_t) op->input_width,
+    .output_height = (uint32_t) op->output_height,
+    .output_width = (uint32_t) op->output_width,
+    .channels = op->groups,
+    .c_pad = op->c_pad,
+    .kernel_height = op->kernel_height,
+    .kernel_width = op->kernel_width,
+    .stride_height = op->stride_height,
+    .stride_width = op->stride_width,
+    .dilation_height = op->dilation_height,
+    .dilation_width = op->dilation_width,
+    .pad_top = op->input_padding_top,
+    .pad_left = op->input_padding_left,
+    .input_stride = (uint32_t) op->input_pixel_stride,
+    .output_stride = (uint32_t) op->output_pixel_stride,
+    .input_zero_point = op->input_zero_point,
+    .rq = op->requant,
+    .variant = op->variant,
+    .plan = &op->dw_plan,
+    .rq_pc = (const struct qnnp_requant_pc_entry*) op->d_requant_pc,
+  };
+  op->residual_folded = 0;
+  return finish_residual_add(op, output, qnnp_hip_dwconv_run(&args, &op->kernel_name));
+}
+
+/* reference operator-run.c:770-804 (gemm) and :805-844 (conv) */
+static int launch_igemm_kernel(struct qnnp_operator* op, const void* input, void* output)
+{
+  const int is_conv = op->ukernel_type == qnnp_ukernel_type_conv;
+  const uint32_t output_size = (uint32_t) (op->output_height * op->output_width);
+  const uint32_t taps = is_conv ? op->kernel_height * op->kernel_width : 1;
+  struct qnnp_hip_igemm_args args = qnnp_igemm_args(op, input, output);
+  args.packed_w = (const int8_t*) op->d_weights;
+  args.packed_w_rows16 = is_conv ? (const int8_t*) op->d_weights_rows16 : NULL;
+  args.bias2_rows = is_conv ? op->d_bias_rows : NULL;
+  args.bias2 = op->d_bias;
+  args.bias2_pair = 1;
+  args.offsets = is_conv ? op->d_offsets : NULL;
+  args.rows = (uint32_t) op->batch_size * output_size;
+  args.rows_per_image = output_size;
+  args.ks = taps;
+  args.k_total = taps * op->kc_slot;
+  args.k_pad = op->k_pad;
+  args.variant = op->variant;
+  args.input_height = (uint32_t) op->input_height;
+  args.input_width = (uint32_t) op->input_width;
+  args.output_height = (uint32_t) op->output_height;
+  args.output_width = (uint32_t) op->output_width;
+  args.kernel_height = op->kernel_height;
+  args.kernel_width = op->kernel_width;
+  args.stride_height = op->stride_height;
+  args.stride_width = op->stride_width;
+  args.dilation_height = op->dilation_height;
+  args.dilation_width = op->dilation_width;
+  args.pad_top = op->input_padding_top;
+  args.pad_left = op->input_padding_left;
+  args.residual = (const uint8_t*) op->residual;
+  args.residual_stride = (uint32_t) op->residual_pixel_stride;
+  args.residual_add = &op->residual_params;
+  args.residual_folded = &op->residual_folded;
+  /* zero-point-centred image (fully-connected.c): its own, or the standard one when that is centred already */
+  args.packed_w_centred = (const int8_t*) (op->d_weights_centred != NULL ? op->d_weights_centred : op->d_weights);
+  args.bias2_centred = op->d_bias_centred != NULL ? op->d_bias_centred : op->d_bias;
+  args.centre_flip = op->centre_flip;
+  args.rq_pc = (const struct qnnp_requant_pc_entry*) op->d_requant_pc;
+  /* grouped 1x1 with a dense image (pack_dense_optional): many rows -> the dense GEMM; "gemm_kernel" 31 forces it (and is
+   * refused where the operator keeps the grouped image), any other forced kernel keeps the grouped image */
+  op->ran_dense = 0;
+  if (op->d_weights_dense != NULL && op->residual == NULL &&
+      (op->variant == 31 || (op->variant == 0 && (uint64_t) op->batch_size * output_size >= 65536u))) {
+    args.packed_w = (const int8_t*) op->d_weights_dense;
+    args.bias2 = op->d_bias_dense;
+    args.groups = 1;
+    args.n = (uint32_t) (op->groups * op->group_output_channels);
+    args.n_pad = op->dense_n_pad;
+    args.kc = (uint32_t) (op->groups * op->group_input_channels);
+    args.kc_slot = args.k_total = args.kc;
+    args.k_pad = op->dense_k_pad;
+    args.variant = 0;
+    args.packed_w_centred = args.packed_w;
+    args.bias2_centred = args.bias2;
+    args.centre_flip = 0;
+    op->ran_dense = 1;
+  }
+  if (op->variant == 31 && !op->ran_dense) return QNNP_HIP_EINVAL;
+  return qnnp_hip_igemm_run(&args, &op->kernel_name);
+}
+
+int qnnp_igemm_launch(struct qnnp_operator* op, const void* input, const void* input2, void* output)
+{
+  (void) input2;
+  op->residual_folded = 0;
+  return finish_residual_add(op, output, launch_igemm_kernel(op, input, output));
+}
+
 /* kernel_scales == NULL: the per-tensor create with `kernel_scale`. Else the per-channel one: `per_channel` is set,
  * `kernel_scale` is unused and kernel_scales holds groups * group_output_channels floats. (per_channel with a NULL array
  * is the refusal the per-channel entry point owes its caller.) */
@@ -451,7 +579,7 @@ static enum qnnp_status qnnp_create_convolution2d_nhwc_q8_impl(
   }
 
   status = qnnp_status_out_of_memory;
-  op = qnnp_allocate_operator(ukernel_type, NULL);
+  op = qnnp_allocate_operator(ukernel_type, ukernel_type == qnnp_ukernel_type_dwconv ? launch_dwconv : qnnp_igemm_launch);
   if (op == NULL) {
     goto error;
   }

@@ -249,6 +249,93 @@ static enum qnnp_status pack_deconvolution(struct qnnp_operator* op, const uint8
   return status;
 }
 
+/* The launch: the depth-to-space GEMM where the create packed one, then the stride-2 streaming kernel, then the phase
+ * GEMMs, each falling through to the next when the kernel answers that it cannot take these tensors (QNNP_HIP_EINVAL:
+ * alignment is part of the choice, so it is made per launch); the one-table form runs like a convolution. */
+static int launch_deconvolution(struct qnnp_operator* op, const void* input, const void* input2, void* output)
+{
+  if (op->deconv_d2s) {
+    /* kernel == stride: one pointwise GEMM over the input pixels, stored depth-to-space (pack_depth_to_space) */
+    struct qnnp_hip_igemm_args dargs = qnnp_igemm_args(op, input, output);
+    dargs.packed_w = (const int8_t*) op->d_weights;
+    dargs.bias2 = op->d_bias;
+    dargs.bias2_pair = 1;
+    dargs.rows = (uint32_t) (op->batch_size * op->input_height * op->input_width);
+    dargs.rows_per_image = (uint32_t) (op->input_height * op->input_width);
+    dargs.image_stride = 0;
+    dargs.groups = 1;
+    dargs.n_pad = op->n_pad * op->stride_height * op->stride_width;
+    dargs.k_pad = op->k_pad;
+    dargs.variant = 5;
+    dargs.d2s_stride_h = op->stride_height;
+    dargs.d2s_stride_w = op->stride_width;
+    dargs.d2s_input_h = (uint32_t) op->input_height;
+    dargs.d2s_input_w = (uint32_t) op->input_width;
+    const int rc_d2s = qnnp_hip_igemm_run(&dargs, &op->kernel_name);
+    if (rc_d2s != QNNP_HIP_EINVAL) {
+      return rc_d2s;
+    }
+    /* the streaming kernel cannot take these tensors (alignment): the phase GEMMs below can */
+  }
+  if (op->deconv_phases == 4 && op->deconv_stream != 1 && op->groups == 1 &&
+      op->stride_height == 2 && op->stride_width == 2 && op->dilation_height == 1 && op->dilation_width == 1 &&
+      op->kernel_height == op->kernel_width && (op->kernel_height == 3 || op->kernel_height == 4)) {
+    /* stride 2, 3x3 / 4x4: one streaming kernel over the input pixels, all four phases (q8deconv.hip) */
+    struct qnnp_hip_deconv_s2_args sargs = {
+      .input = (const uint8_t*) input,
+      .output = (uint8_t*) output,
+      .batch = (uint32_t) op->batch_size,
+      .input_height = (uint32_t) op->input_height,
+      .input_width = (uint32_t) op->input_width,
+      .output_height = (uint32_t) op->output_height,
+      .output_width = (uint32_t) op->output_width,
+      .kernel_height = op->kernel_height,
+      .kernel_width = op->kernel_width,
+      .pad_top = op->input_padding_top,
+      .pad_left = op->input_padding_left,
+      .channels = (uint32_t) op->group_input_channels,
+      .n = (uint32_t) op->group_output_channels,
+      .n_pad = op->n_pad,
+      .input_stride = (uint32_t) op->input_pixel_stride,
+      .output_stride = (uint32_t) op->output_pixel_stride,
+      .row_coeff = 128 - (int32_t) op->kernel_zero_point,
+      .input_zero_point = op->input_zero_point,
+      .rq = op->requant,
+      .bias2_pair = 1,
+    };
+    for (int ph = 0; ph < 4; ph++) {
+      sargs.packed_w[ph] = (const int8_t*) op->phase[ph].d_weights;
+      sargs.bias2[ph] = op->phase[ph].d_bias;
+      sargs.k_pad[ph] = op->phase[ph].k_pad;
+    }
+    const int rc_s2 = qnnp_hip_deconv_s2_run(&sargs, &op->kernel_name);
+    if (rc_s2 != QNNP_HIP_EINVAL || op->deconv_stream == 2) {
+      return rc_s2;
+    }
+    /* outside the streaming kernel's range (channel multiple, LDS, alignment): the phase GEMMs below */
+  } else if (op->deconv_stream == 2) {
+    return QNNP_HIP_EINVAL;
+  }
+  if (op->deconv_phases == 0) {
+    /* one table over all taps: the convolution form, with the transposed table (setup) */
+    return qnnp_igemm_launch(op, input, input2, output);
+  }
+  /* strided deconvolution: one dense implicit GEMM per output phase, all in one launch (upload_phase_table) */
+  if (op->phase_table_entries == 0) return QNNP_HIP_OK;
+  struct qnnp_hip_igemm_args pargs = qnnp_igemm_args(op, input, output);
+  pargs.packed_w = (const int8_t*) op->phase[0].d_weights;   /* per-phase fields come from the table */
+  pargs.bias2 = op->phase[0].d_bias;
+  pargs.offsets = (const int32_t*) op->d_phase_table;          /* non-NULL marks the convolution form */
+  pargs.rows = (uint32_t) (op->batch_size * op->phase_max_rows);
+  pargs.rows_per_image = (uint32_t) op->phase_max_rows;
+  pargs.k_pad = op->phase_max_k_pad;
+  pargs.variant = 1;
+  pargs.out_image_rows = (uint32_t) (op->output_height * op->output_width);
+  pargs.phases = (const struct qnnp_hip_igemm_phase*) op->d_phase_table;
+  pargs.nphases = op->phase_table_entries;
+  return qnnp_hip_igemm_run(&pargs, &op->kernel_name);
+}
+
 static enum qnnp_status qnnp_create_deconvolution2d_nhwc_q8_impl(
     uint32_t input_padding_top,
     uint32_t input_padding_right,
@@ -337,7 +424,7 @@ static enum qnnp_status qnnp_create_deconvolution2d_nhwc_q8_impl(
   }
 
   status = qnnp_status_out_of_memory;
-  op = qnnp_allocate_operator(qnnp_ukernel_type_conv, NULL);   /* reference deconvolution.c:203 */
+  op = qnnp_allocate_operator(qnnp_ukernel_type_conv, launch_deconvolution);   /* reference deconvolution.c:203 */
   if (op == NULL) {
     goto error;
   }

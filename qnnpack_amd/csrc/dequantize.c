@@ -23,8 +23,9 @@
 #include "log.h"
 #include "operator.h"
 
-static int launch_dequantize(struct qnnp_operator* op, const void* input, void* output)
+static int launch_dequantize(struct qnnp_operator* op, const void* input, const void* input2, void* output)
 {
+  (void) input2;
   const struct qnnp_hip_dequantize_args args = {
     .input = (const uint8_t*) input,
     .output = (float*) output,

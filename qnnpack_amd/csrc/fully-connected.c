@@ -125,7 +125,7 @@ static enum qnnp_status qnnp_create_fully_connected_nc_q8_impl(
   }
 
   status = qnnp_status_out_of_memory;
-  op = qnnp_allocate_operator(qnnp_ukernel_type_gemm, NULL);
+  op = qnnp_allocate_operator(qnnp_ukernel_type_gemm, qnnp_igemm_launch);   /* convolution.c */
   if (op == NULL) {
     goto error;
   }

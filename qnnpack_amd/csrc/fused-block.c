@@ -215,6 +215,17 @@ static struct qnnp_hip_fused_strip_args strip_args(const struct qnnp_operator* o
   return a;
 }
 
+static int qnnp_fused_block_launch(struct qnnp_operator* op, const void* input, const void* input2, void* output)
+{
+  (void) input2;
+  if (op->fused_use_strip) {
+    const struct qnnp_hip_fused_strip_args sargs = strip_args(op, input, output);
+    return qnnp_hip_fused_strip_run(&sargs, &op->kernel_name);
+  }
+  const struct qnnp_hip_fused_args args = fused_args(op, input, output);
+  return qnnp_hip_fused_block_run(&args, &op->kernel_name);
+}
+
 static enum qnnp_status qnnp_gfx950_create_fused_block_impl(
     qnnp_operator_t expand, qnnp_operator_t depthwise, qnnp_operator_t project, qnnp_operator_t residual_add,
     qnnp_operator_t* fused_out)
@@ -251,7 +262,7 @@ static enum qnnp_status qnnp_gfx950_create_fused_block_impl(
     qnnp_log_error("cannot create fused block: the operators live on different devices");
     return qnnp_status_invalid_parameter;
   }
-  qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_fused_block, NULL);
+  qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_fused_block, qnnp_fused_block_launch);
   if (op == NULL) {
     return qnnp_status_out_of_memory;
   }
@@ -327,16 +338,6 @@ static enum qnnp_status qnnp_gfx950_setup_fused_block_impl(
     }
   }
   return qnnp_status_success;
-}
-
-int qnnp_fused_block_launch(struct qnnp_operator* op, const void* input, void* output)
-{
-  if (op->fused_use_strip) {
-    const struct qnnp_hip_fused_strip_args sargs = strip_args(op, input, output);
-    return qnnp_hip_fused_strip_run(&sargs, &op->kernel_name);
-  }
-  const struct qnnp_hip_fused_args args = fused_args(op, input, output);
-  return qnnp_hip_fused_block_run(&args, &op->kernel_name);
 }
 
 /* ---- public entry points: the implementations above inside the device guards of lifecycle.h ---- */

@@ -28,6 +28,23 @@ static inline bool scale_is_valid(float scale)
   return scale > 0.0f && isnormal(scale);
 }
 
+/* reference operator-run.c:981-1016 */
+static int launch_global_average_pooling(struct qnnp_operator* op, const void* input, const void* input2, void* output)
+{
+  (void) input2;
+  const struct qnnp_hip_gavgpool_args args = {
+    .input = (const uint8_t*) input,
+    .output = (uint8_t*) output,
+    .batch = op->batch_size,
+    .width = op->input_width,
+    .channels = (uint32_t) op->channels,
+    .input_stride = op->input_pixel_stride,
+    .output_stride = op->output_pixel_stride,
+    .params = op->avgpool_params,
+  };
+  return qnnp_hip_gavgpool_run(&args, &op->kernel_name);
+}
+
 static enum qnnp_status qnnp_create_global_average_pooling_nwc_q8_impl(
     size_t channels,
     uint8_t input_zero_point,
@@ -69,7 +86,7 @@ static enum qnnp_status qnnp_create_global_average_pooling_nwc_q8_impl(
     return qnnp_status_unsupported_parameter;
   }
 
-  qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_global_average_pooling, NULL);
+  qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_global_average_pooling, launch_global_average_pooling);
   if (op == NULL) {
     return qnnp_status_out_of_memory;
   }

@@ -179,7 +179,7 @@ struct qnnp_hip_igemm_args {
   /* optional fused residual add (qnnpack_gfx950.h qnnp_gfx950_attach_residual_add):
    * output = add(a = residual pixel, b = the requantized convolution output) with the add operator's parameters.
    * Kernels that carry the add in their epilogue set *residual_folded = 1; for the others the caller launches the
-   * stand-alone add kernel in place on `output` (operator-run.c). residual == NULL: off. */
+   * stand-alone add kernel in place on `output` (convolution.c). residual == NULL: off. */
   const uint8_t* residual;
   uint32_t residual_stride;   /* bytes between residual pixels */
   const struct qnnp_hip_add_params* residual_add;

@@ -95,13 +95,11 @@ static inline enum qnnp_status qnnp_leave_setup(qnnp_operator_t op, int token, e
   return status;
 }
 
-/* A zeroed operator of the given type on the device the create runs in, or NULL (logged: out of host memory).
- * `launch_hook` is the launch of the operator types whose code is not part of every build (windowed pooling, channel
- * shuffle, clamp, the table operators, softargmax, multiply, resize): launch_kernel's default arm (operator-run.c) calls
- * it with device pointers, which keeps operator-run.c free of references to their kernels, so builds without them still
- * link. NULL for the types operator-run.c launches itself. */
+/* A zeroed operator of the given type on the device the create runs in, or NULL (logged: out of host memory). `launch`
+ * is the operator's launch function (operator.h), which every create passes. */
 static inline qnnp_operator_t qnnp_allocate_operator(
-    enum qnnp_ukernel_type type, int (*launch_hook)(struct qnnp_operator* op, const void* input, void* output))
+    enum qnnp_ukernel_type type,
+    int (*launch)(struct qnnp_operator* op, const void* input, const void* input2, void* output))
 {
   qnnp_operator_t op = calloc(1, sizeof(struct qnnp_operator));
   if (op == NULL) {
@@ -110,7 +108,7 @@ static inline qnnp_operator_t qnnp_allocate_operator(
   }
   op->device = qnnp_hip_device();
   op->ukernel_type = type;
-  op->launch_hook = launch_hook;
+  op->launch = launch;
   return op;
 }
 

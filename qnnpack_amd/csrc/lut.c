@@ -5,7 +5,7 @@
  * The reference has one operator type under sigmoid and leaky ReLU (qnnp_ukernel_type_lut: a 256-byte table made at
  * create, src/sigmoid.c:96-110, src/leaky-relu.c:104-117) and runs y[i] = table[x[i]] (src/operator-run.c:1017-1052).
  * Here the table is uploaded once at create, to the create's device, and kept in op->d_weights (freed by
- * qnnp_delete_operator); the run is the kernel of hip/x8lut.hip, reached through op->launch_hook.
+ * qnnp_delete_operator); the run is the kernel of hip/x8lut.hip, reached through op->launch.
  *
  * The reference's setups (sigmoid.c:125-150, leaky-relu.c:132-157) check nothing but the initialization. Where they
  * would go out of range, this build answers instead:
@@ -30,8 +30,9 @@
 #include "operator.h"
 #include "upload.h"
 
-static int launch_lut(struct qnnp_operator* op, const void* input, void* output)
+static int launch_lut(struct qnnp_operator* op, const void* input, const void* input2, void* output)
 {
+  (void) input2;
   /* reference operator-run.c:1017-1052 */
   const struct qnnp_hip_lut_args args = {
     .input = (const uint8_t*) input,

@@ -25,8 +25,9 @@
 #include "log.h"
 #include "operator.h"
 
-static int launch_max_pooling(struct qnnp_operator* op, const void* input, void* output)
+static int launch_max_pooling(struct qnnp_operator* op, const void* input, const void* input2, void* output)
 {
+  (void) input2;
   /* reference operator-run.c:899-940 */
   const struct qnnp_hip_pool_args args = {
     .input = (const uint8_t*) input,

@@ -9,8 +9,8 @@
  * qnnp_q31_requantize with the scale a_scale * b_scale / product_scale (requantization.h builds the parameters,
  * hip/requant.hip.h consumes them). |acc| <= 255 * 255, which is the accumulator bound of ONE product and no bias.
  *
- * The kernels are hip/q8mul.hip, reached through op->launch_hook; `b` is the operator's second input (op->input2,
- * staged by qnnp_run_operator when it is host memory).
+ * The kernels are hip/q8mul.hip, reached through op->launch; `b` is the operator's second input (op->input2, staged by
+ * qnnp_run_operator when it is host memory), which the launch receives as `input2`.
  *
  * Not part of the seam library (oracle/Makefile).
  */
@@ -34,11 +34,11 @@ static inline bool scale_is_valid(float scale)
   return scale > 0.0f && isnormal(scale);
 }
 
-static int launch_multiply(struct qnnp_operator* op, const void* input, void* output)
+static int launch_multiply(struct qnnp_operator* op, const void* input, const void* input2, void* output)
 {
   const struct qnnp_hip_mul_args args = {
     .a = (const uint8_t*) input,
-    .b = (const uint8_t*) (op->input2_on_device ? op->input2 : op->d_stage_in2),
+    .b = (const uint8_t*) input2,
     .product = (uint8_t*) output,
     .b_rows = (uint32_t) op->mul_b_rows,
     .a_rows_per_b_row = (uint32_t) op->mul_a_rows_per_b_row,

@@ -161,7 +161,7 @@ struct qnnp_operator {
   void* d_weights_rows16; /* igemm, 3-channel first layers: the [ky][16-byte row slot] fragment image (pack.h), or NULL */
   /* grouped 1x1 convolutions (ukernel gemm, groups > 1): the same operator as ONE dense GEMM -- the groups' weight blocks on the diagonal of
    * a [groups * output channels][groups * input channels] matrix whose other elements are the kernel zero point (w - kzp = 0: bit for
-   * bit the grouped result) -- packed like any single-group image; operator-run.c takes it for many rows (convolution.c) */
+   * bit the grouped result) -- packed like any single-group image; the launch takes it for many rows (convolution.c) */
   void* d_weights_dense;
   int32_t* d_bias_dense;  /* bias pair table [2][dense_n_pad] */
   uint32_t dense_n_pad, dense_k_pad;
@@ -215,8 +215,10 @@ struct qnnp_operator {
                            * failed setup cannot be run against half-updated geometry / tables */
   struct qnnp_hip_dwconv_plan dw_plan;   /* depthwise launch plan, computed at the first run after a setup */
 
-  /* the launch of the operator types that operator-run.c does not launch itself (lifecycle.h qnnp_allocate_operator) */
-  int (*launch_hook)(struct qnnp_operator* op, const void* input, void* output);
+  /* The operator's launch, a function of the file that owns its create (lifecycle.h qnnp_allocate_operator): enqueues the
+   * kernel(s) on the library stream of the active context, reading `input` (and `input2` where there is a second operand)
+   * and writing `output`, device pointers all; answers a QNNP_HIP_* code. operator-run.c launches through nothing else. */
+  int (*launch)(struct qnnp_operator* op, const void* input, const void* input2, void* output);
 };
 
 /* Decide where a caller pointer lives and (re)size the device staging buffer a host pointer needs:
@@ -231,5 +233,51 @@ static inline int qnnp_spans_overlap(const void* a, size_t a_bytes, const void* 
   return pa < pb + b_bytes && pb < pa + a_bytes;
 }
 
-/* fused-block.c */
-int qnnp_fused_block_launch(struct qnnp_operator* op, const void* input, void* output);
+/* convolution.c: the launch of the conv and gemm operator types -- convolutions, the operators of fully-connected.c, and
+ * the one-table form of a deconvolution (deconvolution.c; the others have launches of their own) */
+int qnnp_igemm_launch(struct qnnp_operator* op, const void* input, const void* input2, void* output);
+
+/* What every form of an implicit-GEMM launch of `op` hands over (convolution.c, deconvolution.c), as one tap per row: a
+ * form adds its weight image, table and rows, and states where it departs from this. Everything else stays zero. */
+static inline struct qnnp_hip_igemm_args qnnp_igemm_args(const struct qnnp_operator* op, const void* input, void* output)
+{
+  return (struct qnnp_hip_igemm_args) {
+    .input = (const uint8_t*) input,
+    .output = (uint8_t*) output,
+    .image_stride = (uint64_t) op->input_height * op->input_width * op->input_pixel_stride,
+    .groups = op->groups,
+    .n = (uint32_t) op->group_output_channels,
+    .n_pad = op->n_pad,
+    .kc = (uint32_t) op->group_input_channels,
+    .kc_slot = op->kc_slot,
+    .input_bytes = op->input_span,
+    .ks = 1,
+    .k_total = op->kc_slot,
+    .input_stride = (uint32_t) op->input_pixel_stride,
+    .output_stride = (uint32_t) op->output_pixel_stride,
+    .row_coeff = 128 - (int32_t) op->kernel_zero_point,
+    .input_zero_point = op->input_zero_point,
+    .rq = op->requant,
+    .streaming_mode = op->streaming_mode,
+  };
+}
+
+/* sum = add(a, b) over `rows` rows of `channels` bytes with `params`: the add operator (add.c) and the attached residual
+ * add that a convolution's kernel did not carry (convolution.c) */
+static inline struct qnnp_hip_vadd_args qnnp_vadd_args(
+    const struct qnnp_operator* op, const void* a, size_t a_stride, const void* b, size_t b_stride, void* sum,
+    size_t sum_stride, size_t rows, size_t channels, const struct qnnp_hip_add_params* params)
+{
+  return (struct qnnp_hip_vadd_args) {
+    .streaming_mode = op->streaming_mode,
+    .a = (const uint8_t*) a,
+    .b = (const uint8_t*) b,
+    .sum = (uint8_t*) sum,
+    .rows = rows,
+    .channels = (uint32_t) channels,
+    .a_stride = a_stride,
+    .b_stride = b_stride,
+    .sum_stride = sum_stride,
+    .params = *params,
+  };
+}

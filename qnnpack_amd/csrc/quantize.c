@@ -5,7 +5,7 @@
  *
  * No reference counterpart. Create and setup follow multiply.c: validation in the documented order, every setup check
  * before the operator changes, so a refused setup leaves the previous one runnable. The kernels are hip/f32q8.hip, reached
- * through op->launch_hook. The float tensor is op->input: its byte span is 4 bytes per element, and in the rows setup
+ * through op->launch. The float tensor is op->input: its byte span is 4 bytes per element, and in the rows setup
  * op->input_pixel_stride counts elements.
  *
  * Not part of the seam library (oracle/Makefile).
@@ -24,8 +24,9 @@
 #include "log.h"
 #include "operator.h"
 
-static int launch_quantize(struct qnnp_operator* op, const void* input, void* output)
+static int launch_quantize(struct qnnp_operator* op, const void* input, const void* input2, void* output)
 {
+  (void) input2;
   const struct qnnp_hip_quantize_args args = {
     .input = (const float*) input,
     .output = (uint8_t*) output,

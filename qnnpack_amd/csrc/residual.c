@@ -82,7 +82,7 @@ enum qnnp_status qnnp_gfx950_attach_residual_add(
   if (status == qnnp_status_success) {
     /* The kernels read the residual through __restrict__ / streaming loads while they write the output: the two ranges
      * must not overlap -- not even exactly (the in-place form is the stand-alone add operator's business,
-     * operator-run.c). Checked only here, where both are known to be memory of this device: `convolution->output` is
+     * add.c). Checked only here, where both are known to be memory of this device: `convolution->output` is
      * then the address the kernels write (a host-staged output was refused above with its own status). */
     const size_t pixels = convolution->batch_size * convolution->output_height * convolution->output_width;
     const uintptr_t r0 = (uintptr_t) residual;

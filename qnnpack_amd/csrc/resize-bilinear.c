@@ -6,7 +6,7 @@
  * No reference counterpart. The definition is integers only (include/qnnpack_gfx950.h, resize-table.h): setup builds one
  * table per axis on the host -- for every output row / column the two input rows / columns it blends and a Q11 weight --
  * and uploads both into ONE grow-only device allocation the operator owns (rows first, then columns; freed by
- * qnnp_delete_operator). The kernels are hip/u8resize.hip, reached through op->launch_hook.
+ * qnnp_delete_operator). The kernels are hip/u8resize.hip, reached through op->launch.
  *
  * Setup follows lut.c / multiply.c: every check comes before the operator changes, so a refused setup leaves the previous
  * one runnable. What can still fail afterwards is an allocation or a copy (the tables, the staging of host tensors); the
@@ -28,8 +28,9 @@
 #include "resize-table.h"
 #include "upload.h"
 
-static int launch_resize(struct qnnp_operator* op, const void* input, void* output)
+static int launch_resize(struct qnnp_operator* op, const void* input, const void* input2, void* output)
 {
+  (void) input2;
   const struct qnnp_hip_resize_args args = {
     .input = (const uint8_t*) input,
     .output = (uint8_t*) output,

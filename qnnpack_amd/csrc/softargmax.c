@@ -5,7 +5,7 @@
  * codes, and the same table of 256 uint32_t -- the reference's double expressions restated term for term (fmin, exp,
  * lrint) and compiled by the same host compiler against the same libm, never on the device. The table is uploaded once
  * at create, to the create's device, and kept in op->d_weights (freed by qnnp_delete_operator); the run is the kernels
- * of hip/q8softargmax.hip, reached through op->launch_hook.
+ * of hip/q8softargmax.hip, reached through op->launch.
  *
  * The reference's setup checks nothing but the initialization. Where it would go out of range, this build answers
  * instead, as lut.c does:
@@ -31,8 +31,9 @@
 #include "operator.h"
 #include "upload.h"
 
-static int launch_softargmax(struct qnnp_operator* op, const void* input, void* output)
+static int launch_softargmax(struct qnnp_operator* op, const void* input, const void* input2, void* output)
 {
+  (void) input2;
   /* reference operator-run.c:1091-1108 */
   const struct qnnp_hip_softargmax_args args = {
     .input = (const uint8_t*) input,

@@ -4,9 +4,12 @@
  * exercised under AddressSanitizer + UndefinedBehaviorSanitizer on a machine without a GPU (SURVEY.md section 5:
  * host-sanitizer cleanliness). "Device" memory is malloc, copies are memcpy, kernel launches validate their argument
  * block and touch the first and last byte of every tensor / table they were given (so ASan sees an undersized
- * allocation), nothing is computed. Never linked into the product.
+ * allocation), nothing is computed. On request they also record the argument blocks they were handed, as text (the
+ * launch log below). Never linked into the product.
  */
+#include <inttypes.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -86,7 +89,31 @@ int qnnp_hip_h2d(void* dst, const void* src, size_t bytes, int async)
 }
 int qnnp_hip_d2h(void* dst, const void* src, size_t bytes, int async) { (void) async; memcpy(dst, src, bytes); return QNNP_HIP_OK; }
 int qnnp_hip_memset(void* dst, int value, size_t bytes) { memset(dst, value, bytes); return QNNP_HIP_OK; }
-int qnnp_hip_is_device_pointer(const void* p) { (void) p; return 0; }   /* the test hands host tensors: staged path */
+/* whether `p` is what qnnp_hip_alloc returned, and of how many bytes; it reads the 16 bytes in front of ANY pointer, which
+ * for caller memory is an allocator's header or red zone: mapped, but not the sanitizer's business */
+__attribute__((noinline, no_sanitize("address")))
+static int tagged(const void* p, uint64_t* bytes)
+{
+  if (p == NULL || (uintptr_t) p % 8 != 0) return 0;
+  const volatile uint64_t* head = (const volatile uint64_t*) p - 2;
+  if (head[0] != STUB_MAGIC) return 0;
+  *bytes = head[1];
+  return 1;
+}
+/* host tensors by default: every program keeps the staged path. qnnp_stub_set_device_pointers(1) (host_launch_args_test.c)
+ * makes the stub's own allocations count as memory of the device, which opens the device-pointer run path and the timing
+ * entry points */
+static int g_device_pointers = 0;
+void qnnp_stub_set_device_pointers(int on) { g_device_pointers = on != 0; }
+static const void* registered_base(const void* p);
+int qnnp_hip_is_device_pointer(const void* p)
+{
+  uint64_t bytes;
+  if (!g_device_pointers) return 0;
+  /* a pointer into a registered tensor (the launch log below) lives where that tensor does */
+  const void* base = registered_base(p);
+  return tagged(base != NULL ? base : p, &bytes);
+}
 
 int qnnp_hip_timer_create(void** timer) { *timer = malloc(1); return *timer != NULL ? QNNP_HIP_OK : QNNP_HIP_ENOMEM; }
 int qnnp_hip_timer_start(void* timer) { (void) timer; return QNNP_HIP_OK; }
@@ -104,8 +131,195 @@ int qnnp_hip_graph_time_median(void* graph, int warmup, int iters, int samples, 
 int qnnp_hip_graph_sync(void* graph) { (void) graph; return QNNP_HIP_EINVAL; }
 void qnnp_hip_graph_destroy(void* graph) { (void) graph; }
 
+/* ---- launch log (host_launch_args_test.c): while a file is set, every *_run below appends one line -- its name, every
+ * field of its argument block in declaration order, the status it returned. Integers in decimal, nested blocks field by
+ * field, pointers by what they point into and never as addresses, so that the log is the same from run to run:
+ *   NULL | <tensor>+<offset> inside a tensor the test registered | dev(<bytes>) for a qnnp_hip_alloc block | other */
+static FILE* g_log = NULL;
+static struct { const char* name; const uint8_t* base; size_t bytes; } g_tensors[4];
+static int g_refuse_variant = -1;
+void qnnp_stub_log_to(FILE* file) { g_log = file; }
+void qnnp_stub_log_tensor(int slot, const char* name, const void* base, size_t bytes)
+{
+  g_tensors[slot].name = name;
+  g_tensors[slot].base = (const uint8_t*) base;
+  g_tensors[slot].bytes = base != NULL ? bytes : 0;
+}
+/* the next qnnp_hip_igemm_run whose `variant` is this one answers QNNP_HIP_EINVAL, once; < 0 disarms */
+void qnnp_stub_refuse_igemm_variant(int variant) { g_refuse_variant = variant; }
+
+static int registered_slot(const void* p)
+{
+  for (int i = 0; i < 4; i++) {
+    if (g_tensors[i].bytes != 0 && (const uint8_t*) p >= g_tensors[i].base && (const uint8_t*) p < g_tensors[i].base + g_tensors[i].bytes) {
+      return i;
+    }
+  }
+  return -1;
+}
+static const void* registered_base(const void* p)
+{
+  const int slot = registered_slot(p);
+  return slot >= 0 ? g_tensors[slot].base : NULL;
+}
+
+void qnnp_stub_name_pointer(const void* p, char* text, size_t size)
+{
+  uint64_t bytes;
+  if (p == NULL) {
+    snprintf(text, size, "NULL");
+    return;
+  }
+  const int slot = registered_slot(p);
+  if (slot >= 0) {
+    snprintf(text, size, "%s+%zu", g_tensors[slot].name, (size_t) ((const uint8_t*) p - g_tensors[slot].base));
+    return;
+  }
+  if (tagged(p, &bytes)) {
+    snprintf(text, size, "dev(%" PRIu64 ")", bytes);
+  } else {
+    snprintf(text, size, "other");
+  }
+}
+
+static void log_p(const char* name, const void* p)
+{
+  char text[48];
+  qnnp_stub_name_pointer(p, text, sizeof(text));
+  fprintf(g_log, " %s=%s", name, text);
+}
+static void log_u(const char* name, uint64_t v) { fprintf(g_log, " %s=%" PRIu64, name, v); }
+static void log_i(const char* name, int64_t v) { fprintf(g_log, " %s=%" PRId64, name, v); }
+#define P(field) log_p(#field, a->field)
+#define U(field) log_u(#field, a->field)
+#define I(field) log_i(#field, a->field)
+
+static void log_rq(const char* name, const struct qnnp_hip_requant* a)
+{
+  fprintf(g_log, " %s={", name);
+  I(multiplier); I(remainder_mask); I(remainder_threshold); U(shift); I(output_min_less_zero_point);
+  I(output_max_less_zero_point); I(output_zero_point); U(accumulator_bits);
+  fprintf(g_log, " }");
+}
+
+static void log_add(const char* name, const struct qnnp_hip_add_params* a)
+{
+  if (a == NULL) {
+    fprintf(g_log, " %s=NULL", name);
+    return;
+  }
+  fprintf(g_log, " %s={", name);
+  U(a_multiplier); U(b_multiplier); I(zero_point_product); U(shift); I(remainder_mask); I(remainder_threshold);
+  I(y_zero_point); I(y_min); I(y_max);
+  fprintf(g_log, " }");
+}
+
+static void log_avgpool(const char* name, const struct qnnp_hip_avgpool_params* a)
+{
+  fprintf(g_log, " %s={", name);
+  I(bias); I(multiplier); I(rounding); U(right_shift); I(output_min_less_zero_point); I(output_max_less_zero_point);
+  I(output_zero_point);
+  fprintf(g_log, " }");
+}
+
+static void log_plan(const char* name, const struct qnnp_hip_dwconv_plan* a)
+{
+  if (a == NULL) {
+    fprintf(g_log, " %s=NULL", name);
+    return;
+  }
+  fprintf(g_log, " %s={", name);
+  U(key); U(kernel); U(CS); U(TOH); U(IR); U(IC); U(PP); U(bands); U(slabs); U(store_mode); U(vec16);
+  fprintf(g_log, " }");
+}
+
+static void log_igemm(const struct qnnp_hip_igemm_args* a)
+{
+  fprintf(g_log, "qnnp_hip_igemm_run");
+  P(input); P(output); P(packed_w); P(packed_w_rows16); P(bias2_rows); P(bias2); P(offsets); U(rows); U(rows_per_image);
+  U(image_stride); U(groups); U(n); U(n_pad); U(kc); U(kc_slot); U(input_bytes); U(ks); U(k_total); U(k_pad);
+  U(input_stride); U(output_stride); I(row_coeff); U(input_zero_point); log_rq("rq", &a->rq); I(variant); P(out_rows);
+  U(out_image_rows); P(phases); U(nphases); U(d2s_stride_h); U(d2s_stride_w); U(d2s_input_h); U(d2s_input_w);
+  U(input_height); U(input_width); U(output_height); U(output_width); U(kernel_height); U(kernel_width);
+  U(stride_height); U(stride_width); U(dilation_height); U(dilation_width); U(pad_top); U(pad_left); P(residual);
+  U(residual_stride); log_add("residual_add", a->residual_add);
+  if (a->residual_folded != NULL) log_u("*residual_folded", *a->residual_folded); else P(residual_folded);
+  U(bias2_pair); P(packed_w_centred); P(bias2_centred); U(centre_flip); U(streaming_mode); P(rq_pc);
+}
+
+static void log_deconv_s2(const struct qnnp_hip_deconv_s2_args* a)
+{
+  fprintf(g_log, "qnnp_hip_deconv_s2_run");
+  P(input); P(output);
+  P(packed_w[0]); P(packed_w[1]); P(packed_w[2]); P(packed_w[3]);
+  P(bias2[0]); P(bias2[1]); P(bias2[2]); P(bias2[3]);
+  U(k_pad[0]); U(k_pad[1]); U(k_pad[2]); U(k_pad[3]);
+  U(batch); U(input_height); U(input_width); U(output_height); U(output_width); U(kernel_height); U(kernel_width);
+  U(pad_top); U(pad_left); U(channels); U(n); U(n_pad); U(input_stride); U(output_stride); I(row_coeff);
+  U(input_zero_point); log_rq("rq", &a->rq); U(bias2_pair);
+}
+
+static void log_dwconv(const struct qnnp_hip_dwconv_args* a)
+{
+  fprintf(g_log, "qnnp_hip_dwconv_run");
+  P(input); P(output); P(wadj); P(bias1); P(dwm_x); P(dwm_bias); U(dwm_parts); U(w_range); P(dot4); U(c_pad32); U(batch);
+  U(input_height); U(input_width); U(output_height); U(output_width); U(channels); U(c_pad); U(kernel_height);
+  U(kernel_width); U(stride_height); U(stride_width); U(dilation_height); U(dilation_width); U(pad_top); U(pad_left);
+  U(input_stride); U(output_stride); U(input_zero_point); log_rq("rq", &a->rq); I(variant);
+  log_plan("plan", a->plan); U(streaming_mode); P(rq_pc);
+}
+
+static void log_vadd(const struct qnnp_hip_vadd_args* a)
+{
+  fprintf(g_log, "qnnp_hip_vadd_run");
+  P(a); P(b); P(sum); U(rows); U(channels); U(a_stride); U(b_stride); U(sum_stride); log_add("params", &a->params);
+  U(streaming_mode);
+}
+
+static void log_gavgpool(const struct qnnp_hip_gavgpool_args* a)
+{
+  fprintf(g_log, "qnnp_hip_gavgpool_run");
+  P(input); P(output); U(batch); U(width); U(channels); U(input_stride); U(output_stride);
+  log_avgpool("params", &a->params);
+}
+
+static void log_fused_strip(const struct qnnp_hip_fused_strip_args* a)
+{
+  fprintf(g_log, "qnnp_hip_fused_strip_run");
+  P(input); P(output); U(batch); U(input_height); U(input_width); U(output_height); U(output_width); U(input_channels);
+  U(hidden_channels); U(output_channels); U(input_stride); U(output_stride); U(stride); U(has_expand); U(has_residual);
+  P(expand_w); P(expand_bias); U(expand_flip); log_rq("expand_rq", &a->expand_rq);
+  P(dw_w); P(dw_bias); U(dw_flip); U(dw_pad); log_rq("dw_rq", &a->dw_rq);
+  P(project_w); P(project_bias); U(project_flip); log_rq("project_rq", &a->project_rq);
+  U(hidden_pad); U(output_pad); log_add("add", &a->add); U(rows_per_strip); U(weights_in_lds);
+}
+
+static void log_fused(const struct qnnp_hip_fused_args* a)
+{
+  fprintf(g_log, "qnnp_hip_fused_block_run");
+  P(input); P(output); U(batch); U(input_height); U(input_width); U(output_height); U(output_width); U(input_channels);
+  U(hidden_channels); U(output_channels); U(input_stride); U(output_stride); U(stride); U(has_expand);
+  P(expand_w); P(expand_bias2); U(expand_k_pad); U(expand_n_pad); I(expand_row_coeff); log_rq("expand_rq", &a->expand_rq);
+  P(dw_wadj); P(dw_bias1); U(dw_c_pad); U(dw_input_zero_point); log_rq("dw_rq", &a->dw_rq);
+  P(project_w); P(project_bias2); U(project_k_pad); U(project_n_pad); I(project_row_coeff);
+  log_rq("project_rq", &a->project_rq); U(has_residual); log_add("add", &a->add);
+}
+#undef P
+#undef U
+#undef I
+
+/* one public *_run: the block as it arrived, then the kernel stand-in, then its status */
+#define LOGGED_RUN(name, type, log_args, impl) \
+  int name(const type* a, const char** kernel_name) \
+  { \
+    if (g_log != NULL && a != NULL) log_args(a); \
+    const int rc = impl(a, kernel_name); \
+    if (g_log != NULL && a != NULL) fprintf(g_log, " -> %d\n", rc); \
+    return rc; \
+  }
+
 /* ---- "kernels": check the argument block against the documented layout, touch every buffer end to end ---- */
-int qnnp_hip_deconv_s2_run(const struct qnnp_hip_deconv_s2_args* a, const char** kernel_name)
+static int deconv_s2_run(const struct qnnp_hip_deconv_s2_args* a, const char** kernel_name)
 {
   (void) kernel_name;
   if (a == NULL || a->batch == 0) return QNNP_HIP_EINVAL;
@@ -116,8 +330,14 @@ int qnnp_hip_deconv_s2_run(const struct qnnp_hip_deconv_s2_args* a, const char**
   return QNNP_HIP_EINVAL;   /* "outside the streaming kernel's range": the host then takes the phase-table path */
 }
 
-int qnnp_hip_igemm_run(const struct qnnp_hip_igemm_args* a, const char** kernel_name)
+LOGGED_RUN(qnnp_hip_deconv_s2_run, struct qnnp_hip_deconv_s2_args, log_deconv_s2, deconv_s2_run)
+
+static int igemm_run(const struct qnnp_hip_igemm_args* a, const char** kernel_name)
 {
+  if (a != NULL && a->variant == g_refuse_variant) {
+    g_refuse_variant = -1;
+    return QNNP_HIP_EINVAL;
+  }
   if (a == NULL || a->rows == 0 || a->n == 0 || a->n_pad % 32 != 0 || a->k_pad % 64 != 0 || a->n_pad < a->n) return QNNP_HIP_EINVAL;
   if (kernel_name != NULL) *kernel_name = "stub_igemm";
   if (a->phases == NULL) {
@@ -138,7 +358,9 @@ int qnnp_hip_igemm_run(const struct qnnp_hip_igemm_args* a, const char** kernel_
   return QNNP_HIP_OK;
 }
 
-int qnnp_hip_dwconv_run(const struct qnnp_hip_dwconv_args* a, const char** kernel_name)
+LOGGED_RUN(qnnp_hip_igemm_run, struct qnnp_hip_igemm_args, log_igemm, igemm_run)
+
+static int dwconv_run(const struct qnnp_hip_dwconv_args* a, const char** kernel_name)
 {
   if (a == NULL || a->batch == 0 || a->channels == 0 || a->c_pad < a->channels) return QNNP_HIP_EINVAL;
   if (kernel_name != NULL) *kernel_name = "stub_dwconv";
@@ -153,7 +375,9 @@ int qnnp_hip_dwconv_run(const struct qnnp_hip_dwconv_args* a, const char** kerne
   return QNNP_HIP_OK;
 }
 
-int qnnp_hip_vadd_run(const struct qnnp_hip_vadd_args* a, const char** kernel_name)
+LOGGED_RUN(qnnp_hip_dwconv_run, struct qnnp_hip_dwconv_args, log_dwconv, dwconv_run)
+
+static int vadd_run(const struct qnnp_hip_vadd_args* a, const char** kernel_name)
 {
   if (a == NULL || a->rows == 0 || a->channels == 0) return QNNP_HIP_EINVAL;
   if (kernel_name != NULL) *kernel_name = "stub_vadd";
@@ -163,7 +387,9 @@ int qnnp_hip_vadd_run(const struct qnnp_hip_vadd_args* a, const char** kernel_na
   return QNNP_HIP_OK;
 }
 
-int qnnp_hip_gavgpool_run(const struct qnnp_hip_gavgpool_args* a, const char** kernel_name)
+LOGGED_RUN(qnnp_hip_vadd_run, struct qnnp_hip_vadd_args, log_vadd, vadd_run)
+
+static int gavgpool_run(const struct qnnp_hip_gavgpool_args* a, const char** kernel_name)
 {
   if (a == NULL || a->batch == 0 || a->width == 0 || a->channels == 0) return QNNP_HIP_EINVAL;
   if (kernel_name != NULL) *kernel_name = "stub_gavgpool";
@@ -172,16 +398,19 @@ int qnnp_hip_gavgpool_run(const struct qnnp_hip_gavgpool_args* a, const char** k
   return QNNP_HIP_OK;
 }
 
+LOGGED_RUN(qnnp_hip_gavgpool_run, struct qnnp_hip_gavgpool_args, log_gavgpool, gavgpool_run)
+
 int qnnp_hip_fused_strip_bias_offset(const struct qnnp_hip_requant* rq) { return rq != NULL && rq->shift == 0; }
 int qnnp_hip_fused_strip_supported(const struct qnnp_hip_fused_strip_args* a) { return a != NULL && a->hidden_channels % 32 == 0; }
-int qnnp_hip_fused_strip_run(const struct qnnp_hip_fused_strip_args* a, const char** kernel_name)
+static int fused_strip_run(const struct qnnp_hip_fused_strip_args* a, const char** kernel_name)
 {
   if (!qnnp_hip_fused_strip_supported(a)) return QNNP_HIP_EINVAL;
   if (kernel_name != NULL) *kernel_name = "stub_fused_strip";
   return QNNP_HIP_OK;
 }
+LOGGED_RUN(qnnp_hip_fused_strip_run, struct qnnp_hip_fused_strip_args, log_fused_strip, fused_strip_run)
 int qnnp_hip_fused_block_supported(const struct qnnp_hip_fused_args* a) { return a != NULL && a->hidden_channels % 16 == 0; }
-int qnnp_hip_fused_block_run(const struct qnnp_hip_fused_args* a, const char** kernel_name)
+static int fused_block_run(const struct qnnp_hip_fused_args* a, const char** kernel_name)
 {
   if (!qnnp_hip_fused_block_supported(a)) return QNNP_HIP_EINVAL;
   if (kernel_name != NULL) *kernel_name = "stub_fused";
@@ -190,3 +419,4 @@ int qnnp_hip_fused_block_run(const struct qnnp_hip_fused_args* a, const char** k
   if (a->has_expand) touch(a->expand_w, (size_t) a->expand_n_pad * a->expand_k_pad);
   return QNNP_HIP_OK;
 }
+LOGGED_RUN(qnnp_hip_fused_block_run, struct qnnp_hip_fused_args, log_fused, fused_block_run)
