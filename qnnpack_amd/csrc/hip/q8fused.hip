@@ -10,7 +10,7 @@
  *   stage 1  expand: MFMA GEMM (pixels x Cin) x (Cin x Ch), both operands from LDS; Q31 requantization -> uint8
  *            hidden tile in LDS;
  *            pixels outside the image hold the hidden zero point (the depthwise stage's padding)
- *   stage 2  depthwise 3x3 over the hidden tile (v_perm + v_dot2 on int16 tap pairs, as q8dwconv.hip kernel A),
+ *   stage 2  depthwise 3x3 over the hidden tile (v_perm + v_dot2 on int16 tap pairs, as kernel A of q8dwlds.hip),
  *            requantization -> uint8 tile in LDS
  *   stage 3  project: MFMA GEMM (TH*TW pixels x Ch) x (Ch x Cout), requantization, optional quantized residual add
  *            with the block input (still in LDS), stores

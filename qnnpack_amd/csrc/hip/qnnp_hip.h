@@ -269,7 +269,10 @@ struct qnnp_hip_dwconv_args {
   uint32_t input_stride, output_stride;
   uint32_t input_zero_point;
   struct qnnp_hip_requant rq;
-  int variant;                /* 0 auto, 1 generic direct, 2 LDS-tiled, 3 register sliding window (3x3), 4 matrix-core (gather), 5 matrix-core (LDS band), 6 column-sliding window (3x3) */
+  int variant;                /* 0 auto, else one kernel or QNNP_HIP_EINVAL (the table in q8dwconv.hip): 1 generic direct, 2 LDS-tiled,
+                               * 3 register sliding window along a row (3x3), 4 matrix-core (gather), 5 matrix-core (LDS band),
+                               * 6 column-sliding window (3x3, and 5x5 with int8-range weights), 7 matrix-core 16x16x64 walk (3x3),
+                               * 8 the row window on unaligned dwords (3x3, any C >= 4), 9 generic direct, four channels per thread */
   struct qnnp_hip_dwconv_plan* plan;   /* optional plan cache owned by the caller (NULL: plan on every call) */
   uint32_t streaming_mode;    /* as qnnp_hip_igemm_args: 0 = process default, 1 = off, 2 = on */
   /* optional per-channel requantization, as in qnnp_hip_igemm_args: device table [c_pad], pad entries valid. The operator
@@ -277,7 +280,11 @@ struct qnnp_hip_dwconv_args {
   const struct qnnp_requant_pc_entry* rq_pc;
 };
 int qnnp_hip_dwconv_run(const struct qnnp_hip_dwconv_args* args, const char** kernel_name);
-/* the same for arguments with a per-channel table (q8dwconv_pc.hip, linked into libqnnpack_gfx950.so only -- see the
+/* The first half of qnnp_hip_dwconv_run alone: fills `plan` (every field but `key`, which it zeroes) and names the kernel a
+ * run of these arguments would report. Launches nothing and reads no tensor, so it needs no device. Arguments with a
+ * per-channel table are refused (QNNP_HIP_EINVAL): q8dwconv_pc.hip plans those. */
+int qnnp_hip_dwconv_plan(const struct qnnp_hip_dwconv_args* args, struct qnnp_hip_dwconv_plan* plan, const char** kernel_name);
+/* qnnp_hip_dwconv_run for arguments with a per-channel table (q8dwconv_pc.hip, linked into libqnnpack_gfx950.so only -- see the
  * Makefile); qnnp_hip_dwconv_run hands such arguments over, the host code calls only that */
 int qnnp_hip_dwconv_pc_run(const struct qnnp_hip_dwconv_args* args, const char** kernel_name);
 

@@ -421,7 +421,7 @@ static inline void qnnp_pack_dwconv_dot4(
 }
 
 /*
- * The same for 5x5 depthwise operators (q8dwconv.hip, kernel H), eight rows of c_pad words:
+ * The same for 5x5 depthwise operators (q8dwcol5.hip, kernel H), eight rows of c_pad words:
  *   image[ky][c], ky = 0..4 = (x_ky0, x_ky1, x_ky2, x_ky3)   columns 0..3 of kernel row ky, met by the transposed quads
  *   image[5][c]             = (x_04, x_14, x_24, x_34)       column 4 of kernel rows 0..3, met by the sliding column
  *   image[6][c]             = x_44 at byte c % 4, else 0     column 4 of the newest row: one-hot against the raw dword
@@ -456,7 +456,7 @@ static inline void qnnp_pack_dwconv_dot4_5x5(
 }
 
 /*
- * depthwise image for the MFMA kernel (q8dwconv.hip, kernel D): the signed tap weights
+ * depthwise image for the MFMA kernel (q8dwmfma.hip, kernels D and F): the signed tap weights
  *     x[t][c] = w[c][t] - kzp   in [-255, 255]
  * do not fit int8, so they are split into up to three int8 parts x = x0 + x1 + x2
  * (x0 = clamp(x, -128, 127), x1 = clamp(x - x0, -128, 127), x2 = the rest; x2 != 0 only for x = 255),

@@ -1,8 +1,9 @@
 """CPU tier: the INTEGRATION section 2 seam library (oracle/_ref/libqnnpack_hybrid.so: the reference objects + the
 product's objects + one patched statement, oracle/Makefile) must resolve every symbol at load time. Its object lists
-are written out in oracle/Makefile; when a product source file is added and the list is not, the link used to succeed
-(shared libraries may carry undefined symbols) and the first dlopen on the GPU box failed -- the link now runs with
---no-undefined, and this test loads the library the way tests/test_gpu_hybrid_seam.py will."""
+used to be written out in oracle/Makefile; when a product source file was added and the list was not, the link
+succeeded (shared libraries may carry undefined symbols) and the first dlopen on the GPU box failed -- the link now runs
+with --no-undefined, both Makefiles take the lists from qnnpack_amd/csrc/sources.mk, and this test loads the library
+the way tests/test_gpu_hybrid_seam.py will."""
 import ctypes
 import os
 
@@ -26,17 +27,29 @@ def test_hybrid_library_resolves_every_symbol():
 
 
 def test_oracle_makefile_lists_every_product_object():
-    """the seam's object lists against the product's source lists (qnnpack_amd/csrc/Makefile)"""
+    """the seam's object lists against the product's source lists, as make evaluates them in either Makefile: both come
+    from qnnpack_amd/csrc/sources.mk and from nowhere else"""
     import re
-    prod = open(os.path.join(ROOT, "qnnpack_amd", "csrc", "Makefile")).read()
-    orac = open(os.path.join(ROOT, "oracle", "Makefile")).read()
+    import subprocess
 
-    def words(text, var):
-        m = re.search(rf"^{var}\s*:=\s*(.*?)(?<!\\)$", text, re.M | re.S)
-        assert m, var
-        return m.group(1).replace("\\\n", " ").split()
+    def words(directory, var):
+        out = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, directory), "--eval", f"print-{var}: ; @echo $({var})",
+                              f"print-{var}"], capture_output=True, text=True)
+        assert out.returncode == 0, out.stdout + out.stderr
+        return out.stdout.split()
 
-    c_srcs = {os.path.splitext(os.path.basename(w))[0] for w in words(prod, "C_SRCS")}
-    hip_srcs = {os.path.splitext(os.path.basename(w))[0] for w in words(prod, "HIP_SRCS")}
-    assert set(words(orac, "PRODUCT_C_OBJS")) == c_srcs, (sorted(c_srcs), words(orac, "PRODUCT_C_OBJS"))
-    assert set(words(orac, "PRODUCT_HIP_OBJS")) == hip_srcs, (sorted(hip_srcs), words(orac, "PRODUCT_HIP_OBJS"))
+    c_srcs = {os.path.splitext(os.path.basename(w))[0] for w in words("qnnpack_amd/csrc", "C_SRCS")}
+    hip_srcs = {os.path.splitext(os.path.basename(w))[0] for w in words("qnnpack_amd/csrc", "HIP_SRCS")}
+    assert c_srcs and hip_srcs
+    assert set(words("oracle", "PRODUCT_C_OBJS")) == c_srcs, (sorted(c_srcs), words("oracle", "PRODUCT_C_OBJS"))
+    assert set(words("oracle", "PRODUCT_HIP_OBJS")) == hip_srcs, (sorted(hip_srcs), words("oracle", "PRODUCT_HIP_OBJS"))
+    for makefile in ("qnnpack_amd/csrc/Makefile", "oracle/Makefile"):
+        text = open(os.path.join(ROOT, makefile)).read()
+        assert re.search(r"^include .*sources\.mk$", text, re.M), makefile
+        assert not re.search(r"^(C_SRCS|HIP_SRCS)\s*[:+?]?=", text, re.M), makefile
+    # every listed source exists, and every depthwise unit on disk is listed
+    csrc = os.path.join(ROOT, "qnnpack_amd", "csrc")
+    for w in words("qnnpack_amd/csrc", "C_SRCS") + words("qnnpack_amd/csrc", "HIP_SRCS"):
+        assert os.path.exists(os.path.join(csrc, w)), w
+    on_disk = {os.path.splitext(f)[0] for f in os.listdir(os.path.join(csrc, "hip")) if re.fullmatch(r"q8dw\w+\.hip", f)}
+    assert on_disk - {"q8dwconv_pc"} <= hip_srcs, sorted(on_disk - hip_srcs)
