@@ -15,8 +15,9 @@ from oracle import o1
 pytestmark = pytest.mark.gpu
 
 
-def oracle_forward(plan, image, batch):
-    """Returns ({tensor id: uint8 array}, {op name: Quant}) -- the oracle's tensors and the parameters it chose."""
+def oracle_forward(plan, image, batch, clamp=None):
+    """Returns ({tensor id: uint8 array}, {op name: Quant}) -- the oracle's tensors and the parameters it chose.
+    clamp: the output clamp of a convolution as clamp(op, output zero point) -> (qmin, qmax); default (0, 255)."""
     tensors = {0: image}
     zps = {0: 127}
     quant = {}
@@ -29,8 +30,10 @@ def oracle_forward(plan, image, batch):
             acc = o1.conv2d_acc(shape, tensors[op.src[0]], kernel, bias, zps[op.src[0]], 127)
             oscale, ozp = output_quantization(acc)
             cout = op.groups * op.goc
-            out = o1.requantize_rows(acc.reshape(-1, cout), np.float32(1.0) / oscale, ozp, 0, 255).reshape(-1)
-            quant[op.name] = mnv2.Quant(in_zp=zps[op.src[0]], kernel_zp=127, out_scale=float(oscale), out_zp=ozp)
+            qmin, qmax = (0, 255) if clamp is None else clamp(op, ozp)
+            out = o1.requantize_rows(acc.reshape(-1, cout), np.float32(1.0) / oscale, ozp, qmin, qmax).reshape(-1)
+            quant[op.name] = mnv2.Quant(in_zp=zps[op.src[0]], kernel_zp=127, out_scale=float(oscale), out_zp=ozp,
+                                        qmin=qmin, qmax=qmax)
         elif op.kind == "add":
             a, b = tensors[op.src[0]], tensors[op.src[1]]
             out = np.empty_like(a)
