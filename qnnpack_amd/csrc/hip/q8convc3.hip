@@ -843,7 +843,9 @@ bool c3lds_plan(const IgemmParams& p, const C3Geom& cg, C3LdsGeom* out)
   lg.inv_bands = reciprocal_ceil(lg.bands);
   const uint64_t wgs = static_cast<uint64_t>(p.rows / (cg.OH * cg.OW)) * lg.bands;
   if (wgs * lg.bands >= (UINT64_C(1) << 32) || static_cast<uint64_t>(lg.nrows) * lg.cpr * lg.cpr >= (UINT64_C(1) << 32)) return false;
-  *out = lg;
+  // one workgroup per image and band, and the launch counts its grid in work-items, in 32 bits: 2^24 workgroups are refused by
+  // the runtime, more wrap (one-pixel outputs of 1 x 16 x 3 images: 2^24 images are 768 MiB)
+  if (wgs * kC3Threads >= (UINT64_C(1) << 32)) return false;  *out = lg;
   return true;
 }
 

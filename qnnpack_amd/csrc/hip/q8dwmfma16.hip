@@ -332,7 +332,10 @@ bool dwmfma16_plan(DwParams& p, uintptr_t in_addr, uintptr_t out_addr)
   p.IR = cgroups;
   const uint64_t waves = per_seg * p.slabs;
   const uint64_t dmax = strips > p.slabs ? (strips > cgroups ? strips : cgroups) : (p.slabs > cgroups ? p.slabs : cgroups);
-  return (waves + 8u) * dmax < (UINT64_C(1) << 32);
+  // the launch counts its grid in work-items, in 32 bits: a grid past that wraps, and the waves behind the wrap never run
+  // (one-pixel images of 560 channels: 3.5 M images are 122 M waves, of which the first 55 M ran)
+  const uint64_t threads = (waves + (kM16Threads / 64) - 1) / (kM16Threads / 64) * kM16Threads;
+  return (waves + 8u) * dmax < (UINT64_C(1) << 32) && threads < (UINT64_C(1) << 32);
 }
 
 int dwmfma16_launch(const DwParams& geometry, hipStream_t stream)

@@ -125,6 +125,41 @@ class Tensor:
                 f"({(lo + i) / GiB:.4f} GiB): got {int(got[i])}, want {int(want[i])}")
 
 
+class SparseRows(Tensor):
+    """`rows` rows of `channels` bytes, `stride` bytes apart, in a tensor too large to fill: only the rows and `near` bytes
+    on either side of each are ever written or compared, the bytes between them are never touched"""
+
+    def __init__(self, rows: int, stride: int, channels: int, salt: int, near: int = 4096):
+        super().__init__((rows - 1) * stride + channels, salt)
+        self.rows, self.stride, self.channels, self.near = rows, stride, channels, near
+
+    def window(self, r: int):
+        return max(r * self.stride - self.near, 0), min(r * self.stride + self.channels + self.near, self.span)
+
+    def _expected(self, r: int, data, background: int) -> np.ndarray:
+        lo, hi = self.window(r)
+        want = np.full(hi - lo, background, np.uint8)
+        if data is not None:
+            want[r * self.stride - lo:r * self.stride - lo + self.channels] = data[r]
+        return want
+
+    def write(self, data, background: int) -> None:
+        """every window = `background`, with row r = data[r] where data ([rows, channels]) is given"""
+        import torch
+        for r in range(self.rows):
+            lo, hi = self.window(r)
+            self.view[lo:hi].copy_(torch.from_numpy(self._expected(r, data, background)).cuda())
+
+    def assert_rows(self, data, background: int, what: str) -> None:
+        for r in range(self.rows):
+            lo, hi = self.window(r)
+            got, want = self.view[lo:hi].cpu().numpy(), self._expected(r, data, background)
+            bad = np.flatnonzero(got != want)
+            assert bad.size == 0, (f"{what}: row {r} and its neighbourhood differ in {bad.size} bytes, first at byte {lo + int(bad[0])} "
+                                   f"({(lo + int(bad[0])) / GiB:.4f} GiB): got {int(got[bad[0]])}, want {int(want[bad[0]])}")
+        self.assert_guards(what)
+
+
 def units(flat: np.ndarray, unit: int, n: int, fill: int) -> np.ndarray:
     """a tensor of n units whose last one is cut, as (n, unit) with the cut part `fill`"""
     out = np.full(n * unit, fill, np.uint8)

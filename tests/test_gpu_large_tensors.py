@@ -9,8 +9,9 @@ it refuses (another kernel runs, bit-exact). Covered: the 128-row unaligned GEMM
 kernel's weight-stationary flavours (input and output terms), the patch kernel, the weight-stationary 16-channel kernel
 (input and output terms), the 256x256 kernels through the offset table (centred and row-sum images), depthwise kernels
 G (input and output terms) and H, the unaligned and the aligned sliding windows, and the four-channel generic kernel's
-input term. Not covered here: the first-layer (3-channel) kernels, the long-K / one-wave streaming kernels, the 16x16x64
-depthwise walk, deconvolution, the residual add and the fused block (setup limit only).
+input term. The first-layer (3-channel) kernels, the long-K / one-wave streaming kernels, the 16x16x64 depthwise walk,
+deconvolution, the folded residual add, the fused block at its setup limit, the per-channel kernels and multiply are in
+tests/test_large_guards_gpu.py. Not covered in either file: the offset-table term of the first-layer streaming kernel.
 
 At the first refused sizes every forced kernel code must refuse with the output and input untouched or be bit-exact (the
 contract of test_gpu_kernel_contract.py). Tensors are periodic with marker units at the 2^31 / 2^32 boundaries
