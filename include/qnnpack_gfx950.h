@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "qnnpack.h"
+#include "qnnpack_gfx950_squeeze_excite.h"   /* the fused squeeze-and-excite block, beside the fused block below */
 
 #ifdef __cplusplus
 extern "C" {
@@ -434,6 +435,10 @@ enum qnnp_status qnnp_gfx950_create_fused_block(
 enum qnnp_status qnnp_gfx950_setup_fused_block(
     qnnp_operator_t fused, size_t batch_size, size_t input_height, size_t input_width,
     const uint8_t* input, size_t input_stride, uint8_t* output, size_t output_stride);
+
+/* (The other fused operator, a squeeze-and-excite block built from its five stand-alone operators --
+ * qnnp_gfx950_create_squeeze_excite / qnnp_gfx950_setup_squeeze_excite -- is declared in
+ * qnnpack_gfx950_squeeze_excite.h, included above.) */
 
 /* Residual add folded into a convolution (no reference counterpart: there it is a convolution operator followed by
  * an add operator, src/add.c). After a successful qnnp_setup_convolution2d_nhwc_q8 / qnnp_setup_fully_connected_nc_q8

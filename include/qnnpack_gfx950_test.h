@@ -52,6 +52,9 @@ extern "C" {
  *   "fused_weights": 0 / 2 = a chunk's expand / project fragments fetched from L2 by the stage that multiplies them,
  *                    1 = staged in LDS one stage ahead by LDS-DMA where they fit (measured level: measurement builds only,
  *                    the product library ignores it)
+ *   "se_kernel":     fused squeeze-and-excite blocks (qnnpack_gfx950_squeeze_excite.h), read at setup: 0 = auto (the second
+ *                    flavour for more than 1024 channels and 196 pixels or more, else the first: squeeze-excite.c), 1 = the pooling inside the gate kernel (q8_se_gate_pool, hip/q8segate.hip:
+ *                    two launches), 2 = the pooling operator's own launch into the scratch in front of q8_se_gate (three launches)
  *   "dwconv_kernel": 0 = auto, 1 = generic direct kernel, 2 = LDS-tiled kernel, 3 = register sliding-window kernel (3x3),
  *                    4 = matrix-core kernel (diagonal MFMA operands; 3x3, channels % 16 == 0), tap operands gathered
  *                        from global memory, 5 = the same with the input band staged in LDS first,

@@ -257,6 +257,18 @@ PERCHANNEL_API = (
 )
 
 
+# include/qnnpack_gfx950_squeeze_excite.h (which qnnpack_gfx950.h includes): the fused squeeze-and-excite block, built from
+# five stand-alone operators as the fused block is from three. A table of its own like FLOAT_API, for the same reason.
+SQUEEZE_EXCITE_API = (
+    _op("qnnp_gfx950_create_squeeze_excite", "ptr pool, ptr fc1, ptr fc2, ptr gate, ptr multiply, out squeeze_excite",
+        IF_PRESENT, doc="the fused squeeze-and-excite block over its five members, which it borrows and which must "
+                        "outlive it; set it up with setup_squeeze_excite"),
+    _op("qnnp_gfx950_setup_squeeze_excite",
+        "ptr op, size_t batch_size, size_t pixels, tensor input, size_t input_pixel_stride, tensor output, "
+        "size_t output_pixel_stride", IF_PRESENT),
+)
+
+
 def _bind(lib, table) -> None:
     """Set argtypes / restype of the table's symbols on a loaded library."""
     older = bool(os.environ.get("QNNP_GFX950_LIBRARY"))
@@ -344,15 +356,17 @@ class QnnpackLibrary:
         return Status(self.lib.qnnp_deinitialize())
 
 
-@_with_methods_of(GFX950_API + FLOAT_API + PERCHANNEL_API)
+@_with_methods_of(GFX950_API + FLOAT_API + PERCHANNEL_API + SQUEEZE_EXCITE_API)
 class Gfx950Library(QnnpackLibrary):
     """Product library: qnnpack.h plus the extensions of include/qnnpack_gfx950.h (GFX950_API), the float32 <-> uint8
     operators of include/qnnpack_gfx950_float.h (FLOAT_API) and the per-channel creates of
-    include/qnnpack_gfx950_perchannel.h (PERCHANNEL_API).
+    include/qnnpack_gfx950_perchannel.h (PERCHANNEL_API), and the fused squeeze-and-excite block of
+    include/qnnpack_gfx950_squeeze_excite.h (SQUEEZE_EXCITE_API).
 
     Generated as above: the fused inverted-residual block ([create|setup]_fused_block[_status]), the residual add
     folded into a convolution (attach_residual_add[_status]), quantize / dequantize with their two setups each, and
-    create_convolution2d_nhwc_q8_per_channel / create_fully_connected_nc_q8_per_channel.
+    create_convolution2d_nhwc_q8_per_channel / create_fully_connected_nc_q8_per_channel, and
+    [create|setup]_squeeze_excite[_status].
     """
 
     def __init__(self, path: str):
@@ -360,6 +374,7 @@ class Gfx950Library(QnnpackLibrary):
         _bind(self.lib, GFX950_API)
         _bind(self.lib, FLOAT_API)
         _bind(self.lib, PERCHANNEL_API)
+        _bind(self.lib, SQUEEZE_EXCITE_API)
 
     def _check(self, call: str, st: int) -> None:
         if st != 0:
@@ -447,7 +462,7 @@ class Gfx950Library(QnnpackLibrary):
         self.lib.qnnp_gfx950_graph_destroy(graph)
 
     def set_option(self, key: str, value: int) -> None:
-        if key in ("gemm_kernel", "dwconv_kernel", "fused_kernel", "fused_rows", "fused_weights"):
+        if key in ("gemm_kernel", "dwconv_kernel", "fused_kernel", "fused_rows", "fused_weights", "se_kernel"):
             # kernel-forcing codes are test / measurement hooks (include/qnnpack_gfx950_test.h), not product options
             self._check("qnnp_gfx950_test_force_kernel", self.lib.qnnp_gfx950_test_force_kernel(key.encode(), value))
             return

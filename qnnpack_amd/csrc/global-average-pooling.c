@@ -17,6 +17,7 @@
 
 #include <qnnpack.h>
 
+#include "gavgpool-params.h"
 #include "hip/qnnp_hip.h"
 #include "lifecycle.h"
 #include "log.h"
@@ -128,10 +129,9 @@ static enum qnnp_status qnnp_setup_global_average_pooling_nwc_q8_impl(
     qnnp_log_error("cannot set up global average pooling operator: NULL tensor or stride smaller than the channel count");
     return qnnp_status_invalid_parameter;
   }
-  /* the accumulator of one output is width * 255 at most; the scale must stay inside the parameter builder's
-   * range [2^-32, 256) (asserted by the reference, requantization.h:208-209) */
-  const float scale = op->input_scale / (op->output_scale * (float) width);
-  if (width > (size_t) INT32_MAX / 255 || !(scale >= 0x1.0p-32f) || !(scale < 256.0f)) {
+  /* the width's range check and quantization parameters: gavgpool-params.h */
+  struct qnnp_hip_avgpool_params params;
+  if (!qnnp_gavgpool_params_for_width(op, width, &params)) {
     qnnp_log_error("cannot set up global average pooling operator with width %zu: outside the supported range", width);
     return qnnp_status_unsupported_parameter;
   }
@@ -144,9 +144,7 @@ static enum qnnp_status qnnp_setup_global_average_pooling_nwc_q8_impl(
   op->input_pixel_stride = input_stride;
   op->output = output;
   op->output_pixel_stride = output_stride;
-  op->avgpool_params = qnnp_compute_avgpool_params(
-      -(int32_t) width * (int32_t) (uint32_t) op->input_zero_point, scale,
-      op->output_zero_point, op->output_min, op->output_max);
+  op->avgpool_params = params;
 
   op->input_span = (batch_size * width - 1) * input_stride + channels;
   op->output_span = (batch_size - 1) * output_stride + channels;

@@ -426,6 +426,43 @@ struct qnnp_hip_mul_args {
 };
 int qnnp_hip_mul_run(const struct qnnp_hip_mul_args* args, const char** kernel_name);
 
+/* the gate of a squeeze-and-excite block (q8segate.hip, linked into libqnnpack_gfx950.so only -- see the Makefile): global
+ * average pooling, two fully connected layers and a byte table as ONE kernel, one workgroup per image. No reference
+ * counterpart; every stage is the stand-alone operator's arithmetic on that operator's own device images. For image i:
+ *   p[c] = pool == 1 ? qnnp_avgpool_quantize(pool_params.bias + sum_w input[(i * pixels + w) * input_stride + c])
+ *                    : input[i * channels + c]                           (the rows a pooling launch has written, dense)
+ *   h[n] = requant1(fc1.bias2[n] + sum_k p'[k] * w1'(n, k) + fc1.row_coeff * sum_k p'[k])     n < squeeze, k < channels
+ *   e[c] = requant2(fc2.bias2[c] + sum_k h'[k] * w2'(c, k) + fc2.row_coeff * sum_k h'[k])     c < channels, k < squeeze
+ *   gate[i * channels + c] = table[e[c]]
+ * with v' = v ^ 0x80 read as int8 (= v - 128), w'(n, k) the int8 at
+ *   w[(((n / 32) * (k_pad / 32) + k / 32) * 64 + n % 32 + 32 * ((k % 32) / 16)) * 16 + k % 16]
+ * -- the fragment panels of pack.h qnnp_pack_igemm_w, single group -- bias2 the first n_pad entries of the operator's
+ * bias pair table, and requant = qnnp_q31_requantize with `rq`. `table` is 256 bytes of device memory, 4-byte aligned.
+ * channels and squeeze are 1 .. QNNP_HIP_SE_MAX_CHANNELS, k_pad a multiple of 64, n_pad a multiple of 32, both at least
+ * the channel count they pad; batch * pixels is below 2^31 and pixels * 255 fits an int32. */
+#define QNNP_HIP_SE_MAX_CHANNELS 4096u
+struct qnnp_hip_se_fc {
+  const int8_t* w;
+  const int32_t* bias2;
+  uint32_t k_pad, n_pad;
+  int32_t row_coeff;          /* 128 - kernel zero point */
+  struct qnnp_hip_requant rq;
+};
+struct qnnp_hip_se_gate_args {
+  const uint8_t* input;
+  uint8_t* gate;              /* [batch][channels], dense */
+  uint32_t batch;
+  uint32_t pixels;
+  uint32_t channels;
+  uint32_t squeeze;
+  uint64_t input_stride;      /* pool == 1: bytes between pixels */
+  uint32_t pool;              /* 1: the pooling runs inside (kernel q8_se_gate_pool); 0: `input` is the pooled rows (q8_se_gate) */
+  struct qnnp_hip_avgpool_params pool_params;
+  struct qnnp_hip_se_fc fc1, fc2;
+  const uint8_t* table;
+};
+int qnnp_hip_se_gate_run(const struct qnnp_hip_se_gate_args* args, const char** kernel_name);
+
 /* bilinear resize of uint8 NHWC tensors (u8resize.hip, linked into libqnnpack_gfx950.so only -- see the Makefile). No
  * reference counterpart. `table` is device memory, 8-byte aligned: output_height row entries, then output_width column
  * entries, each {uint32_t i0; uint32_t w | step << 11} as resize-table.h builds them (i0 + step < the input size). With

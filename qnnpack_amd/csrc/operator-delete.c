@@ -36,6 +36,7 @@ enum qnnp_status qnnp_delete_operator(qnnp_operator_t op)
   qnnp_hip_free(op->d_offsets);
   qnnp_hip_free(op->d_phase_table);
   qnnp_hip_free(op->d_resize_table);
+  qnnp_hip_free(op->d_se_scratch);
   for (uint32_t i = 0; i < op->deconv_phases && i < QNNP_MAX_DECONV_PHASES; i++) {
     qnnp_hip_free(op->phase[i].d_weights);
     qnnp_hip_free(op->phase[i].d_bias);

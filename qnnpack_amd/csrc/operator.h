@@ -34,6 +34,7 @@ enum qnnp_ukernel_type {
   qnnp_ukernel_type_resize_bilinear,    /* resize-bilinear.c */
   qnnp_ukernel_type_quantize,           /* quantize.c */
   qnnp_ukernel_type_dequantize,         /* dequantize.c */
+  qnnp_ukernel_type_squeeze_excite,     /* squeeze-excite.c */
 };
 
 /* One output phase of a strided deconvolution (deconvolution.c): the output pixels whose (oy + pad_top) % stride_h
@@ -105,6 +106,20 @@ struct qnnp_operator {
   int fused_use_strip;                          /* decided at setup */
   uint32_t fused_rows_per_strip;                /* "fused_rows" option at setup: 0 = the kernel's choice */
   uint32_t fused_weights;                       /* "fused_weights" option at setup (hip/qnnp_hip.h weights_in_lds) */
+
+  /* fused squeeze-and-excite block (squeeze-excite.c): BORROWED handles of the five stand-alone operators it was built
+   * from; batch_size images of input_width pixels of `channels` bytes; avgpool_params are the pooling member's for that
+   * pixel count. The device scratch is ONE grow-only allocation, owned: the gate rows s [batch][channels], then (flavour 2)
+   * the pooled rows p [batch][channels] at se_pooled_offset */
+  const struct qnnp_operator* se_pool;
+  const struct qnnp_operator* se_fc1;
+  const struct qnnp_operator* se_fc2;
+  const struct qnnp_operator* se_gate;
+  const struct qnnp_operator* se_multiply;
+  void* d_se_scratch;
+  size_t se_scratch_capacity;                   /* in bytes */
+  size_t se_pooled_offset;
+  uint32_t se_flavour;                          /* decided at setup: 1 = pooling inside the gate kernel, 2 = a pooling launch in front */
 
   /* residual add attached to a convolution (residual.c, qnnp_gfx950_attach_residual_add): the operator then writes
    * add(a = residual pixel, b = convolution output) -- in the convolution kernel's epilogue where that kernel carries
