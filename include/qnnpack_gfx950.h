@@ -18,6 +18,7 @@
 
 #include "qnnpack.h"
 #include "qnnpack_gfx950_squeeze_excite.h"   /* the fused squeeze-and-excite block, beside the fused block below */
+#include "qnnpack_gfx950_output_table.h"     /* a byte table folded behind a convolution, beside the residual add below */
 
 #ifdef __cplusplus
 extern "C" {

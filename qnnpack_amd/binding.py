@@ -269,6 +269,16 @@ SQUEEZE_EXCITE_API = (
 )
 
 
+# include/qnnpack_gfx950_output_table.h (which qnnpack_gfx950.h includes): a byte table folded behind a convolution. A table
+# of its own like FLOAT_API, for the same reason. `table`: a table operator, or None to detach.
+OUTPUT_TABLE_API = (
+    _op("qnnp_gfx950_attach_output_table", "ptr convolution, ptr table", IF_PRESENT,
+        doc="from now on `convolution` writes table[b] for every output byte b; the table operator's 256 bytes are copied "
+            "(it may be deleted); table=None detaches"),
+    _fn("qnnp_gfx950_operator_table_folded", "ptr op", IF_PRESENT),
+)
+
+
 def _bind(lib, table) -> None:
     """Set argtypes / restype of the table's symbols on a loaded library."""
     older = bool(os.environ.get("QNNP_GFX950_LIBRARY"))
@@ -356,17 +366,18 @@ class QnnpackLibrary:
         return Status(self.lib.qnnp_deinitialize())
 
 
-@_with_methods_of(GFX950_API + FLOAT_API + PERCHANNEL_API + SQUEEZE_EXCITE_API)
+@_with_methods_of(GFX950_API + FLOAT_API + PERCHANNEL_API + SQUEEZE_EXCITE_API + OUTPUT_TABLE_API)
 class Gfx950Library(QnnpackLibrary):
     """Product library: qnnpack.h plus the extensions of include/qnnpack_gfx950.h (GFX950_API), the float32 <-> uint8
     operators of include/qnnpack_gfx950_float.h (FLOAT_API) and the per-channel creates of
     include/qnnpack_gfx950_perchannel.h (PERCHANNEL_API), and the fused squeeze-and-excite block of
-    include/qnnpack_gfx950_squeeze_excite.h (SQUEEZE_EXCITE_API).
+    include/qnnpack_gfx950_squeeze_excite.h (SQUEEZE_EXCITE_API), and the output table of
+    include/qnnpack_gfx950_output_table.h (OUTPUT_TABLE_API).
 
     Generated as above: the fused inverted-residual block ([create|setup]_fused_block[_status]), the residual add
     folded into a convolution (attach_residual_add[_status]), quantize / dequantize with their two setups each, and
     create_convolution2d_nhwc_q8_per_channel / create_fully_connected_nc_q8_per_channel, and
-    [create|setup]_squeeze_excite[_status].
+    [create|setup]_squeeze_excite[_status], and attach_output_table[_status].
     """
 
     def __init__(self, path: str):
@@ -375,6 +386,7 @@ class Gfx950Library(QnnpackLibrary):
         _bind(self.lib, FLOAT_API)
         _bind(self.lib, PERCHANNEL_API)
         _bind(self.lib, SQUEEZE_EXCITE_API)
+        _bind(self.lib, OUTPUT_TABLE_API)
 
     def _check(self, call: str, st: int) -> None:
         if st != 0:
@@ -437,6 +449,10 @@ class Gfx950Library(QnnpackLibrary):
     def operator_residual_folded(self, op) -> int:
         """After a run: 1 = the add rode in the convolution kernel's epilogue, 0 = separate launch, -1 = none attached."""
         return int(self.lib.qnnp_gfx950_operator_residual_folded(op))
+
+    def operator_table_folded(self, op) -> int:
+        """After a run: 1 = the table rode in the convolution kernel's epilogue, 0 = separate launch, -1 = none attached."""
+        return int(self.lib.qnnp_gfx950_operator_table_folded(op))
 
     # ---- hipGraph capture of operator launches (qnnpack_gfx950.h) ----
     def graph_begin(self) -> None:

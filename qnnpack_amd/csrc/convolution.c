@@ -327,6 +327,30 @@ static int finish_residual_add(struct qnnp_operator* op, void* output, int rc)
   return qnnp_hip_vadd_run(&args, &add_kernel);
 }
 
+/* Likewise an attached output table (output-table.c) that the kernel did not carry follows as the table kernel, in place
+ * on the output: with host endpoints `output` is the staged device output, which the caller copies back afterwards.
+ * (hip/x8lut.hip is no part of the seam library, oracle/Makefile: there the symbol is absent, and so is every way to
+ * attach a table.) */
+extern int qnnp_hip_lut_run(const struct qnnp_hip_lut_args* args, const char** kernel_name) __attribute__((weak));
+
+static int finish_output_table(struct qnnp_operator* op, void* output, int rc)
+{
+  if (rc != QNNP_HIP_OK || op->d_output_table == NULL || op->table_folded) return rc;
+  const size_t pixels = op->batch_size * op->output_height * op->output_width;
+  if (qnnp_hip_lut_run == NULL || pixels > (size_t) INT32_MAX) return QNNP_HIP_EINVAL;
+  const struct qnnp_hip_lut_args args = {
+    .input = (const uint8_t*) output,
+    .output = (uint8_t*) output,
+    .table = (const uint8_t*) op->d_output_table,
+    .pixels = (uint32_t) pixels,
+    .channels = (uint32_t) ((size_t) op->groups * op->group_output_channels),
+    .input_stride = op->output_pixel_stride,
+    .output_stride = op->output_pixel_stride,
+  };
+  const char* table_kernel = NULL;   /* qnnp_gfx950_operator_kernel keeps the convolution kernel's name */
+  return qnnp_hip_lut_run(&args, &table_kernel);
+}
+
 static int launch_dwconv(struct qnnp_operator* op, const void* input, const void* input2, void* output)
 {
   (void) input2;
@@ -365,9 +389,12 @@ static int launch_dwconv(struct qnnp_operator* op, const void* input, const void
     .variant = op->variant,
     .plan = &op->dw_plan,
     .rq_pc = (const struct qnnp_requant_pc_entry*) op->d_requant_pc,
+    .table = (const uint8_t*) op->d_output_table,
+    .table_folded = &op->table_folded,
   };
   op->residual_folded = 0;
-  return finish_residual_add(op, output, qnnp_hip_dwconv_run(&args, &op->kernel_name));
+  op->table_folded = 0;
+  return finish_output_table(op, output, finish_residual_add(op, output, qnnp_hip_dwconv_run(&args, &op->kernel_name)));
 }
 
 /* reference operator-run.c:770-804 (gemm) and :805-844 (conv) */
@@ -410,6 +437,8 @@ static int launch_igemm_kernel(struct qnnp_operator* op, const void* input, void
   args.bias2_centred = op->d_bias_centred != NULL ? op->d_bias_centred : op->d_bias;
   args.centre_flip = op->centre_flip;
   args.rq_pc = (const struct qnnp_requant_pc_entry*) op->d_requant_pc;
+  args.table = (const uint8_t*) op->d_output_table;
+  args.table_folded = &op->table_folded;
   /* grouped 1x1 with a dense image (pack_dense_optional): many rows -> the dense GEMM; "gemm_kernel" 31 forces it (and is
    * refused where the operator keeps the grouped image), any other forced kernel keeps the grouped image */
   op->ran_dense = 0;
@@ -437,7 +466,8 @@ int qnnp_igemm_launch(struct qnnp_operator* op, const void* input, const void* i
 {
   (void) input2;
   op->residual_folded = 0;
-  return finish_residual_add(op, output, launch_igemm_kernel(op, input, output));
+  op->table_folded = 0;
+  return finish_output_table(op, output, finish_residual_add(op, output, launch_igemm_kernel(op, input, output)));
 }
 
 /* kernel_scales == NULL: the per-tensor create with `kernel_scale`. Else the per-channel one: `per_channel` is set,

@@ -238,6 +238,12 @@ static enum qnnp_status qnnp_gfx950_create_fused_block_impl(
     qnnp_log_error("cannot create fused block: a member has per-channel weight scales");
     return qnnp_status_unsupported_parameter;
   }
+  /* the block borrows the members' parameters and would lose an attached output table (output-table.c) */
+  if (depthwise->d_output_table != NULL || project->d_output_table != NULL ||
+      (expand != NULL && expand->d_output_table != NULL)) {
+    qnnp_log_error("cannot create fused block: a member has an output table attached");
+    return qnnp_status_unsupported_parameter;
+  }
   /* the shapes the fused kernel is written for; anything else stays with the stand-alone operators */
   if (depthwise->ukernel_type != qnnp_ukernel_type_dwconv ||
       depthwise->kernel_height != 3 || depthwise->kernel_width != 3 ||

@@ -50,6 +50,7 @@ struct DwParams {
   unsigned long long* trace;   // measurement builds only (QNNP_ENABLE_ABLATION + env QNNP_GFX950_TRACE)
   qnnp::RequantDev rq;
   uint32_t stream_out;       // 1: the column-walk kernels mark their output stores as streaming ("streaming_stores")
+  const uint8_t* table;      // kernels G and H: the output table their TAB flavour applies (qnnp_hip_dwconv_args::table), or null
 };
 
 // cycle stamp of thread 0 of the first 4096 workgroups into trace[blockIdx.x * 32 + slot]; compiled out of the product

@@ -25,6 +25,7 @@
 #include "add_math.hip.h"
 #include "device_ops.hip.h"
 #include "igemm_params.h"
+#include "lut_lookup.hip.h"
 #include "requant.hip.h"
 
 namespace qnnp {
@@ -34,7 +35,9 @@ namespace qnnp {
  * 2 = bias only (add the row term here; `bias` ignored). */
 /* RESIDUAL: the requantized bytes are then summed (qnnp_add_quantize, operand b) with the bytes at `res_row`
  * (operand a; same channel offsets as the output row, 4-byte aligned) before they are stored. */
-template <int SHIFT0, bool FULL_RANGE, bool NO_REQUANT = false, int PRE_BIASED = 0, bool RESIDUAL = false>
+/* TABLE: the requantized bytes then go through the 256-byte table whose LDS copy is `lut` (lut_lookup.hip.h; the output
+ * table of qnnpack_gfx950_output_table.h) before they are stored. Never together with RESIDUAL. */
+template <int SHIFT0, bool FULL_RANGE, bool NO_REQUANT = false, int PRE_BIASED = 0, bool RESIDUAL = false, bool TABLE = false>
 __device__ __forceinline__ void igemm_store_tile(
     const v16i& acc, const int4 (&bias)[4], int32_t rowterm,
     uint8_t* out_row,        /* output + m*stride + g*n */
@@ -42,8 +45,9 @@ __device__ __forceinline__ void igemm_store_tile(
     uint32_t khalf,          /* lane >> 5 */
     bool row_ok,             /* m < rows */
     const IgemmParams& p,
-    const uint8_t* res_row = nullptr, const qnnp_hip_add_params* add = nullptr)
+    const uint8_t* res_row = nullptr, const qnnp_hip_add_params* add = nullptr, const uint8_t* lut = nullptr)
 {
+  static_assert(!(RESIDUAL && TABLE), "a residual add and an output table are never attached together");
   uint32_t pk[4];
 #pragma unroll
   for (int rg = 0; rg < 4; rg++) {
@@ -67,6 +71,7 @@ __device__ __forceinline__ void igemm_store_tile(
         pk[rg] = add_quantize4(*reinterpret_cast<const uint32_t*>(res_row + c), pk[rg], *add);
       }
     }
+    if constexpr (TABLE) pk[rg] = lut_u8x4_at(lut, pk[rg]);
   }
   // (the store code is spelled out here and not shared with igemm_store_pk4 on purpose: the generic byte-gather kernels
   //  that end in this function run at the register limit, and their code must not move when the lane forms change)
@@ -171,11 +176,13 @@ __device__ __forceinline__ void igemm_tile_pc(
 
 /* The same for the lane forms of the requantization (requant.hip.h): the accumulators started from the bias table
  * that carries 2^31, `addend` = lane_addend(row term of this lane's row). */
-template <int SEQ, bool FULL_RANGE, bool RESIDUAL = false>
+template <int SEQ, bool FULL_RANGE, bool RESIDUAL = false, bool TABLE = false>
 __device__ __forceinline__ void igemm_store_tile_lane(
     const v16i& acc, uint64_t addend, uint8_t* out_row, uint32_t ncol0, uint32_t khalf, bool row_ok,
-    const IgemmParams& p, const uint8_t* res_row = nullptr, const qnnp_hip_add_params* add = nullptr)
+    const IgemmParams& p, const uint8_t* res_row = nullptr, const qnnp_hip_add_params* add = nullptr,
+    const uint8_t* lut = nullptr)
 {
+  static_assert(!(RESIDUAL && TABLE), "a residual add and an output table are never attached together");
   uint32_t pk[4];
 #pragma unroll
   for (int rg = 0; rg < 4; rg++) {
@@ -186,6 +193,7 @@ __device__ __forceinline__ void igemm_store_tile_lane(
       const uint32_t c = ncol0 + rg * 8 + khalf * 4;
       if (c < p.n) pk[rg] = add_quantize4(*reinterpret_cast<const uint32_t*>(res_row + c), pk[rg], *add);
     }
+    if constexpr (TABLE) pk[rg] = lut_u8x4_at(lut, pk[rg]);                                     // (as igemm_store_tile)
   }
   igemm_store_pk4(pk, out_row, ncol0, khalf, row_ok, p);
 }

@@ -110,6 +110,11 @@ struct IgemmParams {
   // valid, and the operator's clamp (less the zero point) and zero point. nullptr: `rq` is the whole requantization.
   const qnnp_requant_pc_entry* rq_pc;
   int32_t pc_lo, pc_hi, pc_zp;
+  // output table (the TAB flavours of the pointwise streaming kernels only; behind everything else, as above): 256 bytes of
+  // device memory, 4-byte aligned; every requantized byte b is stored as table[b]. The plan never sees it (q8igemm.hip sets
+  // it for the launch of a kernel that carries it, where pwstream_*_folds_table says the kernel's LDS has the room).
+  // nullptr: off. Never together with `residual`.
+  const uint8_t* table;
 };
 
 /* convolution geometry for the LDS-tiled direct-convolution kernel */
@@ -141,6 +146,11 @@ bool pwstream_longk_supported(const IgemmParams& p, uint32_t groups, uint32_t ve
 int pwstream_longk_launch(const IgemmParams& p, hipStream_t stream, const char** name);
 bool pwstream_gw_supported(const IgemmParams& p, uint32_t groups, uint32_t vec);
 int pwstream_gw_launch(const IgemmParams& p, hipStream_t stream, const char** name);
+/* whether a launch of `p` (p.table == nullptr) by the function above them has a table flavour with room for the table:
+ * the same kernel, the same grid, 256 bytes of LDS more */
+bool pwstream_folds_table(const IgemmParams& p, uint32_t vec);
+bool pwstream_longk_folds_table(const IgemmParams& p);
+bool pwstream_gw_folds_table(const IgemmParams& p);
 
 /* q8convc3.hip */
 bool conv_c3rows_supported(const IgemmParams& p, const ConvGeom& g, uint32_t groups, const int8_t* w_rows16, uint32_t real_kc);

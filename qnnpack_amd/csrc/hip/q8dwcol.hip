@@ -12,6 +12,7 @@
 
 #include "device_ops.hip.h"
 #include "dwconv_params.h"
+#include "lut_lookup.hip.h"
 #include "per_device.h"
 #include "qnnp_hip.h"
 #include "requant.hip.h"
@@ -54,12 +55,18 @@ constexpr int kColThreads = 256;
  * p.dh-th input row, so a wave takes (image, residue, segment of that residue's rows, chunk) and walks with a row
  * stride of p.dh rows: `oy0` / `oy1` then count the residue's rows (output row rho + p.dh * t), a row index `iy` of the
  * walk is input row rho - pad_top + p.dh * iy, valid for v_lo <= iy < v_hi. */
-template <int S, bool FIX, int SEQ, bool FULL, bool DEEP, bool QUAD, bool DIL = false>
+/* TAB: the output table flavour (qnnpack_gfx950_output_table.h): every packed output dword goes through the LDS copy of
+ * p.table (`tab`, lut_lookup.hip.h) before its store. The kernel has no barrier and its waves leave early, so every wave
+ * writes the table itself (stage_table_wave): it requests its dword of the table in front of its weights and writes it to
+ * LDS where it has waited for the weights anyway. */
+template <int S, bool FIX, int SEQ, bool FULL, bool DEEP, bool QUAD, bool DIL = false, bool TAB = false>
 __device__ __forceinline__ void dwconv_col3x3_body(
     const DwParams& p, const uint32_t n, const uint32_t oy0, const uint32_t oy1, const uint32_t ox, const uint32_t cg,
-    const bool ok0, const bool ok1, const bool ok2, const uint32_t rho = 0)
+    const bool ok0, const bool ok1, const bool ok2, const uint32_t rho = 0, uint8_t (*tab)[256] = nullptr)
 {
   static_assert(!DIL || (S == 1 && QUAD), "the dilated walk exists for the int8 flavour at stride 1");
+  uint32_t tab_dword = 0;
+  if constexpr (TAB) tab_dword = qnnp::table_dword(p.table);
   // kLate: the walks of the default path (int8 dot-product walk at stride 1, pair walk at stride 2) replace padding
   // where a row is CONSUMED, not where it is requested; the int16 pair walks at stride 1 (weights outside the int8
   // classes) keep the round-2 scheme
@@ -90,6 +97,7 @@ __device__ __forceinline__ void dwconv_col3x3_body(
   auto unpack_weights = [&]() __attribute__((always_inline)) {
     if constexpr (QUAD) __builtin_amdgcn_sched_barrier(0);             // behind the row loads issued so far
     auto lo16 = [](uint2 v, int c) -> uint32_t { return ((c < 2 ? v.x : v.y) >> ((c & 1) * 16)) & 0xFFFFu; };
+    if constexpr (TAB) qnnp::stage_table_wave(*tab, tab_dword);
     bias[0] = bv.x; bias[1] = bv.y; bias[2] = bv.z; bias[3] = bv.w;
     if constexpr (QUAD) {
 #pragma unroll
@@ -294,8 +302,9 @@ __device__ __forceinline__ void dwconv_col3x3_body(
 
   {
     auto finish = [&](int32_t (&acc)[4]) __attribute__((always_inline)) {
-      const uint32_t packed = qnnp::q31_requantize_pack4<SEQ, FULL>(
+      uint32_t packed = qnnp::q31_requantize_pack4<SEQ, FULL>(
           acc[0], acc[1], acc[2], acc[3], p.rq);
+      if constexpr (TAB) packed = qnnp::lut_u8x4(*tab, packed);
       // (a wave's 64 dwords of an output row are contiguous: whole lines, written once -- the streaming hint, under the
       //  "streaming_stores" option; the two builtins differ in an immediate, so hipcc cannot merge them)
       if (p.stream_out) __builtin_amdgcn_raw_buffer_store_b32(packed, out_rsrc, out_voff, out_soff, 2);
@@ -562,7 +571,7 @@ __device__ __forceinline__ void dwconv_col3x3_body(
 
 /* SEQ / FULL: the requantization flavour (requant.hip.h), chosen on the host -- one kernel per flavour, so that the
  * common one is not charged the registers of the rare ones (83 against 77 VGPRs: 5 instead of 6 waves per SIMD) */
-template <int S, int SEQ, bool FULL, bool DEEP, bool QUAD, bool DIL = false>
+template <int S, int SEQ, bool FULL, bool DEEP, bool QUAD, bool DIL = false, bool TAB = false>
 __global__ __launch_bounds__(kColThreads)
 void q8_dwconv_col3x3_kernel(const DwParams p)
 {
@@ -619,10 +628,15 @@ void q8_dwconv_col3x3_kernel(const DwParams p)
   const bool ok0 = ix0 >= 0 && ix0 < static_cast<int32_t>(p.W);
   const bool ok1 = ix0 + dcol >= 0 && ix0 + dcol < static_cast<int32_t>(p.W);
   const bool ok2 = ix0 + 2 * dcol >= 0 && ix0 + 2 * dcol < static_cast<int32_t>(p.W);
+  uint8_t (*tab)[256] = nullptr;
+  if constexpr (TAB) {
+    __shared__ alignas(16) uint8_t tab_lds[256];   // written whole by every wave that reads it (lut_lookup.hip.h)
+    tab = &tab_lds;
+  }
   if (__builtin_amdgcn_ballot_w64(!(ok0 && ok1 && ok2)) != 0) {
-    dwconv_col3x3_body<S, true, SEQ, FULL, DEEP, QUAD, DIL>(p, n, oy0, oy1, ox, cg, ok0, ok1, ok2, rho);
+    dwconv_col3x3_body<S, true, SEQ, FULL, DEEP, QUAD, DIL, TAB>(p, n, oy0, oy1, ox, cg, ok0, ok1, ok2, rho, tab);
   } else {
-    dwconv_col3x3_body<S, false, SEQ, FULL, DEEP, QUAD, DIL>(p, n, oy0, oy1, ox, cg, true, true, true, rho);
+    dwconv_col3x3_body<S, false, SEQ, FULL, DEEP, QUAD, DIL, TAB>(p, n, oy0, oy1, ox, cg, true, true, true, rho, tab);
   }
   QNNP_DW_TRACE(p, 5);
 #ifdef QNNP_ENABLE_ABLATION
@@ -713,14 +727,23 @@ int dwcol_launch(const DwParams& geometry, hipStream_t stream)
                   static_cast<uint64_t>(p.batch) * p.OH * p.OW * p.out_stride) <= (UINT64_C(96) << 20) ? 1u : 0u;
   const uint64_t waves = static_cast<uint64_t>(p.batch) * p.slabs * p.bands;
   const uint32_t blocks = static_cast<uint32_t>((waves + (kColThreads / 64) - 1) / (kColThreads / 64));
+  // every flavour twice: plain, and with the output table in its epilogue (p.table, the TAB flavour of the kernel)
+#define QNNP_DW_COL_LAUNCH(...)                                                                                        \
+  do {                                                                                                               \
+    if (p.table != nullptr) {                                                                                        \
+      hipLaunchKernelGGL((q8_dwconv_col3x3_kernel<__VA_ARGS__, true>), dim3(blocks), dim3(kColThreads), 0, stream, p); \
+    } else {                                                                                                         \
+      hipLaunchKernelGGL((q8_dwconv_col3x3_kernel<__VA_ARGS__, false>), dim3(blocks), dim3(kColThreads), 0, stream, p); \
+    }                                                                                                                \
+  } while (0)
   qnnp::requant_dispatch_ofs(p.rq, [&](auto seq, auto full) {
     constexpr int kSeq = decltype(seq)::value;
     constexpr bool kFull = decltype(full)::value;
     if (p.dh != 1 || p.dw != 1) {                  // (dwcol_plan: stride 1, the int8 flavour)
       if (p.TOH >= 12u) {
-        hipLaunchKernelGGL((q8_dwconv_col3x3_kernel<1, kSeq, kFull, true, true, true>), dim3(blocks), dim3(kColThreads), 0, stream, p);
+        QNNP_DW_COL_LAUNCH(1, kSeq, kFull, true, true, true);
       } else {
-        hipLaunchKernelGGL((q8_dwconv_col3x3_kernel<1, kSeq, kFull, false, true, true>), dim3(blocks), dim3(kColThreads), 0, stream, p);
+        QNNP_DW_COL_LAUNCH(1, kSeq, kFull, false, true, true);
       }
     } else if (p.sw == 1) {
       // four rows in flight (see the kernel) when a segment is long enough to use them: 112x112x32 30.7 -> 29.1 us,
@@ -731,18 +754,19 @@ int dwcol_launch(const DwParams& geometry, hipStream_t stream)
 #endif
       const bool quad = dwcol_uses_dot4(p);
       if (quad && deep) {
-        hipLaunchKernelGGL((q8_dwconv_col3x3_kernel<1, kSeq, kFull, true, true>), dim3(blocks), dim3(kColThreads), 0, stream, p);
+        QNNP_DW_COL_LAUNCH(1, kSeq, kFull, true, true, false);
       } else if (quad) {
-        hipLaunchKernelGGL((q8_dwconv_col3x3_kernel<1, kSeq, kFull, false, true>), dim3(blocks), dim3(kColThreads), 0, stream, p);
+        QNNP_DW_COL_LAUNCH(1, kSeq, kFull, false, true, false);
       } else if (deep) {
-        hipLaunchKernelGGL((q8_dwconv_col3x3_kernel<1, kSeq, kFull, true, false>), dim3(blocks), dim3(kColThreads), 0, stream, p);
+        QNNP_DW_COL_LAUNCH(1, kSeq, kFull, true, false, false);
       } else {
-        hipLaunchKernelGGL((q8_dwconv_col3x3_kernel<1, kSeq, kFull, false, false>), dim3(blocks), dim3(kColThreads), 0, stream, p);
+        QNNP_DW_COL_LAUNCH(1, kSeq, kFull, false, false, false);
       }
     } else {
-      hipLaunchKernelGGL((q8_dwconv_col3x3_kernel<2, kSeq, kFull, false, false>), dim3(blocks), dim3(kColThreads), 0, stream, p);
+      QNNP_DW_COL_LAUNCH(2, kSeq, kFull, false, false, false);
     }
   });
+#undef QNNP_DW_COL_LAUNCH
   return launch_status();
 }
 

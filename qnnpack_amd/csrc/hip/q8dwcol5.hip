@@ -10,6 +10,7 @@
 
 #include "device_ops.hip.h"
 #include "dwconv_params.h"
+#include "lut_lookup.hip.h"
 #include "per_device.h"
 #include "qnnp_hip.h"
 #include "requant.hip.h"
@@ -42,11 +43,16 @@ using qnnp::DwParams;
  */
 constexpr int kColThreads = 256;   // (as kernel G)
 
-template <int S, bool FIX, int SEQ, bool FULL>
+/* TAB: the output table flavour, as kernel G's: every packed output dword goes through the LDS copy of p.table (`tab`,
+ * lut_lookup.hip.h), which every wave writes for itself, before its store; the wave requests its dword of the table in
+ * front of its weights and writes it to LDS where it moves the weights to their registers. */
+template <int S, bool FIX, int SEQ, bool FULL, bool TAB>
 __device__ __forceinline__ void dwconv_col5x5_body(
     const DwParams& p, const uint32_t n, const uint32_t oy0, const uint32_t oy1, const uint32_t ox, const uint32_t cg,
-    const bool (&okc)[5])
+    const bool (&okc)[5], uint8_t (*tab)[256])
 {
+  uint32_t tab_dword = 0;
+  if constexpr (TAB) tab_dword = qnnp::table_dword(p.table);
   const uint32_t kx = p.wrange == 2u ? 0x7f7f7f7fu : 0x80808080u;    // wave-uniform
   uint4 wqv[5];
 #pragma unroll
@@ -139,6 +145,7 @@ __device__ __forceinline__ void dwconv_col5x5_body(
 #pragma unroll
   for (int r = 0; r < 5 - S; r++) X[r] = load_row(kChecked, iy_first + 5 + r);
   __builtin_amdgcn_sched_barrier(0);
+  if constexpr (TAB) qnnp::stage_table_wave(*tab, tab_dword);
   uint32_t wq[5][4], wv[4], w5[4];
   int32_t bias[4];
 #pragma unroll
@@ -208,7 +215,8 @@ __device__ __forceinline__ void dwconv_col5x5_body(
       acc[c] = __builtin_amdgcn_sdot4(static_cast<int32_t>(V[c]), static_cast<int32_t>(wv[c]), acc[c], false);
       acc[c] = __builtin_amdgcn_sdot4(static_cast<int32_t>(e_new), static_cast<int32_t>(w5[c]), acc[c], false);
     }
-    const uint32_t packed = qnnp::q31_requantize_pack4<SEQ, FULL>(acc[0], acc[1], acc[2], acc[3], p.rq);
+    uint32_t packed = qnnp::q31_requantize_pack4<SEQ, FULL>(acc[0], acc[1], acc[2], acc[3], p.rq);
+    if constexpr (TAB) packed = qnnp::lut_u8x4(*tab, packed);
     if (p.stream_out) __builtin_amdgcn_raw_buffer_store_b32(packed, out_rsrc, out_voff, out_soff, 2);   // ("streaming_stores", as kernel G)
     else __builtin_amdgcn_raw_buffer_store_b32(packed, out_rsrc, out_voff, out_soff, 0);
     out_soff += out_step;
@@ -255,7 +263,7 @@ __device__ __forceinline__ void dwconv_col5x5_body(
   }
 }
 
-template <int S, int SEQ, bool FULL>
+template <int S, int SEQ, bool FULL, bool TAB>
 __global__ __launch_bounds__(kColThreads)
 void q8_dwconv_col5x5_kernel(const DwParams p)
 {
@@ -288,11 +296,16 @@ void q8_dwconv_col5x5_kernel(const DwParams p)
     okc[k] = ix0 + k >= 0 && ix0 + k < static_cast<int32_t>(p.W);
     all_ok = all_ok && okc[k];
   }
+  uint8_t (*tab)[256] = nullptr;
+  if constexpr (TAB) {
+    __shared__ alignas(16) uint8_t tab_lds[256];   // written whole by every wave that reads it (lut_lookup.hip.h)
+    tab = &tab_lds;
+  }
   if (__builtin_amdgcn_ballot_w64(!all_ok) != 0) {
-    dwconv_col5x5_body<S, true, SEQ, FULL>(p, n, oy0, oy1, ox, cg, okc);
+    dwconv_col5x5_body<S, true, SEQ, FULL, TAB>(p, n, oy0, oy1, ox, cg, okc, tab);
   } else {
     const bool yes[5] = {true, true, true, true, true};
-    dwconv_col5x5_body<S, false, SEQ, FULL>(p, n, oy0, oy1, ox, cg, yes);
+    dwconv_col5x5_body<S, false, SEQ, FULL, TAB>(p, n, oy0, oy1, ox, cg, yes, tab);
   }
 }
 
@@ -352,10 +365,15 @@ int dwcol5_launch(const DwParams& geometry, hipStream_t stream)
   qnnp::requant_dispatch_ofs(p.rq, [&](auto seq, auto full) {
     constexpr int kSeq = decltype(seq)::value;
     constexpr bool kFull = decltype(full)::value;
-    if (p.sw == 1) {
-      hipLaunchKernelGGL((q8_dwconv_col5x5_kernel<1, kSeq, kFull>), dim3(blocks), dim3(kColThreads), 0, stream, p);
+    // every flavour twice: plain, and with the output table in its epilogue (p.table)
+    if (p.sw == 1 && p.table != nullptr) {
+      hipLaunchKernelGGL((q8_dwconv_col5x5_kernel<1, kSeq, kFull, true>), dim3(blocks), dim3(kColThreads), 0, stream, p);
+    } else if (p.sw == 1) {
+      hipLaunchKernelGGL((q8_dwconv_col5x5_kernel<1, kSeq, kFull, false>), dim3(blocks), dim3(kColThreads), 0, stream, p);
+    } else if (p.table != nullptr) {
+      hipLaunchKernelGGL((q8_dwconv_col5x5_kernel<2, kSeq, kFull, true>), dim3(blocks), dim3(kColThreads), 0, stream, p);
     } else {
-      hipLaunchKernelGGL((q8_dwconv_col5x5_kernel<2, kSeq, kFull>), dim3(blocks), dim3(kColThreads), 0, stream, p);
+      hipLaunchKernelGGL((q8_dwconv_col5x5_kernel<2, kSeq, kFull, false>), dim3(blocks), dim3(kColThreads), 0, stream, p);
     }
   });
   return launch_status();

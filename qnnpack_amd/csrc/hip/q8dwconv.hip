@@ -276,6 +276,7 @@ void params_from_args(DwParams& p, const struct qnnp_hip_dwconv_args* a)
   p.dot4 = a->dot4;
   p.inv_bands = p.inv_slabs = p.inv_q4 = p.inv_dh = 0;
   p.xcd_ranges = 0;
+  p.table = nullptr;         // (the launch switch hands it to the kernels that carry it)
 }
 
 // The name a launch of plan kernel `kernel` reports.
@@ -354,8 +355,14 @@ extern "C" int qnnp_hip_dwconv_run(const struct qnnp_hip_dwconv_args* a, const c
     case kPlanMfma: return qnnp::dwmfma_launch(p, stream);
     case kPlanRow: return qnnp::dwrow_launch(p, stream);
     case kPlanRowAny: return qnnp::dwrow_launch(p, stream, true);
-    case kPlanCol: return qnnp::dwcol_launch(p, stream);
-    case kPlanCol5: return qnnp::dwcol5_launch(p, stream);
+    case kPlanCol:
+    case kPlanCol5: {
+      // the column walks carry an attached output table in their epilogue; it is no part of the plan
+      p.table = a->table;
+      const int rc = plan->kernel == kPlanCol ? qnnp::dwcol_launch(p, stream) : qnnp::dwcol5_launch(p, stream);
+      if (rc == QNNP_HIP_OK && a->table != nullptr && a->table_folded != nullptr) *a->table_folded = 1;
+      return rc;
+    }
     case kPlanM16: return qnnp::dwmfma16_launch(p, stream);
     case kPlanDirect4: {
       const uint64_t total4 = static_cast<uint64_t>(p.batch) * p.OH * p.OW * ((p.C + 3u) / 4u);

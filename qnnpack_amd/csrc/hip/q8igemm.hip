@@ -680,6 +680,12 @@ int derive(const struct qnnp_hip_igemm_args* a, IgemmSetup& s)
   // adds in place with the stand-alone kernel.
   p.residual = nullptr;
   p.residual_stride = 0;
+  // (the output table is no part of the parameters the plan is made from: launch() hands it to a kernel that carries it)
+  p.table = nullptr;
+  if (a->table_folded != nullptr) *a->table_folded = 0;
+  if (a->table != nullptr && (a->table_folded == nullptr || a->residual != nullptr || reinterpret_cast<uintptr_t>(a->table) % 4 != 0)) {
+    return QNNP_HIP_EINVAL;
+  }
   if (a->residual_folded != nullptr) *a->residual_folded = 0;
   if (a->residual != nullptr) {
     if (a->residual_add == nullptr || a->residual_folded == nullptr) return QNNP_HIP_EINVAL;
@@ -950,9 +956,23 @@ int launch(const IgemmSetup& s, const struct qnnp_hip_igemm_args* a, const Igemm
     case Kernel::C3: rc = qnnp::convstream_c3_launch(q, stream, &name); break;
     case Kernel::Mid: rc = qnnp::gemm128x_launch(q, a->groups, stream, &name, plan.option); break;
     case Kernel::U: rc = qnnp::gemm128u_launch(q, a->groups, stream, &name, plan.option); break;
-    case Kernel::Pw: rc = qnnp::pwstream_launch(q, s.vec, stream, &name); break;
-    case Kernel::LongK: rc = qnnp::pwstream_longk_launch(q, stream, &name); break;
-    case Kernel::Gw: rc = qnnp::pwstream_gw_launch(q, stream, &name); break;
+    // the pointwise streaming kernels carry an attached output table in their epilogues where their LDS has the room for
+    // it: the same kernel and grid either way, so the table is handed over here, behind the plan
+    case Kernel::Pw:
+    case Kernel::LongK:
+    case Kernel::Gw: {
+      IgemmParams t = q;
+      if (a->table != nullptr &&
+          (plan.kernel == Kernel::Pw ? qnnp::pwstream_folds_table(q, s.vec)
+                                     : (plan.kernel == Kernel::LongK ? qnnp::pwstream_longk_folds_table(q) : qnnp::pwstream_gw_folds_table(q)))) {
+        t.table = a->table;
+      }
+      if (plan.kernel == Kernel::Pw) rc = qnnp::pwstream_launch(t, s.vec, stream, &name);
+      else if (plan.kernel == Kernel::LongK) rc = qnnp::pwstream_longk_launch(t, stream, &name);
+      else rc = qnnp::pwstream_gw_launch(t, stream, &name);
+      if (rc == QNNP_HIP_OK && t.table != nullptr) *a->table_folded = 1;
+      break;
+    }
     case Kernel::Big:
       rc = qnnp::gemm256_launch(q, a->groups, stream, &name, (plan.option & kBigWaves4) != 0, (plan.option & kBigRows128) != 0,
                                 (plan.option & kBigPingpong) != 0, plan.option & 3u);

@@ -70,10 +70,14 @@ constexpr uint32_t kMaxLds = 64 * 1024;     // weights + bias: two workgroups pe
 /* RES: the residual add of igemm_params.h rides in the epilogue -- a kernel of its own, so that layers without one
  * run exactly the code they ran before it existed (as a wave-uniform run-time branch it cost them 2-6 %, same box:
  * 28x28x144 -> 32 6.7 -> 7.1 us, 56x56x144 -> 24 15.8 -> 16.4) */
-template <int KB, int VEC, bool D2S = false, bool RES = false>
+/* TAB: the output table of igemm_params.h rides in the epilogue -- a kernel of its own for the same reason. The
+ * workgroup's copy of the table (lut_lookup.hip.h) lies behind the bias in LDS and is written in front of the prologue's
+ * barrier, the only one the kernel has. Instantiated without D2S and without RES only. */
+template <int KB, int VEC, bool D2S = false, bool RES = false, bool TAB = false>
 __global__ __launch_bounds__(kThreads, (KB <= 5) ? 4 : 2)
 void q8_pw_stream_mfma_kernel(const IgemmParams p)
 {
+  static_assert(!TAB || (!D2S && !RES), "the table flavour exists without depth-to-space stores and without a residual");
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & 63u;
@@ -152,6 +156,12 @@ void q8_pw_stream_mfma_kernel(const IgemmParams p)
   uint32_t unit = blockIdx.x * kWaves + wave;
   v4i a_next[KB];
   if (unit < units) load_rows(unit, a_next);
+  const uint8_t* lut = nullptr;
+  if constexpr (TAB) {
+    uint8_t* lds_tab = lds + nblocks * KB * 1024 + ((p.n_pad * 4u + 1023u) & ~1023u);      // behind pw_lds_bytes()
+    if (tid < 64u) reinterpret_cast<uint32_t*>(lds_tab)[tid] = reinterpret_cast<const uint32_t*>(p.table)[tid];
+    lut = lds_tab;
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // weights + bias are in LDS (and the first rows landed)
   __syncthreads();
 
@@ -260,6 +270,16 @@ void q8_pw_stream_mfma_kernel(const IgemmParams p)
           }
           continue;
         }
+        if constexpr (TAB) {                              // an activation table behind the layer folded in
+          if constexpr (rq_is_lane<kSeq>()) {
+            igemm_store_tile_lane<kSeq, decltype(full)::value, false, true>(
+                acc, row_addend, out_row, nb * 32, khalf, row_ok, p, nullptr, nullptr, lut);
+          } else {
+            igemm_store_tile<decltype(shift0)::value, decltype(full)::value, false, 2, false, true>(
+                acc, bias4, rowterm, out_row, nb * 32, khalf, row_ok, p, nullptr, nullptr, lut);
+          }
+          continue;
+        }
         if constexpr (rq_is_lane<kSeq>()) {
           igemm_store_tile_lane<kSeq, decltype(full)::value>(acc, row_addend, out_row, nb * 32, khalf, row_ok, p);
         } else {
@@ -279,11 +299,19 @@ void q8_pw_stream_mfma_kernel(const IgemmParams p)
  * block is still ONE contiguous, 16-byte aligned run in memory (32 rows x n bytes), only the image keeps its 16-byte
  * pitch; a lane gathers its 16 output bytes as two 8-byte halves, which may sit in two image rows. Those layers took the
  * direct-store kernel before: 4-byte stores, 3.9-4.3 TB/s where their 16-channel neighbours stream 4.9. */
-template <bool RES = false>
+/* TAB: every piece goes through the LDS copy `lut` of the output table (igemm_params.h, lut_lookup.hip.h) on its way out,
+ * in all three modes. */
+__device__ __forceinline__ uint4 lut_u8x16(const uint8_t* lut, const uint4& v)
+{
+  return make_uint4(lut_u8x4_at(lut, v.x), lut_u8x4_at(lut, v.y), lut_u8x4_at(lut, v.z), lut_u8x4_at(lut, v.w));
+}
+
+template <bool RES = false, bool TAB = false>
 __device__ __forceinline__ void stream_copy_out(
     const uint8_t* stage, bool whole_dense, uint32_t log_cpr, uint32_t unit, uint32_t c0, uint32_t cw,
-    const IgemmParams& p, uint32_t lane, bool dense8 = false)
+    const IgemmParams& p, uint32_t lane, bool dense8 = false, const uint8_t* lut = nullptr)
 {
+  static_assert(!(RES && TAB), "a residual add and an output table are never attached together");
   const uint32_t rows_here = min(32u, p.rows - unit * 32u);
   if (dense8) {
     const uint32_t bytes = rows_here * p.n;                  // a multiple of 8
@@ -297,6 +325,7 @@ __device__ __forceinline__ void stream_copy_out(
       const bool wrap = c + 8 >= p.n;                        // the second half starts the next row
       const uint2 hi = *reinterpret_cast<const uint2*>(stage + (wrap ? (r + 1) * pitch : r * pitch + c + 8));
       uint4 v = make_uint4(lo.x, lo.y, hi.x, hi.y);
+      if constexpr (TAB) v = lut_u8x16(lut, v);
       if constexpr (RES) {
         const uint8_t* res = p.residual + block_ofs + o;
         if (o + 16 <= bytes) {
@@ -347,9 +376,10 @@ __device__ __forceinline__ void stream_copy_out(
     const uint32_t bytes = rows_here * p.n;
     uint8_t* blk = p.output + static_cast<uint64_t>(unit) * 32u * p.n;
     for (uint32_t o = lane * 16; o < bytes; o += 2048) {
-      const uint4 v0 = *reinterpret_cast<const uint4*>(stage + o);
+      uint4 v0 = *reinterpret_cast<const uint4*>(stage + o);
       const bool two = o + 1024 < bytes;
-      const uint4 v1 = *reinterpret_cast<const uint4*>(stage + (two ? o + 1024 : o));
+      uint4 v1 = *reinterpret_cast<const uint4*>(stage + (two ? o + 1024 : o));
+      if constexpr (TAB) { v0 = lut_u8x16(lut, v0); v1 = lut_u8x16(lut, v1); }
       store16_once(blk + o, v0, p.stream_out);
       if (two) store16_once(blk + o + 1024, v1, p.stream_out);
     }
@@ -359,7 +389,8 @@ __device__ __forceinline__ void stream_copy_out(
     for (uint32_t q = lane; q < pieces; q += 64) {
       const uint32_t r = q >> log_cpr;
       const uint32_t cb = (q - (r << log_cpr)) * 16u;
-      const uint4 v = *reinterpret_cast<const uint4*>(stage + q * 16u);
+      uint4 v = *reinterpret_cast<const uint4*>(stage + q * 16u);
+      if constexpr (TAB) v = lut_u8x16(lut, v);
       if (r < rows_here && cb < cw) {
         store16_once(blk + static_cast<uint64_t>(r) * p.output_stride + cb, v, p.stream_out);
       }
@@ -394,7 +425,9 @@ constexpr int staged_waves(int kb) { return kb <= 1 ? 7 : (kb == 2 ? 6 : (kb <= 
 
 /* SEQ / FULL: the requantization flavour (requant.hip.h), chosen on the host -- one kernel per flavour, so that the
  * common ones are not charged the registers of the rare ones */
-template <int KB, int VEC, int SEQ, bool FULL, bool RES = false>
+/* TAB: the output table flavour, as the kernel above; the workgroup's copy of the table lies behind the four waves'
+ * images, is written in front of the prologue's barrier and is applied by stream_copy_out. Without RES only. */
+template <int KB, int VEC, int SEQ, bool FULL, bool RES = false, bool TAB = false>
 __global__ __launch_bounds__(kThreads, staged_waves(KB))
 void q8_pw_stream_staged_kernel(const IgemmParams p, const uint32_t nbp, const uint32_t log_cpr_arg)
 {
@@ -500,6 +533,12 @@ void q8_pw_stream_staged_kernel(const IgemmParams p, const uint32_t nbp, const u
   uint32_t unit = blockIdx.x * kWaves + wave;
   v4i a[KB];
   load_rows(min(unit, units - 1u), a);
+  const uint8_t* lut = nullptr;
+  if constexpr (TAB) {
+    uint8_t* lds_tab = lds + nbp * KB * 1024 + bias_bytes + kWaves * (32u * pitch);        // behind staged_lds_bytes()
+    if (tid < 64u) reinterpret_cast<uint32_t*>(lds_tab)[tid] = reinterpret_cast<const uint32_t*>(p.table)[tid];
+    lut = lds_tab;
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // weights + bias are in LDS (and the first rows landed)
   __syncthreads();
   if (unit >= units) return;
@@ -555,7 +594,7 @@ void q8_pw_stream_staged_kernel(const IgemmParams p, const uint32_t nbp, const u
 #ifdef QNNP_ENABLE_ABLATION
       if (p.izp_fill & 1u) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); if (next >= units) break; unit = next; continue; }
 #endif
-      stream_copy_out<RES>(stage, whole_dense, log_cpr, unit, c0, cw, p, lane, dense8);
+      stream_copy_out<RES, TAB>(stage, whole_dense, log_cpr, unit, c0, cw, p, lane, dense8, lut);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // read back before the next unit overwrites it
       if (next >= units) break;
       unit = next;
@@ -577,7 +616,8 @@ constexpr int longk_waves(int kbmax) { return kbmax <= 12 ? 4 : (kbmax <= 20 ? 3
 /* PF (round 5; KBMAX <= 20): many rows after all -- ResNet-50's 28x28 512 -> 128 is 3136 units, two or more per wave. The rows of
  * a wave's NEXT unit are requested before the current one is multiplied (a second register set, the loop unrolled twice so
  * that the sets swap roles without copies); without it every unit is a full memory round trip in front of its first MFMA. */
-template <int KBMAX, int SEQ, bool FULL, bool RES = false, bool PF = false>
+/* TAB: the output table flavour, as the staged kernel's. Without RES only. */
+template <int KBMAX, int SEQ, bool FULL, bool RES = false, bool PF = false, bool TAB = false>
 __global__ __launch_bounds__(kThreads, PF ? 2 : longk_waves(KBMAX))
 void q8_pw_stream_longk_kernel(const IgemmParams p, const uint32_t nbp, const uint32_t log_cpr)
 {
@@ -661,6 +701,12 @@ void q8_pw_stream_longk_kernel(const IgemmParams p, const uint32_t nbp, const ui
   uint32_t unit = blockIdx.x * kWaves + wave;
   v4i a[KBMAX];
   load_rows(min(unit, units - 1u), a);
+  const uint8_t* lut = nullptr;
+  if constexpr (TAB) {
+    uint8_t* lds_tab = lds + nbp * kbn * 1024 + bias_bytes + kWaves * (32u * pitch);       // behind staged_lds_bytes()
+    if (tid < 64u) reinterpret_cast<uint32_t*>(lds_tab)[tid] = reinterpret_cast<const uint32_t*>(p.table)[tid];
+    lut = lds_tab;
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // weights + bias are in LDS (and the first rows landed)
   __syncthreads();
   if (unit >= units) return;
@@ -700,7 +746,7 @@ void q8_pw_stream_longk_kernel(const IgemmParams p, const uint32_t nbp, const ui
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // image complete before it is read back
-    stream_copy_out<RES>(stage, whole_dense, log_cpr, unit_now, c0, cw, p, lane);
+    stream_copy_out<RES, TAB>(stage, whole_dense, log_cpr, unit_now, c0, cw, p, lane, false, lut);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // read back before the next unit overwrites it
   };
   if constexpr (PF) {
@@ -738,10 +784,14 @@ void q8_pw_stream_longk_kernel(const IgemmParams p, const uint32_t nbp, const ui
  */
 constexpr int kGwUnroll = 4;
 
-template <bool RES>
+/* TAB: the output table flavour. The kernel has no LDS and no barrier and its waves leave early: every wave writes the table
+ * for itself (lut_lookup.hip.h stage_table_wave), requested in front of the operands and written where the reduction is
+ * done. Without RES only. */
+template <bool RES, bool TAB = false>
 __global__ __launch_bounds__(kThreads, 4)
 void q8_pw_stream_gw_kernel(const IgemmParams p)
 {
+  static_assert(!(RES && TAB), "a residual add and an output table are never attached together");
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = threadIdx.x >> 6;
   const uint32_t row_in_block = lane & 31u;
@@ -751,6 +801,13 @@ void q8_pw_stream_gw_kernel(const IgemmParams p)
   const uint32_t units = ((p.rows + 31u) / 32u) * nblocks;
   const uint32_t unit = blockIdx.x * kWaves + wave;        // channel block fastest: neighbours share the rows
   if (unit >= units) return;
+  uint8_t (*tab)[256] = nullptr;
+  uint32_t tab_dword = 0;
+  if constexpr (TAB) {
+    __shared__ alignas(16) uint8_t tab_lds[256];
+    tab = &tab_lds;
+    tab_dword = table_dword(p.table);
+  }
   const uint32_t rb = unit / nblocks;
   const uint32_t nb = unit - rb * nblocks;
 
@@ -818,11 +875,18 @@ void q8_pw_stream_gw_kernel(const IgemmParams p)
   // (pieces beyond K read as zeros: the raw sum is over the k_total real bytes)
   const int32_t rowterm = p.row_coeff * static_cast<int32_t>(rs - 128u * p.k_total);
   uint8_t* out_row = p.output + static_cast<uint64_t>(rb * 32u + row_in_block) * p.output_stride;
+  if constexpr (TAB) stage_table_wave(*tab, tab_dword);
   requant_dispatch_ofs(p.rq, [&](auto shift0, auto full) {
     if constexpr (RES) {
       const uint8_t* res_row = p.residual + static_cast<uint64_t>(row_ok ? rb * 32u + row_in_block : 0u) * p.residual_stride;
       igemm_store_tile<decltype(shift0)::value, decltype(full)::value, false, 0, true>(
           acc, bias4, with_rq_offset<decltype(shift0)::value>(rowterm), out_row, nb * 32, khalf, row_ok, p, res_row, &p.add);
+      return;
+    }
+    if constexpr (TAB) {
+      igemm_store_tile<decltype(shift0)::value, decltype(full)::value, false, 0, false, true>(
+          acc, bias4, with_rq_offset<decltype(shift0)::value>(rowterm), out_row, nb * 32, khalf, row_ok, p, nullptr, nullptr,
+          &(*tab)[0]);
       return;
     }
     igemm_store_tile<decltype(shift0)::value, decltype(full)::value>(
@@ -839,10 +903,13 @@ void q8_pw_stream_gw_kernel(const IgemmParams p)
  * 0's through LDS (12 KiB), and wave 0 requantizes and stores. int32 partial sums are exact, so the split is
  * bit-invisible.
  */
-template <int kGwkDepth, bool RES>       // K blocks a wave has in flight: 4 or 8
+/* TAB: the output table flavour. Wave 0 alone stores: it writes the workgroup's one copy of the table in front of the
+ * barrier at which the partial sums meet, and reads it behind it. Without RES only. */
+template <int kGwkDepth, bool RES, bool TAB = false>       // K blocks a wave has in flight: 4 or 8
 __global__ __launch_bounds__(kThreads, 4)
 void q8_pw_stream_gwk_kernel(const IgemmParams p)
 {
+  static_assert(!(RES && TAB), "a residual add and an output table are never attached together");
   __shared__ __attribute__((aligned(16))) int32_t part[(kWaves - 1) * 17 * 64];   // [wave-1][register | row sum][lane]
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = threadIdx.x >> 6;
@@ -900,6 +967,12 @@ void q8_pw_stream_gwk_kernel(const IgemmParams p)
     for (int r = 0; r < 16; r++) mine[r * 64] = acc[r];
     mine[16 * 64] = rsc;
   }
+  const uint8_t* lut = nullptr;
+  if constexpr (TAB) {
+    __shared__ alignas(16) uint8_t tab_lds[256];
+    if (wave == 0) reinterpret_cast<uint32_t*>(tab_lds)[lane] = reinterpret_cast<const uint32_t*>(p.table)[lane];
+    lut = tab_lds;
+  }
   __syncthreads();
   if (wave != 0) return;
 #pragma unroll
@@ -923,6 +996,11 @@ void q8_pw_stream_gwk_kernel(const IgemmParams p)
       const uint8_t* res_row = p.residual + static_cast<uint64_t>(row_ok ? rb * 32u + row_in_block : 0u) * p.residual_stride;
       igemm_store_tile<decltype(shift0)::value, decltype(full)::value, false, 0, true>(
           acc, bias4, rowterm, out_row, nb * 32, khalf, row_ok, p, res_row, &p.add);
+      return;
+    }
+    if constexpr (TAB) {
+      igemm_store_tile<decltype(shift0)::value, decltype(full)::value, false, 0, false, true>(
+          acc, bias4, rowterm, out_row, nb * 32, khalf, row_ok, p, nullptr, nullptr, lut);
       return;
     }
     igemm_store_tile<decltype(shift0)::value, decltype(full)::value>(
@@ -1271,13 +1349,32 @@ void q8_conv_stream_c3s_kernel(const IgemmParams p, const uint32_t log_cpr)
   }
 }
 
-template <int KB, int VEC, bool D2S = false, bool RES = false>
+constexpr uint32_t kTableLds = 256;          // the table flavours' copy of the output table, behind everything else in LDS
+
+/* residency as the launchers below size it: what the registers allow, or what `lds_bytes` per workgroup leaves of a CU */
+uint32_t resident_per_cu(uint32_t by_registers, uint32_t lds_bytes)
+{
+  const uint32_t by_lds = lds_bytes > 0 ? (160u * 1024u) / lds_bytes : by_registers;
+  return by_lds < by_registers ? (by_lds > 0 ? by_lds : 1u) : by_registers;
+}
+
+/* the table flavour takes a launch planned for `lds_bytes` when the table fits the kernel's budget behind them and the
+ * launch stays as resident as it was: never a lower occupancy for the fold */
+bool table_fits(uint32_t by_registers, uint32_t lds_bytes, uint32_t budget)
+{
+  return lds_bytes + kTableLds <= budget &&
+         resident_per_cu(by_registers, lds_bytes + kTableLds) == resident_per_cu(by_registers, lds_bytes);
+}
+
+template <int KB, int VEC, bool D2S = false, bool RES = false, bool TAB = false>
 int launch_pw(const IgemmParams& p, uint32_t lds_bytes, hipStream_t stream)
 {
-  if constexpr (!RES && !D2S) {
+  if constexpr (!RES && !D2S && !TAB) {
     if (p.residual != nullptr) return launch_pw<KB, VEC, false, true>(p, lds_bytes, stream);
+    // (pwstream_folds_table: the table fits behind lds_bytes at the same residency)
+    if (p.table != nullptr) return launch_pw<KB, VEC, false, false, true>(p, lds_bytes + kTableLds, stream);
   }
-  constexpr auto kernel = q8_pw_stream_mfma_kernel<KB, VEC, D2S, RES>;
+  constexpr auto kernel = q8_pw_stream_mfma_kernel<KB, VEC, D2S, RES, TAB>;
   allow_dynamic_lds<kernel>(kMaxLds);
   // LDS bounds the residency: kMaxLds -> 2 per CU, half of that -> 4
   uint32_t per_cu = (KB <= 5) ? 4u : 2u;
@@ -1404,13 +1501,16 @@ bool plan_staged(const IgemmParams& p, uint32_t kb, StagedPlan* plan, uint32_t v
   return true;
 }
 
-template <int KB, int VEC, int SEQ, bool FULL, bool RES = false>
+template <int KB, int VEC, int SEQ, bool FULL, bool RES = false, bool TAB = false>
 int launch_pw_staged_as(const IgemmParams& p, const StagedPlan& plan, hipStream_t stream)
 {
-  if constexpr (!RES && VEC == 16) {               // (a residual implies 16-byte aligned rows: q8igemm.hip)
+  if constexpr (!RES && !TAB && VEC == 16) {       // (a residual implies 16-byte aligned rows: q8igemm.hip)
     if (p.residual != nullptr) return launch_pw_staged_as<KB, VEC, SEQ, FULL, true>(p, plan, stream);
   }
-  constexpr auto kernel = q8_pw_stream_staged_kernel<KB, VEC, SEQ, FULL, RES>;
+  if constexpr (!RES && !TAB) {
+    if (p.table != nullptr) return launch_pw_staged_as<KB, VEC, SEQ, FULL, false, true>(p, plan, stream);
+  }
+  constexpr auto kernel = q8_pw_stream_staged_kernel<KB, VEC, SEQ, FULL, RES, TAB>;
   allow_dynamic_lds<kernel>(kMaxLds);
   const uint32_t units = (p.rows + 31u) / 32u;
   uint32_t per_cu = plan.per_cu;
@@ -1428,7 +1528,8 @@ int launch_pw_staged_as(const IgemmParams& p, const StagedPlan& plan, hipStream_
   pa.izp_fill = 0;
   if (const char* env = getenv("QNNP_PW_ABL")) pa.izp_fill = static_cast<uint32_t>(atoi(env));
 #endif
-  hipLaunchKernelGGL(kernel, dim3(gx, plan.nsplit), dim3(kThreads), plan.lds_bytes, stream, pa, plan.nbp, log_arg);
+  // (TAB: the table behind the plan's LDS -- pwstream_folds_table found room for it at the same residency)
+  hipLaunchKernelGGL(kernel, dim3(gx, plan.nsplit), dim3(kThreads), plan.lds_bytes + (TAB ? kTableLds : 0u), stream, pa, plan.nbp, log_arg);
   return launch_status();
 }
 
@@ -1507,10 +1608,10 @@ bool plan_longk(const IgemmParams& p, StagedPlan* plan, int* kbmax)
   return true;
 }
 
-template <int KBMAX, int SEQ, bool FULL, bool RES = false, bool PF = false>
+template <int KBMAX, int SEQ, bool FULL, bool RES = false, bool PF = false, bool TAB = false>
 int launch_longk_as(const IgemmParams& p, const StagedPlan& plan, hipStream_t stream)
 {
-  if constexpr (!RES) {
+  if constexpr (!RES && !TAB) {
     if (p.residual != nullptr) return launch_longk_as<KBMAX, SEQ, FULL, true>(p, plan, stream);
   }
   if constexpr (!RES && !PF && KBMAX <= 20) {
@@ -1519,17 +1620,20 @@ int launch_longk_as(const IgemmParams& p, const StagedPlan& plan, hipStream_t st
     uint32_t per_cu = plan.per_cu < 2u ? plan.per_cu : 2u;
     const uint32_t gx_pf = (p.cu_count * per_cu + plan.nsplit - 1) / plan.nsplit;
     if (static_cast<uint64_t>(gx_pf) * kWaves * 5u <= static_cast<uint64_t>(units_all) * 4u) {      // >= 1.25 units per wave
-      return launch_longk_as<KBMAX, SEQ, FULL, false, true>(p, plan, stream);
+      return launch_longk_as<KBMAX, SEQ, FULL, false, true, TAB>(p, plan, stream);
     }
   }
-  constexpr auto kernel = q8_pw_stream_longk_kernel<KBMAX, SEQ, FULL, RES, PF>;
+  if constexpr (!RES && !TAB) {                    // (behind the choice of PF: the table changes nothing about it)
+    if (p.table != nullptr) return launch_longk_as<KBMAX, SEQ, FULL, false, PF, true>(p, plan, stream);
+  }
+  constexpr auto kernel = q8_pw_stream_longk_kernel<KBMAX, SEQ, FULL, RES, PF, TAB>;
   allow_dynamic_lds<kernel>(kMaxLdsLongK);
   const uint32_t units = (p.rows + 31u) / 32u;
   const uint32_t per_cu_now = PF && plan.per_cu > 2u ? 2u : plan.per_cu;       // (PF: 2 waves per SIMD by its registers)
   uint32_t gx = (p.cu_count * per_cu_now + plan.nsplit - 1) / plan.nsplit;
   const uint32_t needed = (units + kWaves - 1) / kWaves;
   if (gx > needed) gx = needed;
-  hipLaunchKernelGGL(kernel, dim3(gx, plan.nsplit), dim3(kThreads), plan.lds_bytes, stream, p, plan.nbp, plan.log_cpr);
+  hipLaunchKernelGGL(kernel, dim3(gx, plan.nsplit), dim3(kThreads), plan.lds_bytes + (TAB ? kTableLds : 0u), stream, p, plan.nbp, plan.log_cpr);
   return launch_status();
 }
 
@@ -1674,11 +1778,14 @@ int pwstream_gw_launch(const IgemmParams& p, hipStream_t stream, const char** na
     *name = "q8_pw_stream_gwk_mfma";
     const uint32_t per_wave = ((p.k_total + 31u) / 32u + kWaves - 1) / kWaves;
     const bool res = p.residual != nullptr;
+    const bool tab = !res && p.table != nullptr;
     if (per_wave <= 4) {
       if (res) hipLaunchKernelGGL((q8_pw_stream_gwk_kernel<4, true>), dim3(units), dim3(kThreads), 0, stream, p);
+      else if (tab) hipLaunchKernelGGL((q8_pw_stream_gwk_kernel<4, false, true>), dim3(units), dim3(kThreads), 0, stream, p);
       else hipLaunchKernelGGL((q8_pw_stream_gwk_kernel<4, false>), dim3(units), dim3(kThreads), 0, stream, p);
     } else {
       if (res) hipLaunchKernelGGL((q8_pw_stream_gwk_kernel<8, true>), dim3(units), dim3(kThreads), 0, stream, p);
+      else if (tab) hipLaunchKernelGGL((q8_pw_stream_gwk_kernel<8, false, true>), dim3(units), dim3(kThreads), 0, stream, p);
       else hipLaunchKernelGGL((q8_pw_stream_gwk_kernel<8, false>), dim3(units), dim3(kThreads), 0, stream, p);
     }
     return launch_status();
@@ -1686,10 +1793,40 @@ int pwstream_gw_launch(const IgemmParams& p, hipStream_t stream, const char** na
   *name = "q8_pw_stream_gw_mfma";
   if (p.residual != nullptr) {
     hipLaunchKernelGGL(q8_pw_stream_gw_kernel<true>, dim3((units + kWaves - 1) / kWaves), dim3(kThreads), 0, stream, p);
+  } else if (p.table != nullptr) {
+    hipLaunchKernelGGL((q8_pw_stream_gw_kernel<false, true>), dim3((units + kWaves - 1) / kWaves), dim3(kThreads), 0, stream, p);
   } else {
     hipLaunchKernelGGL(q8_pw_stream_gw_kernel<false>, dim3((units + kWaves - 1) / kWaves), dim3(kThreads), 0, stream, p);
   }
   return launch_status();
+}
+
+/* The table flavours (igemm_params.h). Each predicate walks its launcher's own choices for `p` without the table and asks
+ * whether the kernel that launch runs has room for the table. */
+bool pwstream_folds_table(const IgemmParams& p, uint32_t vec)
+{
+  if (p.d2s_sh != 0 || p.residual != nullptr) return false;
+  const uint32_t kb = (p.k_total + 31u) / 32u;
+  StagedPlan plan;
+  if (p.n != 32 && plan_staged(p, kb, &plan, vec)) {       // (as pwstream_launch)
+    return table_fits(static_cast<uint32_t>(staged_waves(static_cast<int>(kb))), plan.lds_bytes, kMaxLds);
+  }
+  if (p.offsets != nullptr) return false;
+  return table_fits(kb <= 5 ? 4u : 2u, pw_lds_bytes(p), kMaxLds);
+}
+
+bool pwstream_longk_folds_table(const IgemmParams& p)
+{
+  StagedPlan plan;
+  int kbmax = 0;
+  if (p.residual != nullptr || !plan_longk(p, &plan, &kbmax)) return false;
+  return table_fits(static_cast<uint32_t>(longk_waves(kbmax)), plan.lds_bytes, kMaxLdsLongK);
+}
+
+bool pwstream_gw_folds_table(const IgemmParams& p)
+{
+  // no dynamic LDS to compete with: 256 B, alone or beside the 12 KiB of partial sums
+  return p.residual == nullptr;
 }
 
 int pwstream_launch(const IgemmParams& p0, uint32_t vec, hipStream_t stream, const char** name)

@@ -203,6 +203,13 @@ struct qnnp_hip_igemm_args {
    * the per-channel flavour of the generic kernel (variant 0 or 1; any other code: QNNP_HIP_EINVAL). (Behind everything
    * else, like `residual` in IgemmParams: nothing that was here moves.) */
   const struct qnnp_requant_pc_entry* rq_pc;
+  /* optional output table (qnnpack_gfx950_output_table.h; output-table.c): 256 bytes of device memory, 4-byte aligned;
+   * output = table[the requantized convolution output], byte by byte. Kernels that carry the lookup in their epilogue set
+   * *table_folded = 1; for the others the caller launches the table kernel in place on `output` (convolution.c). The
+   * table never changes which kernel runs. table == NULL: off. Never together with `residual`. (Behind everything else,
+   * as rq_pc: nothing that was here moves.) */
+  const uint8_t* table;
+  uint32_t* table_folded;
 };
 int qnnp_hip_igemm_run(const struct qnnp_hip_igemm_args* args, const char** kernel_name);
 
@@ -278,6 +285,10 @@ struct qnnp_hip_dwconv_args {
   /* optional per-channel requantization, as in qnnp_hip_igemm_args: device table [c_pad], pad entries valid. The operator
    * runs on the kernels of q8dwconv_pc.hip (variant 0 only; any other code: QNNP_HIP_EINVAL). */
   const struct qnnp_requant_pc_entry* rq_pc;
+  /* optional output table, as in qnnp_hip_igemm_args: the 3x3 and 5x5 column walks (q8dwcol.hip, q8dwcol5.hip) carry it
+   * and set *table_folded = 1; it is no part of the plan or of its key */
+  const uint8_t* table;
+  uint32_t* table_folded;
 };
 int qnnp_hip_dwconv_run(const struct qnnp_hip_dwconv_args* args, const char** kernel_name);
 /* The first half of qnnp_hip_dwconv_run alone: fills `plan` (every field but `key`, which it zeroes) and names the kernel a

@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "device_ops.hip.h"
+#include "lut_lookup.hip.h"
 #include "per_device.h"
 #include "qnnp_hip.h"
 #include "row_map.hip.h"
@@ -48,21 +49,7 @@ __device__ __forceinline__ void global_store(uintptr_t a, T v)
   *reinterpret_cast<__attribute__((address_space(1))) T*>(a) = v;
 }
 
-/* the workgroup's copy of the table; every lane of the workgroup must call this (one barrier) */
-__device__ __forceinline__ void stage_table(uint8_t (&lds)[256], const uint8_t* table)
-{
-  if (threadIdx.x < 64u) {
-    reinterpret_cast<uint32_t*>(lds)[threadIdx.x] = reinterpret_cast<const uint32_t*>(table)[threadIdx.x];
-  }
-  __syncthreads();
-}
-
-/* table[b] for each of the four bytes b of v */
-__device__ __forceinline__ uint32_t lut_u8x4(const uint8_t (&lds)[256], uint32_t v)
-{
-  const uint32_t b0 = lds[v & 0xFFu], b1 = lds[(v >> 8) & 0xFFu], b2 = lds[(v >> 16) & 0xFFu], b3 = lds[v >> 24];
-  return b0 | b1 << 8 | b2 << 16 | b3 << 24;
-}
+/* (stage_table and lut_u8x4: lut_lookup.hip.h, shared with the table flavours of the convolution kernels) */
 
 /* one VEC-byte input piece in registers (VEC == 1: the byte) */
 template <int VEC>

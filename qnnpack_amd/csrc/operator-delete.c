@@ -33,6 +33,7 @@ enum qnnp_status qnnp_delete_operator(qnnp_operator_t op)
   qnnp_hip_free(op->d_dwm_bias);
   qnnp_hip_free(op->d_dw_dot4);
   qnnp_hip_free(op->d_requant_pc);
+  qnnp_hip_free(op->d_output_table);
   qnnp_hip_free(op->d_offsets);
   qnnp_hip_free(op->d_phase_table);
   qnnp_hip_free(op->d_resize_table);

@@ -130,6 +130,13 @@ struct qnnp_operator {
   struct qnnp_hip_add_params residual_params;
   uint32_t residual_folded;   /* last launch: 1 = in the epilogue, 0 = separate add launch */
 
+  /* byte table attached to a convolution (output-table.c, qnnp_gfx950_attach_output_table): the operator then writes
+   * table[b] for every output byte b -- in the convolution kernel's epilogue where that kernel has a table flavour, else by
+   * an in-place launch of the table kernel behind it. 256 bytes of device memory, owned; kept across setups. Never
+   * together with `residual`. */
+  void* d_output_table;
+  uint32_t table_folded;      /* last launch: 1 = in the epilogue, 0 = separate table launch */
+
   /* add / global average pooling (reference operator.h:58, 66-67, 75-100) */
   size_t channels;
   const void* input2;

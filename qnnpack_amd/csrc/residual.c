@@ -44,6 +44,11 @@ enum qnnp_status qnnp_gfx950_attach_residual_add(
     qnnp_log_error("failed to attach residual add: the convolution has per-channel weight scales");
     return qnnp_status_unsupported_parameter;
   }
+  if (convolution->d_output_table != NULL) {
+    /* add then table, or table then add: neither chain is this operator's definition (output-table.c) */
+    qnnp_log_error("failed to attach residual add: the convolution has an output table attached");
+    return qnnp_status_unsupported_parameter;
+  }
   if (convolution->device != add->device) {
     qnnp_log_error("failed to attach residual add: the operators belong to different devices");
     return qnnp_status_invalid_parameter;

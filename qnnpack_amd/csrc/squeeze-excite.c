@@ -169,6 +169,11 @@ static enum qnnp_status create_squeeze_excite(
     qnnp_log_error("cannot create squeeze-and-excite operator: a fully connected member has per-channel weight scales");
     return qnnp_status_unsupported_parameter;
   }
+  /* the gate kernel borrows the members' parameters and would lose an attached output table (output-table.c) */
+  if (fc1->d_output_table != NULL || fc2->d_output_table != NULL) {
+    qnnp_log_error("cannot create squeeze-and-excite operator: a fully connected member has an output table attached");
+    return qnnp_status_unsupported_parameter;
+  }
   if (pool->channels > QNNP_GFX950_SQUEEZE_EXCITE_MAX_CHANNELS ||
       fc1->group_output_channels > QNNP_GFX950_SQUEEZE_EXCITE_MAX_CHANNELS) {
     qnnp_log_error("cannot create squeeze-and-excite operator with %zu channels squeezed to %zu: the gate kernel takes %u "
