@@ -129,7 +129,7 @@ done:
 
 /* Kernel == stride (the usual 2x upsampling): every output pixel has exactly one tap and every input pixel
  * feeds stride_h*stride_w output pixels, so the whole operator is ONE pointwise GEMM over the input pixels with
- * phases * n_pad columns (phase-major) whose 32-channel blocks are stored depth-to-space (q8pwconv.hip).
+ * phases * n_pad columns (phase-major) whose 32-channel blocks are stored depth-to-space (q8pwstream.hip).
  * Packed beside the phase kernels; the run falls back to those if the streaming kernel cannot take the tensors. */
 static enum qnnp_status pack_depth_to_space(struct qnnp_operator* op, const uint8_t* conv_order, const int32_t* bias)
 {

@@ -112,7 +112,7 @@ struct IgemmParams {
   int32_t pc_lo, pc_hi, pc_zp;
   // output table (the TAB flavours of the pointwise streaming kernels only; behind everything else, as above): 256 bytes of
   // device memory, 4-byte aligned; every requantized byte b is stored as table[b]. The plan never sees it (q8igemm.hip sets
-  // it for the launch of a kernel that carries it, where pwstream_*_folds_table says the kernel's LDS has the room).
+  // it for the launch of a kernel that carries it, where the streaming plan says the kernel's LDS has the room: PwPlan::tab).
   // nullptr: off. Never together with `residual`.
   const uint8_t* table;
 };
@@ -137,20 +137,40 @@ int convwave_launch(const IgemmParams& p, const ConvGeom& g, uint32_t batch, hip
 bool convpatch_supported(const IgemmParams& p, const ConvGeom& g, uint32_t groups, uint32_t vec, uint32_t batch);
 int convpatch_launch(const IgemmParams& p, const ConvGeom& g, uint32_t batch, hipStream_t stream, const char** name);
 
-/* q8pwconv.hip */
-bool pwstream_supported(const IgemmParams& p, uint32_t groups, uint32_t vec);
-int pwstream_launch(const IgemmParams& p, uint32_t vec, hipStream_t stream, const char** name);
-bool convstream_c3_supported(const IgemmParams& p, uint32_t groups);
-int convstream_c3_launch(const IgemmParams& p, hipStream_t stream, const char** name);
-bool pwstream_longk_supported(const IgemmParams& p, uint32_t groups, uint32_t vec);
-int pwstream_longk_launch(const IgemmParams& p, hipStream_t stream, const char** name);
-bool pwstream_gw_supported(const IgemmParams& p, uint32_t groups, uint32_t vec);
-int pwstream_gw_launch(const IgemmParams& p, hipStream_t stream, const char** name);
-/* whether a launch of `p` (p.table == nullptr) by the function above them has a table flavour with room for the table:
- * the same kernel, the same grid, 256 bytes of LDS more */
-bool pwstream_folds_table(const IgemmParams& p, uint32_t vec);
-bool pwstream_longk_folds_table(const IgemmParams& p);
-bool pwstream_gw_folds_table(const IgemmParams& p);
+/* The launch of a streaming kernel: everything its planner decides -- the instantiation, the grid, the dynamic LDS, the
+ * staged kinds' channel columns. The plan decides speed, not bytes (tests/test_igemm_plan_host.py holds it to a record). */
+enum class PwFamily : uint8_t { None, Stream, Staged, LongK, Gw, Gwk, C3 };
+struct PwPlan {
+  PwFamily family;
+  uint32_t kb;             // KB (stream, staged) or KBMAX (long-K)
+  uint32_t vec;            // VEC
+  uint32_t depth;          // gwk: K blocks a wave has in flight
+  bool d2s, res, tab, pf;  // the flavour; tab: the table folds, and lds_bytes has its 256 bytes
+  bool c3_staged;          // C3: q8_conv_stream_c3s_kernel
+  int seq, full;           // the requantization flavour the host's dispatch picks; -1: the kernel dispatches itself
+  uint32_t grid_x, grid_y;
+  uint32_t lds_bytes;      // dynamic LDS
+  uint32_t nbp, log_cpr;   // the staged kinds' kernel arguments (log_cpr as passed: bit 31 = dense8)
+  uint32_t per_cu;         // resident workgroups per CU the persistent grid is sized for (0: one workgroup per unit)
+};
+
+/* q8pwconv.hip: the pointwise streaming kernels' plans and their launch switch. A plan function answers whether its family
+ * takes `p` (p.table == nullptr), and fills the plan; want_table: the caller has an output table it would like folded, and
+ * plan->tab answers whether the launch carries it -- the same kernel and grid either way, 256 bytes of LDS more. The caller
+ * then sets p.table for the launch. */
+bool pwstream_plan(const IgemmParams& p, uint32_t groups, uint32_t vec, bool want_table, PwPlan* plan);
+bool pwstream_longk_plan(const IgemmParams& p, uint32_t groups, uint32_t vec, bool want_table, PwPlan* plan);
+bool pwstream_gw_plan(const IgemmParams& p, uint32_t groups, uint32_t vec, bool want_table, PwPlan* plan);
+const char* pwstream_kernel_name(const PwPlan& plan);
+int pwstream_launch(const IgemmParams& p, const PwPlan& plan, hipStream_t stream, const char** name);
+/* q8pwstream.hip, q8pwstaged.hip, q8pwlongk.hip, q8pwgw.hip: the launch of a plan of their family */
+int pw_stream_launch(const IgemmParams& p, const PwPlan& plan, hipStream_t stream);
+int pw_staged_launch(const IgemmParams& p, const PwPlan& plan, hipStream_t stream);
+int pw_longk_launch(const IgemmParams& p, const PwPlan& plan, hipStream_t stream);
+int pw_gw_launch(const IgemmParams& p, const PwPlan& plan, hipStream_t stream);
+/* q8convc3s.hip: 3-channel images on the streaming scheme */
+bool convstream_c3_plan(const IgemmParams& p, uint32_t groups, PwPlan* plan);
+int convstream_c3_launch(const IgemmParams& p, const PwPlan& plan, hipStream_t stream, const char** name);
 
 /* q8convc3.hip */
 bool conv_c3rows_supported(const IgemmParams& p, const ConvGeom& g, uint32_t groups, const int8_t* w_rows16, uint32_t real_kc);

@@ -1,6 +1,6 @@
 /*
  * lut_lookup.hip.h -- the byte lookup of the table kernels (x8lut.hip) and of the table flavours of the convolution
- * kernels (qnnpack_gfx950_output_table.h: q8pwconv.hip, q8dwcol.hip, q8dwcol5.hip): the 256-byte table in LDS, one LDS
+ * kernels (qnnpack_gfx950_output_table.h: q8pwconv.hip's kernel units, q8dwcol.hip, q8dwcol5.hip): the 256-byte table in LDS, one LDS
  * byte read (ds_read_u8) per byte, four of them packed into each dword.
  *
  * Two ways to stage the table:

@@ -6,7 +6,7 @@
  * src/indirection.c:18-79) for the network-entry layers of bench/convolution.cc (MobileNetV2 line 457: 224x224x3 ->
  * 112x112x32, 3x3 stride 2).
  *
- * Why a third kernel for this shape: the offset-table kernel of q8pwconv.hip (q8_conv_stream_c3s_kernel) gathers a
+ * Why a third kernel for this shape: the offset-table kernel of q8convc3s.hip (q8_conv_stream_c3s_kernel) gathers a
  * pixel's nine taps with eight unaligned dword loads per lane and assembles the MFMA operand from them -- 245 VALU + 140
  * scalar instructions per 32 output pixels for ONE useful MFMA, and a SIMD issues one instruction per four cycles
  * whatever its waves do: 22 us of the 35 were instruction issue with no memory operation at all.

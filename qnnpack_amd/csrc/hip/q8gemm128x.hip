@@ -2,7 +2,7 @@
  * q8gemm128x.hip -- the zero-point-centred uint8 GEMM on v_mfma_i32_16x16x64_i8 in 128 x 128 tiles of four waves (round 6).
  *
  * Role. The 1x1 convolutions and fully connected layers that are neither long-and-wide (q8gemm256x.hip: 256 x 256 tiles, one
- * workgroup per CU, >= 8 K tiles) nor output-streaming with a short reduction (q8pwconv.hip): MobileNetV2's late pointwise
+ * workgroup per CU, >= 8 K tiles) nor output-streaming with a short reduction (q8pwconv.hip and its kernel units): MobileNetV2's late pointwise
  * layers (14 x 14 and 7 x 7 maps, K = 192 ... 960, N = 64 ... 1280: bench/convolution.cc:496-536) and ResNet-50's 7 x 7 / 14 x 14
  * bottleneck convolutions (:690-718). The reference runs them through the same q8gemm microkernel as everything else
  * (src/q8gemm/4x4c2-sse2.c:14-318 under compute_q8gemm, src/operator-run.c:39-70, 797-802). On this chip they are a few

@@ -562,6 +562,9 @@ struct IgemmSetup {
   bool pad3;               // 3-channel slot mode
   uint32_t vec;            // activation load width
   qnnp::ConvGeom geom;
+  // the streaming kernels' launch plans (igemm_params.h), made where supported() asks whether the kernel takes the operator --
+  // once per run -- and handed to launch(); family None: not asked, or refused
+  mutable qnnp::PwPlan pw, longk, gw, c3;
 };
 
 // Kernel zero points 127 / 128: the zero-point-centred image (convolution.c / fully-connected.c), with its own bias pair and no
@@ -703,6 +706,7 @@ int derive(const struct qnnp_hip_igemm_args* a, IgemmSetup& s)
   geom.KH = a->kernel_height; geom.KW = a->kernel_width; geom.sh = a->stride_height; geom.sw = a->stride_width;
   geom.dh = a->dilation_height; geom.dw = a->dilation_width; geom.pad_top = a->pad_top; geom.pad_left = a->pad_left;
   s.centred = centred_params(p, a, &s.pc);
+  s.pw = s.longk = s.gw = s.c3 = qnnp::PwPlan{};
   return QNNP_HIP_OK;
 }
 
@@ -781,7 +785,21 @@ bool big_image_ok(const IgemmSetup& s, const struct qnnp_hip_igemm_args* a, Imag
   return has_image && qnnp::gemm256c_supported(image_params(s, a, image, built), s.vec);
 }
 
-// Whether a kernel takes the operator: its *_supported predicate and what the dispatch adds to it
+// The streaming plan of a kernel that has one (supported() made it), else nullptr
+const qnnp::PwPlan* stream_plan(const IgemmSetup& s, Kernel k)
+{
+  switch (k) {
+    case Kernel::Pw: return &s.pw;
+    case Kernel::LongK: return &s.longk;
+    case Kernel::Gw: return &s.gw;
+    case Kernel::C3: return &s.c3;
+    default: return nullptr;
+  }
+}
+
+// Whether a kernel takes the operator: its *_supported predicate and what the dispatch adds to it. For the streaming kernels
+// the predicate is "the plan succeeds", and the plan stays in `s` for launch(): an attached output table is no part of the
+// parameters, so the plan is asked beside them whether the launch would carry it.
 bool supported(const IgemmSetup& s, const struct qnnp_hip_igemm_args* a, Kernel k, Image image = Image::Standard)
 {
   const IgemmParams& p = s.p;
@@ -797,12 +815,12 @@ bool supported(const IgemmSetup& s, const struct qnnp_hip_igemm_args* a, Kernel 
       return s.pad3 && (p.store_mode == 2 || (p.store_mode == 1 && a->n % 8u == 0)) &&
              qnnp::conv_c3rows_supported(p, s.geom, a->groups, a->packed_w_rows16, a->kc);
     case Kernel::Rows32: return s.pad3 && p.store_mode == 2 && qnnp::conv_c3rows32_supported(p, s.geom, a->groups, a->packed_w_rows16, a->kc);
-    case Kernel::C3: return s.pad3 && qnnp::convstream_c3_supported(p, a->groups);
+    case Kernel::C3: return s.pad3 && qnnp::convstream_c3_plan(p, a->groups, &s.c3);
     case Kernel::Mid: return !s.pad3 && s.centred && a->groups == 1 && qnnp::gemm128x_supported(s.pc, s.vec);
     case Kernel::U: return !s.pad3 && qnnp::gemm128u_supported(p);
-    case Kernel::Pw: return !s.pad3 && qnnp::pwstream_supported(p, a->groups, s.vec) && (p.d2s_sh == 0 || s.vec == 16);
-    case Kernel::LongK: return !s.pad3 && qnnp::pwstream_longk_supported(p, a->groups, s.vec);
-    case Kernel::Gw: return !s.pad3 && qnnp::pwstream_gw_supported(p, a->groups, s.vec);
+    case Kernel::Pw: return !s.pad3 && qnnp::pwstream_plan(p, a->groups, s.vec, a->table != nullptr, &s.pw);
+    case Kernel::LongK: return !s.pad3 && qnnp::pwstream_longk_plan(p, a->groups, s.vec, a->table != nullptr, &s.longk);
+    case Kernel::Gw: return !s.pad3 && qnnp::pwstream_gw_plan(p, a->groups, s.vec, a->table != nullptr, &s.gw);
     case Kernel::Big: return !s.pad3 && qnnp::gemm256_supported(p, s.vec);
     case Kernel::BigC: case Kernel::BigX: return supported(s, a, Kernel::Big) && big_image_ok(s, a, image);
     case Kernel::Generic: break;
@@ -953,7 +971,7 @@ int launch(const IgemmSetup& s, const struct qnnp_hip_igemm_args* a, const Igemm
     case Kernel::Lds: rc = qnnp::convlds_launch(q, s.geom, batch, stream, &name); break;
     case Kernel::Rows16: rc = qnnp::conv_c3rows_launch(q, s.geom, a->packed_w_rows16, stream, &name, plan.option); break;
     case Kernel::Rows32: rc = qnnp::conv_c3rows32_launch(q, s.geom, a->packed_w_rows16, stream, &name, plan.option); break;
-    case Kernel::C3: rc = qnnp::convstream_c3_launch(q, stream, &name); break;
+    case Kernel::C3: rc = qnnp::convstream_c3_launch(q, s.c3, stream, &name); break;
     case Kernel::Mid: rc = qnnp::gemm128x_launch(q, a->groups, stream, &name, plan.option); break;
     case Kernel::U: rc = qnnp::gemm128u_launch(q, a->groups, stream, &name, plan.option); break;
     // the pointwise streaming kernels carry an attached output table in their epilogues where their LDS has the room for
@@ -961,16 +979,11 @@ int launch(const IgemmSetup& s, const struct qnnp_hip_igemm_args* a, const Igemm
     case Kernel::Pw:
     case Kernel::LongK:
     case Kernel::Gw: {
+      const qnnp::PwPlan& sp = *stream_plan(s, plan.kernel);
       IgemmParams t = q;
-      if (a->table != nullptr &&
-          (plan.kernel == Kernel::Pw ? qnnp::pwstream_folds_table(q, s.vec)
-                                     : (plan.kernel == Kernel::LongK ? qnnp::pwstream_longk_folds_table(q) : qnnp::pwstream_gw_folds_table(q)))) {
-        t.table = a->table;
-      }
-      if (plan.kernel == Kernel::Pw) rc = qnnp::pwstream_launch(t, s.vec, stream, &name);
-      else if (plan.kernel == Kernel::LongK) rc = qnnp::pwstream_longk_launch(t, stream, &name);
-      else rc = qnnp::pwstream_gw_launch(t, stream, &name);
-      if (rc == QNNP_HIP_OK && t.table != nullptr) *a->table_folded = 1;
+      if (sp.tab) t.table = a->table;
+      rc = qnnp::pwstream_launch(t, sp, stream, &name);
+      if (rc == QNNP_HIP_OK && sp.tab) *a->table_folded = 1;
       break;
     }
     case Kernel::Big:
@@ -1007,4 +1020,41 @@ extern "C" int qnnp_hip_igemm_run(const struct qnnp_hip_igemm_args* a, const cha
   int rc = derive(a, s);
   if (rc == QNNP_HIP_OK) rc = make_plan(s, a, &plan);
   return rc == QNNP_HIP_OK ? launch(s, a, plan, kernel_name) : rc;
+}
+
+extern "C" int qnnp_hip_igemm_plan(const struct qnnp_hip_igemm_args* a, struct qnnp_hip_igemm_plan* out, const char** kernel_name)
+{
+  static const uint8_t no_table[1] = {0};
+  IgemmSetup s;
+  IgemmPlan plan;
+  if (out == nullptr) return QNNP_HIP_EINVAL;
+  const struct qnnp_hip_igemm_plan nothing{};
+  *out = nothing;
+  if (kernel_name != nullptr) *kernel_name = nullptr;
+  int rc = derive(a, s);
+  if (rc != QNNP_HIP_OK) return rc;
+  // Without a device there is no fill table, and the streaming kernels' predicates refuse on that. No plan reads the table,
+  // so this entry plans as if it were there.
+  if (s.p.fill_table == nullptr) s.p.fill_table = s.pc.fill_table = no_table;
+  rc = make_plan(s, a, &plan);
+  if (rc != QNNP_HIP_OK) return rc;
+  out->kernel = static_cast<uint32_t>(plan.kernel);
+  out->image = static_cast<uint32_t>(plan.image);
+  out->option = plan.option;
+  out->vec = s.vec;
+  out->store_mode = s.p.store_mode;
+  if (const qnnp::PwPlan* sp = stream_plan(s, plan.kernel)) {
+    const bool pointwise = plan.kernel != Kernel::C3;
+    if (kernel_name != nullptr) *kernel_name = qnnp::pwstream_kernel_name(*sp);
+    out->family = static_cast<uint32_t>(sp->family);
+    out->kb = sp->kb; out->kvec = sp->vec; out->depth = sp->depth;
+    out->d2s = sp->d2s; out->res = sp->res; out->tab = sp->tab; out->pf = sp->pf; out->c3_staged = sp->c3_staged;
+    out->seq = sp->seq; out->full = sp->full;
+    out->grid_x = sp->grid_x; out->grid_y = sp->grid_y; out->lds_bytes = sp->lds_bytes;
+    out->nbp = sp->nbp; out->log_cpr = sp->log_cpr; out->per_cu = sp->per_cu;
+    // (as launch() reports them)
+    out->residual_folded = pointwise && s.p.residual != nullptr;
+    out->table_folded = pointwise && sp->tab;
+  }
+  return rc;
 }

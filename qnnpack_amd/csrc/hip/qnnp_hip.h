@@ -212,6 +212,28 @@ struct qnnp_hip_igemm_args {
   uint32_t* table_folded;
 };
 int qnnp_hip_igemm_run(const struct qnnp_hip_igemm_args* args, const char** kernel_name);
+/* What a run of an argument block decides before it launches, as plain integers (tests/host_igemm_plan_test.c prints it;
+ * nothing else reads it). `kernel`, `image` and `option` are q8igemm.hip's plan, the enumerators by value. The fields from
+ * `family` on describe the launch of the streaming kernels (q8pwconv.hip, q8convc3s.hip) and are zero for every other one. */
+struct qnnp_hip_igemm_plan {
+  uint32_t kernel, image, option;
+  uint32_t vec, store_mode;   /* activation load width and store width (IgemmParams::store_mode) of the argument block */
+  uint32_t family;            /* 1 stream, 2 staged, 3 long-K, 4 gw, 5 gwk, 6 c3 */
+  uint32_t kb;                /* the instantiation: KB (stream, staged) or KBMAX (long-K), */
+  uint32_t kvec;              /* VEC, */
+  uint32_t d2s, res, tab, pf; /* the flavours, */
+  uint32_t depth;             /* K blocks a gwk wave has in flight, */
+  int32_t seq, full;          /* the requantization flavour where the host picks it (-1: the kernel dispatches itself), */
+  uint32_t c3_staged;         /* and which of the two 3-channel kernels */
+  uint32_t grid_x, grid_y, lds_bytes;   /* launch geometry; lds_bytes is the dynamic LDS */
+  uint32_t nbp, log_cpr;      /* kernel arguments of the staged kinds (log_cpr as passed: bit 31 = dense8) */
+  uint32_t per_cu;            /* resident workgroups per CU the persistent grid is sized for (0: one workgroup per unit) */
+  uint32_t residual_folded, table_folded;   /* what a run would report through the argument block's pointers */
+};
+/* The first half of qnnp_hip_igemm_run alone: the argument checks, the kernel choice and, for the streaming kernels, all
+ * their launchers decide. Launches nothing, makes no HIP call and reads no tensor, so it needs no device: it plans for
+ * 256 compute units then. *kernel_name: the name a run would report for a streaming kernel, else NULL. */
+int qnnp_hip_igemm_plan(const struct qnnp_hip_igemm_args* args, struct qnnp_hip_igemm_plan* plan, const char** kernel_name);
 
 /* ---- q8 deconvolution, stride 2, 3x3 / 4x4 kernels (q8deconv.hip) --------------------------------------
  * One streaming kernel over the input pixels in place of the phase-table GEMMs above (same packed per-phase

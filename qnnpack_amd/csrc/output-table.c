@@ -3,7 +3,7 @@
  * the byte table behind it. No reference counterpart: in the reference an activation that is not a clamp is a table
  * operator behind the convolution (src/sigmoid.c, src/leaky-relu.c + x8lut), i.e. one more launch and one more pass over
  * the tensor. Here the lookup rides in the epilogue of the convolution's kernel where that kernel has a table flavour
- * (the pointwise streaming kernels, q8pwconv.hip, and the depthwise column walks, q8dwcol.hip / q8dwcol5.hip), and runs
+ * (the pointwise streaming kernels, q8pwconv.hip and its kernel units, and the depthwise column walks, q8dwcol.hip / q8dwcol5.hip), and runs
  * as an in-place launch of the table kernel behind the convolution otherwise (convolution.c finish_output_table); either
  * way the bytes are those of convolution -> qnnp_gfx950_setup_lut_nc_x8 in place on its output.
  *

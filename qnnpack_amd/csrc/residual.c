@@ -3,7 +3,7 @@
  * add behind it. No reference counterpart: in the reference a residual connection is a convolution operator followed
  * by an add operator (src/add.c + q8vadd, the MobileNetV2 pattern of SURVEY.md section 8f row 4), i.e. one more pass
  * over the tensor -- HBM traffic that is the whole cost of the add on this chip. Here the add rides in the epilogue
- * of the convolution's kernel where that kernel carries it (the pointwise streaming kernels, q8pwconv.hip: every
+ * of the convolution's kernel where that kernel carries it (the pointwise streaming kernels, q8pwconv.hip and its kernel units: every
  * MobileNetV2 project layer), and runs as an in-place launch of the add kernel behind the convolution otherwise;
  * either way the bytes are those of convolution -> qnnp_setup_add_nc_q8(a = residual, b = convolution output).
  *

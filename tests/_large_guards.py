@@ -101,13 +101,13 @@ def c3lds_guard(case: ConvCase):
 
 
 def stream_c3_guard(case: ConvCase):
-    """q8pwconv.hip: convstream_c3_launch, the condition of the staged flavour (the unstaged one takes what fails it)"""
+    """q8convc3s.hip: convstream_c3_plan, the condition of the staged flavour (the unstaged one takes what fails it)"""
     oh, ow = output_hw(case)
     return {"input": (spans(case)[0], B31), "table": (oh * ow * case.kernel_size[0] * case.kernel_size[1] * 4, B31)}
 
 
 def gw_guard(case: FcCase):
-    """q8pwconv.hip: pwstream_gw_supported"""
+    """q8pwconv.hip: pwstream_gw_plan"""
     n_pad = (case.output_channels + 31) // 32 * 32
     return {"input": ((case.batch - 1) * case.in_stride + case.input_channels, B31),
             "units": ((case.batch + 31) // 32 * (n_pad // 32), B31)}
@@ -260,7 +260,7 @@ STREAM_C3 = [
     _c3("c3s_64x64_n32_out_past_4g", (64, 64), 3, 1, 2, 32, B32 // (32 * 32 * 32) + 3),
 ]
 
-# 2.3  q8_pw_stream_longk_mfma (code 9): plan_longk and plan_staged hold no size term (LDS, channel and K conditions only), so
+# 2.3  q8_pw_stream_longk_mfma (code 9): pwstream_longk_plan and plan_staged hold no size term (LDS, channel and K conditions only), so
 # it is run past 2^32 on each side: 512 -> 64 (K blocks 16: the 20-block flavour) and 272 -> 256 (9 blocks: the 12-block one)
 LONGK_CASES = [
     FcCase("longk_512_64_in_past_4g", (1 << 23) + 7, 512, 64),

@@ -1,5 +1,5 @@
 """GPU tier: the barrier-free streaming kernel for convolutions over 3-channel images
-(q8_conv_stream_c3_kernel in qnnpack_amd/csrc/hip/q8pwconv.hip), forced with "gemm_kernel" = 7, against the
+(q8_conv_stream_c3_kernel in qnnpack_amd/csrc/hip/q8convc3s.hip), forced with "gemm_kernel" = 7, against the
 scalar oracle: first-layer shapes, strides, paddings, pixel strides, 1..16 taps, ragged pixel blocks and
 channel counts, zero points; the very last pixel of the tensor (read bytewise) is covered by every case."""
 import pytest

@@ -1,5 +1,5 @@
 """GPU tier: the barrier-free streaming kernel for short-K pointwise / fully-connected layers
-(qnnpack_amd/csrc/hip/q8pwconv.hip), forced with "gemm_kernel" = 5, against the scalar oracle: row-block
+(qnnpack_amd/csrc/hip/q8pwstream.hip and q8pwstaged.hip, planned by q8pwconv.hip), forced with "gemm_kernel" = 5, against the scalar oracle: row-block
 edges, every K-block count and both load widths (16- and 8-byte aligned rows), channel-count edges and the
 three store modes, strides, zero-point / clamp variants, and the 1x1 convolution form. MobileNetV2's
 pointwise layers (BASELINE configs[3]) take this kernel automatically; test_gpu_fullsize.py asserts that."""

@@ -1,5 +1,5 @@
 """GPU tier: the residual add folded into a convolution (qnnp_gfx950_attach_residual_add, residual.c; epilogues in
-hip/q8pwconv.hip). The reference runs a convolution operator and then an add operator (src/add.c + q8vadd); here
+hip/q8pwconv.hip and its kernel units). The reference runs a convolution operator and then an add operator (src/add.c + q8vadd); here
 the same bytes must come out of ONE operator, whether the add rides in the convolution kernel's epilogue or is
 launched in place behind it:
 

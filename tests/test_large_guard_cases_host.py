@@ -84,7 +84,7 @@ def test_stream_c3_cases_sit_on_both_sides_of_the_staged_flavour():
 def test_gwk_rows_sit_on_both_sides_of_the_span():
     last, refused = G.GWK_CASE, dataclasses.replace(G.GWK_CASE, batch=G.GWK_CASE.batch + 1)
     assert G.crossed(G.gw_guard(last)) == set() and G.crossed(G.gw_guard(refused)) == {"input"}
-    # the split-K flavour: K >= 256 and at most two blocks per CU (q8pwconv.hip:pwstream_gw_launch), on any device of 4 CUs or more
+    # the split-K flavour: K >= 256 and at most two blocks per CU (q8pwconv.hip:pwstream_gw_plan), on any device of 4 CUs or more
     assert last.input_channels >= 256 and G.gw_guard(refused)["units"][0] <= 8
     assert G.spans(refused)[0] + refused.batch * 64 <= lg.BUDGET
 
@@ -94,7 +94,7 @@ def test_cases_past_4g_are_past_4g_and_fit():
         assert max(G.spans(case)) > G.B32, case.name
         assert all(v <= most for v, most in G.setup_limits(case).values()), case.name
         assert G.nbytes(case) <= lg.BUDGET, case.name
-        if isinstance(case, FcCase):           # plan_longk's K conditions: 256 < K <= 1024 in whole 16-byte pieces
+        if isinstance(case, FcCase):           # pwstream_longk_plan's K conditions: 256 < K <= 1024 in whole 16-byte pieces
             assert 256 < case.input_channels <= 1024 and case.input_channels % 16 == 0 and case.output_channels % 16 == 0
     assert G.spans(G.LONGK_CASES[0])[0] > G.B32 and G.spans(G.LONGK_CASES[1])[1] > G.B32
     # residual: input + residual + output; per-channel: 64 -> 40 rows and 58-channel images; multiply: three tensors

@@ -18,7 +18,7 @@ Pairs:
   q8convc3.hip c3lds_plan                grid (added with this file, after the depthwise finding below: one workgroup per image
                                          and band; 2^24 one-pixel outputs of 1 x 16 x 3 images, which the plan took, answered
                                          unsupported_hardware from the launch under the automatic choice)
-  q8pwconv.hip pwstream_gw_supported     input span, by rows (q8_pw_stream_gw_mfma) and by stride (q8_pw_stream_gwk_mfma,
+  q8pwconv.hip pwstream_gw_plan          input span, by rows (q8_pw_stream_gw_mfma) and by stride (q8_pw_stream_gwk_mfma,
                                          test_gwk_rows_by_stride: sparse rows)
   q8dwmfma16.hip dwmfma16_plan           output, input, (waves+8)*dmax -- reachable inside the other two: 1 x 1 images of 1040
                                          channels are 65 channel groups of one block, (65 batch + 8) * 65 passes 2^32 at
@@ -30,7 +30,7 @@ Pairs:
                                          those images), and dwmfma16_grid holds both sides of that
   q8deconv.hip qnnp_hip_deconv_s2_run    output, input
 Both sides of a condition that is no refusal:
-  q8pwconv.hip convstream_c3_launch      input 2^31: the staged flavour below, the unstaged from there, one kernel name
+  q8convc3s.hip convstream_c3_plan       input 2^31: the staged flavour below, the unstaged from there, one kernel name
 Terms that no tensor reaches:
   q8convc3.hip c3lds_plan wgs*bands      = batch * bands^2 <= batch * pairs^2 <= units*pairs, which conv_c3rows*_supported
                                          holds below 2^32 first (bands <= pairs; asserted per case in the host tier)
@@ -38,10 +38,10 @@ Terms that no tensor reaches:
   q8deconv.hip bases + 32 < 2^31         at least 32 input channels keep the input term's tensor below 2^27 pixels, and
                                          BH <= H + 2, BW <= W + 2 (kernel <= 4, adjustment <= 1): bases <= 9 * 2^27
 Left out:
-  q8pwconv.hip convstream_c3 table       rows_per_image * taps * 4 reaches 2^31 only with 2^25 output pixels in ONE image
+  q8convc3s.hip convstream_c3 table      rows_per_image * taps * 4 reaches 2^31 only with 2^25 output pixels in ONE image
                                          under a 16-tap window: a 2 GiB offset table and an oracle run over 100 MB images
 No size term at all:
-  q8pwconv.hip plan_longk, plan_staged   hold no size term (LDS bytes, channel and K conditions): q8_pw_stream_longk_mfma is
+  q8pwconv.hip long-K, staged plans    hold no size term (LDS bytes, channel and K conditions): q8_pw_stream_longk_mfma is
                                          run with the input past 2^32 and with the output past 2^32 instead
 Past 2^32 without a guard (64-bit addressing): q8_conv_stream_c3_mfma's output, q8_pw_stream_d2s_mfma's output, the residual
 add folded into a pointwise layer, the fused block at the last batch fused-block.c accepts, the per-channel kernels

@@ -1,5 +1,5 @@
 """GPU tier: a byte table attached to a convolution (qnnp_gfx950_attach_output_table, output-table.c; the table flavours
-of hip/q8pwconv.hip, hip/q8dwcol.hip and hip/q8dwcol5.hip, the in-place launch of hip/x8lut.hip everywhere else).
+of hip/q8pwconv.hip's kernel units, hip/q8dwcol.hip and hip/q8dwcol5.hip, the in-place launch of hip/x8lut.hip everywhere else).
 
 Every case is compared twice -- with the ORACLE's convolution bytes mapped through the table in numpy, and with the
 library's own chain (convolution, then the stand-alone table operator in place on its output) -- on guarded outputs whose

@@ -1,5 +1,5 @@
 """CPU tier of the output table behind a convolution (qnnp_gfx950_attach_output_table / qnnp_gfx950_operator_table_folded:
-output-table.c, the table flavours of hip/q8pwconv.hip, hip/q8dwcol.hip and hip/q8dwcol5.hip):
+output-table.c, the table flavours of hip/q8pwconv.hip's kernel units, hip/q8dwcol.hip and hip/q8dwcol5.hip):
 
  * interface: the prototypes in include/qnnpack_gfx950_output_table.h are the specified ones, qnnpack_gfx950.h includes
    that header, binding.OUTPUT_TABLE_API is its image while API stays the 65 functions of the three older headers, the
