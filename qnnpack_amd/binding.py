@@ -62,12 +62,12 @@ _CTYPES = {
     "size_t": c_size_t, "u32": c_uint32, "u8": c_uint8, "f32": c_float, "int": c_int, "str": c_char_p,
     "ptr": c_void_p,        # passed as it is: an operator handle (named `op` where it is the function's own), stream, graph
     "tensor": c_void_p,     # through address_of
-    "u8[]": c_void_p, "i32[]": c_void_p, "f32[]": c_void_p, "u8[256]": c_void_p,   # host array of that dtype (and size), None -> NULL
+    "u8[]": c_void_p, "i8[]": c_void_p, "i32[]": c_void_p, "f32[]": c_void_p, "u8[256]": c_void_p,   # host array of that dtype (and size), None -> NULL
     "out": POINTER(c_void_p),   # a create's trailing handle: not a Python parameter, returned
     "null": c_void_p,           # the setups' threadpool: not a Python parameter, always NULL
     "ptr*": POINTER(c_void_p), "f32*": POINTER(c_float), "int*": POINTER(c_int), "size_t*": POINTER(c_size_t),
 }
-_HOST_ARRAYS = {"u8[]": (np.uint8, None), "i32[]": (np.int32, None), "f32[]": (np.float32, None), "u8[256]": (np.uint8, 256)}
+_HOST_ARRAYS = {"u8[]": (np.uint8, None), "i8[]": (np.int8, None), "i32[]": (np.int32, None), "f32[]": (np.float32, None), "u8[256]": (np.uint8, 256)}
 
 # When a symbol is bound at load. QNNP_GFX950_LIBRARY may name an OLDER build for a same-box A/B: entry points younger
 # than it are then simply not bound; the product library must have them all (tests/test_abi.py).
@@ -279,6 +279,20 @@ OUTPUT_TABLE_API = (
 )
 
 
+# include/qnnpack_gfx950_dynamic.h: the dynamically quantized fully connected operator, float32 in and out. A table of its
+# own like FLOAT_API, for the same reason. `kernel`: output_channels x input_channels int8; `kernel_scales`, `bias` (or
+# None): output_channels floats; both strides count elements.
+DYNAMIC_API = (
+    _op("qnnp_gfx950_create_fully_connected_nc_f32_qd8",
+        "size_t input_channels, size_t output_channels, i8[] kernel, f32[] kernel_scales, f32[] bias, "
+        "f32 output_min, f32 output_max, u32 flags=0, out fully_connected", IF_PRESENT,
+        doc="the product's dynamically quantized fully connected operator: float32 rows in and out, int8 weights with one "
+            "scale per output channel; set it up with setup_fully_connected_nc_f32_qd8"),
+    _op("qnnp_gfx950_setup_fully_connected_nc_f32_qd8", _SETUP_NC, IF_PRESENT),
+    _fn("qnnp_gfx950_dynamic_rows_kernel", "ptr op", IF_PRESENT, restype=c_char_p),
+)
+
+
 def _bind(lib, table) -> None:
     """Set argtypes / restype of the table's symbols on a loaded library."""
     older = bool(os.environ.get("QNNP_GFX950_LIBRARY"))
@@ -366,18 +380,20 @@ class QnnpackLibrary:
         return Status(self.lib.qnnp_deinitialize())
 
 
-@_with_methods_of(GFX950_API + FLOAT_API + PERCHANNEL_API + SQUEEZE_EXCITE_API + OUTPUT_TABLE_API)
+@_with_methods_of(GFX950_API + FLOAT_API + PERCHANNEL_API + SQUEEZE_EXCITE_API + OUTPUT_TABLE_API + DYNAMIC_API)
 class Gfx950Library(QnnpackLibrary):
     """Product library: qnnpack.h plus the extensions of include/qnnpack_gfx950.h (GFX950_API), the float32 <-> uint8
     operators of include/qnnpack_gfx950_float.h (FLOAT_API) and the per-channel creates of
     include/qnnpack_gfx950_perchannel.h (PERCHANNEL_API), and the fused squeeze-and-excite block of
     include/qnnpack_gfx950_squeeze_excite.h (SQUEEZE_EXCITE_API), and the output table of
-    include/qnnpack_gfx950_output_table.h (OUTPUT_TABLE_API).
+    include/qnnpack_gfx950_output_table.h (OUTPUT_TABLE_API), and the dynamically quantized fully connected operator of
+    include/qnnpack_gfx950_dynamic.h (DYNAMIC_API).
 
     Generated as above: the fused inverted-residual block ([create|setup]_fused_block[_status]), the residual add
     folded into a convolution (attach_residual_add[_status]), quantize / dequantize with their two setups each, and
     create_convolution2d_nhwc_q8_per_channel / create_fully_connected_nc_q8_per_channel, and
-    [create|setup]_squeeze_excite[_status], and attach_output_table[_status].
+    [create|setup]_squeeze_excite[_status], and attach_output_table[_status], and
+    [create|setup]_fully_connected_nc_f32_qd8[_status].
     """
 
     def __init__(self, path: str):
@@ -387,6 +403,7 @@ class Gfx950Library(QnnpackLibrary):
         _bind(self.lib, PERCHANNEL_API)
         _bind(self.lib, SQUEEZE_EXCITE_API)
         _bind(self.lib, OUTPUT_TABLE_API)
+        _bind(self.lib, DYNAMIC_API)
 
     def _check(self, call: str, st: int) -> None:
         if st != 0:
@@ -491,6 +508,11 @@ class Gfx950Library(QnnpackLibrary):
     def operator_ran_dense(self, op) -> bool:
         """include/qnnpack_gfx950_test.h: the operator's last run took the dense image of a grouped 1x1 convolution"""
         return bool(self.lib.qnnp_gfx950_test_operator_ran_dense(op))
+
+    def dynamic_rows_kernel(self, op) -> Optional[str]:
+        """the row kernel a dynamically quantized fully connected operator's last run launched first"""
+        name = self.lib.qnnp_gfx950_dynamic_rows_kernel(op)
+        return name.decode() if name else None
 
     def operator_kernel(self, op) -> Optional[str]:
         name = self.lib.qnnp_gfx950_operator_kernel(op)

@@ -1,0 +1,288 @@
+/*
+ * dynamic-fully-connected.c -- qnnp_gfx950_create_fully_connected_nc_f32_qd8 / qnnp_gfx950_setup_fully_connected_nc_f32_qd8
+ * (include/qnnpack_gfx950_dynamic.h has the arithmetic and the statuses): float32 rows in, float32 rows out, each input row
+ * quantized to its own range on the device and multiplied with int8 weights on the matrix cores.
+ *
+ * No reference counterpart. Create packs the weights into the fragment image of hip/qd8f32gemm.hip and uploads one table
+ * entry per output channel (as per-channel.h does for the per-channel operators); setup follows quantize.c -- validation
+ * in the documented order, every check before the operator changes -- and grows the one device scratch the operator owns
+ * (as squeeze-excite.c owns its gate rows; freed by qnnp_delete_operator). The run is two launches, reached through
+ * op->launch: the rows kernel of hip/f32qd8rows.hip into the scratch, then the GEMM or GEMV kernel out of it. The scratch
+ * needs no clearing when it grows: the rows kernel writes every byte the second launch reads, the K pad included.
+ *
+ * Not part of the seam library (oracle/Makefile).
+ */
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <stdlib.h>
+
+#include <qnnpack.h>
+#include <qnnpack_gfx950_dynamic.h>
+
+#include "hip/qnnp_hip.h"
+#include "lifecycle.h"
+#include "log.h"
+#include "operator.h"
+#include "upload.h"
+
+#define QNNP_QD8_MAX_INPUT_CHANNELS ((size_t) 32768)          /* K * 255 * 128 stays below 2^31 */
+#define QNNP_QD8_MAX_OUTPUT_CHANNELS ((size_t) 1 << 24)       /* exclusive */
+
+static int launch_dynamic_fully_connected(struct qnnp_operator* op, const void* input, const void* input2, void* output)
+{
+  (void) input2;
+  int8_t* quantized = (int8_t*) op->d_qd8_scratch;
+  struct qnnp_hip_qd8_row_entry* row_table =
+      (struct qnnp_hip_qd8_row_entry*) ((uint8_t*) op->d_qd8_scratch + op->qd8_row_table_offset);
+  const struct qnnp_hip_qd8_rows_args rows_args = {
+    .input = (const float*) input,
+    .quantized = quantized,
+    .row_table = row_table,
+    .rows = (uint32_t) op->batch_size,
+    .k = (uint32_t) op->group_input_channels,
+    .k_pad = op->k_pad,
+    .input_stride = op->input_pixel_stride,
+  };
+  const int rc = qnnp_hip_qd8_rows_run(&rows_args, &op->qd8_rows_kernel);
+  if (rc != QNNP_HIP_OK) {
+    return rc;
+  }
+  const struct qnnp_hip_qd8_gemm_args gemm_args = {
+    .quantized = quantized,
+    .row_table = row_table,
+    .packed_w = (const int8_t*) op->d_weights,
+    .channel_table = (const struct qnnp_hip_qd8_channel_entry*) op->d_qd8_channels,
+    .output = (float*) output,
+    .rows = (uint32_t) op->batch_size,
+    .n = (uint32_t) op->channels,
+    .n_pad = op->n_pad,
+    .k_pad = op->k_pad,
+    .output_stride = op->output_pixel_stride,
+    .output_min = op->f32_output_min,
+    .output_max = op->f32_output_max,
+  };
+  return qnnp_hip_qd8_gemm_run(&gemm_args, &op->kernel_name);
+}
+
+/* The fragment image (hip/qnnp_hip.h): for channel block nb and K tile kt, lane l of fragment nb * ktiles + kt holds the
+ * sixteen weights of channel nb * 16 + l % 16 at K positions kt * 64 + (l / 16) * 16 .. + 15; padding is zero. */
+static void pack_weights(size_t k, size_t n, uint32_t k_pad, uint32_t n_pad, const int8_t* kernel, int8_t* packed)
+{
+  const size_t ktiles = k_pad / 64;
+  for (size_t nb = 0; nb < n_pad / 16; nb++) {
+    for (size_t kt = 0; kt < ktiles; kt++) {
+      int8_t* fragment = packed + (nb * ktiles + kt) * 1024;
+      for (size_t l = 0; l < 64; l++) {
+        const size_t c = nb * 16 + l % 16;
+        const size_t k0 = kt * 64 + (l / 16) * 16;
+        for (size_t j = 0; j < 16; j++) {
+          fragment[l * 16 + j] = c < n && k0 + j < k ? kernel[c * k + k0 + j] : 0;
+        }
+      }
+    }
+  }
+}
+
+static enum qnnp_status create_dynamic_fully_connected(
+    size_t input_channels, size_t output_channels, const int8_t* kernel, const float* kernel_scales, const float* bias,
+    float output_min, float output_max, qnnp_operator_t* fully_connected)
+{
+  qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_dynamic_fully_connected, launch_dynamic_fully_connected);
+  if (op == NULL) {
+    return qnnp_status_out_of_memory;
+  }
+  const uint32_t k_pad = ((uint32_t) input_channels + 63u) & ~63u;
+  const uint32_t n_pad = ((uint32_t) output_channels + 15u) & ~15u;
+  const size_t w_bytes = (size_t) n_pad * k_pad;
+  const size_t t_bytes = (size_t) n_pad * sizeof(struct qnnp_hip_qd8_channel_entry);
+  int8_t* packed = (int8_t*) malloc(w_bytes);
+  struct qnnp_hip_qd8_channel_entry* table = (struct qnnp_hip_qd8_channel_entry*) malloc(t_bytes);
+  if (packed != NULL && table != NULL) {
+    pack_weights(input_channels, output_channels, k_pad, n_pad, kernel, packed);
+    for (size_t c = 0; c < n_pad; c++) {
+      /* the padding channels: valid entries whose results are never stored */
+      table[c] = (struct qnnp_hip_qd8_channel_entry) { .kernel_scale = 1.0f, .bias = 0.0f, .wsum = 0 };
+      if (c < output_channels) {
+        int32_t wsum = 0;
+        for (size_t k = 0; k < input_channels; k++) {
+          wsum += kernel[c * input_channels + k];        /* at most 128 * 32768 in magnitude */
+        }
+        table[c].kernel_scale = kernel_scales[c];
+        table[c].bias = bias != NULL ? bias[c] : 0.0f;
+        table[c].wsum = wsum;
+      }
+    }
+    op->d_weights = qnnp_upload(packed, w_bytes);
+    op->d_qd8_channels = qnnp_upload(table, t_bytes);
+  } else {
+    qnnp_log_error("out of host memory: %zu bytes for packed weights", w_bytes + t_bytes);
+  }
+  free(packed);
+  free(table);
+  if (op->d_weights == NULL || op->d_qd8_channels == NULL) {
+    qnnp_log_error("cannot create dynamic fully connected operator: %zu bytes of packed weights could not be placed on the "
+        "device", w_bytes + t_bytes);
+    qnnp_delete_operator(op);
+    return qnnp_status_out_of_memory;
+  }
+  op->group_input_channels = input_channels;
+  op->channels = output_channels;          /* of the output: what operator-run.c compares the output stride with */
+  op->k_pad = k_pad;
+  op->n_pad = n_pad;
+  op->f32_output_min = output_min;
+  op->f32_output_max = output_max;
+  *fully_connected = op;
+  return qnnp_status_success;
+}
+
+enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8(
+    size_t input_channels,
+    size_t output_channels,
+    const int8_t* kernel,
+    const float* kernel_scales,
+    const float* bias,
+    float output_min,
+    float output_max,
+    uint32_t flags,
+    qnnp_operator_t* fully_connected)
+{
+  (void) flags;
+  enum qnnp_status status = qnnp_check_initialized("qnnp_gfx950_create_fully_connected_nc_f32_qd8");
+  if (status != qnnp_status_success) {
+    return status;
+  }
+  if (input_channels == 0 || output_channels == 0 || kernel == NULL || kernel_scales == NULL) {
+    qnnp_log_error("cannot create dynamic fully connected operator with %zu input and %zu output channels: channel counts, "
+        "kernel and kernel scales may not be zero", input_channels, output_channels);
+    return qnnp_status_invalid_parameter;
+  }
+  for (size_t c = 0; c < output_channels; c++) {
+    if (!(kernel_scales[c] > 0.0f && isnormal(kernel_scales[c]))) {
+      qnnp_log_error("cannot create dynamic fully connected operator with %.7g kernel scale of channel %zu: a scale has to "
+          "be a finite number above zero", kernel_scales[c], c);
+      return qnnp_status_invalid_parameter;
+    }
+  }
+  for (size_t c = 0; bias != NULL && c < output_channels; c++) {
+    if (bias[c] != 0.0f && !isnormal(bias[c])) {
+      qnnp_log_error("cannot create dynamic fully connected operator with %.7g bias of channel %zu: a bias has to be zero "
+          "or a normal number", bias[c], c);
+      return qnnp_status_invalid_parameter;
+    }
+  }
+  if (isnan(output_min) || isnan(output_max) || output_min > output_max) {
+    qnnp_log_error("cannot create dynamic fully connected operator with [%.7g, %.7g] output range: the bounds may not be "
+        "NaN and min may not exceed max", output_min, output_max);
+    return qnnp_status_invalid_parameter;
+  }
+  for (size_t c = 0; c < output_channels; c++) {
+    if (!(kernel_scales[c] >= 0x1.0p-20f && kernel_scales[c] <= 0x1.0p+20f)) {
+      qnnp_log_error("cannot create dynamic fully connected operator with %.7g kernel scale of channel %zu: scale must be "
+          "in [2**-20, 2**20] range", kernel_scales[c], c);
+      return qnnp_status_unsupported_parameter;
+    }
+  }
+  if (input_channels > QNNP_QD8_MAX_INPUT_CHANNELS || output_channels >= QNNP_QD8_MAX_OUTPUT_CHANNELS) {
+    qnnp_log_error("cannot create dynamic fully connected operator with %zu input and %zu output channels: at most %zu "
+        "input channels (the int32 accumulator) and fewer than %zu output channels", input_channels, output_channels,
+        QNNP_QD8_MAX_INPUT_CHANNELS, QNNP_QD8_MAX_OUTPUT_CHANNELS);
+    return qnnp_status_unsupported_parameter;
+  }
+
+  int token;
+  status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
+  if (status != qnnp_status_success) {
+    return status;
+  }
+  return qnnp_leave_create(token, create_dynamic_fully_connected(
+      input_channels, output_channels, kernel, kernel_scales, bias, output_min, output_max, fully_connected));
+}
+
+static enum qnnp_status setup_dynamic_fully_connected(
+    qnnp_operator_t op, size_t batch_size, const float* input, size_t input_stride, float* output, size_t output_stride)
+{
+  if (op->ukernel_type != qnnp_ukernel_type_dynamic_fully_connected) {
+    return qnnp_status_invalid_parameter;
+  }
+  if (batch_size == 0) {
+    op->batch_size = 0;
+    return qnnp_status_success;
+  }
+  const size_t input_channels = op->group_input_channels, output_channels = op->channels;
+  if (input == NULL || output == NULL) {
+    qnnp_log_error("cannot set up dynamic fully connected operator: NULL tensor");
+    return qnnp_status_invalid_parameter;
+  }
+  if ((uintptr_t) input % sizeof(float) != 0 || (uintptr_t) output % sizeof(float) != 0) {
+    qnnp_log_error("cannot set up dynamic fully connected operator: a tensor is not 4-byte aligned");
+    return qnnp_status_invalid_parameter;
+  }
+  if (input_stride < input_channels || output_stride < output_channels) {
+    qnnp_log_error("cannot set up dynamic fully connected operator: row stride smaller than the channel count");
+    return qnnp_status_invalid_parameter;
+  }
+  if (batch_size > (size_t) INT32_MAX) {
+    qnnp_log_error("cannot set up dynamic fully connected operator with batch %zu: outside the device kernels' index range",
+        batch_size);
+    return qnnp_status_unsupported_parameter;
+  }
+  const size_t input_span = ((batch_size - 1) * input_stride + input_channels) * sizeof(float);
+  const size_t output_span = ((batch_size - 1) * output_stride + output_channels) * sizeof(float);
+  if (qnnp_spans_overlap(input, input_span, output, output_span)) {
+    qnnp_log_error("cannot set up dynamic fully connected operator: the input and output tensors overlap");
+    return qnnp_status_invalid_parameter;
+  }
+  if (qnnp_hip_is_device_pointer(input) < 0 || qnnp_hip_is_device_pointer(output) < 0) {
+    qnnp_log_error("cannot set up dynamic fully connected operator: a tensor lives on a different device than the operator");
+    return qnnp_status_invalid_parameter;
+  }
+  /* the quantized rows (k_pad is a multiple of 64: the table behind them is 8-byte aligned), then the row table */
+  const size_t row_table_offset = batch_size * op->k_pad;
+  const size_t scratch_bytes = row_table_offset + batch_size * sizeof(struct qnnp_hip_qd8_row_entry);
+
+  op->setup_valid = 0;   /* from here on the operator changes: until every allocation below has succeeded */
+  if (op->qd8_scratch_capacity < scratch_bytes) {
+    qnnp_hip_free(op->d_qd8_scratch);
+    op->qd8_scratch_capacity = 0;
+    op->d_qd8_scratch = qnnp_hip_alloc(scratch_bytes);
+    if (op->d_qd8_scratch == NULL) {
+      qnnp_log_error("failed to allocate %zu bytes of device scratch for the quantized rows", scratch_bytes);
+      return qnnp_status_out_of_memory;
+    }
+    op->qd8_scratch_capacity = scratch_bytes;
+  }
+  op->qd8_row_table_offset = row_table_offset;
+  op->batch_size = batch_size;
+  op->input = input;
+  op->input_pixel_stride = input_stride;
+  op->output = output;
+  op->output_pixel_stride = output_stride;
+  op->input_span = input_span;
+  op->output_span = output_span;
+  return qnnp_bind_tensors(op, "qnnp_gfx950_setup_fully_connected_nc_f32_qd8");
+}
+
+enum qnnp_status qnnp_gfx950_setup_fully_connected_nc_f32_qd8(
+    qnnp_operator_t fully_connected,
+    size_t batch_size,
+    const float* input,
+    size_t input_stride,
+    float* output,
+    size_t output_stride)
+{
+  int token;
+  const enum qnnp_status status =
+      qnnp_enter_setup("qnnp_gfx950_setup_fully_connected_nc_f32_qd8", fully_connected, &token);
+  if (status != qnnp_status_success) {
+    return status;
+  }
+  return qnnp_leave_setup(fully_connected, token,
+      setup_dynamic_fully_connected(fully_connected, batch_size, input, input_stride, output, output_stride));
+}
+
+const char* qnnp_gfx950_dynamic_rows_kernel(qnnp_operator_t fully_connected)
+{
+  return fully_connected != NULL && fully_connected->ukernel_type == qnnp_ukernel_type_dynamic_fully_connected
+      ? fully_connected->qd8_rows_kernel : NULL;
+}

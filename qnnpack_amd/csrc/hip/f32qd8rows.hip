@@ -1,0 +1,293 @@
+/*
+ * f32qd8rows.hip -- the first launch of the dynamically quantized fully connected operator (dynamic-fully-connected.c;
+ * include/qnnpack_gfx950_dynamic.h has the definition): per input row, ONE launch finds the range, derives the row's
+ * scale and zero point and writes the quantized row. No reference counterpart. Float32, every operation rounded once:
+ * no multiply is followed by an add anywhere in this file, so nothing can fuse.
+ *
+ *   lo = min(0, min_k x), hi = max(0, max_k x)                  NaN elements drop out of fminf / fmaxf
+ *   scale = (hi - lo) / 255;  outside [2^-60, 2^60] (or NaN): 1
+ *   inv = 1 / scale;  zp = (int) rintf(min(-lo * inv, 255))
+ *   t = x * inv;  NaN -> 0;  clamp to [-zp, 255 - zp];  q = (int) rintf(t) + zp
+ * The row goes out as int8 q - 128 (q ^ 0x80), k_pad bytes, the bytes from K on zero, and {scale, 128 - zp} into the row
+ * table: what qd8f32gemm.hip reads.
+ *
+ * A lane's piece is SIXTEEN consecutive elements of one row: four 16-byte float loads in, one 16-byte store out, so the
+ * int8 row is written in whole 16-byte pieces and the pad up to k_pad (a multiple of 64) by the same stores. Three
+ * kernels by K, so that a row is read from HBM once wherever it fits in registers:
+ *   f32_qd8_rows_wave     K <= 1024: one wave per row, one piece per lane, four rows per workgroup; nothing but lane
+ *                         exchanges between the loads and the stores
+ *   f32_qd8_rows_block    K <= 16384: one 256-thread workgroup per row, up to four pieces (64 floats) per lane in registers
+ *   f32_qd8_rows_twopass  beyond: the workgroup walks the row for the range, then again to quantize (the second walk
+ *                         finds a row of up to 128 KiB in L2)
+ * The range is reduced inside a wave by ds_swizzle butterflies over 32 lanes and one v_permlane32_swap across the halves,
+ * across the four waves of a workgroup through LDS. Every lane ends up with the SAME lo and hi and computes scale, inv and
+ * zp from those two floats itself: no lane can disagree, and nothing is broadcast.
+ * The _x4 flavours (input base, or with more than one row the row stride, no multiple of 16 bytes) load the sixteen
+ * elements as dwords; so does the one piece of a row that K cuts, in both flavours.
+ */
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "device_ops.hip.h"
+#include "per_device.h"
+#include "qnnp_hip.h"
+
+#pragma clang fp contract(off)
+
+namespace qnnp {
+
+namespace {
+
+constexpr uint32_t kRowsThreads = 256;
+constexpr uint32_t kPiece = 16;                                  // elements of a lane's piece
+constexpr uint32_t kWaveMaxK = 64 * kPiece;                      // 1024
+constexpr int kBlockPieces = 4;                                  // pieces a lane of the block kernel keeps in registers
+constexpr uint32_t kBlockMaxK = kRowsThreads * kPiece * kBlockPieces;   // 16384
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+struct RowsParams {
+  const float* x;
+  int8_t* q;
+  qnnp_hip_qd8_row_entry* table;
+  uint64_t x_stride;     // elements
+  uint32_t rows, k, k_pad;
+};
+
+struct Piece {
+  float v[kPiece];
+};
+
+/* the piece at elements e0 .. e0 + 15 of the row; elements from K on read as 0, which neither end of the range sees */
+template <bool VEC>
+__device__ __forceinline__ Piece load_piece(const float* row, uint32_t e0, uint32_t k)
+{
+  Piece p;
+  if (VEC && e0 + kPiece <= k) {
+    const f32x4* src = reinterpret_cast<const f32x4*>(row + e0);
+    const f32x4 a = src[0], b = src[1], c = src[2], d = src[3];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      p.v[i] = a[i];
+      p.v[4 + i] = b[i];
+      p.v[8 + i] = c[i];
+      p.v[12 + i] = d[i];
+    }
+  } else {
+#pragma unroll
+    for (uint32_t i = 0; i < kPiece; i++) p.v[i] = e0 + i < k ? row[e0 + i] : 0.0f;
+  }
+  return p;
+}
+
+__device__ __forceinline__ void piece_range(const Piece& p, float& lo, float& hi)
+{
+#pragma unroll
+  for (uint32_t i = 0; i < kPiece; i++) {
+    lo = fminf(lo, p.v[i]);
+    hi = fmaxf(hi, p.v[i]);
+  }
+}
+
+/* the xor butterfly over the 32 lanes of a half (ds_swizzle, bit mode: and 0x1F, or 0, xor X), then the other half */
+template <int X>
+__device__ __forceinline__ float swizzle_xor(float v)
+{
+  return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (X << 10) | 0x1F));
+}
+/* v of lanes 0 .. 31 in `low` and of lanes 32 .. 63 in `high`, in every lane (v is uniform within each half by now) */
+__device__ __forceinline__ void both_halves(float v, float& low, float& high)
+{
+  const uint32_t bits = static_cast<uint32_t>(__float_as_int(v));
+  const auto s = __builtin_amdgcn_permlane32_swap(bits, bits, false, false);
+  low = __int_as_float(static_cast<int>(s[0]));
+  high = __int_as_float(static_cast<int>(s[1]));
+}
+__device__ __forceinline__ void wave_range(float& lo, float& hi)
+{
+  float a, b;
+  lo = fminf(lo, swizzle_xor<1>(lo));   hi = fmaxf(hi, swizzle_xor<1>(hi));
+  lo = fminf(lo, swizzle_xor<2>(lo));   hi = fmaxf(hi, swizzle_xor<2>(hi));
+  lo = fminf(lo, swizzle_xor<4>(lo));   hi = fmaxf(hi, swizzle_xor<4>(hi));
+  lo = fminf(lo, swizzle_xor<8>(lo));   hi = fmaxf(hi, swizzle_xor<8>(hi));
+  lo = fminf(lo, swizzle_xor<16>(lo));  hi = fmaxf(hi, swizzle_xor<16>(hi));
+  both_halves(lo, a, b);
+  lo = fminf(a, b);                     // (min and max are exact: the order of the operands changes no bit but the sign of a zero,
+  both_halves(hi, a, b);                //  and here every lane uses the same order)
+  hi = fmaxf(a, b);
+}
+
+/* the workgroup's range from the four waves' (all lanes of a wave hold the same pair), in the same order in every lane */
+__device__ __forceinline__ void block_range(float& lo, float& hi, float (*lds)[2])
+{
+  const uint32_t wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63u) == 0) {
+    lds[wave][0] = lo;
+    lds[wave][1] = hi;
+  }
+  __syncthreads();
+  lo = fminf(fminf(lds[0][0], lds[1][0]), fminf(lds[2][0], lds[3][0]));
+  hi = fmaxf(fmaxf(lds[0][1], lds[1][1]), fmaxf(lds[2][1], lds[3][1]));
+}
+
+struct RowQuant {
+  float scale, inv, t_lo, t_hi;
+  int32_t zp;
+};
+
+__device__ __forceinline__ RowQuant row_quant(float lo, float hi)
+{
+  RowQuant r;
+  float scale = (hi - lo) / 255.0f;
+  if (!(scale >= 0x1.0p-60f && scale <= 0x1.0p+60f)) scale = 1.0f;
+  r.scale = scale;
+  r.inv = 1.0f / scale;
+  r.zp = static_cast<int32_t>(rintf(fminf(-lo * r.inv, 255.0f)));   // -lo >= 0: in [0, 255]
+  r.t_lo = static_cast<float>(-r.zp);
+  r.t_hi = static_cast<float>(255 - r.zp);
+  return r;
+}
+
+__device__ __forceinline__ uint32_t quantize_one(float x, const RowQuant& r)
+{
+  float t = x * r.inv;
+  t = t != t ? 0.0f : t;
+  t = fminf(fmaxf(t, r.t_lo), r.t_hi);
+  return static_cast<uint32_t>(static_cast<int32_t>(rintf(t)) + r.zp) ^ 0x80u;   // q in [0, 255] -> q - 128 as a byte
+}
+
+/* the piece as sixteen int8 at q_row + e0 (e0 < k_pad); elements from K on are the pad: zero */
+__device__ __forceinline__ void store_piece(const Piece& p, int8_t* q_row, uint32_t e0, uint32_t k, const RowQuant& r)
+{
+  u32x4 out;
+#pragma unroll
+  for (uint32_t d = 0; d < 4; d++) {
+    uint32_t word = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < 4; b++) {
+      const uint32_t e = e0 + 4 * d + b;
+      const uint32_t byte = e < k ? quantize_one(p.v[4 * d + b], r) : 0u;
+      word |= byte << (8 * b);
+    }
+    out[d] = word;
+  }
+  *reinterpret_cast<u32x4*>(q_row + e0) = out;
+}
+
+__device__ __forceinline__ void store_entry(qnnp_hip_qd8_row_entry* entry, const RowQuant& r)
+{
+  entry->scale = r.scale;
+  entry->zero_offset = 128 - r.zp;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(kRowsThreads)
+void f32_qd8_rows_wave_kernel(const RowsParams p)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t row = static_cast<uint64_t>(blockIdx.x) * (kRowsThreads / 64) + (threadIdx.x >> 6);
+  if (row >= p.rows) return;                                  // (wave-uniform; no barrier in this kernel)
+  const float* x_row = p.x + row * p.x_stride;
+  const uint32_t e0 = lane * kPiece;
+  const Piece piece = load_piece<VEC>(x_row, e0, p.k);        // lanes past K hold zeros
+  float lo = 0.0f, hi = 0.0f;
+  piece_range(piece, lo, hi);
+  wave_range(lo, hi);
+  const RowQuant r = row_quant(lo, hi);
+  if (e0 < p.k_pad) store_piece(piece, p.q + row * p.k_pad, e0, p.k, r);
+  if (lane == 0) store_entry(p.table + row, r);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(kRowsThreads)
+void f32_qd8_rows_block_kernel(const RowsParams p)
+{
+  __shared__ float range[4][2];
+  const uint64_t row = blockIdx.x;
+  const float* x_row = p.x + row * p.x_stride;
+  Piece piece[kBlockPieces];
+  float lo = 0.0f, hi = 0.0f;
+#pragma unroll
+  for (int i = 0; i < kBlockPieces; i++) {
+    const uint32_t e0 = (i * kRowsThreads + threadIdx.x) * kPiece;
+    piece[i] = load_piece<VEC>(x_row, e0, p.k);
+    piece_range(piece[i], lo, hi);
+  }
+  wave_range(lo, hi);
+  block_range(lo, hi, range);
+  const RowQuant r = row_quant(lo, hi);
+  int8_t* q_row = p.q + row * p.k_pad;
+#pragma unroll
+  for (int i = 0; i < kBlockPieces; i++) {
+    const uint32_t e0 = (i * kRowsThreads + threadIdx.x) * kPiece;
+    if (e0 < p.k_pad) store_piece(piece[i], q_row, e0, p.k, r);
+  }
+  if (threadIdx.x == 0) store_entry(p.table + row, r);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(kRowsThreads)
+void f32_qd8_rows_twopass_kernel(const RowsParams p)
+{
+  __shared__ float range[4][2];
+  const uint64_t row = blockIdx.x;
+  const float* x_row = p.x + row * p.x_stride;
+  float lo = 0.0f, hi = 0.0f;
+  for (uint32_t e0 = threadIdx.x * kPiece; e0 < p.k; e0 += kRowsThreads * kPiece) {
+    const Piece piece = load_piece<VEC>(x_row, e0, p.k);
+    piece_range(piece, lo, hi);
+  }
+  wave_range(lo, hi);
+  block_range(lo, hi, range);
+  const RowQuant r = row_quant(lo, hi);
+  int8_t* q_row = p.q + row * p.k_pad;
+  for (uint32_t e0 = threadIdx.x * kPiece; e0 < p.k_pad; e0 += kRowsThreads * kPiece) {
+    const Piece piece = load_piece<VEC>(x_row, e0, p.k);
+    store_piece(piece, q_row, e0, p.k, r);
+  }
+  if (threadIdx.x == 0) store_entry(p.table + row, r);
+}
+
+}  // namespace
+
+}  // namespace qnnp
+
+extern "C" int qnnp_hip_qd8_rows_run(const struct qnnp_hip_qd8_rows_args* a, const char** kernel_name)
+{
+  using namespace qnnp;
+  if (a == nullptr || a->input == nullptr || a->quantized == nullptr || a->row_table == nullptr ||
+      (reinterpret_cast<uintptr_t>(a->input) & 3u) != 0 || (reinterpret_cast<uintptr_t>(a->quantized) & 15u) != 0 ||
+      a->k == 0 || a->k > 32768u || a->k_pad != ((a->k + 63u) & ~63u) || a->rows > 0x7FFFFFFFu || a->input_stride < a->k) {
+    return QNNP_HIP_EINVAL;
+  }
+  if (a->rows == 0) return QNNP_HIP_OK;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(qnnp_hip_get_stream());
+  RowsParams p;
+  p.x = a->input;
+  p.q = a->quantized;
+  p.table = a->row_table;
+  p.x_stride = a->input_stride;
+  p.rows = a->rows;
+  p.k = a->k;
+  p.k_pad = a->k_pad;
+  const bool vec = (reinterpret_cast<uintptr_t>(a->input) & 15u) == 0 && (a->rows == 1 || a->input_stride % 4 == 0);
+  const char* name;
+  if (a->k <= kWaveMaxK) {
+    const dim3 grid((a->rows + 3u) / 4u);
+    if (vec) hipLaunchKernelGGL((f32_qd8_rows_wave_kernel<true>), grid, dim3(kRowsThreads), 0, stream, p);
+    else hipLaunchKernelGGL((f32_qd8_rows_wave_kernel<false>), grid, dim3(kRowsThreads), 0, stream, p);
+    name = vec ? "f32_qd8_rows_wave" : "f32_qd8_rows_wave_x4";
+  } else if (a->k <= kBlockMaxK) {
+    if (vec) hipLaunchKernelGGL((f32_qd8_rows_block_kernel<true>), dim3(a->rows), dim3(kRowsThreads), 0, stream, p);
+    else hipLaunchKernelGGL((f32_qd8_rows_block_kernel<false>), dim3(a->rows), dim3(kRowsThreads), 0, stream, p);
+    name = vec ? "f32_qd8_rows_block" : "f32_qd8_rows_block_x4";
+  } else {
+    if (vec) hipLaunchKernelGGL((f32_qd8_rows_twopass_kernel<true>), dim3(a->rows), dim3(kRowsThreads), 0, stream, p);
+    else hipLaunchKernelGGL((f32_qd8_rows_twopass_kernel<false>), dim3(a->rows), dim3(kRowsThreads), 0, stream, p);
+    name = vec ? "f32_qd8_rows_twopass" : "f32_qd8_rows_twopass_x4";
+  }
+  if (kernel_name != nullptr) *kernel_name = name;
+  return launch_status();
+}

@@ -559,6 +559,56 @@ struct qnnp_hip_dequantize_args {
 };
 int qnnp_hip_dequantize_run(const struct qnnp_hip_dequantize_args* args, const char** kernel_name);
 
+/* dynamically quantized fully connected, float32 in and out (f32qd8rows.hip, qd8f32gemm.hip, linked into
+ * libqnnpack_gfx950.so only -- see the Makefile; include/qnnpack_gfx950_dynamic.h has the arithmetic). No reference
+ * counterpart. Two launches share one device scratch of the operator:
+ *   rows   per input row r: the range, (scale_r, zp_r), and the quantized row as int8 q - 128 at quantized + r * k_pad,
+ *          bytes K .. k_pad - 1 written as zero; row_table[r] = {scale_r, 128 - zp_r}
+ *   gemm   acc = sum_k (q - 128) * w (MFMA) + (128 - zp_r) * wsum[c], then the float epilogue of the header
+ * `packed_w` holds, for the 16-channel block nb and the 64-byte K tile kt, the 1-KiB fragment (nb * (k_pad / 64) + kt):
+ * sixteen bytes per lane, lane l = channel nb * 16 + l % 16, K positions kt * 64 + (l / 16) * 16 .. + 15; zero where the
+ * channel or the K position is padding. `channel_table` has n_pad entries, the padding ones {1, 0, 0}.
+ * k_pad is K rounded up to 64, n_pad is N rounded up to 16; K <= 32768, N < 2^24, rows < 2^31; `input` and `output` are
+ * 4-byte aligned and their strides count ELEMENTS; `quantized` is 16-byte aligned. */
+struct qnnp_hip_qd8_row_entry {
+  float scale;                /* scale_r */
+  int32_t zero_offset;        /* 128 - zp_r */
+};
+struct qnnp_hip_qd8_channel_entry {
+  float kernel_scale;
+  float bias;
+  int32_t wsum;               /* sum_k kernel[c][k] */
+};
+struct qnnp_hip_qd8_rows_args {
+  const float* input;
+  int8_t* quantized;          /* [rows][k_pad] */
+  struct qnnp_hip_qd8_row_entry* row_table;   /* [rows] */
+  uint32_t rows;
+  uint32_t k;
+  uint32_t k_pad;
+  uint64_t input_stride;      /* float elements between rows */
+};
+/* f32_qd8_rows_wave (K <= 1024: one wave per row), _block (K <= 16384: one workgroup per row, the row in registers),
+ * _twopass (beyond: the row is read twice); with _x4 behind the name where the input base or, with more than one row,
+ * its stride is no multiple of 16 bytes (4-byte loads) */
+int qnnp_hip_qd8_rows_run(const struct qnnp_hip_qd8_rows_args* args, const char** kernel_name);
+
+struct qnnp_hip_qd8_gemm_args {
+  const int8_t* quantized;    /* [rows][k_pad], what the rows launch wrote */
+  const struct qnnp_hip_qd8_row_entry* row_table;
+  const int8_t* packed_w;
+  const struct qnnp_hip_qd8_channel_entry* channel_table;   /* [n_pad] */
+  float* output;
+  uint32_t rows;
+  uint32_t n;
+  uint32_t n_pad;
+  uint32_t k_pad;
+  uint64_t output_stride;     /* float elements between rows */
+  float output_min, output_max;
+};
+/* qd8_f32_gemv_mfma_16 for rows <= 16, else qd8_f32_gemm_mfma_128x128 */
+int qnnp_hip_qd8_gemm_run(const struct qnnp_hip_qd8_gemm_args* args, const char** kernel_name);
+
 /* softargmax (q8softargmax.hip, linked into libqnnpack_gfx950.so only -- see the Makefile): replaces u8rmax_ukernel__sse2,
  * u8lut32norm_ukernel__scalar and the softargmax case of src/operator-run.c:625-637, 1091-1108. For each of `rows` rows
  * of `channels` bytes, each `*_stride` bytes apart, all in uint32_t:

@@ -35,6 +35,7 @@ enum qnnp_ukernel_type {
   qnnp_ukernel_type_quantize,           /* quantize.c */
   qnnp_ukernel_type_dequantize,         /* dequantize.c */
   qnnp_ukernel_type_squeeze_excite,     /* squeeze-excite.c */
+  qnnp_ukernel_type_dynamic_fully_connected,   /* dynamic-fully-connected.c */
 };
 
 /* One output phase of a strided deconvolution (deconvolution.c): the output pixels whose (oy + pad_top) % stride_h
@@ -166,6 +167,16 @@ struct qnnp_operator {
   int f32_planar;
   size_t f32_pixels;
   float f32_inv_scale;
+  /* dynamically quantized fully connected (dynamic-fully-connected.c): group_input_channels -> channels floats per row,
+   * both strides in elements; d_weights is the int8 fragment image (n_pad x k_pad bytes), d_qd8_channels the n_pad channel
+   * entries, both owned. The device scratch is ONE grow-only allocation, owned: batch_size * k_pad bytes of quantized rows,
+   * then batch_size row entries at qd8_row_table_offset. qd8_rows_kernel names the first of the two launches. */
+  void* d_qd8_channels;
+  void* d_qd8_scratch;
+  size_t qd8_scratch_capacity;                  /* in bytes */
+  size_t qd8_row_table_offset;
+  float f32_output_min, f32_output_max;
+  const char* qd8_rows_kernel;
 
   uint8_t input_zero_point;
   uint8_t kernel_zero_point;

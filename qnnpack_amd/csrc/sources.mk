@@ -4,3 +4,8 @@
 # unit missing there breaks the build).
 C_SRCS   := init.c convolution.c deconvolution.c fully-connected.c add.c global-average-pooling.c fused-block.c residual.c output-table.c operator-run.c operator-delete.c indirection.c
 HIP_SRCS := hip/runtime.hip hip/q8igemm.hip hip/q8gemm256.hip hip/q8gemm256c.hip hip/q8gemm256x.hip hip/q8gemm128x.hip hip/q8gemm128u.hip hip/q8pwconv.hip hip/q8pwstream.hip hip/q8pwstaged.hip hip/q8pwlongk.hip hip/q8pwgw.hip hip/q8convlds.hip hip/q8convwave.hip hip/q8convws16s.hip hip/q8convpatch.hip hip/q8convc3.hip hip/q8convc3s.hip hip/q8deconv.hip hip/q8dwconv.hip hip/q8dwlds.hip hip/q8dwrow.hip hip/q8dwcol.hip hip/q8dwcol5.hip hip/q8dwmfma.hip hip/q8dwmfma16.hip hip/q8pointwise.hip hip/q8fused.hip hip/q8fusedstrip.hip
+# The dynamically quantized fully connected operator (include/qnnpack_gfx950_dynamic.h): linked into libqnnpack_gfx950.so only
+# (qnnpack_amd/csrc/Makefile), like the other operators without a reference counterpart -- not part of C_SRCS / HIP_SRCS, which
+# are also the product half of the seam library.
+DYNAMIC_C_SRCS   := dynamic-fully-connected.c
+DYNAMIC_HIP_SRCS := hip/f32qd8rows.hip hip/qd8f32gemm.hip

@@ -1,0 +1,100 @@
+"""Measurement aid: the dynamically quantized fully connected operator (qnnp_gfx950_create_fully_connected_nc_f32_qd8:
+two launches) on the MI355X against the closest thing the library offered before it: quantize at a fixed, pre-computed
+scale -> per-channel fully connected -> dequantize, three operators and a uint8 tensor on either side of the GEMM.
+
+Every operator is timed with qnnp_gfx950_time_operator_rotating over --sets pairs of input and output tensors (the
+launches of one sample recorded into a hipGraph, median of five samples), the four operators in turn, --rounds times
+over; the median round is reported with the spread between rounds, (max - min) / median. The chain's figure is the sum
+of its three operators' medians: kernel time without the gaps between launches, as for the new operator. The tensors
+rotate; the weights of one operator cannot, so at small batches they are served by the 256 MiB last-level cache and
+`weights_gb_s` (weight bytes / time) is a cache figure wherever the image fits there, not an HBM figure.
+
+    python tools/bench_dynamic_fc.py [--shapes 1x4096x4096,...] [--sets 4] [--iters 20] [--rounds 5] [--json out.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+# (batch, K, N): a dynamic linear at batch 1, 16 and 4096, and the ViT-B MLP's first layer
+SHAPES = [(1, 4096, 4096), (16, 4096, 4096), (4096, 4096, 4096), (197, 768, 3072)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default=None, help="BATCHxKxN,... instead of the built-in list")
+    ap.add_argument("--sets", type=int, default=4)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+    import qnnpack_amd
+
+    assert torch.cuda.is_available(), "bench_dynamic_fc needs the MI355X"
+    torch.cuda.set_device(0)
+    torch.zeros(1, device="cuda")
+    lib = qnnpack_amd.load()
+    lib.initialize()
+    lib.set_stream(torch.cuda.current_stream().cuda_stream)
+    lib.set_async(False)
+    rng = np.random.default_rng(23)
+    gen = torch.Generator(device="cuda").manual_seed(23)
+
+    shapes = SHAPES if args.shapes is None else [tuple(int(v) for v in item.split("x")) for item in args.shapes.split(",")]
+    rows_out = []
+    for batch, k, n in shapes:
+        kernel = rng.integers(-128, 128, size=(n, k), dtype=np.int8)
+        scales = rng.uniform(0.005, 0.02, size=n).astype(np.float32)
+        bias = rng.standard_normal(n).astype(np.float32)
+        in_scale, out_scale = 0.05, 4.0
+        ops = {"dynamic": lib.create_fully_connected_nc_f32_qd8(k, n, kernel, scales, bias, float("-inf"), float("inf")),
+               "quantize": lib.create_quantize_nc_f32_q8(k, 128, in_scale, 0, 255),
+               "fc": lib.create_fully_connected_nc_q8_per_channel(k, n, 128, in_scale, 128, scales, (kernel.astype(np.int16) + 128).astype(np.uint8),
+                                                                  np.zeros(n, np.int32), 128, out_scale, 0, 255),
+               "dequantize": lib.create_dequantize_nc_q8_f32(n, 128, out_scale)}
+        try:
+            x = [torch.randn(batch * k, dtype=torch.float32, device="cuda", generator=gen) for _ in range(args.sets)]
+            y = [torch.empty(batch * n, dtype=torch.float32, device="cuda") for _ in range(args.sets)]
+            xq = [torch.empty(batch * k, dtype=torch.uint8, device="cuda") for _ in range(args.sets)]
+            yq = [torch.empty(batch * n, dtype=torch.uint8, device="cuda") for _ in range(args.sets)]
+            lib.setup_fully_connected_nc_f32_qd8(ops["dynamic"], batch, x[0], k, y[0], n)
+            lib.setup_quantize_nc_f32_q8(ops["quantize"], batch, x[0], k, xq[0], k)
+            lib.setup_fully_connected_nc_q8(ops["fc"], batch, xq[0], k, yq[0], n)
+            lib.setup_dequantize_nc_q8_f32(ops["dequantize"], batch, yq[0], n, y[0], n)
+            tensors = {"dynamic": (x, y), "quantize": (x, xq), "fc": (xq, yq), "dequantize": (yq, y)}
+            for op in ops.values():
+                lib.run_operator(op)
+            kernels = {"rows": lib.dynamic_rows_kernel(ops["dynamic"]), "dynamic": lib.operator_kernel(ops["dynamic"]),
+                       "fc": lib.operator_kernel(ops["fc"])}
+            t = {key: [] for key in ops}
+            for _ in range(args.rounds):
+                for key, op in ops.items():
+                    t[key].append(lib.time_operator_rotating(op, *tensors[key], args.warmup, args.iters))
+            us = {key: statistics.median(v) * 1e3 for key, v in t.items()}
+            spread = {key: round((max(v) - min(v)) / statistics.median(v), 3) for key, v in t.items()}
+            chain = us["quantize"] + us["fc"] + us["dequantize"]
+            row = {"batch": batch, "k": k, "n": n, "dynamic_us": round(us["dynamic"], 2), "chain_us": round(chain, 2),
+                   "quantize_us": round(us["quantize"], 2), "fc_us": round(us["fc"], 2), "dequantize_us": round(us["dequantize"], 2),
+                   "chain_over_dynamic": round(chain / us["dynamic"], 3), "spread": spread,
+                   "weights_gb_s": round(n * k / us["dynamic"] * 1e-3, 1), "tops": round(2.0 * batch * k * n / us["dynamic"] * 1e-6, 1),
+                   "kernels": kernels, "sets": args.sets, "rounds": args.rounds, "launches_per_sample": args.iters}
+            rows_out.append(row)
+            print(json.dumps(row), flush=True)
+        finally:
+            for op in ops.values():
+                lib.delete_operator(op)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump({"device": lib.device_info(), "rows": rows_out}, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
