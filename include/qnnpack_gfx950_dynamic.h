@@ -79,6 +79,33 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8(
     uint32_t flags,
     qnnp_operator_t* fully_connected);
 
+/*
+ * The same operator with 4-BIT weights (qd8-f32-qc4w: one scale per output channel, no block-wise scales). Byte k / 2 of
+ * row c of `kernel` holds weight (c, k) in bits 4 (k % 2) .. 4 (k % 2) + 3, a two's-complement signed nibble in [-8, 7];
+ * with an odd input_channels the high nibble of a row's last byte is ignored, whatever it holds. The definition above
+ * holds with kernel[c][k] read as that nibble, and nothing else changes: |acc| <= 255 * 8 * 32768 < 2^31. The kernels
+ * feed the matrix cores 16 * kernel[c][k] (the nibble in the top half of an int8), so their loop sums
+ * 16 * sum_k (q - 128) * kernel[c][k], at most 128 * 128 * 32768 = 2^29 in magnitude, and shift it right by four: exact.
+ *
+ * Statuses and their order are those of qnnp_gfx950_create_fully_connected_nc_f32_qd8, the limits
+ * input_channels <= 32768 and output_channels < 2^24 included. The handle is set up with
+ * qnnp_gfx950_setup_fully_connected_nc_f32_qd8 and is run, captured, named and deleted like the int8 one: the row launch and
+ * the scratch are the same, only the weight image (half the bytes, K rounded up to 128) and the second launch differ
+ * (hip/qd8f32gemm4.hip; qnnp_gfx950_operator_kernel names it):
+ *     qd8_f32_qc4w_gemv_mfma_16        batch_size <= 16
+ *     qd8_f32_qc4w_gemm_mfma_128x128   batch_size > 16
+ */
+enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qc4w(
+    size_t input_channels,
+    size_t output_channels,
+    const uint8_t* kernel,         /* [output_channels][(input_channels + 1) / 2], two signed nibbles per byte, host */
+    const float* kernel_scales,    /* [output_channels], host */
+    const float* bias,             /* [output_channels] float32, host; NULL means all zero */
+    float output_min,
+    float output_max,
+    uint32_t flags,
+    qnnp_operator_t* fully_connected);
+
 enum qnnp_status qnnp_gfx950_setup_fully_connected_nc_f32_qd8(
     qnnp_operator_t fully_connected,
     size_t batch_size,

@@ -1,9 +1,10 @@
 /*
- * dynamic-fully-connected.c -- qnnp_gfx950_create_fully_connected_nc_f32_qd8 / qnnp_gfx950_setup_fully_connected_nc_f32_qd8
+ * dynamic-fully-connected.c -- qnnp_gfx950_create_fully_connected_nc_f32_qd8[_qc4w] / qnnp_gfx950_setup_fully_connected_nc_f32_qd8
  * (include/qnnpack_gfx950_dynamic.h has the arithmetic and the statuses): float32 rows in, float32 rows out, each input row
- * quantized to its own range on the device and multiplied with int8 weights on the matrix cores.
+ * quantized to its own range on the device and multiplied with int8 or 4-bit weights on the matrix cores.
  *
- * No reference counterpart. Create packs the weights into the fragment image of hip/qd8f32gemm.hip and uploads one table
+ * No reference counterpart. Create packs the weights into the fragment image of hip/qd8f32gemm.hip (4-bit weights: the
+ * pair-fragment image of hip/qd8f32gemm4.hip; the operator remembers the width, nothing else differs) and uploads one table
  * entry per output channel (as per-channel.h does for the per-channel operators); setup follows quantize.c -- validation
  * in the documented order, every check before the operator changes -- and grows the one device scratch the operator owns
  * (as squeeze-excite.c owns its gate rows; freed by qnnp_delete_operator). The run is two launches, reached through
@@ -62,7 +63,19 @@ static int launch_dynamic_fully_connected(struct qnnp_operator* op, const void* 
     .output_min = op->f32_output_min,
     .output_max = op->f32_output_max,
   };
-  return qnnp_hip_qd8_gemm_run(&gemm_args, &op->kernel_name);
+  return op->qd8_weight_bits == 4 ? qnnp_hip_qd8_qc4w_gemm_run(&gemm_args, &op->kernel_name)
+                                  : qnnp_hip_qd8_gemm_run(&gemm_args, &op->kernel_name);
+}
+
+/* weight (c, k) of either kernel layout: int8 [n][k], or nibbles [n][(k + 1) / 2] with position k in bits
+ * 4 (k % 2) .. 4 (k % 2) + 3 of byte k / 2, two's complement */
+static inline int32_t weight_at(const void* kernel, uint32_t bits, size_t k_total, size_t c, size_t k)
+{
+  if (bits == 8) {
+    return ((const int8_t*) kernel)[c * k_total + k];
+  }
+  const uint32_t nibble = (((const uint8_t*) kernel)[c * ((k_total + 1) / 2) + k / 2] >> (4 * (k % 2))) & 15u;
+  return (int32_t) (nibble ^ 8u) - 8;
 }
 
 /* The fragment image (hip/qnnp_hip.h): for channel block nb and K tile kt, lane l of fragment nb * ktiles + kt holds the
@@ -84,9 +97,31 @@ static void pack_weights(size_t k, size_t n, uint32_t k_pad, uint32_t n_pad, con
   }
 }
 
+/* The pair-fragment image (hip/qnnp_hip.h): for channel block nb and K-tile pair kp, byte j of lane l of fragment
+ * nb * kpairs + kp holds two weights of channel nb * 16 + l % 16: K position kp * 128 + (l / 16) * 16 + j in its low
+ * nibble and that position plus 64 in its high nibble; padding is zero. */
+static void pack_weights_qc4w(size_t k, size_t n, uint32_t k_pad4, uint32_t n_pad, const uint8_t* kernel, uint8_t* packed)
+{
+  const size_t kpairs = k_pad4 / 128;
+  for (size_t nb = 0; nb < n_pad / 16; nb++) {
+    for (size_t kp = 0; kp < kpairs; kp++) {
+      uint8_t* fragment = packed + (nb * kpairs + kp) * 1024;
+      for (size_t l = 0; l < 64; l++) {
+        const size_t c = nb * 16 + l % 16;
+        const size_t k0 = kp * 128 + (l / 16) * 16;
+        for (size_t j = 0; j < 16; j++) {
+          const uint32_t low = c < n && k0 + j < k ? (uint32_t) weight_at(kernel, 4, k, c, k0 + j) & 15u : 0u;
+          const uint32_t high = c < n && k0 + 64 + j < k ? (uint32_t) weight_at(kernel, 4, k, c, k0 + 64 + j) & 15u : 0u;
+          fragment[l * 16 + j] = (uint8_t) (low | (high << 4));
+        }
+      }
+    }
+  }
+}
+
 static enum qnnp_status create_dynamic_fully_connected(
-    size_t input_channels, size_t output_channels, const int8_t* kernel, const float* kernel_scales, const float* bias,
-    float output_min, float output_max, qnnp_operator_t* fully_connected)
+    size_t input_channels, size_t output_channels, const void* kernel, uint32_t weight_bits, const float* kernel_scales,
+    const float* bias, float output_min, float output_max, qnnp_operator_t* fully_connected)
 {
   qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_dynamic_fully_connected, launch_dynamic_fully_connected);
   if (op == NULL) {
@@ -94,19 +129,24 @@ static enum qnnp_status create_dynamic_fully_connected(
   }
   const uint32_t k_pad = ((uint32_t) input_channels + 63u) & ~63u;
   const uint32_t n_pad = ((uint32_t) output_channels + 15u) & ~15u;
-  const size_t w_bytes = (size_t) n_pad * k_pad;
+  const uint32_t k_pad4 = ((uint32_t) input_channels + 127u) & ~127u;       /* whole K-tile pairs */
+  const size_t w_bytes = weight_bits == 4 ? (size_t) n_pad * (k_pad4 / 2) : (size_t) n_pad * k_pad;
   const size_t t_bytes = (size_t) n_pad * sizeof(struct qnnp_hip_qd8_channel_entry);
   int8_t* packed = (int8_t*) malloc(w_bytes);
   struct qnnp_hip_qd8_channel_entry* table = (struct qnnp_hip_qd8_channel_entry*) malloc(t_bytes);
   if (packed != NULL && table != NULL) {
-    pack_weights(input_channels, output_channels, k_pad, n_pad, kernel, packed);
+    if (weight_bits == 4) {
+      pack_weights_qc4w(input_channels, output_channels, k_pad4, n_pad, (const uint8_t*) kernel, (uint8_t*) packed);
+    } else {
+      pack_weights(input_channels, output_channels, k_pad, n_pad, (const int8_t*) kernel, packed);
+    }
     for (size_t c = 0; c < n_pad; c++) {
       /* the padding channels: valid entries whose results are never stored */
       table[c] = (struct qnnp_hip_qd8_channel_entry) { .kernel_scale = 1.0f, .bias = 0.0f, .wsum = 0 };
       if (c < output_channels) {
         int32_t wsum = 0;
         for (size_t k = 0; k < input_channels; k++) {
-          wsum += kernel[c * input_channels + k];        /* at most 128 * 32768 in magnitude */
+          wsum += weight_at(kernel, weight_bits, input_channels, c, k);        /* at most 128 * 32768 in magnitude */
         }
         table[c].kernel_scale = kernel_scales[c];
         table[c].bias = bias != NULL ? bias[c] : 0.0f;
@@ -130,25 +170,19 @@ static enum qnnp_status create_dynamic_fully_connected(
   op->channels = output_channels;          /* of the output: what operator-run.c compares the output stride with */
   op->k_pad = k_pad;
   op->n_pad = n_pad;
+  op->qd8_weight_bits = weight_bits;
   op->f32_output_min = output_min;
   op->f32_output_max = output_max;
   *fully_connected = op;
   return qnnp_status_success;
 }
 
-enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8(
-    size_t input_channels,
-    size_t output_channels,
-    const int8_t* kernel,
-    const float* kernel_scales,
-    const float* bias,
-    float output_min,
-    float output_max,
-    uint32_t flags,
-    qnnp_operator_t* fully_connected)
+/* both creates: the checks in the header's order, then the packing under the device */
+static enum qnnp_status create_checked(
+    const char* function, size_t input_channels, size_t output_channels, const void* kernel, uint32_t weight_bits,
+    const float* kernel_scales, const float* bias, float output_min, float output_max, qnnp_operator_t* fully_connected)
 {
-  (void) flags;
-  enum qnnp_status status = qnnp_check_initialized("qnnp_gfx950_create_fully_connected_nc_f32_qd8");
+  enum qnnp_status status = qnnp_check_initialized(function);
   if (status != qnnp_status_success) {
     return status;
   }
@@ -196,7 +230,39 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8(
     return status;
   }
   return qnnp_leave_create(token, create_dynamic_fully_connected(
-      input_channels, output_channels, kernel, kernel_scales, bias, output_min, output_max, fully_connected));
+      input_channels, output_channels, kernel, weight_bits, kernel_scales, bias, output_min, output_max, fully_connected));
+}
+
+enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8(
+    size_t input_channels,
+    size_t output_channels,
+    const int8_t* kernel,
+    const float* kernel_scales,
+    const float* bias,
+    float output_min,
+    float output_max,
+    uint32_t flags,
+    qnnp_operator_t* fully_connected)
+{
+  (void) flags;
+  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8", input_channels, output_channels, kernel, 8,
+      kernel_scales, bias, output_min, output_max, fully_connected);
+}
+
+enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qc4w(
+    size_t input_channels,
+    size_t output_channels,
+    const uint8_t* kernel,
+    const float* kernel_scales,
+    const float* bias,
+    float output_min,
+    float output_max,
+    uint32_t flags,
+    qnnp_operator_t* fully_connected)
+{
+  (void) flags;
+  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qc4w", input_channels, output_channels, kernel, 4,
+      kernel_scales, bias, output_min, output_max, fully_connected);
 }
 
 static enum qnnp_status setup_dynamic_fully_connected(

@@ -608,6 +608,12 @@ struct qnnp_hip_qd8_gemm_args {
 };
 /* qd8_f32_gemv_mfma_16 for rows <= 16, else qd8_f32_gemm_mfma_128x128 */
 int qnnp_hip_qd8_gemm_run(const struct qnnp_hip_qd8_gemm_args* args, const char** kernel_name);
+/* The same with 4-bit weights (qd8f32gemm4.hip): `packed_w` is the image of 1-KiB PAIR fragments, fragment
+ * nb * ceil(k_pad / 128) + kp = channels 16 nb .. 16 nb + 15 x K positions 128 kp .. 128 kp + 127; byte j of lane l's
+ * sixteen holds, as two's-complement nibbles, K position 128 kp + 16 (l / 16) + j (low) and that plus 64 (high) of channel
+ * 16 nb + l % 16, zero where the channel or the K position is padding. Everything else as above.
+ * qd8_f32_qc4w_gemv_mfma_16 for rows <= 16, else qd8_f32_qc4w_gemm_mfma_128x128 */
+int qnnp_hip_qd8_qc4w_gemm_run(const struct qnnp_hip_qd8_gemm_args* args, const char** kernel_name);
 
 /* softargmax (q8softargmax.hip, linked into libqnnpack_gfx950.so only -- see the Makefile): replaces u8rmax_ukernel__sse2,
  * u8lut32norm_ukernel__scalar and the softargmax case of src/operator-run.c:625-637, 1091-1108. For each of `rows` rows

@@ -170,7 +170,10 @@ struct qnnp_operator {
   /* dynamically quantized fully connected (dynamic-fully-connected.c): group_input_channels -> channels floats per row,
    * both strides in elements; d_weights is the int8 fragment image (n_pad x k_pad bytes), d_qd8_channels the n_pad channel
    * entries, both owned. The device scratch is ONE grow-only allocation, owned: batch_size * k_pad bytes of quantized rows,
-   * then batch_size row entries at qd8_row_table_offset. qd8_rows_kernel names the first of the two launches. */
+   * then batch_size row entries at qd8_row_table_offset. qd8_rows_kernel names the first of the two launches.
+   * qd8_weight_bits is 8, or 4 for the _qc4w create: d_weights is then the pair-fragment image of hip/qd8f32gemm4.hip
+   * (n_pad x k_pad4 / 2 bytes, k_pad4 = K rounded up to 128) and the second launch is that unit's. */
+  uint32_t qd8_weight_bits;
   void* d_qd8_channels;
   void* d_qd8_scratch;
   size_t qd8_scratch_capacity;                  /* in bytes */

@@ -2,8 +2,12 @@
 two launches) on the MI355X against the closest thing the library offered before it: quantize at a fixed, pre-computed
 scale -> per-channel fully connected -> dequantize, three operators and a uint8 tensor on either side of the GEMM.
 
+`qc4w` is the same operator with 4-bit weights (qnnp_gfx950_create_fully_connected_nc_f32_qd8_qc4w: the same weights
+rounded down into [-8, 7], half the bytes), timed in turn with the int8 one; `qc4w_over_dynamic` is its time over the
+int8 operator's of the same run.
+
 Every operator is timed with qnnp_gfx950_time_operator_rotating over --sets pairs of input and output tensors (the
-launches of one sample recorded into a hipGraph, median of five samples), the four operators in turn, --rounds times
+launches of one sample recorded into a hipGraph, median of five samples), the five operators in turn, --rounds times
 over; the median round is reported with the spread between rounds, (max - min) / median. The chain's figure is the sum
 of its three operators' medians: kernel time without the gaps between launches, as for the new operator. The tensors
 rotate; the weights of one operator cannot, so at small batches they are served by the 256 MiB last-level cache and
@@ -20,8 +24,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-# (batch, K, N): a dynamic linear at batch 1, 16 and 4096, and the ViT-B MLP's first layer
-SHAPES = [(1, 4096, 4096), (16, 4096, 4096), (4096, 4096, 4096), (197, 768, 3072)]
+# (batch, K, N): a dynamic linear at batch 1, 16 and 4096, the ViT-B MLP's first layer, and a layer whose int8 weight image
+# (256 MiB) is about the size of the last-level cache
+SHAPES = [(1, 4096, 4096), (16, 4096, 4096), (4096, 4096, 4096), (197, 768, 3072), (1, 16384, 16384), (16, 16384, 16384)]
 
 
 def main():
@@ -55,7 +60,11 @@ def main():
         scales = rng.uniform(0.005, 0.02, size=n).astype(np.float32)
         bias = rng.standard_normal(n).astype(np.float32)
         in_scale, out_scale = 0.05, 4.0
+        nibbles = (kernel >> 4).view(np.uint8) & 15             # [-8, 7]; weight k of a row in bits 4 (k % 2) .. of byte k / 2
+        nibbles = np.pad(nibbles, ((0, 0), (0, k % 2)))
         ops = {"dynamic": lib.create_fully_connected_nc_f32_qd8(k, n, kernel, scales, bias, float("-inf"), float("inf")),
+               "qc4w": lib.create_fully_connected_nc_f32_qd8_qc4w(k, n, nibbles[:, 0::2] | (nibbles[:, 1::2] << 4), scales, bias,
+                                                                  float("-inf"), float("inf")),
                "quantize": lib.create_quantize_nc_f32_q8(k, 128, in_scale, 0, 255),
                "fc": lib.create_fully_connected_nc_q8_per_channel(k, n, 128, in_scale, 128, scales, (kernel.astype(np.int16) + 128).astype(np.uint8),
                                                                   np.zeros(n, np.int32), 128, out_scale, 0, 255),
@@ -66,14 +75,15 @@ def main():
             xq = [torch.empty(batch * k, dtype=torch.uint8, device="cuda") for _ in range(args.sets)]
             yq = [torch.empty(batch * n, dtype=torch.uint8, device="cuda") for _ in range(args.sets)]
             lib.setup_fully_connected_nc_f32_qd8(ops["dynamic"], batch, x[0], k, y[0], n)
+            lib.setup_fully_connected_nc_f32_qd8(ops["qc4w"], batch, x[0], k, y[0], n)
             lib.setup_quantize_nc_f32_q8(ops["quantize"], batch, x[0], k, xq[0], k)
             lib.setup_fully_connected_nc_q8(ops["fc"], batch, xq[0], k, yq[0], n)
             lib.setup_dequantize_nc_q8_f32(ops["dequantize"], batch, yq[0], n, y[0], n)
-            tensors = {"dynamic": (x, y), "quantize": (x, xq), "fc": (xq, yq), "dequantize": (yq, y)}
+            tensors = {"dynamic": (x, y), "qc4w": (x, y), "quantize": (x, xq), "fc": (xq, yq), "dequantize": (yq, y)}
             for op in ops.values():
                 lib.run_operator(op)
             kernels = {"rows": lib.dynamic_rows_kernel(ops["dynamic"]), "dynamic": lib.operator_kernel(ops["dynamic"]),
-                       "fc": lib.operator_kernel(ops["fc"])}
+                       "qc4w": lib.operator_kernel(ops["qc4w"]), "fc": lib.operator_kernel(ops["fc"])}
             t = {key: [] for key in ops}
             for _ in range(args.rounds):
                 for key, op in ops.items():
@@ -81,10 +91,13 @@ def main():
             us = {key: statistics.median(v) * 1e3 for key, v in t.items()}
             spread = {key: round((max(v) - min(v)) / statistics.median(v), 3) for key, v in t.items()}
             chain = us["quantize"] + us["fc"] + us["dequantize"]
-            row = {"batch": batch, "k": k, "n": n, "dynamic_us": round(us["dynamic"], 2), "chain_us": round(chain, 2),
+            row = {"batch": batch, "k": k, "n": n, "dynamic_us": round(us["dynamic"], 2), "qc4w_us": round(us["qc4w"], 2),
+                   "qc4w_over_dynamic": round(us["qc4w"] / us["dynamic"], 3), "chain_us": round(chain, 2),
                    "quantize_us": round(us["quantize"], 2), "fc_us": round(us["fc"], 2), "dequantize_us": round(us["dequantize"], 2),
                    "chain_over_dynamic": round(chain / us["dynamic"], 3), "spread": spread,
-                   "weights_gb_s": round(n * k / us["dynamic"] * 1e-3, 1), "tops": round(2.0 * batch * k * n / us["dynamic"] * 1e-6, 1),
+                   "weights_gb_s": round(n * k / us["dynamic"] * 1e-3, 1),
+                   "qc4w_weights_gb_s": round(n * k / 2 / us["qc4w"] * 1e-3, 1),
+                   "weights_mib": {"dynamic": round(n * k / 2 ** 20, 1), "qc4w": round(n * k / 2 ** 21, 1)}, "tops": round(2.0 * batch * k * n / us["dynamic"] * 1e-6, 1),
                    "kernels": kernels, "sets": args.sets, "rounds": args.rounds, "launches_per_sample": args.iters}
             rows_out.append(row)
             print(json.dumps(row), flush=True)
