@@ -106,6 +106,64 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qc4w(
     uint32_t flags,
     qnnp_operator_t* fully_connected);
 
+/*
+ * The 4-bit operator with BLOCK-WISE weight scales (qd8-f32-qb4w: what GPTQ, AWQ and GGUF weights carry): one scale per
+ * output channel and per block of B = block_size consecutive K positions. `kernel` is the _qc4w layout,
+ * [output_channels][input_channels / 2] bytes (K is even here: no spare nibble); `kernel_scales` is
+ * [output_channels][input_channels / block_size].
+ *
+ * Definition (bit-exact, no tolerance). Per input row, q, zp_r and scale_r are exactly those above. With nb = K / B, all
+ * float operations float32, each rounded once, no fused multiply-add; per output (r, c):
+ *   acc_b = sum_{k in [b B, (b + 1) B)} (q[r][k] - zp_r) * kernel[c][k]      exact in int32, b = 0 .. nb - 1
+ *   t_b   = (float) acc_b * kernel_scales[c][b]                 the conversion is exact: |acc_b| <= 255 * 8 * 256 < 2^19
+ *   ysum  = 0.0f;  for b = 0, 1, ..., nb - 1 IN THIS ORDER:  ysum = ysum + t_b
+ *   y     = ysum * scale_r;  y = y + bias[c];  y = min(max(y, output_min), output_max)
+ * The acc_b are exact integers and every t_b depends on its own block alone, so the kernels split K between waves, passes
+ * and matrix instructions at any block boundary, in any order. Only the chain ysum = ysum + t_b is ordered: it has ONE
+ * owner per output, which walks b upward.
+ *
+ * The block table. Per (channel, block) the device holds s16 = kernel_scales[c][b] / 16 and
+ * wsum16 = 16 * sum_{k in block} kernel[c][k]. The kernels' loop sum is L = 16 * sum (q - 128) * kernel[c][k] (the nibble
+ * in the top half of an int8), at most 128 * 128 * 256 = 2^22 per block, and L + (128 - zp_r) * wsum16 = 16 * acc_b exactly,
+ * below 2^24. They compute t_b = (float) (16 acc_b) * s16 without the shift of _qc4w: both conversions are exact, s16 is
+ * exact, and (16 acc_b) * (s / 16) is the same real number as acc_b * s with no underflow in between, so the one rounding
+ * gives the same bits.
+ *
+ * Block scales lie in [2^-16, 2^16], narrower than the [2^-20, 2^20] of the other creates, and each is a normal number
+ * above zero: that keeps the results independent of the denormal mode here too. A nonzero t_b is at least 2^-16 in
+ * magnitude and, |acc_b| < 2^19 having at most 19 significant bits, a multiple of 2^-39 (the last place of a scale of
+ * 2^-16 is 2^-39). So every partial ysum is zero or a multiple of 2^-39, never a denormal, and below 2^9 * 2^19 * 2^16 <
+ * 2^44. ysum * scale_r is zero or at least 2^-39 * 2^-60 = 2^-99 in magnitude, and a sum with a normal bias that cancels
+ * is zero or a multiple of the product's last place, at least 2^-99 * 2^-24 = 2^-123: still normal. With scales down to
+ * 2^-20 the same chain would end at 2^-127, a denormal.
+ *
+ * Create answers, in the order of the other creates: uninitialized; invalid_parameter as above and for block_size == 0 (the
+ * scale checks read input_channels / block_size scales per channel, rounded down); unsupported_parameter for a
+ * block_size other than 64, 128 and 256, an input_channels that is no multiple of block_size, a scale outside
+ * [2^-16, 2^16], input_channels > 32768, output_channels >= 2^24; out_of_memory. An argument set that is both invalid and
+ * unsupported answers invalid_parameter. Block size 32 is refused on purpose: one v_mfma_i32_16x16x64_i8 sums 64
+ * consecutive K positions, so a 32-wide block needs the 16x16x32 instruction and a different fragment image.
+ *
+ * The handle is set up with qnnp_gfx950_setup_fully_connected_nc_f32_qd8 and run, captured, named and deleted like the
+ * others: the row launch, the scratch and the weight image (the _qc4w one) are the same, the second launch is
+ * hip/qd8f32gemm4b.hip's (qnnp_gfx950_operator_kernel names it):
+ *     qd8_f32_qb4w_gemv_mfma_16        batch_size <= 16
+ *     qd8_f32_qb4w_gemm_mfma_128x128   batch_size > 16    (128 x 128 tiles fit the register file without scratch memory)
+ * The block table adds 8 bytes per channel and block to the device image: 25 %, 12.5 % and 6.25 % of the weight bytes at
+ * B = 64, 128 and 256.
+ */
+enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w(
+    size_t input_channels,
+    size_t output_channels,
+    size_t block_size,             /* 64, 128 or 256; divides input_channels */
+    const uint8_t* kernel,         /* [output_channels][input_channels / 2], two signed nibbles per byte as _qc4w, host */
+    const float* kernel_scales,    /* [output_channels][input_channels / block_size], host */
+    const float* bias,             /* [output_channels] float32, host; NULL means all zero */
+    float output_min,
+    float output_max,
+    uint32_t flags,
+    qnnp_operator_t* fully_connected);
+
 enum qnnp_status qnnp_gfx950_setup_fully_connected_nc_f32_qd8(
     qnnp_operator_t fully_connected,
     size_t batch_size,

@@ -293,6 +293,11 @@ DYNAMIC_API = (
         "f32 output_min, f32 output_max, u32 flags=0, out fully_connected", IF_PRESENT,
         doc="the same operator with 4-bit weights: `kernel` is output_channels x (input_channels + 1) / 2 bytes, weight k "
             "of a row the signed nibble in bits 4 (k % 2) .. of byte k / 2; set it up with setup_fully_connected_nc_f32_qd8"),
+    _op("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w",
+        "size_t input_channels, size_t output_channels, size_t block_size, u8[] kernel, f32[] kernel_scales, f32[] bias, "
+        "f32 output_min, f32 output_max, u32 flags=0, out fully_connected", IF_PRESENT,
+        doc="the 4-bit operator with block-wise scales: `kernel` as for _qc4w, `kernel_scales` output_channels x "
+            "input_channels / block_size floats, block_size 64, 128 or 256; set it up with setup_fully_connected_nc_f32_qd8"),
     _op("qnnp_gfx950_setup_fully_connected_nc_f32_qd8", _SETUP_NC, IF_PRESENT),
     _fn("qnnp_gfx950_dynamic_rows_kernel", "ptr op", IF_PRESENT, restype=c_char_p),
 )
@@ -398,7 +403,8 @@ class Gfx950Library(QnnpackLibrary):
     folded into a convolution (attach_residual_add[_status]), quantize / dequantize with their two setups each, and
     create_convolution2d_nhwc_q8_per_channel / create_fully_connected_nc_q8_per_channel, and
     [create|setup]_squeeze_excite[_status], and attach_output_table[_status], and
-    [create|setup]_fully_connected_nc_f32_qd8[_status], and create_fully_connected_nc_f32_qd8_qc4w[_status].
+    [create|setup]_fully_connected_nc_f32_qd8[_status], and create_fully_connected_nc_f32_qd8_qc4w[_status],
+    and create_fully_connected_nc_f32_qd8_qb4w[_status].
     """
 
     def __init__(self, path: str):

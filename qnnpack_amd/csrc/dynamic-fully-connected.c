@@ -1,11 +1,11 @@
 /*
- * dynamic-fully-connected.c -- qnnp_gfx950_create_fully_connected_nc_f32_qd8[_qc4w] / qnnp_gfx950_setup_fully_connected_nc_f32_qd8
+ * dynamic-fully-connected.c -- qnnp_gfx950_create_fully_connected_nc_f32_qd8[_qc4w, _qb4w] / qnnp_gfx950_setup_fully_connected_nc_f32_qd8
  * (include/qnnpack_gfx950_dynamic.h has the arithmetic and the statuses): float32 rows in, float32 rows out, each input row
  * quantized to its own range on the device and multiplied with int8 or 4-bit weights on the matrix cores.
  *
  * No reference counterpart. Create packs the weights into the fragment image of hip/qd8f32gemm.hip (4-bit weights: the
  * pair-fragment image of hip/qd8f32gemm4.hip; the operator remembers the width, nothing else differs) and uploads one table
- * entry per output channel (as per-channel.h does for the per-channel operators); setup follows quantize.c -- validation
+ * entry per output channel -- for block-wise 4-bit scales also one per channel and block, the block table of hip/qd8f32gemm4b.hip -- (as per-channel.h does for the per-channel operators); setup follows quantize.c -- validation
  * in the documented order, every check before the operator changes -- and grows the one device scratch the operator owns
  * (as squeeze-excite.c owns its gate rows; freed by qnnp_delete_operator). The run is two launches, reached through
  * op->launch: the rows kernel of hip/f32qd8rows.hip into the scratch, then the GEMM or GEMV kernel out of it. The scratch
@@ -63,6 +63,14 @@ static int launch_dynamic_fully_connected(struct qnnp_operator* op, const void* 
     .output_min = op->f32_output_min,
     .output_max = op->f32_output_max,
   };
+  if (op->qd8_block_size != 0) {
+    const struct qnnp_hip_qd8_qb4w_gemm_args block_args = {
+      .gemm = gemm_args,
+      .block_table = (const struct qnnp_hip_qd8_block_entry*) op->d_qd8_blocks,
+      .block_size = op->qd8_block_size,
+    };
+    return qnnp_hip_qd8_qb4w_gemm_run(&block_args, &op->kernel_name);
+  }
   return op->qd8_weight_bits == 4 ? qnnp_hip_qd8_qc4w_gemm_run(&gemm_args, &op->kernel_name)
                                   : qnnp_hip_qd8_gemm_run(&gemm_args, &op->kernel_name);
 }
@@ -119,9 +127,32 @@ static void pack_weights_qc4w(size_t k, size_t n, uint32_t k_pad4, uint32_t n_pa
   }
 }
 
+/* The block table (hip/qnnp_hip.h): entry ((c / 16) * nblk + b) * 16 + c % 16 = {kernel_scales[c][b] / 16 -- exact, the
+ * scale is at least 2^-16 --, 16 * the sum of the block's weights, at most 16 * 8 * 256 in magnitude}; padding channels
+ * {1 / 16, 0}. */
+static void fill_block_table(size_t k, size_t n, uint32_t n_pad, size_t block_size, const uint8_t* kernel,
+                             const float* kernel_scales, struct qnnp_hip_qd8_block_entry* table)
+{
+  const size_t nblk = k / block_size;
+  for (size_t c = 0; c < n_pad; c++) {
+    for (size_t b = 0; b < nblk; b++) {
+      struct qnnp_hip_qd8_block_entry* entry = &table[((c / 16) * nblk + b) * 16 + c % 16];
+      *entry = (struct qnnp_hip_qd8_block_entry) { .s16 = 0.0625f, .wsum16 = 0 };
+      if (c < n) {
+        int32_t wsum = 0;
+        for (size_t i = b * block_size; i < (b + 1) * block_size; i++) {
+          wsum += weight_at(kernel, 4, k, c, i);
+        }
+        entry->s16 = kernel_scales[c * nblk + b] * 0.0625f;
+        entry->wsum16 = 16 * wsum;
+      }
+    }
+  }
+}
+
 static enum qnnp_status create_dynamic_fully_connected(
-    size_t input_channels, size_t output_channels, const void* kernel, uint32_t weight_bits, const float* kernel_scales,
-    const float* bias, float output_min, float output_max, qnnp_operator_t* fully_connected)
+    size_t input_channels, size_t output_channels, size_t block_size, const void* kernel, uint32_t weight_bits,
+    const float* kernel_scales, const float* bias, float output_min, float output_max, qnnp_operator_t* fully_connected)
 {
   qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_dynamic_fully_connected, launch_dynamic_fully_connected);
   if (op == NULL) {
@@ -132,9 +163,13 @@ static enum qnnp_status create_dynamic_fully_connected(
   const uint32_t k_pad4 = ((uint32_t) input_channels + 127u) & ~127u;       /* whole K-tile pairs */
   const size_t w_bytes = weight_bits == 4 ? (size_t) n_pad * (k_pad4 / 2) : (size_t) n_pad * k_pad;
   const size_t t_bytes = (size_t) n_pad * sizeof(struct qnnp_hip_qd8_channel_entry);
+  /* block-wise scales: one more table; without them a token byte, so that one test serves every allocation */
+  const size_t b_bytes = block_size != 0
+      ? (size_t) n_pad * (input_channels / block_size) * sizeof(struct qnnp_hip_qd8_block_entry) : 1;
   int8_t* packed = (int8_t*) malloc(w_bytes);
   struct qnnp_hip_qd8_channel_entry* table = (struct qnnp_hip_qd8_channel_entry*) malloc(t_bytes);
-  if (packed != NULL && table != NULL) {
+  struct qnnp_hip_qd8_block_entry* blocks = (struct qnnp_hip_qd8_block_entry*) malloc(b_bytes);
+  if (packed != NULL && table != NULL && blocks != NULL) {
     if (weight_bits == 4) {
       pack_weights_qc4w(input_channels, output_channels, k_pad4, n_pad, (const uint8_t*) kernel, (uint8_t*) packed);
     } else {
@@ -143,7 +178,9 @@ static enum qnnp_status create_dynamic_fully_connected(
     for (size_t c = 0; c < n_pad; c++) {
       /* the padding channels: valid entries whose results are never stored */
       table[c] = (struct qnnp_hip_qd8_channel_entry) { .kernel_scale = 1.0f, .bias = 0.0f, .wsum = 0 };
-      if (c < output_channels) {
+      if (c < output_channels && block_size != 0) {
+        table[c].bias = bias != NULL ? bias[c] : 0.0f;       /* the scales and weight sums are the block table's */
+      } else if (c < output_channels) {
         int32_t wsum = 0;
         for (size_t k = 0; k < input_channels; k++) {
           wsum += weight_at(kernel, weight_bits, input_channels, c, k);        /* at most 128 * 32768 in magnitude */
@@ -155,12 +192,17 @@ static enum qnnp_status create_dynamic_fully_connected(
     }
     op->d_weights = qnnp_upload(packed, w_bytes);
     op->d_qd8_channels = qnnp_upload(table, t_bytes);
+    if (block_size != 0) {
+      fill_block_table(input_channels, output_channels, n_pad, block_size, (const uint8_t*) kernel, kernel_scales, blocks);
+      op->d_qd8_blocks = qnnp_upload(blocks, b_bytes);
+    }
   } else {
-    qnnp_log_error("out of host memory: %zu bytes for packed weights", w_bytes + t_bytes);
+    qnnp_log_error("out of host memory: %zu bytes for packed weights", w_bytes + t_bytes + b_bytes);
   }
   free(packed);
   free(table);
-  if (op->d_weights == NULL || op->d_qd8_channels == NULL) {
+  free(blocks);
+  if (op->d_weights == NULL || op->d_qd8_channels == NULL || (block_size != 0 && op->d_qd8_blocks == NULL)) {
     qnnp_log_error("cannot create dynamic fully connected operator: %zu bytes of packed weights could not be placed on the "
         "device", w_bytes + t_bytes);
     qnnp_delete_operator(op);
@@ -171,29 +213,35 @@ static enum qnnp_status create_dynamic_fully_connected(
   op->k_pad = k_pad;
   op->n_pad = n_pad;
   op->qd8_weight_bits = weight_bits;
+  op->qd8_block_size = (uint32_t) block_size;
   op->f32_output_min = output_min;
   op->f32_output_max = output_max;
   *fully_connected = op;
   return qnnp_status_success;
 }
 
-/* both creates: the checks in the header's order, then the packing under the device */
+/* every create: the checks in the header's order, then the packing under the device. `blockwise`: the _qb4w create, with
+ * input_channels / block_size (rounded down, where the create is going to be refused) scales per channel, each in
+ * [2^-16, 2^16]; otherwise block_size is 0 and there is one scale per channel in [2^-20, 2^20]. */
 static enum qnnp_status create_checked(
-    const char* function, size_t input_channels, size_t output_channels, const void* kernel, uint32_t weight_bits,
-    const float* kernel_scales, const float* bias, float output_min, float output_max, qnnp_operator_t* fully_connected)
+    const char* function, size_t input_channels, size_t output_channels, int blockwise, size_t block_size, const void* kernel,
+    uint32_t weight_bits, const float* kernel_scales, const float* bias, float output_min, float output_max,
+    qnnp_operator_t* fully_connected)
 {
   enum qnnp_status status = qnnp_check_initialized(function);
   if (status != qnnp_status_success) {
     return status;
   }
-  if (input_channels == 0 || output_channels == 0 || kernel == NULL || kernel_scales == NULL) {
+  if (input_channels == 0 || output_channels == 0 || kernel == NULL || kernel_scales == NULL || (blockwise && block_size == 0)) {
     qnnp_log_error("cannot create dynamic fully connected operator with %zu input and %zu output channels: channel counts, "
-        "kernel and kernel scales may not be zero", input_channels, output_channels);
+        "block size, kernel and kernel scales may not be zero", input_channels, output_channels);
     return qnnp_status_invalid_parameter;
   }
-  for (size_t c = 0; c < output_channels; c++) {
+  const size_t scale_count = output_channels * (blockwise ? input_channels / block_size : 1);
+  const float scale_min = blockwise ? 0x1.0p-16f : 0x1.0p-20f, scale_max = blockwise ? 0x1.0p+16f : 0x1.0p+20f;
+  for (size_t c = 0; c < scale_count; c++) {
     if (!(kernel_scales[c] > 0.0f && isnormal(kernel_scales[c]))) {
-      qnnp_log_error("cannot create dynamic fully connected operator with %.7g kernel scale of channel %zu: a scale has to "
+      qnnp_log_error("cannot create dynamic fully connected operator with %.7g kernel scale %zu: a scale has to "
           "be a finite number above zero", kernel_scales[c], c);
       return qnnp_status_invalid_parameter;
     }
@@ -210,10 +258,15 @@ static enum qnnp_status create_checked(
         "NaN and min may not exceed max", output_min, output_max);
     return qnnp_status_invalid_parameter;
   }
-  for (size_t c = 0; c < output_channels; c++) {
-    if (!(kernel_scales[c] >= 0x1.0p-20f && kernel_scales[c] <= 0x1.0p+20f)) {
-      qnnp_log_error("cannot create dynamic fully connected operator with %.7g kernel scale of channel %zu: scale must be "
-          "in [2**-20, 2**20] range", kernel_scales[c], c);
+  if (blockwise && ((block_size != 64 && block_size != 128 && block_size != 256) || input_channels % block_size != 0)) {
+    qnnp_log_error("cannot create dynamic fully connected operator with %zu input channels in blocks of %zu: a block is 64, "
+        "128 or 256 wide and divides the input channels", input_channels, block_size);
+    return qnnp_status_unsupported_parameter;
+  }
+  for (size_t c = 0; c < scale_count; c++) {
+    if (!(kernel_scales[c] >= scale_min && kernel_scales[c] <= scale_max)) {
+      qnnp_log_error("cannot create dynamic fully connected operator with %.7g kernel scale %zu: scale must be "
+          "in [%g, %g] range", kernel_scales[c], c, scale_min, scale_max);
       return qnnp_status_unsupported_parameter;
     }
   }
@@ -230,7 +283,8 @@ static enum qnnp_status create_checked(
     return status;
   }
   return qnnp_leave_create(token, create_dynamic_fully_connected(
-      input_channels, output_channels, kernel, weight_bits, kernel_scales, bias, output_min, output_max, fully_connected));
+      input_channels, output_channels, block_size, kernel, weight_bits, kernel_scales, bias, output_min, output_max,
+      fully_connected));
 }
 
 enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8(
@@ -245,7 +299,7 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8(
     qnnp_operator_t* fully_connected)
 {
   (void) flags;
-  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8", input_channels, output_channels, kernel, 8,
+  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8", input_channels, output_channels, 0, 0, kernel, 8,
       kernel_scales, bias, output_min, output_max, fully_connected);
 }
 
@@ -261,8 +315,25 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qc4w(
     qnnp_operator_t* fully_connected)
 {
   (void) flags;
-  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qc4w", input_channels, output_channels, kernel, 4,
+  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qc4w", input_channels, output_channels, 0, 0, kernel, 4,
       kernel_scales, bias, output_min, output_max, fully_connected);
+}
+
+enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w(
+    size_t input_channels,
+    size_t output_channels,
+    size_t block_size,
+    const uint8_t* kernel,
+    const float* kernel_scales,
+    const float* bias,
+    float output_min,
+    float output_max,
+    uint32_t flags,
+    qnnp_operator_t* fully_connected)
+{
+  (void) flags;
+  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w", input_channels, output_channels, 1, block_size,
+      kernel, 4, kernel_scales, bias, output_min, output_max, fully_connected);
 }
 
 static enum qnnp_status setup_dynamic_fully_connected(

@@ -45,6 +45,14 @@ __device__ __forceinline__ float qd8_finish(int32_t acc, const qnnp_hip_qd8_row_
   return fminf(fmaxf(y, out_min), out_max);
 }
 
+/* block-wise scales (qd8f32gemm4b.hip): one output from the ordered float sum of its blocks' terms */
+__device__ __forceinline__ float qb4w_finish(float ysum, const qnnp_hip_qd8_row_entry& row, float bias, float out_min, float out_max)
+{
+  float y = ysum * row.scale;
+  y = y + bias;
+  return fminf(fmaxf(y, out_min), out_max);
+}
+
 /* One 16 x 16 accumulator tile: lane l holds rows row0 + 4 (l / 16) + r (r = 0 .. 3) of channel c0 + l % 16. The four row
  * entries are one 32-byte run of the table, loaded once per tile row (rows past the batch re-read the last entry). */
 struct RowQuad {

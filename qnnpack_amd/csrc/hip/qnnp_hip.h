@@ -614,6 +614,26 @@ int qnnp_hip_qd8_gemm_run(const struct qnnp_hip_qd8_gemm_args* args, const char*
  * 16 nb + l % 16, zero where the channel or the K position is padding. Everything else as above.
  * qd8_f32_qc4w_gemv_mfma_16 for rows <= 16, else qd8_f32_qc4w_gemm_mfma_128x128 */
 int qnnp_hip_qd8_qc4w_gemm_run(const struct qnnp_hip_qd8_gemm_args* args, const char** kernel_name);
+/* 4-bit weights with one scale per BLOCK of `block_size` (64, 128 or 256) consecutive K positions (qd8f32gemm4b.hip; the
+ * _qb4w create). `packed_w` is the pair-fragment image above; k_pad = K is a multiple of block_size. `block_table` has one
+ * entry per (channel, block), laid out [n_pad / 16][k_pad / block_size][16 channels] so that the sixteen channels of a
+ * fragment read 128 contiguous bytes: s16 = kernel_scales[c][b] / 16 (exact) and wsum16 = 16 * sum_{k in block} kernel[c][k];
+ * the padding channels hold {1 / 16, 0}. Of `channel_table` only the bias is read. Per output the kernels compute
+ *   t_b = (float) (L_b + (128 - zp_r) * wsum16) * s16      L_b = 16 * sum_{k in block} (q - 128) * w: the MFMA sum, unshifted
+ *   ysum = ((0 + t_0) + t_1) + ...                           ONE owner per output walks b upward
+ *   y = ysum * scale_r;  y = y + bias[c];  clamp
+ * which is the header's definition bit for bit: L_b + (128 - zp_r) * wsum16 = 16 * acc_b exactly, below 2^24 in magnitude.
+ * qd8_f32_qb4w_gemv_mfma_16 for rows <= 16, else qd8_f32_qb4w_gemm_mfma_128x128 */
+struct qnnp_hip_qd8_block_entry {
+  float s16;                  /* kernel_scales[c][b] / 16 */
+  int32_t wsum16;             /* 16 * sum_{k in block b} kernel[c][k] */
+};
+struct qnnp_hip_qd8_qb4w_gemm_args {
+  struct qnnp_hip_qd8_gemm_args gemm;
+  const struct qnnp_hip_qd8_block_entry* block_table;
+  uint32_t block_size;
+};
+int qnnp_hip_qd8_qb4w_gemm_run(const struct qnnp_hip_qd8_qb4w_gemm_args* args, const char** kernel_name);
 
 /* softargmax (q8softargmax.hip, linked into libqnnpack_gfx950.so only -- see the Makefile): replaces u8rmax_ukernel__sse2,
  * u8lut32norm_ukernel__scalar and the softargmax case of src/operator-run.c:625-637, 1091-1108. For each of `rows` rows

@@ -172,9 +172,14 @@ struct qnnp_operator {
    * entries, both owned. The device scratch is ONE grow-only allocation, owned: batch_size * k_pad bytes of quantized rows,
    * then batch_size row entries at qd8_row_table_offset. qd8_rows_kernel names the first of the two launches.
    * qd8_weight_bits is 8, or 4 for the _qc4w create: d_weights is then the pair-fragment image of hip/qd8f32gemm4.hip
-   * (n_pad x k_pad4 / 2 bytes, k_pad4 = K rounded up to 128) and the second launch is that unit's. */
+   * (n_pad x k_pad4 / 2 bytes, k_pad4 = K rounded up to 128) and the second launch is that unit's.
+   * qd8_block_size is 0 (one weight scale per channel), or 64, 128 or 256 for the _qb4w create: d_qd8_blocks is then the
+   * block table [n_pad / 16][K / block size][16] of hip/qnnp_hip.h, owned, the channel table's scale and wsum are unused and
+   * the second launch is hip/qd8f32gemm4b.hip's. */
   uint32_t qd8_weight_bits;
+  uint32_t qd8_block_size;
   void* d_qd8_channels;
+  void* d_qd8_blocks;
   void* d_qd8_scratch;
   size_t qd8_scratch_capacity;                  /* in bytes */
   size_t qd8_row_table_offset;

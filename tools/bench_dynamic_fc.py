@@ -6,6 +6,12 @@ scale -> per-channel fully connected -> dequantize, three operators and a uint8 
 rounded down into [-8, 7], half the bytes), timed in turn with the int8 one; `qc4w_over_dynamic` is its time over the
 int8 operator's of the same run.
 
+`--qb4w` times something else: the 4-bit operator with block-wise scales
+(qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w) at block sizes 64, 128 and 256 against the `qc4w` operator on the
+same weights and tensors -- the four operators in turn, --rounds times over, medians and spreads as below;
+`qb4w<B>_over_qc4w` is a time ratio within the run, `image_over_qc4w` the device image (weights and block table) over the
+qc4w weight image.
+
 Every operator is timed with qnnp_gfx950_time_operator_rotating over --sets pairs of input and output tensors (the
 launches of one sample recorded into a hipGraph, median of five samples), the five operators in turn, --rounds times
 over; the median round is reported with the spread between rounds, (max - min) / median. The chain's figure is the sum
@@ -13,7 +19,7 @@ of its three operators' medians: kernel time without the gaps between launches, 
 rotate; the weights of one operator cannot, so at small batches they are served by the 256 MiB last-level cache and
 `weights_gb_s` (weight bytes / time) is a cache figure wherever the image fits there, not an HBM figure.
 
-    python tools/bench_dynamic_fc.py [--shapes 1x4096x4096,...] [--sets 4] [--iters 20] [--rounds 5] [--json out.json]
+    python tools/bench_dynamic_fc.py [--qb4w] [--shapes 1x4096x4096,...] [--sets 4] [--iters 20] [--rounds 5] [--json out.json]
 """
 import argparse
 import json
@@ -29,8 +35,55 @@ sys.path.insert(0, ROOT)
 SHAPES = [(1, 4096, 4096), (16, 4096, 4096), (4096, 4096, 4096), (197, 768, 3072), (1, 16384, 16384), (16, 16384, 16384)]
 
 
+BLOCKS = (64, 128, 256)
+
+
+def qb4w_rows(lib, args, shapes, rng, gen, np, torch):
+    """one record per shape: qc4w and qb4w at every block size, whole operators, alternating"""
+    rows_out, inf = [], float("inf")
+    for k, n in dict.fromkeys((k, n) for _, k, n in shapes):        # operators are made once per weight shape
+        nibbles = rng.integers(0, 16, size=(n, k), dtype=np.uint8)
+        packed = nibbles[:, 0::2] | (nibbles[:, 1::2] << 4)
+        del nibbles
+        bias = rng.standard_normal(n).astype(np.float32)
+        ops = {"qc4w": lib.create_fully_connected_nc_f32_qd8_qc4w(k, n, packed, rng.uniform(0.005, 0.02, size=n).astype(np.float32),
+                                                                  bias, -inf, inf)}
+        for block in BLOCKS:
+            scales = rng.uniform(0.005, 0.02, size=(n, k // block)).astype(np.float32)
+            ops[f"qb4w{block}"] = lib.create_fully_connected_nc_f32_qd8_qb4w(k, n, block, packed, scales, bias, -inf, inf)
+        try:
+            for batch in [b for b, kk, nn in shapes if (kk, nn) == (k, n)]:
+                x = [torch.randn(batch * k, dtype=torch.float32, device="cuda", generator=gen) for _ in range(args.sets)]
+                y = [torch.empty(batch * n, dtype=torch.float32, device="cuda") for _ in range(args.sets)]
+                for op in ops.values():
+                    lib.setup_fully_connected_nc_f32_qd8(op, batch, x[0], k, y[0], n)
+                    lib.run_operator(op)
+                t = {key: [] for key in ops}
+                for _ in range(args.rounds):
+                    for key, op in ops.items():
+                        t[key].append(lib.time_operator_rotating(op, x, y, args.warmup, args.iters))
+                us = {key: statistics.median(v) * 1e3 for key, v in t.items()}
+                row = {"batch": batch, "k": k, "n": n,
+                       "us": {key: round(v, 2) for key, v in us.items()},
+                       "spread": {key: round((max(v) - min(v)) / statistics.median(v), 3) for key, v in t.items()},
+                       "kernels": {key: lib.operator_kernel(op) for key, op in ops.items()},
+                       "image_mib": {"qc4w": round(n * k / 2 ** 21, 1),
+                                     **{f"qb4w{b}": round((n * k / 2 + 8 * n * (k // b)) / 2 ** 20, 1) for b in BLOCKS}},
+                       "sets": args.sets, "rounds": args.rounds, "launches_per_sample": args.iters}
+                for b in BLOCKS:
+                    row[f"qb4w{b}_over_qc4w"] = round(us[f"qb4w{b}"] / us["qc4w"], 3)
+                    row.setdefault("image_over_qc4w", {})[f"qb4w{b}"] = round(1 + 16 / b, 4)
+                rows_out.append(row)
+                print(json.dumps(row), flush=True)
+        finally:
+            for op in ops.values():
+                lib.delete_operator(op)
+    return rows_out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--qb4w", action="store_true", help="time the block-wise 4-bit operator against the qc4w one instead")
     ap.add_argument("--shapes", default=None, help="BATCHxKxN,... instead of the built-in list")
     ap.add_argument("--sets", type=int, default=4)
     ap.add_argument("--iters", type=int, default=20)
@@ -54,8 +107,8 @@ def main():
     gen = torch.Generator(device="cuda").manual_seed(23)
 
     shapes = SHAPES if args.shapes is None else [tuple(int(v) for v in item.split("x")) for item in args.shapes.split(",")]
-    rows_out = []
-    for batch, k, n in shapes:
+    rows_out = qb4w_rows(lib, args, shapes, rng, gen, np, torch) if args.qb4w else []
+    for batch, k, n in ([] if args.qb4w else shapes):
         kernel = rng.integers(-128, 128, size=(n, k), dtype=np.int8)
         scales = rng.uniform(0.005, 0.02, size=n).astype(np.float32)
         bias = rng.standard_normal(n).astype(np.float32)
