@@ -107,7 +107,8 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qc4w(
     qnnp_operator_t* fully_connected);
 
 /*
- * The 4-bit operator with BLOCK-WISE weight scales (qd8-f32-qb4w: what GPTQ, AWQ and GGUF weights carry): one scale per
+ * The 4-bit operator with BLOCK-WISE weight scales (qd8-f32-qb4w: what symmetric GPTQ and GGUF weights carry; AWQ and
+ * asymmetric GPTQ weights also carry a zero point per block: _qb4w_zp below): one scale per
  * output channel and per block of B = block_size consecutive K positions. `kernel` is the _qc4w layout,
  * [output_channels][input_channels / 2] bytes (K is even here: no spare nibble); `kernel_scales` is
  * [output_channels][input_channels / block_size].
@@ -159,6 +160,64 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w(
     const uint8_t* kernel,         /* [output_channels][input_channels / 2], two signed nibbles per byte as _qc4w, host */
     const float* kernel_scales,    /* [output_channels][input_channels / block_size], host */
     const float* bias,             /* [output_channels] float32, host; NULL means all zero */
+    float output_min,
+    float output_max,
+    uint32_t flags,
+    qnnp_operator_t* fully_connected);
+
+/*
+ * The block-wise 4-bit operator with one integer ZERO POINT per output channel and block (w = (u - z) * scale: the form of
+ * AWQ weights, of GPTQ weights with sym=False, of torchao's int4 and HQQ's integer mode). `kernel` has the _qb4w layout,
+ * [output_channels][input_channels / 2] bytes with weight k in bits 4 (k % 2) .. 4 (k % 2) + 3 of byte k / 2, but each
+ * nibble is UNSIGNED, u in [0, 15]; `kernel_scales` and `kernel_zero_points` are [output_channels][input_channels /
+ * block_size], every zero point in [0, 15]. The zero point cannot be folded into the nibbles: u - z spans [-15, 15].
+ *
+ * Definition (bit-exact, no tolerance). Per input row, q, zp_r and scale_r are exactly those above. With B = block_size,
+ * nb = K / B, u[c][k] the nibble and z[c][b] the zero point, all float operations float32, each rounded once, no fused
+ * multiply-add; per output (r, c):
+ *   acc_b = sum_{k in [b B, (b + 1) B)} (q[r][k] - zp_r) * (u[c][k] - z[c][b])     exact in int32, b = 0 .. nb - 1
+ *   t_b   = (float) acc_b * kernel_scales[c][b]                 the conversion is exact: |acc_b| <= 255 * 15 * 256 < 2^20
+ *   ysum  = 0.0f;  for b = 0, 1, ..., nb - 1 IN THIS ORDER:  ysum = ysum + t_b
+ *   y     = ysum * scale_r;  y = y + bias[c];  y = min(max(y, output_min), output_max)
+ * The chain and the finish are _qb4w's: ONE owner per output walks b upward, everything else may happen anywhere.
+ *
+ * Consequence: with every zero point 8 and u = w + 8 (the signed nibble w of _qb4w with bit 3 flipped, byte ^ 0x88), the
+ * acc_b are those of _qb4w, and the result equals the _qb4w operator's bit for bit on equal scales.
+ *
+ * Where the zero point enters. The kernels subtract it while they unpack the nibbles, so that the matrix cores multiply
+ * (q - 128) with the int8 u - z itself; their loop sum is L = sum (q - 128) * (u - z), at most 128 * 15 * 256 per block. Per
+ * (channel, block) the device holds the scale as given and wsum = sum_{k in block} (u - z), at most 15 * 256 in magnitude,
+ * and L + (128 - zp_r) * wsum = acc_b exactly. There is no factor 16 as in _qb4w: t_b is computed as the definition writes it.
+ * The zero points themselves travel in a second table of one uint16 per channel and 128 K positions (both 64-wide halves'
+ * zero points), 1 / 32 of the weight bytes, next to the 8 bytes per channel and block of the block table.
+ *
+ * Block scales lie in [2^-16, 2^16] and each is a normal number above zero, as for _qb4w, and no result depends on the
+ * denormal mode: a nonzero t_b is at least 2^-16 in magnitude and, |acc_b| < 2^20 having at most 20 significant bits, a
+ * multiple of 2^-39 (the last place of a scale of 2^-16 is 2^-39). So every partial ysum is zero or a multiple of 2^-39, never
+ * a denormal, and below 2^9 * 2^20 * 2^16 = 2^45. ysum * scale_r is zero or at least 2^-39 * 2^-60 = 2^-99 in magnitude, and
+ * a sum with a normal bias that cancels is zero or a multiple of the product's last place, at least 2^-99 * 2^-24 = 2^-123:
+ * still normal.
+ *
+ * Create answers in _qb4w's order, with two additions: a NULL kernel_zero_points is invalid_parameter with the other NULL
+ * pointers, and a zero point above 15 is invalid_parameter, checked behind the scales' validity (a normal number above
+ * zero) and in front of the bias, over input_channels / block_size entries per channel, rounded down, like the scale
+ * checks. An argument set that is both invalid and unsupported answers invalid_parameter; a refused create writes no
+ * handle; block size 32 stays refused; input_channels <= 32768 and output_channels < 2^24 as before.
+ *
+ * The handle is set up with qnnp_gfx950_setup_fully_connected_nc_f32_qd8 and run, captured, named and deleted like the
+ * others: the row launch and the scratch are the same, the second launch is hip/qd8f32gemm4z.hip's
+ * (qnnp_gfx950_operator_kernel names it):
+ *     qd8_f32_qb4w_zp_gemv_mfma_16        batch_size <= 16
+ *     qd8_f32_qb4w_zp_gemm_mfma_128x128   batch_size > 16    (no scratch memory at any block size)
+ */
+enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_zp(
+    size_t input_channels,
+    size_t output_channels,
+    size_t block_size,                   /* 64, 128 or 256; divides input_channels */
+    const uint8_t* kernel,               /* [output_channels][input_channels / 2], two UNSIGNED nibbles per byte, host */
+    const float* kernel_scales,          /* [output_channels][input_channels / block_size], host */
+    const uint8_t* kernel_zero_points,   /* [output_channels][input_channels / block_size], each in [0, 15], host */
+    const float* bias,                   /* [output_channels] float32, host; NULL means all zero */
     float output_min,
     float output_max,
     uint32_t flags,

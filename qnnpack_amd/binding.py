@@ -298,6 +298,11 @@ DYNAMIC_API = (
         "f32 output_min, f32 output_max, u32 flags=0, out fully_connected", IF_PRESENT,
         doc="the 4-bit operator with block-wise scales: `kernel` as for _qc4w, `kernel_scales` output_channels x "
             "input_channels / block_size floats, block_size 64, 128 or 256; set it up with setup_fully_connected_nc_f32_qd8"),
+    _op("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_zp",
+        "size_t input_channels, size_t output_channels, size_t block_size, u8[] kernel, f32[] kernel_scales, "
+        "u8[] kernel_zero_points, f32[] bias, f32 output_min, f32 output_max, u32 flags=0, out fully_connected", IF_PRESENT,
+        doc="the block-wise 4-bit operator with UNSIGNED nibbles and one zero point in [0, 15] per channel and block (AWQ, "
+            "asymmetric GPTQ): `kernel_zero_points` shaped like `kernel_scales`; set it up with setup_fully_connected_nc_f32_qd8"),
     _op("qnnp_gfx950_setup_fully_connected_nc_f32_qd8", _SETUP_NC, IF_PRESENT),
     _fn("qnnp_gfx950_dynamic_rows_kernel", "ptr op", IF_PRESENT, restype=c_char_p),
 )
@@ -404,7 +409,7 @@ class Gfx950Library(QnnpackLibrary):
     create_convolution2d_nhwc_q8_per_channel / create_fully_connected_nc_q8_per_channel, and
     [create|setup]_squeeze_excite[_status], and attach_output_table[_status], and
     [create|setup]_fully_connected_nc_f32_qd8[_status], and create_fully_connected_nc_f32_qd8_qc4w[_status],
-    and create_fully_connected_nc_f32_qd8_qb4w[_status].
+    and create_fully_connected_nc_f32_qd8_qb4w[_status], and create_fully_connected_nc_f32_qd8_qb4w_zp[_status].
     """
 
     def __init__(self, path: str):

@@ -1,11 +1,12 @@
 /*
- * dynamic-fully-connected.c -- qnnp_gfx950_create_fully_connected_nc_f32_qd8[_qc4w, _qb4w] / qnnp_gfx950_setup_fully_connected_nc_f32_qd8
+ * dynamic-fully-connected.c -- qnnp_gfx950_create_fully_connected_nc_f32_qd8[_qc4w, _qb4w, _qb4w_zp] / qnnp_gfx950_setup_fully_connected_nc_f32_qd8
  * (include/qnnpack_gfx950_dynamic.h has the arithmetic and the statuses): float32 rows in, float32 rows out, each input row
  * quantized to its own range on the device and multiplied with int8 or 4-bit weights on the matrix cores.
  *
  * No reference counterpart. Create packs the weights into the fragment image of hip/qd8f32gemm.hip (4-bit weights: the
  * pair-fragment image of hip/qd8f32gemm4.hip; the operator remembers the width, nothing else differs) and uploads one table
- * entry per output channel -- for block-wise 4-bit scales also one per channel and block, the block table of hip/qd8f32gemm4b.hip -- (as per-channel.h does for the per-channel operators); setup follows quantize.c -- validation
+ * entry per output channel -- for block-wise 4-bit scales also one per channel and block, the block table of hip/qd8f32gemm4b.hip, and with
+ * per-block zero points the block table and the zero-point pair table of hip/qd8f32gemm4z.hip -- (as per-channel.h does for the per-channel operators); setup follows quantize.c -- validation
  * in the documented order, every check before the operator changes -- and grows the one device scratch the operator owns
  * (as squeeze-excite.c owns its gate rows; freed by qnnp_delete_operator). The run is two launches, reached through
  * op->launch: the rows kernel of hip/f32qd8rows.hip into the scratch, then the GEMM or GEMV kernel out of it. The scratch
@@ -63,6 +64,17 @@ static int launch_dynamic_fully_connected(struct qnnp_operator* op, const void* 
     .output_min = op->f32_output_min,
     .output_max = op->f32_output_max,
   };
+  if (op->qd8_zero_points != 0) {
+    const size_t table_bytes =
+        (size_t) op->n_pad * (op->k_pad / op->qd8_block_size) * sizeof(struct qnnp_hip_qd8_zp_block_entry);
+    const struct qnnp_hip_qd8_qb4w_zp_gemm_args zp_args = {
+      .gemm = gemm_args,
+      .block_table = (const struct qnnp_hip_qd8_zp_block_entry*) op->d_qd8_blocks,
+      .zero_point_pairs = (const uint16_t*) ((const uint8_t*) op->d_qd8_blocks + table_bytes),
+      .block_size = op->qd8_block_size,
+    };
+    return qnnp_hip_qd8_qb4w_zp_gemm_run(&zp_args, &op->kernel_name);
+  }
   if (op->qd8_block_size != 0) {
     const struct qnnp_hip_qd8_qb4w_gemm_args block_args = {
       .gemm = gemm_args,
@@ -150,9 +162,42 @@ static void fill_block_table(size_t k, size_t n, uint32_t n_pad, size_t block_si
   }
 }
 
+/* The two tables of the _qb4w_zp create (hip/qnnp_hip.h), in one allocation. `kernel` holds UNSIGNED nibbles u. The block
+ * table: entry ((c / 16) * nblk + b) * 16 + c % 16 = {kernel_scales[c][b], the sum of u - z over the block, at most 15 * 256
+ * in magnitude}; padding channels {1, 0}. Behind it the zero-point pair table: uint16 ((c / 16) * kpairs + kp) * 16 + c % 16 =
+ * the zero point of the block of K tile 2 kp in the low byte and of K tile 2 kp + 1 in the high byte; zero for padding
+ * channels and for a tile past K. */
+static void fill_block_table_zp(size_t k, size_t n, uint32_t n_pad, uint32_t k_pad4, size_t block_size, const uint8_t* kernel,
+                                const float* kernel_scales, const uint8_t* kernel_zero_points,
+                                struct qnnp_hip_qd8_zp_block_entry* table)
+{
+  const size_t nblk = k / block_size, kpairs = k_pad4 / 128;
+  uint16_t* pairs = (uint16_t*) (table + (size_t) n_pad * nblk);
+  for (size_t c = 0; c < n_pad; c++) {
+    for (size_t b = 0; b < nblk; b++) {
+      struct qnnp_hip_qd8_zp_block_entry* entry = &table[((c / 16) * nblk + b) * 16 + c % 16];
+      *entry = (struct qnnp_hip_qd8_zp_block_entry) { .scale = 1.0f, .wsum = 0 };
+      if (c < n) {
+        int32_t usum = 0;
+        for (size_t i = b * block_size; i < (b + 1) * block_size; i++) {
+          usum += (kernel[c * (k / 2) + i / 2] >> (4 * (i % 2))) & 15;
+        }
+        entry->scale = kernel_scales[c * nblk + b];
+        entry->wsum = usum - (int32_t) block_size * kernel_zero_points[c * nblk + b];
+      }
+    }
+    for (size_t kp = 0; kp < kpairs; kp++) {
+      const size_t k_even = kp * 128, k_odd = kp * 128 + 64;
+      const uint32_t low = c < n ? kernel_zero_points[c * nblk + k_even / block_size] : 0u;
+      const uint32_t high = c < n && k_odd < k ? kernel_zero_points[c * nblk + k_odd / block_size] : 0u;
+      pairs[((c / 16) * kpairs + kp) * 16 + c % 16] = (uint16_t) (low | (high << 8));
+    }
+  }
+}
+
 static enum qnnp_status create_dynamic_fully_connected(
     size_t input_channels, size_t output_channels, size_t block_size, const void* kernel, uint32_t weight_bits,
-    const float* kernel_scales, const float* bias, float output_min, float output_max, qnnp_operator_t* fully_connected)
+    const float* kernel_scales, const uint8_t* kernel_zero_points, const float* bias, float output_min, float output_max, qnnp_operator_t* fully_connected)
 {
   qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_dynamic_fully_connected, launch_dynamic_fully_connected);
   if (op == NULL) {
@@ -163,9 +208,11 @@ static enum qnnp_status create_dynamic_fully_connected(
   const uint32_t k_pad4 = ((uint32_t) input_channels + 127u) & ~127u;       /* whole K-tile pairs */
   const size_t w_bytes = weight_bits == 4 ? (size_t) n_pad * (k_pad4 / 2) : (size_t) n_pad * k_pad;
   const size_t t_bytes = (size_t) n_pad * sizeof(struct qnnp_hip_qd8_channel_entry);
-  /* block-wise scales: one more table; without them a token byte, so that one test serves every allocation */
-  const size_t b_bytes = block_size != 0
-      ? (size_t) n_pad * (input_channels / block_size) * sizeof(struct qnnp_hip_qd8_block_entry) : 1;
+  /* block-wise scales: one more table (with zero points: eight bytes per entry as well, and the pair table behind it);
+   * without them a token byte, so that one test serves every allocation */
+  const size_t b_bytes = block_size == 0 ? 1
+      : (size_t) n_pad * (input_channels / block_size) * sizeof(struct qnnp_hip_qd8_block_entry)
+          + (kernel_zero_points != NULL ? (size_t) n_pad * (k_pad4 / 128) * sizeof(uint16_t) : 0);
   int8_t* packed = (int8_t*) malloc(w_bytes);
   struct qnnp_hip_qd8_channel_entry* table = (struct qnnp_hip_qd8_channel_entry*) malloc(t_bytes);
   struct qnnp_hip_qd8_block_entry* blocks = (struct qnnp_hip_qd8_block_entry*) malloc(b_bytes);
@@ -192,7 +239,11 @@ static enum qnnp_status create_dynamic_fully_connected(
     }
     op->d_weights = qnnp_upload(packed, w_bytes);
     op->d_qd8_channels = qnnp_upload(table, t_bytes);
-    if (block_size != 0) {
+    if (kernel_zero_points != NULL) {
+      fill_block_table_zp(input_channels, output_channels, n_pad, k_pad4, block_size, (const uint8_t*) kernel, kernel_scales,
+          kernel_zero_points, (struct qnnp_hip_qd8_zp_block_entry*) blocks);
+      op->d_qd8_blocks = qnnp_upload(blocks, b_bytes);
+    } else if (block_size != 0) {
       fill_block_table(input_channels, output_channels, n_pad, block_size, (const uint8_t*) kernel, kernel_scales, blocks);
       op->d_qd8_blocks = qnnp_upload(blocks, b_bytes);
     }
@@ -214,27 +265,30 @@ static enum qnnp_status create_dynamic_fully_connected(
   op->n_pad = n_pad;
   op->qd8_weight_bits = weight_bits;
   op->qd8_block_size = (uint32_t) block_size;
+  op->qd8_zero_points = kernel_zero_points != NULL;
   op->f32_output_min = output_min;
   op->f32_output_max = output_max;
   *fully_connected = op;
   return qnnp_status_success;
 }
 
-/* every create: the checks in the header's order, then the packing under the device. `blockwise`: the _qb4w create, with
- * input_channels / block_size (rounded down, where the create is going to be refused) scales per channel, each in
- * [2^-16, 2^16]; otherwise block_size is 0 and there is one scale per channel in [2^-20, 2^20]. */
+/* every create: the checks in the header's order, then the packing under the device. `blockwise`: the _qb4w and _qb4w_zp
+ * creates, with input_channels / block_size (rounded down, where the create is going to be refused) scales per channel, each
+ * in [2^-16, 2^16]; otherwise block_size is 0 and there is one scale per channel in [2^-20, 2^20]. `zero_points`: the
+ * _qb4w_zp create, with as many kernel_zero_points as scales, each at most 15; otherwise kernel_zero_points is NULL. */
 static enum qnnp_status create_checked(
     const char* function, size_t input_channels, size_t output_channels, int blockwise, size_t block_size, const void* kernel,
-    uint32_t weight_bits, const float* kernel_scales, const float* bias, float output_min, float output_max,
+    uint32_t weight_bits, const float* kernel_scales, int zero_points, const uint8_t* kernel_zero_points, const float* bias, float output_min, float output_max,
     qnnp_operator_t* fully_connected)
 {
   enum qnnp_status status = qnnp_check_initialized(function);
   if (status != qnnp_status_success) {
     return status;
   }
-  if (input_channels == 0 || output_channels == 0 || kernel == NULL || kernel_scales == NULL || (blockwise && block_size == 0)) {
+  if (input_channels == 0 || output_channels == 0 || kernel == NULL || kernel_scales == NULL || (blockwise && block_size == 0) ||
+      (zero_points && kernel_zero_points == NULL)) {
     qnnp_log_error("cannot create dynamic fully connected operator with %zu input and %zu output channels: channel counts, "
-        "block size, kernel and kernel scales may not be zero", input_channels, output_channels);
+        "block size, kernel, kernel scales and kernel zero points may not be zero", input_channels, output_channels);
     return qnnp_status_invalid_parameter;
   }
   const size_t scale_count = output_channels * (blockwise ? input_channels / block_size : 1);
@@ -243,6 +297,13 @@ static enum qnnp_status create_checked(
     if (!(kernel_scales[c] > 0.0f && isnormal(kernel_scales[c]))) {
       qnnp_log_error("cannot create dynamic fully connected operator with %.7g kernel scale %zu: a scale has to "
           "be a finite number above zero", kernel_scales[c], c);
+      return qnnp_status_invalid_parameter;
+    }
+  }
+  for (size_t c = 0; zero_points && c < scale_count; c++) {
+    if (kernel_zero_points[c] > 15) {
+      qnnp_log_error("cannot create dynamic fully connected operator with kernel zero point %zu = %u: a zero point of 4-bit "
+          "weights is at most 15", c, (unsigned) kernel_zero_points[c]);
       return qnnp_status_invalid_parameter;
     }
   }
@@ -283,8 +344,8 @@ static enum qnnp_status create_checked(
     return status;
   }
   return qnnp_leave_create(token, create_dynamic_fully_connected(
-      input_channels, output_channels, block_size, kernel, weight_bits, kernel_scales, bias, output_min, output_max,
-      fully_connected));
+      input_channels, output_channels, block_size, kernel, weight_bits, kernel_scales, kernel_zero_points, bias, output_min,
+      output_max, fully_connected));
 }
 
 enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8(
@@ -300,7 +361,7 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8(
 {
   (void) flags;
   return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8", input_channels, output_channels, 0, 0, kernel, 8,
-      kernel_scales, bias, output_min, output_max, fully_connected);
+      kernel_scales, 0, NULL, bias, output_min, output_max, fully_connected);
 }
 
 enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qc4w(
@@ -316,7 +377,7 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qc4w(
 {
   (void) flags;
   return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qc4w", input_channels, output_channels, 0, 0, kernel, 4,
-      kernel_scales, bias, output_min, output_max, fully_connected);
+      kernel_scales, 0, NULL, bias, output_min, output_max, fully_connected);
 }
 
 enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w(
@@ -333,7 +394,25 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w(
 {
   (void) flags;
   return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w", input_channels, output_channels, 1, block_size,
-      kernel, 4, kernel_scales, bias, output_min, output_max, fully_connected);
+      kernel, 4, kernel_scales, 0, NULL, bias, output_min, output_max, fully_connected);
+}
+
+enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_zp(
+    size_t input_channels,
+    size_t output_channels,
+    size_t block_size,
+    const uint8_t* kernel,
+    const float* kernel_scales,
+    const uint8_t* kernel_zero_points,
+    const float* bias,
+    float output_min,
+    float output_max,
+    uint32_t flags,
+    qnnp_operator_t* fully_connected)
+{
+  (void) flags;
+  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_zp", input_channels, output_channels, 1, block_size,
+      kernel, 4, kernel_scales, 1, kernel_zero_points, bias, output_min, output_max, fully_connected);
 }
 
 static enum qnnp_status setup_dynamic_fully_connected(

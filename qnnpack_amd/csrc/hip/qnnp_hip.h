@@ -634,6 +634,30 @@ struct qnnp_hip_qd8_qb4w_gemm_args {
   uint32_t block_size;
 };
 int qnnp_hip_qd8_qb4w_gemm_run(const struct qnnp_hip_qd8_qb4w_gemm_args* args, const char** kernel_name);
+/* UNSIGNED 4-bit weights with one scale and one integer zero point per block (qd8f32gemm4z.hip; the _qb4w_zp create):
+ * w = (u - z) * scale, u and z in [0, 15]. `packed_w` is the pair-fragment image above holding the raw nibbles u (padding
+ * zero); k_pad = K is a multiple of block_size. `block_table` is laid out as the _qb4w one, [n_pad / 16][k_pad / block_size][16
+ * channels]: scale = kernel_scales[c][b] as given and wsum = sum_{k in block} (u[c][k] - z[c][b]), at most 15 * 256 in
+ * magnitude; the padding channels hold {1, 0}. `zero_point_pairs` has one uint16 per channel and K-tile PAIR, laid out like
+ * the weight image, [n_pad / 16][ceil(k_pad / 128)][16 channels]: the low byte is the zero point of the block that holds K
+ * tile 2 kp, the high byte that of K tile 2 kp + 1 (the same block for block_size >= 128); zero for padding channels and
+ * for an odd half past k_pad. The kernels subtract the zero point while they unpack, so that the MFMA operand is u - z:
+ *   t_b = (float) (L_b + (128 - zp_r) * wsum) * scale       L_b = sum_{k in block} (q - 128) * (u - z): the MFMA sum
+ *   ysum = ((0 + t_0) + t_1) + ...                            ONE owner per output walks b upward
+ *   y = ysum * scale_r;  y = y + bias[c];  clamp
+ * L_b + (128 - zp_r) * wsum = acc_b of the header exactly, below 2^20 in magnitude. Of `channel_table` only the bias is read.
+ * qd8_f32_qb4w_zp_gemv_mfma_16 for rows <= 16, else qd8_f32_qb4w_zp_gemm_mfma_128x128 */
+struct qnnp_hip_qd8_zp_block_entry {
+  float scale;                /* kernel_scales[c][b] */
+  int32_t wsum;               /* sum_{k in block b} (u[c][k] - z[c][b]) */
+};
+struct qnnp_hip_qd8_qb4w_zp_gemm_args {
+  struct qnnp_hip_qd8_gemm_args gemm;
+  const struct qnnp_hip_qd8_zp_block_entry* block_table;
+  const uint16_t* zero_point_pairs;
+  uint32_t block_size;
+};
+int qnnp_hip_qd8_qb4w_zp_gemm_run(const struct qnnp_hip_qd8_qb4w_zp_gemm_args* args, const char** kernel_name);
 
 /* softargmax (q8softargmax.hip, linked into libqnnpack_gfx950.so only -- see the Makefile): replaces u8rmax_ukernel__sse2,
  * u8lut32norm_ukernel__scalar and the softargmax case of src/operator-run.c:625-637, 1091-1108. For each of `rows` rows

@@ -175,9 +175,13 @@ struct qnnp_operator {
    * (n_pad x k_pad4 / 2 bytes, k_pad4 = K rounded up to 128) and the second launch is that unit's.
    * qd8_block_size is 0 (one weight scale per channel), or 64, 128 or 256 for the _qb4w create: d_qd8_blocks is then the
    * block table [n_pad / 16][K / block size][16] of hip/qnnp_hip.h, owned, the channel table's scale and wsum are unused and
-   * the second launch is hip/qd8f32gemm4b.hip's. */
+   * the second launch is hip/qd8f32gemm4b.hip's.
+   * qd8_zero_points is 1 for the _qb4w_zp create (unsigned nibbles, one zero point per block), else 0: d_qd8_blocks is then
+   * the block table of hip/qd8f32gemm4z.hip with the zero-point pair table ([n_pad / 16][k_pad4 / 128][16] uint16) behind
+   * it, in the one allocation, and the second launch is that unit's. */
   uint32_t qd8_weight_bits;
   uint32_t qd8_block_size;
+  uint32_t qd8_zero_points;
   void* d_qd8_channels;
   void* d_qd8_blocks;
   void* d_qd8_scratch;

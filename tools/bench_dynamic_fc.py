@@ -12,6 +12,11 @@ same weights and tensors -- the four operators in turn, --rounds times over, med
 `qb4w<B>_over_qc4w` is a time ratio within the run, `image_over_qc4w` the device image (weights and block table) over the
 qc4w weight image.
 
+`--qb4w-zp` times the block-wise operator with per-block zero points
+(qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_zp) against the `qb4w` operator at the same block size, on the same
+nibble bytes (read as unsigned by the one, as signed by the other), scales and tensors, in the same process -- the six
+operators in turn, --rounds times over; `qb4w_zp<B>_over_qb4w<B>` is a time ratio within the run.
+
 Every operator is timed with qnnp_gfx950_time_operator_rotating over --sets pairs of input and output tensors (the
 launches of one sample recorded into a hipGraph, median of five samples), the five operators in turn, --rounds times
 over; the median round is reported with the spread between rounds, (max - min) / median. The chain's figure is the sum
@@ -19,7 +24,7 @@ of its three operators' medians: kernel time without the gaps between launches, 
 rotate; the weights of one operator cannot, so at small batches they are served by the 256 MiB last-level cache and
 `weights_gb_s` (weight bytes / time) is a cache figure wherever the image fits there, not an HBM figure.
 
-    python tools/bench_dynamic_fc.py [--qb4w] [--shapes 1x4096x4096,...] [--sets 4] [--iters 20] [--rounds 5] [--json out.json]
+    python tools/bench_dynamic_fc.py [--qb4w | --qb4w-zp] [--shapes 1x4096x4096,...] [--sets 4] [--iters 20] [--rounds 5] [--json out.json]
 """
 import argparse
 import json
@@ -81,9 +86,54 @@ def qb4w_rows(lib, args, shapes, rng, gen, np, torch):
     return rows_out
 
 
+def qb4w_zp_rows(lib, args, shapes, rng, gen, np, torch):
+    """one record per shape: qb4w and qb4w_zp at every block size on the same nibble bytes, whole operators, alternating"""
+    rows_out, inf = [], float("inf")
+    for k, n in dict.fromkeys((k, n) for _, k, n in shapes):        # operators are made once per weight shape
+        nibbles = rng.integers(0, 16, size=(n, k), dtype=np.uint8)
+        packed = nibbles[:, 0::2] | (nibbles[:, 1::2] << 4)
+        del nibbles
+        bias = rng.standard_normal(n).astype(np.float32)
+        ops = {}
+        for block in BLOCKS:
+            scales = rng.uniform(0.005, 0.02, size=(n, k // block)).astype(np.float32)
+            zps = rng.integers(0, 16, size=(n, k // block), dtype=np.uint8)
+            ops[f"qb4w{block}"] = lib.create_fully_connected_nc_f32_qd8_qb4w(k, n, block, packed, scales, bias, -inf, inf)
+            ops[f"qb4w_zp{block}"] = lib.create_fully_connected_nc_f32_qd8_qb4w_zp(k, n, block, packed, scales, zps, bias, -inf, inf)
+        try:
+            for batch in [b for b, kk, nn in shapes if (kk, nn) == (k, n)]:
+                x = [torch.randn(batch * k, dtype=torch.float32, device="cuda", generator=gen) for _ in range(args.sets)]
+                y = [torch.empty(batch * n, dtype=torch.float32, device="cuda") for _ in range(args.sets)]
+                for op in ops.values():
+                    lib.setup_fully_connected_nc_f32_qd8(op, batch, x[0], k, y[0], n)
+                    lib.run_operator(op)
+                t = {key: [] for key in ops}
+                for _ in range(args.rounds):
+                    for key, op in ops.items():
+                        t[key].append(lib.time_operator_rotating(op, x, y, args.warmup, args.iters))
+                us = {key: statistics.median(v) * 1e3 for key, v in t.items()}
+                row = {"batch": batch, "k": k, "n": n,
+                       "us": {key: round(v, 2) for key, v in us.items()},
+                       "spread": {key: round((max(v) - min(v)) / statistics.median(v), 3) for key, v in t.items()},
+                       "kernels": {key: lib.operator_kernel(op) for key, op in ops.items()},
+                       "image_mib": {f"qb4w_zp{b}": round((n * k / 2 + 8 * n * (k // b) + 2 * n * ((k + 127) // 128)) / 2 ** 20, 1)
+                                     for b in BLOCKS},
+                       "sets": args.sets, "rounds": args.rounds, "launches_per_sample": args.iters}
+                for b in BLOCKS:
+                    row[f"qb4w_zp{b}_over_qb4w{b}"] = round(us[f"qb4w_zp{b}"] / us[f"qb4w{b}"], 3)
+                rows_out.append(row)
+                print(json.dumps(row), flush=True)
+        finally:
+            for op in ops.values():
+                lib.delete_operator(op)
+    return rows_out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--qb4w", action="store_true", help="time the block-wise 4-bit operator against the qc4w one instead")
+    ap.add_argument("--qb4w-zp", action="store_true",
+                    help="time the block-wise 4-bit operator with zero points against the one without instead")
     ap.add_argument("--shapes", default=None, help="BATCHxKxN,... instead of the built-in list")
     ap.add_argument("--sets", type=int, default=4)
     ap.add_argument("--iters", type=int, default=20)
@@ -108,7 +158,9 @@ def main():
 
     shapes = SHAPES if args.shapes is None else [tuple(int(v) for v in item.split("x")) for item in args.shapes.split(",")]
     rows_out = qb4w_rows(lib, args, shapes, rng, gen, np, torch) if args.qb4w else []
-    for batch, k, n in ([] if args.qb4w else shapes):
+    if args.qb4w_zp:
+        rows_out += qb4w_zp_rows(lib, args, shapes, rng, gen, np, torch)
+    for batch, k, n in ([] if args.qb4w or args.qb4w_zp else shapes):
         kernel = rng.integers(-128, 128, size=(n, k), dtype=np.int8)
         scales = rng.uniform(0.005, 0.02, size=n).astype(np.float32)
         bias = rng.standard_normal(n).astype(np.float32)
