@@ -142,8 +142,9 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qc4w(
  * scale checks read input_channels / block_size scales per channel, rounded down); unsupported_parameter for a
  * block_size other than 64, 128 and 256, an input_channels that is no multiple of block_size, a scale outside
  * [2^-16, 2^16], input_channels > 32768, output_channels >= 2^24; out_of_memory. An argument set that is both invalid and
- * unsupported answers invalid_parameter. Block size 32 is refused on purpose: one v_mfma_i32_16x16x64_i8 sums 64
- * consecutive K positions, so a 32-wide block needs the 16x16x32 instruction and a different fragment image.
+ * unsupported answers invalid_parameter. Block size 32 is refused here and by _qb4w_zp: one v_mfma_i32_16x16x64_i8 sums 64
+ * consecutive K positions, so a 32-wide block needs the 16x16x32 instruction and a different fragment image. Those are
+ * qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_b32's, below.
  *
  * The handle is set up with qnnp_gfx950_setup_fully_connected_nc_f32_qd8 and run, captured, named and deleted like the
  * others: the row launch, the scratch and the weight image (the _qc4w one) are the same, the second launch is
@@ -217,6 +218,55 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_zp(
     const uint8_t* kernel,               /* [output_channels][input_channels / 2], two UNSIGNED nibbles per byte, host */
     const float* kernel_scales,          /* [output_channels][input_channels / block_size], host */
     const uint8_t* kernel_zero_points,   /* [output_channels][input_channels / block_size], each in [0, 15], host */
+    const float* bias,                   /* [output_channels] float32, host; NULL means all zero */
+    float output_min,
+    float output_max,
+    uint32_t flags,
+    qnnp_operator_t* fully_connected);
+
+/*
+ * The block-wise 4-bit operator with BLOCKS OF 32 K positions: the block of GGUF Q4_0 and Q4_1 and of GPTQ, AWQ and torchao
+ * checkpoints made with group_size = 32. `kernel` has the _qb4w nibble layout, `kernel_scales` and `kernel_zero_points` are
+ * [output_channels][input_channels / 32].
+ *
+ * Definition (bit-exact, no tolerance): _qb4w_zp's with B = 32. Per input row, q, zp_r and scale_r are those above; all float
+ * operations float32, each rounded once, no fused multiply-add; per output (r, c), with nb = K / 32:
+ *   acc_b = sum_{k in [32 b, 32 b + 32)} (q[r][k] - zp_r) * (u[c][k] - z[c][b])     exact in int32, b = 0 .. nb - 1
+ *   t_b   = (float) acc_b * kernel_scales[c][b]                 the conversion is exact: |acc_b| <= 255 * 15 * 32 < 2^17
+ *   ysum  = 0.0f;  for b = 0, 1, ..., nb - 1 IN THIS ORDER:  ysum = ysum + t_b
+ *   y     = ysum * scale_r;  y = y + bias[c];  y = min(max(y, output_min), output_max)
+ * With kernel_zero_points == NULL the nibbles are SIGNED, w in [-8, 7] as in _qb4w, and the definition holds with u - z read
+ * as w. The create turns that form into the other while it packs: u = w ^ 8 and z = 8 give the same acc_b, hence the same
+ * bits, and one kernel pair serves both forms.
+ *
+ * Block scales lie in [2^-16, 2^16] and each is a normal number above zero, and no result depends on the denormal mode: a
+ * nonzero t_b is at least 2^-16 in magnitude and, |acc_b| < 2^17 having at most 17 significant bits, a multiple of 2^-39 (the
+ * last place of a scale of 2^-16). There are at most 32768 / 32 = 2^10 blocks, so every partial ysum is zero or a multiple of
+ * 2^-39, never a denormal, and below 2^10 * 2^17 * 2^16 = 2^43. ysum * scale_r is zero or at least 2^-39 * 2^-60 = 2^-99 in
+ * magnitude, and a sum with a normal bias that cancels is zero or a multiple of the product's last place, at least
+ * 2^-99 * 2^-24 = 2^-123: still normal.
+ *
+ * Create answers in _qb4w_zp's order: uninitialized; invalid_parameter for a zero channel count, a NULL kernel or
+ * kernel_scales, a scale that is not a normal number above zero, a zero point above 15 (checked only where zero points are
+ * given), a bad bias, a bad clamp; unsupported_parameter for an input_channels that is no multiple of 32, a scale outside
+ * [2^-16, 2^16], input_channels > 32768, output_channels >= 2^24; out_of_memory. The scale and zero-point checks read
+ * input_channels / 32 entries per channel, rounded down. An argument set that is both invalid and unsupported answers
+ * invalid_parameter; a refused create writes no handle.
+ *
+ * The handle is set up with qnnp_gfx950_setup_fully_connected_nc_f32_qd8 and run, captured, named and deleted like the
+ * others: the row launch and the scratch are the same (K rounded up to 64 per row, so K may be an odd multiple of 32), the
+ * weight image and the second launch are hip/qd8f32gemm4s.hip's (qnnp_gfx950_operator_kernel names it), on
+ * v_mfma_i32_16x16x32_i8, one instruction per block and 16 x 16 outputs:
+ *     qd8_f32_qb4w_b32_gemv_mfma_16        batch_size <= 16
+ *     qd8_f32_qb4w_b32_gemm_mfma_128x128   batch_size > 16    (no scratch memory)
+ * Scales, weight sums and zero points add 6 bytes per channel and block to the device image: 37.5 % of the weight bytes.
+ */
+enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_b32(
+    size_t input_channels,               /* a multiple of 32 */
+    size_t output_channels,
+    const uint8_t* kernel,               /* [output_channels][input_channels / 2], the _qb4w nibble layout, host */
+    const float* kernel_scales,          /* [output_channels][input_channels / 32], host */
+    const uint8_t* kernel_zero_points,   /* [output_channels][input_channels / 32], each in [0, 15]; NULL: signed nibbles */
     const float* bias,                   /* [output_channels] float32, host; NULL means all zero */
     float output_min,
     float output_max,

@@ -303,6 +303,12 @@ DYNAMIC_API = (
         "u8[] kernel_zero_points, f32[] bias, f32 output_min, f32 output_max, u32 flags=0, out fully_connected", IF_PRESENT,
         doc="the block-wise 4-bit operator with UNSIGNED nibbles and one zero point in [0, 15] per channel and block (AWQ, "
             "asymmetric GPTQ): `kernel_zero_points` shaped like `kernel_scales`; set it up with setup_fully_connected_nc_f32_qd8"),
+    _op("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_b32",
+        "size_t input_channels, size_t output_channels, u8[] kernel, f32[] kernel_scales, u8[] kernel_zero_points, "
+        "f32[] bias, f32 output_min, f32 output_max, u32 flags=0, out fully_connected", IF_PRESENT,
+        doc="the block-wise 4-bit operator with blocks of 32 (GGUF Q4_0 / Q4_1, group_size = 32): `kernel_scales` and "
+            "`kernel_zero_points` are output_channels x input_channels / 32; kernel_zero_points=None reads the nibbles as "
+            "signed, as _qb4w does; set it up with setup_fully_connected_nc_f32_qd8"),
     _op("qnnp_gfx950_setup_fully_connected_nc_f32_qd8", _SETUP_NC, IF_PRESENT),
     _fn("qnnp_gfx950_dynamic_rows_kernel", "ptr op", IF_PRESENT, restype=c_char_p),
 )
@@ -409,7 +415,8 @@ class Gfx950Library(QnnpackLibrary):
     create_convolution2d_nhwc_q8_per_channel / create_fully_connected_nc_q8_per_channel, and
     [create|setup]_squeeze_excite[_status], and attach_output_table[_status], and
     [create|setup]_fully_connected_nc_f32_qd8[_status], and create_fully_connected_nc_f32_qd8_qc4w[_status],
-    and create_fully_connected_nc_f32_qd8_qb4w[_status], and create_fully_connected_nc_f32_qd8_qb4w_zp[_status].
+    and create_fully_connected_nc_f32_qd8_qb4w[_status], and create_fully_connected_nc_f32_qd8_qb4w_zp[_status],
+    and create_fully_connected_nc_f32_qd8_qb4w_b32[_status].
     """
 
     def __init__(self, path: str):

@@ -1,12 +1,12 @@
 /*
- * dynamic-fully-connected.c -- qnnp_gfx950_create_fully_connected_nc_f32_qd8[_qc4w, _qb4w, _qb4w_zp] / qnnp_gfx950_setup_fully_connected_nc_f32_qd8
+ * dynamic-fully-connected.c -- qnnp_gfx950_create_fully_connected_nc_f32_qd8[_qc4w, _qb4w, _qb4w_zp, _qb4w_b32] / qnnp_gfx950_setup_fully_connected_nc_f32_qd8
  * (include/qnnpack_gfx950_dynamic.h has the arithmetic and the statuses): float32 rows in, float32 rows out, each input row
  * quantized to its own range on the device and multiplied with int8 or 4-bit weights on the matrix cores.
  *
  * No reference counterpart. Create packs the weights into the fragment image of hip/qd8f32gemm.hip (4-bit weights: the
  * pair-fragment image of hip/qd8f32gemm4.hip; the operator remembers the width, nothing else differs) and uploads one table
  * entry per output channel -- for block-wise 4-bit scales also one per channel and block, the block table of hip/qd8f32gemm4b.hip, and with
- * per-block zero points the block table and the zero-point pair table of hip/qd8f32gemm4z.hip -- (as per-channel.h does for the per-channel operators); setup follows quantize.c -- validation
+ * per-block zero points the block table and the zero-point pair table of hip/qd8f32gemm4z.hip, for blocks of 32 the image and the two pair-indexed tables of hip/qd8f32gemm4s.hip -- (as per-channel.h does for the per-channel operators); setup follows quantize.c -- validation
  * in the documented order, every check before the operator changes -- and grows the one device scratch the operator owns
  * (as squeeze-excite.c owns its gate rows; freed by qnnp_delete_operator). The run is two launches, reached through
  * op->launch: the rows kernel of hip/f32qd8rows.hip into the scratch, then the GEMM or GEMV kernel out of it. The scratch
@@ -64,6 +64,15 @@ static int launch_dynamic_fully_connected(struct qnnp_operator* op, const void* 
     .output_min = op->f32_output_min,
     .output_max = op->f32_output_max,
   };
+  if (op->qd8_block_size == 32) {
+    const size_t scale_bytes = (size_t) op->n_pad * ((op->k_pad + 127u) / 128u) * 4 * sizeof(float);
+    const struct qnnp_hip_qd8_qb4w_b32_gemm_args b32_args = {
+      .gemm = gemm_args,
+      .block_scales = (const float*) op->d_qd8_blocks,
+      .block_sums = (const int16_t*) ((const uint8_t*) op->d_qd8_blocks + scale_bytes),
+    };
+    return qnnp_hip_qd8_qb4w_b32_gemm_run(&b32_args, &op->kernel_name);
+  }
   if (op->qd8_zero_points != 0) {
     const size_t table_bytes =
         (size_t) op->n_pad * (op->k_pad / op->qd8_block_size) * sizeof(struct qnnp_hip_qd8_zp_block_entry);
@@ -195,6 +204,63 @@ static void fill_block_table_zp(size_t k, size_t n, uint32_t n_pad, uint32_t k_p
   }
 }
 
+/* The _qb4w_b32 create's image and tables (hip/qnnp_hip.h). `flip` is 0 for unsigned nibbles with `kernel_zero_points`, and 8
+ * for signed nibbles w (kernel_zero_points == NULL): u = w ^ 8 with every zero point 8 has the same u - z. */
+static inline uint32_t nibble_b32(const uint8_t* kernel, uint32_t flip, size_t k_total, size_t c, size_t k)
+{
+  return ((kernel[c * (k_total / 2) + k / 2] >> (4 * (k % 2))) & 15u) ^ flip;
+}
+
+/* The block-32 pair-fragment image: byte j of lane l of fragment nb * kpairs + kp holds two weights of channel
+ * nb * 16 + l % 16: K position kp * 128 + (j / 8) * 32 + (l / 16) * 8 + j % 8 in its low nibble and that position plus 64 in
+ * its high nibble; padding is zero. Bytes 0 .. 7 of a lane lie in the first 32-block of either K tile, bytes 8 .. 15 in the
+ * second. */
+static void pack_weights_qb4w_b32(size_t k, size_t n, uint32_t k_pad4, uint32_t n_pad, const uint8_t* kernel, uint32_t flip,
+                                  uint8_t* packed)
+{
+  const size_t kpairs = k_pad4 / 128;
+  for (size_t nb = 0; nb < n_pad / 16; nb++) {
+    for (size_t kp = 0; kp < kpairs; kp++) {
+      uint8_t* fragment = packed + (nb * kpairs + kp) * 1024;
+      for (size_t l = 0; l < 64; l++) {
+        const size_t c = nb * 16 + l % 16;
+        for (size_t j = 0; j < 16; j++) {
+          const size_t k0 = kp * 128 + (j / 8) * 32 + (l / 16) * 8 + j % 8;
+          const uint32_t low = c < n && k0 < k ? nibble_b32(kernel, flip, k, c, k0) : 0u;
+          const uint32_t high = c < n && k0 + 64 < k ? nibble_b32(kernel, flip, k, c, k0 + 64) : 0u;
+          fragment[l * 16 + j] = (uint8_t) (low | (high << 4));
+        }
+      }
+    }
+  }
+}
+
+/* The two tables of the _qb4w_b32 create (hip/qnnp_hip.h), in one allocation, entry ((c / 16) * kpairs + kp) * 16 + c % 16 of
+ * either: four scales (1 for padding channels and blocks past K), and behind all of them four int16 of 16 * wsum + z with
+ * wsum the block's sum of u - z, at most 15 * 32 in magnitude (0 for padding channels and blocks past K). */
+static void fill_tables_b32(size_t k, size_t n, uint32_t n_pad, uint32_t k_pad4, const uint8_t* kernel, uint32_t flip,
+                            const float* kernel_scales, const uint8_t* kernel_zero_points, float* scales)
+{
+  const size_t nblk = k / 32, kpairs = k_pad4 / 128;
+  int16_t* sums = (int16_t*) (scales + (size_t) n_pad * kpairs * 4);
+  for (size_t c = 0; c < n_pad; c++) {
+    for (size_t b = 0; b < kpairs * 4; b++) {
+      const size_t at = (((c / 16) * kpairs + b / 4) * 16 + c % 16) * 4 + b % 4;
+      scales[at] = 1.0f;
+      sums[at] = 0;
+      if (c < n && b < nblk) {
+        const int32_t z = kernel_zero_points != NULL ? kernel_zero_points[c * nblk + b] : 8;
+        int32_t wsum = 0;
+        for (size_t i = b * 32; i < (b + 1) * 32; i++) {
+          wsum += (int32_t) nibble_b32(kernel, flip, k, c, i) - z;
+        }
+        scales[at] = kernel_scales[c * nblk + b];
+        sums[at] = (int16_t) (16 * wsum + z);
+      }
+    }
+  }
+}
+
 static enum qnnp_status create_dynamic_fully_connected(
     size_t input_channels, size_t output_channels, size_t block_size, const void* kernel, uint32_t weight_bits,
     const float* kernel_scales, const uint8_t* kernel_zero_points, const float* bias, float output_min, float output_max, qnnp_operator_t* fully_connected)
@@ -211,13 +277,17 @@ static enum qnnp_status create_dynamic_fully_connected(
   /* block-wise scales: one more table (with zero points: eight bytes per entry as well, and the pair table behind it);
    * without them a token byte, so that one test serves every allocation */
   const size_t b_bytes = block_size == 0 ? 1
+      : block_size == 32 ? (size_t) n_pad * (k_pad4 / 128) * (4 * sizeof(float) + 4 * sizeof(int16_t))
       : (size_t) n_pad * (input_channels / block_size) * sizeof(struct qnnp_hip_qd8_block_entry)
           + (kernel_zero_points != NULL ? (size_t) n_pad * (k_pad4 / 128) * sizeof(uint16_t) : 0);
   int8_t* packed = (int8_t*) malloc(w_bytes);
   struct qnnp_hip_qd8_channel_entry* table = (struct qnnp_hip_qd8_channel_entry*) malloc(t_bytes);
   struct qnnp_hip_qd8_block_entry* blocks = (struct qnnp_hip_qd8_block_entry*) malloc(b_bytes);
   if (packed != NULL && table != NULL && blocks != NULL) {
-    if (weight_bits == 4) {
+    const uint32_t flip = kernel_zero_points == NULL ? 8u : 0u;      /* block size 32 alone: signed nibbles become unsigned */
+    if (block_size == 32) {
+      pack_weights_qb4w_b32(input_channels, output_channels, k_pad4, n_pad, (const uint8_t*) kernel, flip, (uint8_t*) packed);
+    } else if (weight_bits == 4) {
       pack_weights_qc4w(input_channels, output_channels, k_pad4, n_pad, (const uint8_t*) kernel, (uint8_t*) packed);
     } else {
       pack_weights(input_channels, output_channels, k_pad, n_pad, (const int8_t*) kernel, packed);
@@ -239,7 +309,11 @@ static enum qnnp_status create_dynamic_fully_connected(
     }
     op->d_weights = qnnp_upload(packed, w_bytes);
     op->d_qd8_channels = qnnp_upload(table, t_bytes);
-    if (kernel_zero_points != NULL) {
+    if (block_size == 32) {
+      fill_tables_b32(input_channels, output_channels, n_pad, k_pad4, (const uint8_t*) kernel, flip, kernel_scales,
+          kernel_zero_points, (float*) blocks);
+      op->d_qd8_blocks = qnnp_upload(blocks, b_bytes);
+    } else if (kernel_zero_points != NULL) {
       fill_block_table_zp(input_channels, output_channels, n_pad, k_pad4, block_size, (const uint8_t*) kernel, kernel_scales,
           kernel_zero_points, (struct qnnp_hip_qd8_zp_block_entry*) blocks);
       op->d_qd8_blocks = qnnp_upload(blocks, b_bytes);
@@ -265,15 +339,15 @@ static enum qnnp_status create_dynamic_fully_connected(
   op->n_pad = n_pad;
   op->qd8_weight_bits = weight_bits;
   op->qd8_block_size = (uint32_t) block_size;
-  op->qd8_zero_points = kernel_zero_points != NULL;
+  op->qd8_zero_points = kernel_zero_points != NULL || block_size == 32;
   op->f32_output_min = output_min;
   op->f32_output_max = output_max;
   *fully_connected = op;
   return qnnp_status_success;
 }
 
-/* every create: the checks in the header's order, then the packing under the device. `blockwise`: the _qb4w and _qb4w_zp
- * creates, with input_channels / block_size (rounded down, where the create is going to be refused) scales per channel, each
+/* every create: the checks in the header's order, then the packing under the device. `blockwise`: 1 for the _qb4w and
+ * _qb4w_zp creates and 2 for the _qb4w_b32 create (whose block_size is 32, the one value the other two refuse), with input_channels / block_size (rounded down, where the create is going to be refused) scales per channel, each
  * in [2^-16, 2^16]; otherwise block_size is 0 and there is one scale per channel in [2^-20, 2^20]. `zero_points`: the
  * _qb4w_zp create, with as many kernel_zero_points as scales, each at most 15; otherwise kernel_zero_points is NULL. */
 static enum qnnp_status create_checked(
@@ -319,9 +393,10 @@ static enum qnnp_status create_checked(
         "NaN and min may not exceed max", output_min, output_max);
     return qnnp_status_invalid_parameter;
   }
-  if (blockwise && ((block_size != 64 && block_size != 128 && block_size != 256) || input_channels % block_size != 0)) {
+  if (blockwise && ((blockwise == 2 ? block_size != 32 : (block_size != 64 && block_size != 128 && block_size != 256)) ||
+      input_channels % block_size != 0)) {
     qnnp_log_error("cannot create dynamic fully connected operator with %zu input channels in blocks of %zu: a block is 64, "
-        "128 or 256 wide and divides the input channels", input_channels, block_size);
+        "128 or 256 wide (32 through the _qb4w_b32 create) and divides the input channels", input_channels, block_size);
     return qnnp_status_unsupported_parameter;
   }
   for (size_t c = 0; c < scale_count; c++) {
@@ -413,6 +488,23 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_zp(
   (void) flags;
   return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_zp", input_channels, output_channels, 1, block_size,
       kernel, 4, kernel_scales, 1, kernel_zero_points, bias, output_min, output_max, fully_connected);
+}
+
+enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_b32(
+    size_t input_channels,
+    size_t output_channels,
+    const uint8_t* kernel,
+    const float* kernel_scales,
+    const uint8_t* kernel_zero_points,
+    const float* bias,
+    float output_min,
+    float output_max,
+    uint32_t flags,
+    qnnp_operator_t* fully_connected)
+{
+  (void) flags;
+  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_b32", input_channels, output_channels, 2, 32,
+      kernel, 4, kernel_scales, kernel_zero_points != NULL, kernel_zero_points, bias, output_min, output_max, fully_connected);
 }
 
 static enum qnnp_status setup_dynamic_fully_connected(

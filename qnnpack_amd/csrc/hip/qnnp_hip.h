@@ -658,6 +658,30 @@ struct qnnp_hip_qd8_qb4w_zp_gemm_args {
   uint32_t block_size;
 };
 int qnnp_hip_qd8_qb4w_zp_gemm_run(const struct qnnp_hip_qd8_qb4w_zp_gemm_args* args, const char** kernel_name);
+/* UNSIGNED 4-bit weights in blocks of 32 K positions, one scale and one zero point per block (qd8f32gemm4s.hip; the
+ * _qb4w_b32 create). k_pad is K (a multiple of 32) rounded up to 64. `packed_w` is an image of 1-KiB pair fragments indexed
+ * like the _qc4w one, fragment nb * ceil(k_pad / 128) + kp, with the positions dealt for the 16x16x32 instruction: of lane
+ * l's sixteen bytes, byte j < 8 holds K position 128 kp + 8 (l / 16) + j (low nibble) and that plus 64 (high nibble), byte
+ * 8 + j position 128 kp + 32 + 8 (l / 16) + j (low) and that plus 64 (high), of channel 16 nb + l % 16: raw nibbles u, zero
+ * where the channel or the K position is padding. A lane's bytes 0 .. 7 belong to the first 32-block of either tile, bytes
+ * 8 .. 15 to the second. Two tables, both [n_pad / 16][ceil(k_pad / 128)][16 channels], one entry per channel and pair,
+ * the pair's four blocks in K order:
+ *   block_scales   four float: kernel_scales[c][4 kp + i] as given; 1 for padding channels and blocks past K
+ *   block_sums     four int16: 16 * wsum + z, wsum = sum_{k in block} (u[c][k] - z[c][b]) in [-480, 480], z in [0, 15], so
+ *                  that z = v & 15 and wsum = v >> 4 (arithmetic); 0 for padding channels and blocks past K
+ * 24 bytes per channel and pair against 64 bytes of nibbles: 6 bytes per block, 0.6875 bytes per weight in all (B = 64 with
+ * zero points: 0.640625). An 8-byte {scale, wsum, z} entry per block would make it 0.75. Per output the kernels compute
+ *   t_b = (float) (L_b + (128 - zp_r) * wsum) * scale       L_b = sum_{k in block} (q - 128) * (u - z): ONE 16x16x32 MFMA
+ *   ysum = ((0 + t_0) + t_1) + ...                            ONE owner per output walks b upward
+ *   y = ysum * scale_r;  y = y + bias[c];  clamp
+ * Of `channel_table` only the bias is read.
+ * qd8_f32_qb4w_b32_gemv_mfma_16 for rows <= 16, else qd8_f32_qb4w_b32_gemm_mfma_128x128 */
+struct qnnp_hip_qd8_qb4w_b32_gemm_args {
+  struct qnnp_hip_qd8_gemm_args gemm;
+  const float* block_scales;      /* 16-byte aligned */
+  const int16_t* block_sums;      /* 8-byte aligned */
+};
+int qnnp_hip_qd8_qb4w_b32_gemm_run(const struct qnnp_hip_qd8_qb4w_b32_gemm_args* args, const char** kernel_name);
 
 /* softargmax (q8softargmax.hip, linked into libqnnpack_gfx950.so only -- see the Makefile): replaces u8rmax_ukernel__sse2,
  * u8lut32norm_ukernel__scalar and the softargmax case of src/operator-run.c:625-637, 1091-1108. For each of `rows` rows

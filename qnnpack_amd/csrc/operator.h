@@ -178,7 +178,11 @@ struct qnnp_operator {
    * the second launch is hip/qd8f32gemm4b.hip's.
    * qd8_zero_points is 1 for the _qb4w_zp create (unsigned nibbles, one zero point per block), else 0: d_qd8_blocks is then
    * the block table of hip/qd8f32gemm4z.hip with the zero-point pair table ([n_pad / 16][k_pad4 / 128][16] uint16) behind
-   * it, in the one allocation, and the second launch is that unit's. */
+   * it, in the one allocation, and the second launch is that unit's.
+   * qd8_block_size is 32 for the _qb4w_b32 create alone (qd8_zero_points is then 1: signed nibbles were turned into
+   * unsigned ones with zero point 8): d_weights is the block-32 pair-fragment image of hip/qd8f32gemm4s.hip and d_qd8_blocks
+   * its scale table ([n_pad / 16][k_pad4 / 128][16] of four floats) with the table of sums and zero points (four int16 per
+   * entry) behind it, and the second launch is that unit's. */
   uint32_t qd8_weight_bits;
   uint32_t qd8_block_size;
   uint32_t qd8_zero_points;
