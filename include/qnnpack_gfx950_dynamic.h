@@ -273,6 +273,58 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_b32(
     uint32_t flags,
     qnnp_operator_t* fully_connected);
 
+/*
+ * The operator with MXFP4 weights (OCP Microscaling: what FP4 checkpoints for this hardware generation carry): 4-bit
+ * FLOATING-POINT codes, E2M1, two per byte in the _qb4w nibble layout, and one E8M0 power-of-two scale per output channel and
+ * block of 32 consecutive K positions, `kernel_scales` [output_channels][input_channels / 32] bytes e, scale = 2^(e - 127).
+ *
+ * Definition (bit-exact, no tolerance). An E2M1 code c has its sign in bit 3 and a magnitude index c & 7 into
+ * {0, 0.5, 1, 1.5, 2, 3, 4, 6}. Let w2[c][k] be TWICE that value, an integer in {0, +-1, +-2, +-3, +-4, +-6, +-8, +-12}; code
+ * 8 (-0) is 0. Per input row, q, zp_r and scale_r are those of the first definition above; all float operations float32, each
+ * rounded once, no fused multiply-add; per output (r, c), with nb = K / 32 and e[c][b] the block's scale byte:
+ *   acc_b = sum_{k in [32 b, 32 b + 32)} (q[r][k] - zp_r) * w2[c][k]     exact; |acc_b| <= 255 * 12 * 32 = 97920 < 2^17
+ *   t_b   = (float) acc_b * 2^(e[c][b] - 128)                            exact: a 17-bit integer times a power of two
+ *   ysum  = 0.0f;  for b = 0, 1, ..., nb - 1 IN THIS ORDER:  ysum = ysum + t_b
+ *   y     = ysum * scale_r;  y = y + bias[c];  y = min(max(y, output_min), output_max)
+ * The halving of w2 is the 128 in the exponent where the scale has 127. Twice an E2M1 value being an integer is what puts
+ * the format on the INTEGER matrix cores: a block is one v_mfma_i32_16x16x32_i8 as in _qb4w_b32, the term is exact, and the
+ * only roundings are those of the chain and the finish, which are _qb4w's: ONE owner per output walks b upward.
+ *
+ * Scales are restricted to 2^-16 .. 2^16 (e in [111, 143]), the range of the other block-wise creates, and no result depends
+ * on the denormal mode: a nonzero t_b is a nonzero integer times 2^(e - 128), so a multiple of 2^-17 and at least that large.
+ * There are at most 32768 / 32 = 2^10 blocks, so every partial ysum is zero or a multiple of 2^-17, never a denormal, and
+ * below 2^10 * 2^17 * 2^15 = 2^42. ysum * scale_r is zero or at least 2^-17 * 2^-60 = 2^-77 in magnitude, and a sum with a
+ * normal bias that cancels is zero or a multiple of the product's last place, at least 2^-77 * 2^-24 = 2^-101: still normal.
+ *
+ * Consequence: where every code's w2 lies in [-8, 7] (no +4, no +-6) and e is in [112, 143], the _qb4w_b32 operator on the
+ * signed nibbles w2, kernel_zero_points == NULL and block scales 2^(e - 128) has the same acc_b and the same t_b, hence the
+ * same bits. At e = 111 that scale would be 2^-17, below _qb4w_b32's range.
+ *
+ * Create answers, in the order of the other creates: uninitialized; invalid_parameter for a zero channel count, a NULL kernel
+ * or kernel_scales, a scale byte of 255 (E8M0's NaN; checked where the other creates check for a normal number above zero,
+ * over input_channels / 32 entries per channel, rounded down), a bad bias, a bad clamp; unsupported_parameter for an
+ * input_channels that is no multiple of 32, a scale byte outside [111, 143] (refused, not clamped), input_channels > 32768,
+ * output_channels >= 2^24; out_of_memory. An argument set that is both invalid and unsupported answers invalid_parameter; a
+ * refused create writes no handle.
+ *
+ * The handle is set up with qnnp_gfx950_setup_fully_connected_nc_f32_qd8 and run, captured, named and deleted like the
+ * others: the row launch and the scratch are the same, the weight image is _qb4w_b32's holding the raw codes, and the second
+ * launch is hip/qd8f32gemm4m.hip's (qnnp_gfx950_operator_kernel names it), which decodes the codes to w2 in registers:
+ *     qd8_f32_mxfp4w_gemv_mfma_16        batch_size <= 16
+ *     qd8_f32_mxfp4w_gemm_mfma_128x128   batch_size > 16    (no scratch memory)
+ * Scale and weight sum share one 32-bit word per block: 4 bytes per block, 25 % of the weight bytes (_qb4w_b32: 6 and 37.5 %).
+ */
+enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_mxfp4w(
+    size_t input_channels,               /* a multiple of 32, <= 32768 */
+    size_t output_channels,              /* < 2^24 */
+    const uint8_t* kernel,               /* [output_channels][input_channels / 2]: E2M1 code of weight k in bits 4 (k % 2) .. + 3 of byte k / 2, host */
+    const uint8_t* kernel_scales,        /* [output_channels][input_channels / 32]: E8M0, scale = 2^(e - 127), host */
+    const float* bias,                   /* [output_channels] float32, host; NULL means all zero */
+    float output_min,
+    float output_max,
+    uint32_t flags,
+    qnnp_operator_t* fully_connected);
+
 enum qnnp_status qnnp_gfx950_setup_fully_connected_nc_f32_qd8(
     qnnp_operator_t fully_connected,
     size_t batch_size,

@@ -309,6 +309,12 @@ DYNAMIC_API = (
         doc="the block-wise 4-bit operator with blocks of 32 (GGUF Q4_0 / Q4_1, group_size = 32): `kernel_scales` and "
             "`kernel_zero_points` are output_channels x input_channels / 32; kernel_zero_points=None reads the nibbles as "
             "signed, as _qb4w does; set it up with setup_fully_connected_nc_f32_qd8"),
+    _op("qnnp_gfx950_create_fully_connected_nc_f32_qd8_mxfp4w",
+        "size_t input_channels, size_t output_channels, u8[] kernel, u8[] kernel_scales, f32[] bias, "
+        "f32 output_min, f32 output_max, u32 flags=0, out fully_connected", IF_PRESENT,
+        doc="the operator with MXFP4 weights: `kernel` holds two E2M1 codes per byte in the _qb4w nibble layout, "
+            "`kernel_scales` output_channels x input_channels / 32 E8M0 bytes e (scale 2^(e - 127), e in [111, 143]); set it up "
+            "with setup_fully_connected_nc_f32_qd8"),
     _op("qnnp_gfx950_setup_fully_connected_nc_f32_qd8", _SETUP_NC, IF_PRESENT),
     _fn("qnnp_gfx950_dynamic_rows_kernel", "ptr op", IF_PRESENT, restype=c_char_p),
 )
@@ -416,7 +422,7 @@ class Gfx950Library(QnnpackLibrary):
     [create|setup]_squeeze_excite[_status], and attach_output_table[_status], and
     [create|setup]_fully_connected_nc_f32_qd8[_status], and create_fully_connected_nc_f32_qd8_qc4w[_status],
     and create_fully_connected_nc_f32_qd8_qb4w[_status], and create_fully_connected_nc_f32_qd8_qb4w_zp[_status],
-    and create_fully_connected_nc_f32_qd8_qb4w_b32[_status].
+    and create_fully_connected_nc_f32_qd8_qb4w_b32[_status], and create_fully_connected_nc_f32_qd8_mxfp4w[_status].
     """
 
     def __init__(self, path: str):

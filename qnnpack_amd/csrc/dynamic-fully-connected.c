@@ -1,12 +1,12 @@
 /*
- * dynamic-fully-connected.c -- qnnp_gfx950_create_fully_connected_nc_f32_qd8[_qc4w, _qb4w, _qb4w_zp, _qb4w_b32] / qnnp_gfx950_setup_fully_connected_nc_f32_qd8
+ * dynamic-fully-connected.c -- qnnp_gfx950_create_fully_connected_nc_f32_qd8[_qc4w, _qb4w, _qb4w_zp, _qb4w_b32, _mxfp4w] / qnnp_gfx950_setup_fully_connected_nc_f32_qd8
  * (include/qnnpack_gfx950_dynamic.h has the arithmetic and the statuses): float32 rows in, float32 rows out, each input row
  * quantized to its own range on the device and multiplied with int8 or 4-bit weights on the matrix cores.
  *
  * No reference counterpart. Create packs the weights into the fragment image of hip/qd8f32gemm.hip (4-bit weights: the
  * pair-fragment image of hip/qd8f32gemm4.hip; the operator remembers the width, nothing else differs) and uploads one table
  * entry per output channel -- for block-wise 4-bit scales also one per channel and block, the block table of hip/qd8f32gemm4b.hip, and with
- * per-block zero points the block table and the zero-point pair table of hip/qd8f32gemm4z.hip, for blocks of 32 the image and the two pair-indexed tables of hip/qd8f32gemm4s.hip -- (as per-channel.h does for the per-channel operators); setup follows quantize.c -- validation
+ * per-block zero points the block table and the zero-point pair table of hip/qd8f32gemm4z.hip, for blocks of 32 the image and the two pair-indexed tables of hip/qd8f32gemm4s.hip, for MXFP4 weights that image with the raw codes and the one table of hip/qd8f32gemm4m.hip -- (as per-channel.h does for the per-channel operators); setup follows quantize.c -- validation
  * in the documented order, every check before the operator changes -- and grows the one device scratch the operator owns
  * (as squeeze-excite.c owns its gate rows; freed by qnnp_delete_operator). The run is two launches, reached through
  * op->launch: the rows kernel of hip/f32qd8rows.hip into the scratch, then the GEMM or GEMV kernel out of it. The scratch
@@ -64,6 +64,13 @@ static int launch_dynamic_fully_connected(struct qnnp_operator* op, const void* 
     .output_min = op->f32_output_min,
     .output_max = op->f32_output_max,
   };
+  if (op->qd8_mxfp4 != 0) {
+    const struct qnnp_hip_qd8_mxfp4w_gemm_args mx_args = {
+      .gemm = gemm_args,
+      .block_table = (const int32_t*) op->d_qd8_blocks,
+    };
+    return qnnp_hip_qd8_mxfp4w_gemm_run(&mx_args, &op->kernel_name);
+  }
   if (op->qd8_block_size == 32) {
     const size_t scale_bytes = (size_t) op->n_pad * ((op->k_pad + 127u) / 128u) * 4 * sizeof(float);
     const struct qnnp_hip_qd8_qb4w_b32_gemm_args b32_args = {
@@ -261,14 +268,42 @@ static void fill_tables_b32(size_t k, size_t n, uint32_t n_pad, uint32_t k_pad4,
   }
 }
 
+/* Twice the value of an E2M1 code: sign in bit 3, magnitude index in bits 0 .. 2 into {0, 0.5, 1, 1.5, 2, 3, 4, 6} */
+static const int8_t mxfp4_w2[16] = { 0, 1, 2, 3, 4, 6, 8, 12, 0, -1, -2, -3, -4, -6, -8, -12 };
+
+/* The one table of the _mxfp4w create (hip/qnnp_hip.h), entry ((c / 16) * kpairs + kp) * 16 + c % 16: four int32 of
+ * 256 * wsum2 + e, wsum2 the block's sum of w2 (at most 12 * 32 in magnitude) and e its E8M0 byte; 128 (wsum2 0, the term's
+ * exponent 0) for padding channels and blocks past K. */
+static void fill_table_mxfp4w(size_t k, size_t n, uint32_t n_pad, uint32_t k_pad4, const uint8_t* kernel,
+                              const uint8_t* kernel_scales, int32_t* table)
+{
+  const size_t nblk = k / 32, kpairs = k_pad4 / 128;
+  for (size_t c = 0; c < n_pad; c++) {
+    for (size_t b = 0; b < kpairs * 4; b++) {
+      const size_t at = (((c / 16) * kpairs + b / 4) * 16 + c % 16) * 4 + b % 4;
+      table[at] = 128;
+      if (c < n && b < nblk) {
+        int32_t wsum2 = 0;
+        for (size_t i = b * 32; i < (b + 1) * 32; i++) {
+          wsum2 += mxfp4_w2[nibble_b32(kernel, 0, k, c, i)];
+        }
+        table[at] = 256 * wsum2 + (int32_t) kernel_scales[c * nblk + b];
+      }
+    }
+  }
+}
+
+/* `mxfp4`: the _mxfp4w create -- block_size is 32, `kernel` holds E2M1 codes, `kernel_scales` E8M0 bytes and there are no zero
+ * points; otherwise `kernel_scales` are floats */
 static enum qnnp_status create_dynamic_fully_connected(
-    size_t input_channels, size_t output_channels, size_t block_size, const void* kernel, uint32_t weight_bits,
-    const float* kernel_scales, const uint8_t* kernel_zero_points, const float* bias, float output_min, float output_max, qnnp_operator_t* fully_connected)
+    size_t input_channels, size_t output_channels, size_t block_size, const void* kernel, uint32_t weight_bits, int mxfp4,
+    const void* kernel_scales_any, const uint8_t* kernel_zero_points, const float* bias, float output_min, float output_max, qnnp_operator_t* fully_connected)
 {
   qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_dynamic_fully_connected, launch_dynamic_fully_connected);
   if (op == NULL) {
     return qnnp_status_out_of_memory;
   }
+  const float* kernel_scales = mxfp4 ? NULL : (const float*) kernel_scales_any;
   const uint32_t k_pad = ((uint32_t) input_channels + 63u) & ~63u;
   const uint32_t n_pad = ((uint32_t) output_channels + 15u) & ~15u;
   const uint32_t k_pad4 = ((uint32_t) input_channels + 127u) & ~127u;       /* whole K-tile pairs */
@@ -277,6 +312,7 @@ static enum qnnp_status create_dynamic_fully_connected(
   /* block-wise scales: one more table (with zero points: eight bytes per entry as well, and the pair table behind it);
    * without them a token byte, so that one test serves every allocation */
   const size_t b_bytes = block_size == 0 ? 1
+      : mxfp4 ? (size_t) n_pad * (k_pad4 / 128) * (4 * sizeof(int32_t))
       : block_size == 32 ? (size_t) n_pad * (k_pad4 / 128) * (4 * sizeof(float) + 4 * sizeof(int16_t))
       : (size_t) n_pad * (input_channels / block_size) * sizeof(struct qnnp_hip_qd8_block_entry)
           + (kernel_zero_points != NULL ? (size_t) n_pad * (k_pad4 / 128) * sizeof(uint16_t) : 0);
@@ -284,7 +320,8 @@ static enum qnnp_status create_dynamic_fully_connected(
   struct qnnp_hip_qd8_channel_entry* table = (struct qnnp_hip_qd8_channel_entry*) malloc(t_bytes);
   struct qnnp_hip_qd8_block_entry* blocks = (struct qnnp_hip_qd8_block_entry*) malloc(b_bytes);
   if (packed != NULL && table != NULL && blocks != NULL) {
-    const uint32_t flip = kernel_zero_points == NULL ? 8u : 0u;      /* block size 32 alone: signed nibbles become unsigned */
+    /* block size 32 alone: signed nibbles become unsigned; E2M1 codes travel as they are */
+    const uint32_t flip = kernel_zero_points == NULL && !mxfp4 ? 8u : 0u;
     if (block_size == 32) {
       pack_weights_qb4w_b32(input_channels, output_channels, k_pad4, n_pad, (const uint8_t*) kernel, flip, (uint8_t*) packed);
     } else if (weight_bits == 4) {
@@ -309,7 +346,11 @@ static enum qnnp_status create_dynamic_fully_connected(
     }
     op->d_weights = qnnp_upload(packed, w_bytes);
     op->d_qd8_channels = qnnp_upload(table, t_bytes);
-    if (block_size == 32) {
+    if (mxfp4) {
+      fill_table_mxfp4w(input_channels, output_channels, n_pad, k_pad4, (const uint8_t*) kernel,
+          (const uint8_t*) kernel_scales_any, (int32_t*) blocks);
+      op->d_qd8_blocks = qnnp_upload(blocks, b_bytes);
+    } else if (block_size == 32) {
       fill_tables_b32(input_channels, output_channels, n_pad, k_pad4, (const uint8_t*) kernel, flip, kernel_scales,
           kernel_zero_points, (float*) blocks);
       op->d_qd8_blocks = qnnp_upload(blocks, b_bytes);
@@ -339,7 +380,8 @@ static enum qnnp_status create_dynamic_fully_connected(
   op->n_pad = n_pad;
   op->qd8_weight_bits = weight_bits;
   op->qd8_block_size = (uint32_t) block_size;
-  op->qd8_zero_points = kernel_zero_points != NULL || block_size == 32;
+  op->qd8_zero_points = kernel_zero_points != NULL || (block_size == 32 && !mxfp4);
+  op->qd8_mxfp4 = mxfp4 ? 1 : 0;
   op->f32_output_min = output_min;
   op->f32_output_max = output_max;
   *fully_connected = op;
@@ -348,18 +390,21 @@ static enum qnnp_status create_dynamic_fully_connected(
 
 /* every create: the checks in the header's order, then the packing under the device. `blockwise`: 1 for the _qb4w and
  * _qb4w_zp creates and 2 for the _qb4w_b32 create (whose block_size is 32, the one value the other two refuse), with input_channels / block_size (rounded down, where the create is going to be refused) scales per channel, each
- * in [2^-16, 2^16]; otherwise block_size is 0 and there is one scale per channel in [2^-20, 2^20]. `zero_points`: the
+ * in [2^-16, 2^16], and 3 for the _mxfp4w create (block_size 32 as well; `kernel_scales` are then E8M0 BYTES e, scale 2^(e - 127): 255, the format's NaN, is invalid where a float scale is when it is no normal number above zero, and a byte outside [111, 143] = [2^-16, 2^16] is unsupported); otherwise block_size is 0 and there is one scale per channel in [2^-20, 2^20]. `zero_points`: the
  * _qb4w_zp create, with as many kernel_zero_points as scales, each at most 15; otherwise kernel_zero_points is NULL. */
 static enum qnnp_status create_checked(
     const char* function, size_t input_channels, size_t output_channels, int blockwise, size_t block_size, const void* kernel,
-    uint32_t weight_bits, const float* kernel_scales, int zero_points, const uint8_t* kernel_zero_points, const float* bias, float output_min, float output_max,
+    uint32_t weight_bits, const void* kernel_scales_any, int zero_points, const uint8_t* kernel_zero_points, const float* bias, float output_min, float output_max,
     qnnp_operator_t* fully_connected)
 {
+  const int mxfp4 = blockwise == 3;
+  const float* kernel_scales = mxfp4 ? NULL : (const float*) kernel_scales_any;
+  const uint8_t* e8m0 = mxfp4 ? (const uint8_t*) kernel_scales_any : NULL;
   enum qnnp_status status = qnnp_check_initialized(function);
   if (status != qnnp_status_success) {
     return status;
   }
-  if (input_channels == 0 || output_channels == 0 || kernel == NULL || kernel_scales == NULL || (blockwise && block_size == 0) ||
+  if (input_channels == 0 || output_channels == 0 || kernel == NULL || kernel_scales_any == NULL || (blockwise && block_size == 0) ||
       (zero_points && kernel_zero_points == NULL)) {
     qnnp_log_error("cannot create dynamic fully connected operator with %zu input and %zu output channels: channel counts, "
         "block size, kernel, kernel scales and kernel zero points may not be zero", input_channels, output_channels);
@@ -367,7 +412,13 @@ static enum qnnp_status create_checked(
   }
   const size_t scale_count = output_channels * (blockwise ? input_channels / block_size : 1);
   const float scale_min = blockwise ? 0x1.0p-16f : 0x1.0p-20f, scale_max = blockwise ? 0x1.0p+16f : 0x1.0p+20f;
-  for (size_t c = 0; c < scale_count; c++) {
+  for (size_t c = 0; mxfp4 && c < scale_count; c++) {
+    if (e8m0[c] == 255) {
+      qnnp_log_error("cannot create dynamic fully connected operator with E8M0 kernel scale %zu = 255: not a number", c);
+      return qnnp_status_invalid_parameter;
+    }
+  }
+  for (size_t c = 0; !mxfp4 && c < scale_count; c++) {
     if (!(kernel_scales[c] > 0.0f && isnormal(kernel_scales[c]))) {
       qnnp_log_error("cannot create dynamic fully connected operator with %.7g kernel scale %zu: a scale has to "
           "be a finite number above zero", kernel_scales[c], c);
@@ -393,13 +444,20 @@ static enum qnnp_status create_checked(
         "NaN and min may not exceed max", output_min, output_max);
     return qnnp_status_invalid_parameter;
   }
-  if (blockwise && ((blockwise == 2 ? block_size != 32 : (block_size != 64 && block_size != 128 && block_size != 256)) ||
+  if (blockwise && ((blockwise >= 2 ? block_size != 32 : (block_size != 64 && block_size != 128 && block_size != 256)) ||
       input_channels % block_size != 0)) {
     qnnp_log_error("cannot create dynamic fully connected operator with %zu input channels in blocks of %zu: a block is 64, "
         "128 or 256 wide (32 through the _qb4w_b32 create) and divides the input channels", input_channels, block_size);
     return qnnp_status_unsupported_parameter;
   }
-  for (size_t c = 0; c < scale_count; c++) {
+  for (size_t c = 0; mxfp4 && c < scale_count; c++) {
+    if (e8m0[c] < 111 || e8m0[c] > 143) {
+      qnnp_log_error("cannot create dynamic fully connected operator with E8M0 kernel scale %zu = %u: scale must be in "
+          "[111, 143] = [2^-16, 2^16] range", c, (unsigned) e8m0[c]);
+      return qnnp_status_unsupported_parameter;
+    }
+  }
+  for (size_t c = 0; !mxfp4 && c < scale_count; c++) {
     if (!(kernel_scales[c] >= scale_min && kernel_scales[c] <= scale_max)) {
       qnnp_log_error("cannot create dynamic fully connected operator with %.7g kernel scale %zu: scale must be "
           "in [%g, %g] range", kernel_scales[c], c, scale_min, scale_max);
@@ -419,8 +477,8 @@ static enum qnnp_status create_checked(
     return status;
   }
   return qnnp_leave_create(token, create_dynamic_fully_connected(
-      input_channels, output_channels, block_size, kernel, weight_bits, kernel_scales, kernel_zero_points, bias, output_min,
-      output_max, fully_connected));
+      input_channels, output_channels, block_size, kernel, weight_bits, mxfp4, kernel_scales_any, kernel_zero_points, bias,
+      output_min, output_max, fully_connected));
 }
 
 enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8(
@@ -505,6 +563,22 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_b32(
   (void) flags;
   return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_b32", input_channels, output_channels, 2, 32,
       kernel, 4, kernel_scales, kernel_zero_points != NULL, kernel_zero_points, bias, output_min, output_max, fully_connected);
+}
+
+enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_mxfp4w(
+    size_t input_channels,
+    size_t output_channels,
+    const uint8_t* kernel,
+    const uint8_t* kernel_scales,
+    const float* bias,
+    float output_min,
+    float output_max,
+    uint32_t flags,
+    qnnp_operator_t* fully_connected)
+{
+  (void) flags;
+  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_mxfp4w", input_channels, output_channels, 3, 32,
+      kernel, 4, kernel_scales, 0, NULL, bias, output_min, output_max, fully_connected);
 }
 
 static enum qnnp_status setup_dynamic_fully_connected(

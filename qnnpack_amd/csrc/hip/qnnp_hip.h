@@ -682,6 +682,25 @@ struct qnnp_hip_qd8_qb4w_b32_gemm_args {
   const int16_t* block_sums;      /* 8-byte aligned */
 };
 int qnnp_hip_qd8_qb4w_b32_gemm_run(const struct qnnp_hip_qd8_qb4w_b32_gemm_args* args, const char** kernel_name);
+/* MXFP4 weights: E2M1 codes in blocks of 32 K positions, one E8M0 scale 2^(e - 127) per block (qd8f32gemm4m.hip; the _mxfp4w
+ * create). k_pad is K (a multiple of 32) rounded up to 64. `packed_w` is the block-32 pair-fragment image above, holding the
+ * raw codes (sign in bit 3, magnitude index in bits 0 .. 2); code 0 where the channel or the K position is padding. The
+ * kernels turn a code into w2 = twice its value, an int8 in {0, +-1, +-2, +-3, +-4, +-6, +-8, +-12}, in registers. ONE
+ * table, [n_pad / 16][ceil(k_pad / 128)][16 channels], one entry per channel and pair, the pair's four blocks in K order:
+ *   block_table    four int32: 256 * wsum2 + e, wsum2 = sum_{k in block} w2[c][k] in [-384, 384] and e in [111, 143], so
+ *                  that e = v & 255 and wsum2 = v >> 8 (arithmetic); 128 for padding channels and blocks past K
+ * 16 bytes per channel and pair against 64 bytes of codes: 4 bytes per block, 0.625 bytes per weight in all (_qb4w_b32:
+ * 0.6875). Per output the kernels compute
+ *   t_b = ldexp((float) (L_b + (128 - zp_r) * wsum2), e - 128)      L_b = sum_{k in block} (q - 128) * w2: ONE 16x16x32 MFMA
+ *   ysum = ((0 + t_0) + t_1) + ...                                   ONE owner per output walks b upward
+ *   y = ysum * scale_r;  y = y + bias[c];  clamp
+ * Of `channel_table` only the bias is read.
+ * qd8_f32_mxfp4w_gemv_mfma_16 for rows <= 16, else qd8_f32_mxfp4w_gemm_mfma_128x128 */
+struct qnnp_hip_qd8_mxfp4w_gemm_args {
+  struct qnnp_hip_qd8_gemm_args gemm;
+  const int32_t* block_table;     /* 16-byte aligned */
+};
+int qnnp_hip_qd8_mxfp4w_gemm_run(const struct qnnp_hip_qd8_mxfp4w_gemm_args* args, const char** kernel_name);
 
 /* softargmax (q8softargmax.hip, linked into libqnnpack_gfx950.so only -- see the Makefile): replaces u8rmax_ukernel__sse2,
  * u8lut32norm_ukernel__scalar and the softargmax case of src/operator-run.c:625-637, 1091-1108. For each of `rows` rows

@@ -182,10 +182,14 @@ struct qnnp_operator {
    * qd8_block_size is 32 for the _qb4w_b32 create alone (qd8_zero_points is then 1: signed nibbles were turned into
    * unsigned ones with zero point 8): d_weights is the block-32 pair-fragment image of hip/qd8f32gemm4s.hip and d_qd8_blocks
    * its scale table ([n_pad / 16][k_pad4 / 128][16] of four floats) with the table of sums and zero points (four int16 per
-   * entry) behind it, and the second launch is that unit's. */
+   * entry) behind it, and the second launch is that unit's.
+   * qd8_mxfp4 is 1 for the _mxfp4w create alone (qd8_block_size is then 32 and qd8_zero_points 0): d_weights is that image
+   * holding raw E2M1 codes, d_qd8_blocks the one table of hip/qd8f32gemm4m.hip ([n_pad / 16][k_pad4 / 128][16] of four
+   * int32, 256 * wsum2 + e), and the second launch is that unit's. */
   uint32_t qd8_weight_bits;
   uint32_t qd8_block_size;
   uint32_t qd8_zero_points;
+  uint32_t qd8_mxfp4;
   void* d_qd8_channels;
   void* d_qd8_blocks;
   void* d_qd8_scratch;

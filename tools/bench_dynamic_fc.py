@@ -23,6 +23,11 @@ process -- the two operators in turn, --rounds times over; `qb4w_b32_over_qb4w_z
 `bytes_moved_ratio` the ratio of the bytes one run of either moves (device image, float rows in and out, quantized rows
 written and read).
 
+`--mxfp4w` times the MXFP4 operator (qnnp_gfx950_create_fully_connected_nc_f32_qd8_mxfp4w) against the `qb4w_b32` operator
+in its signed form on the same nibble bytes (read as E2M1 codes by the one, as signed nibbles by the other), power-of-two
+scales and tensors, in the same process -- the two operators in turn, --rounds times over; `mxfp4w_over_qb4w_b32` is a time
+ratio within the run and `bytes_moved_ratio` as above.
+
 Every operator is timed with qnnp_gfx950_time_operator_rotating over --sets pairs of input and output tensors (the
 launches of one sample recorded into a hipGraph, median of five samples), the five operators in turn, --rounds times
 over; the median round is reported with the spread between rounds, (max - min) / median. The chain's figure is the sum
@@ -30,7 +35,7 @@ of its three operators' medians: kernel time without the gaps between launches, 
 rotate; the weights of one operator cannot, so at small batches they are served by the 256 MiB last-level cache and
 `weights_gb_s` (weight bytes / time) is a cache figure wherever the image fits there, not an HBM figure.
 
-    python tools/bench_dynamic_fc.py [--qb4w | --qb4w-zp | --qb4w-b32] [--shapes 1x4096x4096,...] [--sets 4] [--iters 20] [--rounds 5] [--json out.json]
+    python tools/bench_dynamic_fc.py [--qb4w | --qb4w-zp | --qb4w-b32 | --mxfp4w] [--shapes 1x4096x4096,...] [--sets 4] [--iters 20] [--rounds 5] [--json out.json]
 """
 import argparse
 import json
@@ -179,6 +184,50 @@ def qb4w_b32_rows(lib, args, shapes, rng, gen, np, torch):
     return rows_out
 
 
+def mxfp4w_rows(lib, args, shapes, rng, gen, np, torch):
+    """one record per shape: qb4w_b32 (signed form) and mxfp4w on the same nibble bytes, whole operators, alternating"""
+    rows_out, inf = [], float("inf")
+    for k, n in dict.fromkeys((k, n) for _, k, n in shapes):        # operators are made once per weight shape
+        nibbles = rng.integers(0, 16, size=(n, k), dtype=np.uint8)
+        packed = nibbles[:, 0::2] | (nibbles[:, 1::2] << 4)
+        del nibbles
+        bias = rng.standard_normal(n).astype(np.float32)
+        exponents = rng.integers(118, 123, size=(n, k // 32), dtype=np.uint8)          # 2^-9 .. 2^-5: the range of the float scales
+        scales = np.ldexp(np.float32(1), exponents.astype(np.int32) - 127).astype(np.float32)
+        ops = {"qb4w_b32": lib.create_fully_connected_nc_f32_qd8_qb4w_b32(k, n, packed, scales, None, bias, -inf, inf),
+               "mxfp4w": lib.create_fully_connected_nc_f32_qd8_mxfp4w(k, n, packed, exponents, bias, -inf, inf)}
+        # device bytes per weight: nibbles + tables (6 bytes per block of 32; 4 bytes per block of 32)
+        image = {"qb4w_b32": 0.5 + 6 / 32, "mxfp4w": 0.5 + 4 / 32}
+        try:
+            for batch in [b for b, kk, nn in shapes if (kk, nn) == (k, n)]:
+                x = [torch.randn(batch * k, dtype=torch.float32, device="cuda", generator=gen) for _ in range(args.sets)]
+                y = [torch.empty(batch * n, dtype=torch.float32, device="cuda") for _ in range(args.sets)]
+                for op in ops.values():
+                    lib.setup_fully_connected_nc_f32_qd8(op, batch, x[0], k, y[0], n)
+                    lib.run_operator(op)
+                t = {key: [] for key in ops}
+                for _ in range(args.rounds):
+                    for key, op in ops.items():
+                        t[key].append(lib.time_operator_rotating(op, x, y, args.warmup, args.iters))
+                us = {key: statistics.median(v) * 1e3 for key, v in t.items()}
+                # bytes one run moves: the image once, the float rows in, the quantized rows out and in again, the float rows out
+                moved = {key: n * k * image[key] + batch * (4 * k + 2 * k + 4 * n) for key in ops}
+                row = {"batch": batch, "k": k, "n": n,
+                       "us": {key: round(v, 2) for key, v in us.items()},
+                       "spread": {key: round((max(v) - min(v)) / statistics.median(v), 3) for key, v in t.items()},
+                       "kernels": {key: lib.operator_kernel(op) for key, op in ops.items()},
+                       "image_mib": {key: round(n * k * image[key] / 2 ** 20, 1) for key in ops},
+                       "mxfp4w_over_qb4w_b32": round(us["mxfp4w"] / us["qb4w_b32"], 3),
+                       "bytes_moved_ratio": round(moved["mxfp4w"] / moved["qb4w_b32"], 3),
+                       "sets": args.sets, "rounds": args.rounds, "launches_per_sample": args.iters}
+                rows_out.append(row)
+                print(json.dumps(row), flush=True)
+        finally:
+            for op in ops.values():
+                lib.delete_operator(op)
+    return rows_out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--qb4w", action="store_true", help="time the block-wise 4-bit operator against the qc4w one instead")
@@ -186,6 +235,8 @@ def main():
                     help="time the block-wise 4-bit operator with zero points against the one without instead")
     ap.add_argument("--qb4w-b32", action="store_true",
                     help="time the 4-bit operator with blocks of 32 against the zero-point one at block size 64 instead")
+    ap.add_argument("--mxfp4w", action="store_true",
+                    help="time the MXFP4 operator against the signed 4-bit operator with blocks of 32 instead")
     ap.add_argument("--shapes", default=None, help="BATCHxKxN,... instead of the built-in list")
     ap.add_argument("--sets", type=int, default=4)
     ap.add_argument("--iters", type=int, default=20)
@@ -214,7 +265,9 @@ def main():
         rows_out += qb4w_zp_rows(lib, args, shapes, rng, gen, np, torch)
     if args.qb4w_b32:
         rows_out += qb4w_b32_rows(lib, args, shapes, rng, gen, np, torch)
-    for batch, k, n in ([] if args.qb4w or args.qb4w_zp or args.qb4w_b32 else shapes):
+    if args.mxfp4w:
+        rows_out += mxfp4w_rows(lib, args, shapes, rng, gen, np, torch)
+    for batch, k, n in ([] if args.qb4w or args.qb4w_zp or args.qb4w_b32 or args.mxfp4w else shapes):
         kernel = rng.integers(-128, 128, size=(n, k), dtype=np.int8)
         scales = rng.uniform(0.005, 0.02, size=n).astype(np.float32)
         bias = rng.standard_normal(n).astype(np.float32)
