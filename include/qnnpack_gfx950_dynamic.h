@@ -333,6 +333,72 @@ enum qnnp_status qnnp_gfx950_setup_fully_connected_nc_f32_qd8(
     float* output,
     size_t output_stride);
 
+/*
+ * The GROUPED operator with MXFP4 weights, for the expert matrices of a mixture-of-experts layer: `groups` weight sets of
+ * the _mxfp4w kind in ONE operator, and per output row an id that says which set multiplies it. The ids live in device
+ * memory and are read BY THE DEVICE WHEN THE OPERATOR RUNS: a router's choice needs no read-back, no gather, no launch per
+ * expert, and the run can be captured in a graph.
+ *
+ * `kernel`, `kernel_scales` and `bias` are those of the _mxfp4w create, `groups` of them one behind the other. Setup takes
+ * batch_size input rows (tokens), `assignments` = A output rows per input row (the router's top-k) and group_ids
+ * [batch_size * A]; the output has R = batch_size * A rows, row j belonging to input row j / A.
+ *
+ * Definition (bit-exact, no tolerance). For j in [0, R) let g = group_ids[j], read at run time.
+ *   0 <= g < groups: output row j is what the _mxfp4w definition above gives for input row j / A with group g's codes, scales
+ *       and bias: the row quantization, the exact block sums acc_b, the terms t_b, the float32 chain over b in ascending order
+ *       and the finish, all unchanged. It equals the stand-alone _mxfp4w operator's result on that group's weights bit for bit.
+ *   any other g: the row is SKIPPED, no byte of output row j is written. Negative ids are the masked rows of a padded batch,
+ *       ids at or above `groups` the experts that live on another device.
+ * Only the bytes of group_ids at the moment of the run count: overwriting them and running again (or replaying a graph)
+ * routes the new way with no setup in between. They must not change WHILE a run is in flight.
+ *
+ * Create answers in the _mxfp4w order: invalid_parameter also for groups == 0 (with the zero channel counts),
+ * unsupported_parameter also for groups > 1024 (with the other limits, so behind the scale checks, which run over every
+ * group, as the bias check does).
+ *
+ * Setup follows qnnp_gfx950_setup_fully_connected_nc_f32_qd8, which refuses a grouped handle as this one refuses any other
+ * (invalid_parameter). batch_size == 0 succeeds and the run does nothing. invalid_parameter: a NULL tensor or group_ids,
+ * assignments == 0, a tensor or group_ids that is not 4-byte aligned, a stride below the channel count, an output whose byte
+ * span shares a byte with the input's or with that of group_ids, a tensor or group_ids that is not memory of the operator's
+ * device (host memory included: the device reads the ids, and a staged output could not leave skipped rows alone), a call
+ * inside a capture. unsupported_parameter: assignments > 8, R >= 2^20, more than 2^31 bytes of quantized input rows
+ * (batch_size * K rounded up to 64: a gathered row is addressed by a 32-bit offset), a launch grid beyond 2^31 - 1
+ * workgroups; these are answered from the sizes alone, before the spans are formed or a pointer is looked at. A refused setup
+ * leaves the previous one runnable.
+ *
+ * A run is three launches (hip/qd8f32gemm4g.hip). The row kernel above over the batch_size INPUT rows: a token routed to
+ * four experts is quantized once. qd8_grouped_plan, one workgroup: a histogram of the ids, a prefix sum, the permutation of
+ * the rows bucketed by group, one tile entry per H rows of a group, and the number of tiles. The product kernel, on a grid
+ * fixed at setup from T = floor(R / H) + min(groups, R) row tiles, which is at least the number any routing needs (every
+ * group with a row adds at most one partial tile); workgroups past the device's tile count leave at once. Its rows are
+ * gathered through the permutation and its results scattered to their output rows. qnnp_gfx950_operator_kernel names it:
+ *     qd8_f32_mxfp4w_grouped_mfma_16        R <= 16 * groups   (H = 16)
+ *     qd8_f32_mxfp4w_grouped_mfma_128x128   otherwise          (H = 128; no scratch memory)
+ * At a mean of 16 rows per group or fewer a 128-row tile is at least 7 / 8 padding. The handle is run, captured, named
+ * (qnnp_gfx950_dynamic_rows_kernel too) and deleted like the others. The scratch grows by 4 bytes per output row and 16 per tile.
+ */
+enum qnnp_status qnnp_gfx950_create_grouped_fully_connected_nc_f32_qd8_mxfp4w(
+    size_t groups,                       /* 1 .. 1024 */
+    size_t input_channels,               /* a multiple of 32, <= 32768 */
+    size_t output_channels,              /* < 2^24 */
+    const uint8_t* kernel,               /* [groups][output_channels][input_channels / 2], the _mxfp4w code layout, host */
+    const uint8_t* kernel_scales,        /* [groups][output_channels][input_channels / 32]: E8M0, e in [111, 143], host */
+    const float* bias,                   /* [groups][output_channels] float32, host; NULL means all zero */
+    float output_min,
+    float output_max,
+    uint32_t flags,
+    qnnp_operator_t* fully_connected);
+
+enum qnnp_status qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8(
+    qnnp_operator_t fully_connected,
+    size_t batch_size,                   /* input rows */
+    size_t assignments,                  /* A = groups per input row, 1 .. 8 */
+    const float* input,                  /* [batch_size] rows of input_channels floats, device */
+    size_t input_stride,                 /* in elements */
+    const int32_t* group_ids,            /* [batch_size * A], device; read when the operator runs */
+    float* output,                       /* [batch_size * A] rows of output_channels floats, device */
+    size_t output_stride);
+
 /* Name of the row kernel the operator's last run launched in front of the kernel qnnp_gfx950_operator_kernel names
  * (static string), or NULL: before the first run, or for a handle of another kind. */
 const char* qnnp_gfx950_dynamic_rows_kernel(qnnp_operator_t fully_connected);

@@ -66,6 +66,8 @@ extern "C" {
  *                        kernel kept for such shapes (A/B): any window, stride and base address, >= 4 channels, a channel pad of
  *                        whole dwords and 32-bit offsets; unsupported_parameter otherwise (never the LDS or byte-per-thread kernel)
  *                    (1 keeps the byte-per-thread direct kernel; auto takes its four-channel flavour for C >= 4 and windows other than 3x3)
+ *   "qd8_grouped_kernel": the grouped dynamically quantized fully connected operator (qnnpack_gfx950_dynamic.h), read at
+ *                    setup: 0 = auto (by rows and groups), 1 = qd8_f32_mxfp4w_grouped_mfma_16, 2 = ..._grouped_mfma_128x128
  * Unknown family or code -> invalid_parameter. 0 = the automatic choice, always. */
 enum qnnp_status qnnp_gfx950_test_force_kernel(const char* family, int code);
 

@@ -316,6 +316,17 @@ DYNAMIC_API = (
             "`kernel_scales` output_channels x input_channels / 32 E8M0 bytes e (scale 2^(e - 127), e in [111, 143]); set it up "
             "with setup_fully_connected_nc_f32_qd8"),
     _op("qnnp_gfx950_setup_fully_connected_nc_f32_qd8", _SETUP_NC, IF_PRESENT),
+    _op("qnnp_gfx950_create_grouped_fully_connected_nc_f32_qd8_mxfp4w",
+        "size_t groups, size_t input_channels, size_t output_channels, u8[] kernel, u8[] kernel_scales, f32[] bias, "
+        "f32 output_min, f32 output_max, u32 flags=0, out fully_connected", IF_PRESENT,
+        doc="`groups` _mxfp4w weight sets in one operator (mixture-of-experts): `kernel`, `kernel_scales` and `bias` carry a "
+            "leading groups axis; set it up with setup_grouped_fully_connected_nc_f32_qd8"),
+    # group_ids is an int32 DEVICE array the launches read, so it is passed like a tensor and not copied like a host array
+    _op("qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8",
+        "ptr op, size_t batch_size, size_t assignments, tensor input, size_t input_stride, tensor group_ids, "
+        "tensor output, size_t output_stride", IF_PRESENT,
+        doc="batch_size input rows, `assignments` output rows each; group_ids: int32 [batch_size * assignments] in device "
+            "memory, read when the operator runs"),
     _fn("qnnp_gfx950_dynamic_rows_kernel", "ptr op", IF_PRESENT, restype=c_char_p),
 )
 
@@ -422,7 +433,8 @@ class Gfx950Library(QnnpackLibrary):
     [create|setup]_squeeze_excite[_status], and attach_output_table[_status], and
     [create|setup]_fully_connected_nc_f32_qd8[_status], and create_fully_connected_nc_f32_qd8_qc4w[_status],
     and create_fully_connected_nc_f32_qd8_qb4w[_status], and create_fully_connected_nc_f32_qd8_qb4w_zp[_status],
-    and create_fully_connected_nc_f32_qd8_qb4w_b32[_status], and create_fully_connected_nc_f32_qd8_mxfp4w[_status].
+    and create_fully_connected_nc_f32_qd8_qb4w_b32[_status], and create_fully_connected_nc_f32_qd8_mxfp4w[_status],
+    and create_grouped_fully_connected_nc_f32_qd8_mxfp4w[_status] / setup_grouped_fully_connected_nc_f32_qd8[_status].
     """
 
     def __init__(self, path: str):
@@ -524,7 +536,8 @@ class Gfx950Library(QnnpackLibrary):
         self.lib.qnnp_gfx950_graph_destroy(graph)
 
     def set_option(self, key: str, value: int) -> None:
-        if key in ("gemm_kernel", "dwconv_kernel", "fused_kernel", "fused_rows", "fused_weights", "se_kernel"):
+        if key in ("gemm_kernel", "dwconv_kernel", "fused_kernel", "fused_rows", "fused_weights", "se_kernel",
+                   "qd8_grouped_kernel"):
             # kernel-forcing codes are test / measurement hooks (include/qnnpack_gfx950_test.h), not product options
             self._check("qnnp_gfx950_test_force_kernel", self.lib.qnnp_gfx950_test_force_kernel(key.encode(), value))
             return

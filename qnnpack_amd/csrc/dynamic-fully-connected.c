@@ -1,5 +1,5 @@
 /*
- * dynamic-fully-connected.c -- qnnp_gfx950_create_fully_connected_nc_f32_qd8[_qc4w, _qb4w, _qb4w_zp, _qb4w_b32, _mxfp4w] / qnnp_gfx950_setup_fully_connected_nc_f32_qd8
+ * dynamic-fully-connected.c -- qnnp_gfx950_create_fully_connected_nc_f32_qd8[_qc4w, _qb4w, _qb4w_zp, _qb4w_b32, _mxfp4w] / qnnp_gfx950_setup_fully_connected_nc_f32_qd8 and their GROUPED forms
  * (include/qnnpack_gfx950_dynamic.h has the arithmetic and the statuses): float32 rows in, float32 rows out, each input row
  * quantized to its own range on the device and multiplied with int8 or 4-bit weights on the matrix cores.
  *
@@ -11,6 +11,12 @@
  * (as squeeze-excite.c owns its gate rows; freed by qnnp_delete_operator). The run is two launches, reached through
  * op->launch: the rows kernel of hip/f32qd8rows.hip into the scratch, then the GEMM or GEMV kernel out of it. The scratch
  * needs no clearing when it grows: the rows kernel writes every byte the second launch reads, the K pad included.
+ *
+ * The GROUPED create (qnnp_gfx950_create_grouped_fully_connected_nc_f32_qd8_mxfp4w) keeps `groups` MXFP4 weight sets in one
+ * operator: that many images and tables, one behind the other, written by the packers of the _mxfp4w create. Its setup takes a
+ * device array of group ids, one per output row, which the launches read when they run; the scratch then also holds the
+ * permutation, the tile list and the tile count of hip/qd8f32gemm4g.hip, and the run is three launches: the rows kernel over
+ * the INPUT rows, that unit's plan kernel, and its product kernel on a grid fixed here, before any id is known.
  *
  * Not part of the seam library (oracle/Makefile).
  */
@@ -26,10 +32,15 @@
 #include "lifecycle.h"
 #include "log.h"
 #include "operator.h"
+#include "state.h"
 #include "upload.h"
 
 #define QNNP_QD8_MAX_INPUT_CHANNELS ((size_t) 32768)          /* K * 255 * 128 stays below 2^31 */
 #define QNNP_QD8_MAX_OUTPUT_CHANNELS ((size_t) 1 << 24)       /* exclusive */
+#define QNNP_QD8_MAX_GROUPS ((size_t) 1024)                   /* the plan kernel has one thread per group */
+#define QNNP_QD8_MAX_ASSIGNMENTS ((size_t) 8)
+#define QNNP_QD8_MAX_GROUPED_ROWS ((size_t) 1 << 20)          /* exclusive: output rows of the grouped operator */
+#define QNNP_QD8_MAX_GATHER_BYTES ((size_t) 1 << 31)          /* the grouped kernels' 32-bit offset of a gathered row */
 
 static int launch_dynamic_fully_connected(struct qnnp_operator* op, const void* input, const void* input2, void* output)
 {
@@ -101,6 +112,51 @@ static int launch_dynamic_fully_connected(struct qnnp_operator* op, const void* 
   }
   return op->qd8_weight_bits == 4 ? qnnp_hip_qd8_qc4w_gemm_run(&gemm_args, &op->kernel_name)
                                   : qnnp_hip_qd8_gemm_run(&gemm_args, &op->kernel_name);
+}
+
+/* the grouped operator: op->batch_size INPUT rows, qd8_assignments output rows each */
+static int launch_grouped_fully_connected(struct qnnp_operator* op, const void* input, const void* input2, void* output)
+{
+  (void) input2;
+  uint8_t* scratch = (uint8_t*) op->d_qd8_scratch;
+  struct qnnp_hip_qd8_row_entry* row_table = (struct qnnp_hip_qd8_row_entry*) (scratch + op->qd8_row_table_offset);
+  const struct qnnp_hip_qd8_rows_args rows_args = {
+    .input = (const float*) input,
+    .quantized = (int8_t*) scratch,
+    .row_table = row_table,
+    .rows = (uint32_t) op->batch_size,
+    .k = (uint32_t) op->group_input_channels,
+    .k_pad = op->k_pad,
+    .input_stride = op->input_pixel_stride,
+  };
+  const int rc = qnnp_hip_qd8_rows_run(&rows_args, &op->qd8_rows_kernel);
+  if (rc != QNNP_HIP_OK) {
+    return rc;
+  }
+  const struct qnnp_hip_qd8_mxfp4w_grouped_args args = {
+    .quantized = (const int8_t*) scratch,
+    .row_table = row_table,
+    .packed_w = (const int8_t*) op->d_weights,
+    .block_table = (const int32_t*) op->d_qd8_blocks,
+    .bias = (const float*) op->d_qd8_channels,
+    .group_ids = op->qd8_group_ids,
+    .perm = (uint32_t*) (scratch + op->qd8_perm_offset),
+    .tiles = (struct qnnp_hip_qd8_grouped_tile*) (scratch + op->qd8_tiles_offset),
+    .tile_count = (uint32_t*) (scratch + op->qd8_tile_count_offset),
+    .output = (float*) output,
+    .rows = (uint32_t) (op->batch_size * op->qd8_assignments),
+    .assignments = op->qd8_assignments,
+    .groups = op->qd8_groups,
+    .tile_rows = op->qd8_tile_rows,
+    .max_tiles = op->qd8_max_tiles,
+    .n = (uint32_t) op->channels,
+    .n_pad = op->n_pad,
+    .k_pad = op->k_pad,
+    .output_stride = op->output_pixel_stride,
+    .output_min = op->f32_output_min,
+    .output_max = op->f32_output_max,
+  };
+  return qnnp_hip_qd8_mxfp4w_grouped_run(&args, &op->kernel_name);
 }
 
 /* weight (c, k) of either kernel layout: int8 [n][k], or nibbles [n][(k + 1) / 2] with position k in bits
@@ -388,12 +444,79 @@ static enum qnnp_status create_dynamic_fully_connected(
   return qnnp_status_success;
 }
 
+/* The grouped create's device side: per group the image of pack_weights_qb4w_b32 and the table of fill_table_mxfp4w, group
+ * after group in ONE allocation each (64-bit offsets; the host holds one group's at a time), and the bias floats
+ * [groups][n_pad], zero in the padding. */
+static enum qnnp_status create_grouped_fully_connected(
+    size_t groups, size_t input_channels, size_t output_channels, const uint8_t* kernel, const uint8_t* kernel_scales,
+    const float* bias, float output_min, float output_max, qnnp_operator_t* fully_connected)
+{
+  qnnp_operator_t op = qnnp_allocate_operator(qnnp_ukernel_type_dynamic_fully_connected, launch_grouped_fully_connected);
+  if (op == NULL) {
+    return qnnp_status_out_of_memory;
+  }
+  const uint32_t k_pad = ((uint32_t) input_channels + 63u) & ~63u;
+  const uint32_t n_pad = ((uint32_t) output_channels + 15u) & ~15u;
+  const uint32_t k_pad4 = ((uint32_t) input_channels + 127u) & ~127u;
+  const size_t w_bytes = (size_t) n_pad * (k_pad4 / 2);
+  const size_t b_bytes = (size_t) n_pad * (k_pad4 / 128) * (4 * sizeof(int32_t));
+  const size_t bias_bytes = groups * n_pad * sizeof(float);
+  uint8_t* packed = (uint8_t*) malloc(w_bytes);
+  int32_t* blocks = (int32_t*) malloc(b_bytes);
+  float* biases = (float*) calloc(groups * n_pad, sizeof(float));
+  int uploaded = 0;
+  if (packed != NULL && blocks != NULL && biases != NULL) {
+    op->d_weights = qnnp_hip_alloc(groups * w_bytes);
+    op->d_qd8_blocks = qnnp_hip_alloc(groups * b_bytes);
+    uploaded = op->d_weights != NULL && op->d_qd8_blocks != NULL;
+    for (size_t g = 0; uploaded && g < groups; g++) {
+      const uint8_t* group_kernel = kernel + g * output_channels * (input_channels / 2);
+      pack_weights_qb4w_b32(input_channels, output_channels, k_pad4, n_pad, group_kernel, 0, packed);
+      fill_table_mxfp4w(input_channels, output_channels, n_pad, k_pad4, group_kernel,
+          kernel_scales + g * output_channels * (input_channels / 32), blocks);
+      for (size_t c = 0; bias != NULL && c < output_channels; c++) {
+        biases[g * n_pad + c] = bias[g * output_channels + c];
+      }
+      uploaded = qnnp_hip_h2d((uint8_t*) op->d_weights + g * w_bytes, packed, w_bytes, 0) == QNNP_HIP_OK &&
+          qnnp_hip_h2d((uint8_t*) op->d_qd8_blocks + g * b_bytes, blocks, b_bytes, 0) == QNNP_HIP_OK;
+    }
+    if (uploaded) {
+      op->d_qd8_channels = qnnp_upload(biases, bias_bytes);
+    }
+  } else {
+    qnnp_log_error("out of host memory: %zu bytes for packed weights", w_bytes + b_bytes + bias_bytes);
+  }
+  free(packed);
+  free(blocks);
+  free(biases);
+  if (!uploaded || op->d_qd8_channels == NULL) {
+    qnnp_log_error("cannot create grouped dynamic fully connected operator: %zu bytes of packed weights could not be placed "
+        "on the device", groups * (w_bytes + b_bytes) + bias_bytes);
+    qnnp_delete_operator(op);
+    return qnnp_status_out_of_memory;
+  }
+  op->group_input_channels = input_channels;
+  op->channels = output_channels;
+  op->k_pad = k_pad;
+  op->n_pad = n_pad;
+  op->qd8_weight_bits = 4;
+  op->qd8_block_size = 32;
+  op->qd8_mxfp4 = 1;
+  op->qd8_groups = (uint32_t) groups;
+  op->f32_output_min = output_min;
+  op->f32_output_max = output_max;
+  *fully_connected = op;
+  return qnnp_status_success;
+}
+
 /* every create: the checks in the header's order, then the packing under the device. `blockwise`: 1 for the _qb4w and
  * _qb4w_zp creates and 2 for the _qb4w_b32 create (whose block_size is 32, the one value the other two refuse), with input_channels / block_size (rounded down, where the create is going to be refused) scales per channel, each
  * in [2^-16, 2^16], and 3 for the _mxfp4w create (block_size 32 as well; `kernel_scales` are then E8M0 BYTES e, scale 2^(e - 127): 255, the format's NaN, is invalid where a float scale is when it is no normal number above zero, and a byte outside [111, 143] = [2^-16, 2^16] is unsupported); otherwise block_size is 0 and there is one scale per channel in [2^-20, 2^20]. `zero_points`: the
- * _qb4w_zp create, with as many kernel_zero_points as scales, each at most 15; otherwise kernel_zero_points is NULL. */
+ * _qb4w_zp create, with as many kernel_zero_points as scales, each at most 15; otherwise kernel_zero_points is NULL.
+ * `grouped`: the grouped _mxfp4w create, whose arrays hold `groups` weight sets one behind the other: every count below is
+ * taken `groups` times; otherwise groups is 1. */
 static enum qnnp_status create_checked(
-    const char* function, size_t input_channels, size_t output_channels, int blockwise, size_t block_size, const void* kernel,
+    const char* function, int grouped, size_t groups, size_t input_channels, size_t output_channels, int blockwise, size_t block_size, const void* kernel,
     uint32_t weight_bits, const void* kernel_scales_any, int zero_points, const uint8_t* kernel_zero_points, const float* bias, float output_min, float output_max,
     qnnp_operator_t* fully_connected)
 {
@@ -404,13 +527,13 @@ static enum qnnp_status create_checked(
   if (status != qnnp_status_success) {
     return status;
   }
-  if (input_channels == 0 || output_channels == 0 || kernel == NULL || kernel_scales_any == NULL || (blockwise && block_size == 0) ||
+  if (groups == 0 || input_channels == 0 || output_channels == 0 || kernel == NULL || kernel_scales_any == NULL || (blockwise && block_size == 0) ||
       (zero_points && kernel_zero_points == NULL)) {
     qnnp_log_error("cannot create dynamic fully connected operator with %zu input and %zu output channels: channel counts, "
         "block size, kernel, kernel scales and kernel zero points may not be zero", input_channels, output_channels);
     return qnnp_status_invalid_parameter;
   }
-  const size_t scale_count = output_channels * (blockwise ? input_channels / block_size : 1);
+  const size_t scale_count = groups * output_channels * (blockwise ? input_channels / block_size : 1);
   const float scale_min = blockwise ? 0x1.0p-16f : 0x1.0p-20f, scale_max = blockwise ? 0x1.0p+16f : 0x1.0p+20f;
   for (size_t c = 0; mxfp4 && c < scale_count; c++) {
     if (e8m0[c] == 255) {
@@ -432,7 +555,7 @@ static enum qnnp_status create_checked(
       return qnnp_status_invalid_parameter;
     }
   }
-  for (size_t c = 0; bias != NULL && c < output_channels; c++) {
+  for (size_t c = 0; bias != NULL && c < groups * output_channels; c++) {
     if (bias[c] != 0.0f && !isnormal(bias[c])) {
       qnnp_log_error("cannot create dynamic fully connected operator with %.7g bias of channel %zu: a bias has to be zero "
           "or a normal number", bias[c], c);
@@ -464,10 +587,12 @@ static enum qnnp_status create_checked(
       return qnnp_status_unsupported_parameter;
     }
   }
-  if (input_channels > QNNP_QD8_MAX_INPUT_CHANNELS || output_channels >= QNNP_QD8_MAX_OUTPUT_CHANNELS) {
-    qnnp_log_error("cannot create dynamic fully connected operator with %zu input and %zu output channels: at most %zu "
-        "input channels (the int32 accumulator) and fewer than %zu output channels", input_channels, output_channels,
-        QNNP_QD8_MAX_INPUT_CHANNELS, QNNP_QD8_MAX_OUTPUT_CHANNELS);
+  if (input_channels > QNNP_QD8_MAX_INPUT_CHANNELS || output_channels >= QNNP_QD8_MAX_OUTPUT_CHANNELS ||
+      groups > QNNP_QD8_MAX_GROUPS) {
+    qnnp_log_error("cannot create dynamic fully connected operator with %zu input and %zu output channels in %zu groups: at "
+        "most %zu input channels (the int32 accumulator), fewer than %zu output channels and at most %zu groups",
+        input_channels, output_channels, groups, QNNP_QD8_MAX_INPUT_CHANNELS, QNNP_QD8_MAX_OUTPUT_CHANNELS,
+        QNNP_QD8_MAX_GROUPS);
     return qnnp_status_unsupported_parameter;
   }
 
@@ -475,6 +600,10 @@ static enum qnnp_status create_checked(
   status = qnnp_enter_for_update(qnnp_hip_device(), qnnp_status_unsupported_hardware, &token);
   if (status != qnnp_status_success) {
     return status;
+  }
+  if (grouped) {
+    return qnnp_leave_create(token, create_grouped_fully_connected(groups, input_channels, output_channels,
+        (const uint8_t*) kernel, e8m0, bias, output_min, output_max, fully_connected));
   }
   return qnnp_leave_create(token, create_dynamic_fully_connected(
       input_channels, output_channels, block_size, kernel, weight_bits, mxfp4, kernel_scales_any, kernel_zero_points, bias,
@@ -493,7 +622,7 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8(
     qnnp_operator_t* fully_connected)
 {
   (void) flags;
-  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8", input_channels, output_channels, 0, 0, kernel, 8,
+  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8", 0, 1, input_channels, output_channels, 0, 0, kernel, 8,
       kernel_scales, 0, NULL, bias, output_min, output_max, fully_connected);
 }
 
@@ -509,7 +638,7 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qc4w(
     qnnp_operator_t* fully_connected)
 {
   (void) flags;
-  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qc4w", input_channels, output_channels, 0, 0, kernel, 4,
+  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qc4w", 0, 1, input_channels, output_channels, 0, 0, kernel, 4,
       kernel_scales, 0, NULL, bias, output_min, output_max, fully_connected);
 }
 
@@ -526,7 +655,7 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w(
     qnnp_operator_t* fully_connected)
 {
   (void) flags;
-  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w", input_channels, output_channels, 1, block_size,
+  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w", 0, 1, input_channels, output_channels, 1, block_size,
       kernel, 4, kernel_scales, 0, NULL, bias, output_min, output_max, fully_connected);
 }
 
@@ -544,7 +673,7 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_zp(
     qnnp_operator_t* fully_connected)
 {
   (void) flags;
-  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_zp", input_channels, output_channels, 1, block_size,
+  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_zp", 0, 1, input_channels, output_channels, 1, block_size,
       kernel, 4, kernel_scales, 1, kernel_zero_points, bias, output_min, output_max, fully_connected);
 }
 
@@ -561,7 +690,7 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_b32(
     qnnp_operator_t* fully_connected)
 {
   (void) flags;
-  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_b32", input_channels, output_channels, 2, 32,
+  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_qb4w_b32", 0, 1, input_channels, output_channels, 2, 32,
       kernel, 4, kernel_scales, kernel_zero_points != NULL, kernel_zero_points, bias, output_min, output_max, fully_connected);
 }
 
@@ -577,14 +706,31 @@ enum qnnp_status qnnp_gfx950_create_fully_connected_nc_f32_qd8_mxfp4w(
     qnnp_operator_t* fully_connected)
 {
   (void) flags;
-  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_mxfp4w", input_channels, output_channels, 3, 32,
+  return create_checked("qnnp_gfx950_create_fully_connected_nc_f32_qd8_mxfp4w", 0, 1, input_channels, output_channels, 3, 32,
       kernel, 4, kernel_scales, 0, NULL, bias, output_min, output_max, fully_connected);
+}
+
+enum qnnp_status qnnp_gfx950_create_grouped_fully_connected_nc_f32_qd8_mxfp4w(
+    size_t groups,
+    size_t input_channels,
+    size_t output_channels,
+    const uint8_t* kernel,
+    const uint8_t* kernel_scales,
+    const float* bias,
+    float output_min,
+    float output_max,
+    uint32_t flags,
+    qnnp_operator_t* fully_connected)
+{
+  (void) flags;
+  return create_checked("qnnp_gfx950_create_grouped_fully_connected_nc_f32_qd8_mxfp4w", 1, groups, input_channels,
+      output_channels, 3, 32, kernel, 4, kernel_scales, 0, NULL, bias, output_min, output_max, fully_connected);
 }
 
 static enum qnnp_status setup_dynamic_fully_connected(
     qnnp_operator_t op, size_t batch_size, const float* input, size_t input_stride, float* output, size_t output_stride)
 {
-  if (op->ukernel_type != qnnp_ukernel_type_dynamic_fully_connected) {
+  if (op->ukernel_type != qnnp_ukernel_type_dynamic_fully_connected || op->qd8_groups != 0) {
     return qnnp_status_invalid_parameter;
   }
   if (batch_size == 0) {
@@ -661,6 +807,127 @@ enum qnnp_status qnnp_gfx950_setup_fully_connected_nc_f32_qd8(
   }
   return qnnp_leave_setup(fully_connected, token,
       setup_dynamic_fully_connected(fully_connected, batch_size, input, input_stride, output, output_stride));
+}
+
+static inline size_t round_up_16(size_t bytes)
+{
+  return (bytes + 15) & ~(size_t) 15;
+}
+
+static enum qnnp_status setup_grouped_fully_connected(
+    qnnp_operator_t op, size_t batch_size, size_t assignments, const float* input, size_t input_stride,
+    const int32_t* group_ids, float* output, size_t output_stride)
+{
+  if (op->ukernel_type != qnnp_ukernel_type_dynamic_fully_connected || op->qd8_groups == 0) {
+    return qnnp_status_invalid_parameter;
+  }
+  if (batch_size == 0) {
+    op->batch_size = 0;
+    return qnnp_status_success;
+  }
+  const size_t input_channels = op->group_input_channels, output_channels = op->channels;
+  if (input == NULL || output == NULL || group_ids == NULL || assignments == 0) {
+    qnnp_log_error("cannot set up grouped dynamic fully connected operator: NULL tensor or group ids, or no assignments");
+    return qnnp_status_invalid_parameter;
+  }
+  if ((uintptr_t) input % sizeof(float) != 0 || (uintptr_t) output % sizeof(float) != 0 ||
+      (uintptr_t) group_ids % sizeof(int32_t) != 0) {
+    qnnp_log_error("cannot set up grouped dynamic fully connected operator: a tensor or the group ids are not 4-byte aligned");
+    return qnnp_status_invalid_parameter;
+  }
+  if (input_stride < input_channels || output_stride < output_channels) {
+    qnnp_log_error("cannot set up grouped dynamic fully connected operator: row stride smaller than the channel count");
+    return qnnp_status_invalid_parameter;
+  }
+  /* the limits, before any product of the sizes is formed and before anything is looked at */
+  if (assignments > QNNP_QD8_MAX_ASSIGNMENTS || batch_size >= QNNP_QD8_MAX_GROUPED_ROWS ||
+      batch_size * assignments >= QNNP_QD8_MAX_GROUPED_ROWS || batch_size * op->k_pad > QNNP_QD8_MAX_GATHER_BYTES) {
+    qnnp_log_error("cannot set up grouped dynamic fully connected operator with batch %zu and %zu assignments: at most %zu "
+        "assignments, fewer than %zu output rows and at most %zu bytes of quantized input rows", batch_size, assignments,
+        QNNP_QD8_MAX_ASSIGNMENTS, QNNP_QD8_MAX_GROUPED_ROWS, QNNP_QD8_MAX_GATHER_BYTES);
+    return qnnp_status_unsupported_parameter;
+  }
+  const size_t rows = batch_size * assignments;
+  /* H and the grid: by the sizes alone. At a mean of 16 rows per group or fewer a 128-row tile is at least 7 / 8 padding and
+   * the groups' weights are streamed once each, the 16-row kernel's regime. */
+  const int forced = qnnp_state.opt_qd8_grouped_kernel;
+  const uint32_t tile_rows = forced == 1 || (forced == 0 && rows <= 16 * (size_t) op->qd8_groups) ? 16 : 128;
+  const size_t max_tiles = rows / tile_rows + (op->qd8_groups < rows ? op->qd8_groups : rows);
+  const size_t tiles_n = tile_rows == 16 ? op->n_pad / 16 : (output_channels + 127) / 128;
+  if (max_tiles * tiles_n > (size_t) INT32_MAX) {
+    qnnp_log_error("cannot set up grouped dynamic fully connected operator: %zu x %zu tiles are outside the launch range",
+        max_tiles, tiles_n);
+    return qnnp_status_unsupported_parameter;
+  }
+  const size_t input_span = ((batch_size - 1) * input_stride + input_channels) * sizeof(float);
+  const size_t output_span = ((rows - 1) * output_stride + output_channels) * sizeof(float);
+  const size_t ids_span = rows * sizeof(int32_t);
+  if (qnnp_spans_overlap(input, input_span, output, output_span) || qnnp_spans_overlap(group_ids, ids_span, output, output_span)) {
+    qnnp_log_error("cannot set up grouped dynamic fully connected operator: the output overlaps the input or the group ids");
+    return qnnp_status_invalid_parameter;
+  }
+  /* all three in device memory: the ids are read by the launches, and an output staged through the device would bring
+   * back bytes for the rows that were skipped */
+  if (qnnp_hip_is_device_pointer(input) != 1 || qnnp_hip_is_device_pointer(output) != 1 ||
+      qnnp_hip_is_device_pointer(group_ids) != 1) {
+    qnnp_log_error("cannot set up grouped dynamic fully connected operator: the tensors and the group ids have to be memory "
+        "of the operator's device");
+    return qnnp_status_invalid_parameter;
+  }
+  /* the quantized rows, the row table, the permutation, the tile list (16-byte entries), the tile count */
+  const size_t row_table_offset = batch_size * op->k_pad;
+  const size_t perm_offset = row_table_offset + batch_size * sizeof(struct qnnp_hip_qd8_row_entry);
+  const size_t tiles_offset = round_up_16(perm_offset + rows * sizeof(uint32_t));
+  const size_t tile_count_offset = tiles_offset + max_tiles * sizeof(struct qnnp_hip_qd8_grouped_tile);
+  const size_t scratch_bytes = tile_count_offset + sizeof(uint32_t);
+
+  op->setup_valid = 0;   /* from here on the operator changes: until every allocation below has succeeded */
+  if (op->qd8_scratch_capacity < scratch_bytes) {
+    qnnp_hip_free(op->d_qd8_scratch);
+    op->qd8_scratch_capacity = 0;
+    op->d_qd8_scratch = qnnp_hip_alloc(scratch_bytes);
+    if (op->d_qd8_scratch == NULL) {
+      qnnp_log_error("failed to allocate %zu bytes of device scratch for the quantized rows and the plan", scratch_bytes);
+      return qnnp_status_out_of_memory;
+    }
+    op->qd8_scratch_capacity = scratch_bytes;
+  }
+  op->qd8_row_table_offset = row_table_offset;
+  op->qd8_perm_offset = perm_offset;
+  op->qd8_tiles_offset = tiles_offset;
+  op->qd8_tile_count_offset = tile_count_offset;
+  op->qd8_assignments = (uint32_t) assignments;
+  op->qd8_tile_rows = tile_rows;
+  op->qd8_max_tiles = (uint32_t) max_tiles;
+  op->qd8_group_ids = group_ids;
+  op->batch_size = batch_size;
+  op->input = input;
+  op->input_pixel_stride = input_stride;
+  op->output = output;
+  op->output_pixel_stride = output_stride;
+  op->input_span = input_span;
+  op->output_span = output_span;
+  return qnnp_bind_tensors(op, "qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8");
+}
+
+enum qnnp_status qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8(
+    qnnp_operator_t fully_connected,
+    size_t batch_size,
+    size_t assignments,
+    const float* input,
+    size_t input_stride,
+    const int32_t* group_ids,
+    float* output,
+    size_t output_stride)
+{
+  int token;
+  const enum qnnp_status status =
+      qnnp_enter_setup("qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8", fully_connected, &token);
+  if (status != qnnp_status_success) {
+    return status;
+  }
+  return qnnp_leave_setup(fully_connected, token, setup_grouped_fully_connected(
+      fully_connected, batch_size, assignments, input, input_stride, group_ids, output, output_stride));
 }
 
 const char* qnnp_gfx950_dynamic_rows_kernel(qnnp_operator_t fully_connected)

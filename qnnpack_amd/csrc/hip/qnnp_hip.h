@@ -701,6 +701,47 @@ struct qnnp_hip_qd8_mxfp4w_gemm_args {
   const int32_t* block_table;     /* 16-byte aligned */
 };
 int qnnp_hip_qd8_mxfp4w_gemm_run(const struct qnnp_hip_qd8_mxfp4w_gemm_args* args, const char** kernel_name);
+/* The GROUPED MXFP4 operator (qd8f32gemm4g.hip; the grouped create): `groups` weight sets, and output row j < rows is input
+ * row j / assignments times the weights of group group_ids[j], which the DEVICE reads when the launches run; an id outside
+ * [0, groups) leaves row j unwritten. `packed_w` is `groups` images as above, one behind the other, `block_table` as many
+ * tables, `bias` [groups][n_pad] floats. `quantized` and `row_table` hold rows / assignments rows, and
+ * (rows / assignments) * k_pad is at most 2^31: a gathered row is addressed by a 32-bit byte offset. Two launches:
+ *   qd8_grouped_plan    one workgroup: `perm`, the rows j with a valid id bucketed by group (rows entries, any order inside a
+ *       group); `tiles`, one entry {group, first position in perm, rows (1 .. tile_rows), 0} per tile_rows rows of a group; and
+ *       *tile_count. There are at most max_tiles = rows / tile_rows + min(groups, rows) tiles, whatever the ids.
+ *   the product kernel  max_tiles x column tiles workgroups, those at or past *tile_count leaving at once:
+ *       qd8_f32_mxfp4w_grouped_mfma_16        tile_rows 16,  a column tile is 16 channels
+ *       qd8_f32_mxfp4w_grouped_mfma_128x128   tile_rows 128, a column tile is 128 channels
+ * The caller chooses tile_rows (dynamic-fully-connected.c has the rule); kernel_name names the product kernel. */
+struct qnnp_hip_qd8_grouped_tile {
+  int32_t group;
+  uint32_t first;
+  uint32_t rows;
+  uint32_t zero;
+};
+struct qnnp_hip_qd8_mxfp4w_grouped_args {
+  const int8_t* quantized;        /* 16-byte aligned */
+  const struct qnnp_hip_qd8_row_entry* row_table;
+  const int8_t* packed_w;         /* 16-byte aligned */
+  const int32_t* block_table;     /* 16-byte aligned */
+  const float* bias;
+  const int32_t* group_ids;       /* [rows], 4-byte aligned, device memory */
+  uint32_t* perm;                 /* [rows] */
+  struct qnnp_hip_qd8_grouped_tile* tiles;   /* [max_tiles], 16-byte aligned */
+  uint32_t* tile_count;
+  float* output;
+  uint32_t rows;                  /* batch * assignments, < 2^20 */
+  uint32_t assignments;           /* 1 .. 8 */
+  uint32_t groups;                /* 1 .. 1024 */
+  uint32_t tile_rows;             /* 16 or 128 */
+  uint32_t max_tiles;
+  uint32_t n;
+  uint32_t n_pad;
+  uint32_t k_pad;
+  uint64_t output_stride;
+  float output_min, output_max;
+};
+int qnnp_hip_qd8_mxfp4w_grouped_run(const struct qnnp_hip_qd8_mxfp4w_grouped_args* args, const char** kernel_name);
 
 /* softargmax (q8softargmax.hip, linked into libqnnpack_gfx950.so only -- see the Makefile): replaces u8rmax_ukernel__sse2,
  * u8lut32norm_ukernel__scalar and the softargmax case of src/operator-run.c:625-637, 1091-1108. For each of `rows` rows

@@ -185,7 +185,19 @@ struct qnnp_operator {
    * entry) behind it, and the second launch is that unit's.
    * qd8_mxfp4 is 1 for the _mxfp4w create alone (qd8_block_size is then 32 and qd8_zero_points 0): d_weights is that image
    * holding raw E2M1 codes, d_qd8_blocks the one table of hip/qd8f32gemm4m.hip ([n_pad / 16][k_pad4 / 128][16] of four
-   * int32, 256 * wsum2 + e), and the second launch is that unit's. */
+   * int32, 256 * wsum2 + e), and the second launch is that unit's.
+   * qd8_groups is 0, or the number of weight sets of the GROUPED _mxfp4w create (qd8_mxfp4 is then 1): d_weights and
+   * d_qd8_blocks hold that many images and tables, one behind the other, and d_qd8_channels [groups][n_pad] bias FLOATS. Such
+   * an operator is set up by the grouped setup alone: batch_size counts INPUT rows, each of which has qd8_assignments output
+   * rows, qd8_group_ids is the caller's device array of batch_size * qd8_assignments ids, and the scratch also holds the
+   * permutation (at qd8_perm_offset), the tile list (qd8_tiles_offset, qd8_max_tiles entries of qd8_tile_rows rows) and
+   * the tile count (qd8_tile_count_offset) of hip/qd8f32gemm4g.hip. */
+  uint32_t qd8_groups;
+  uint32_t qd8_assignments;
+  uint32_t qd8_tile_rows;
+  uint32_t qd8_max_tiles;
+  const int32_t* qd8_group_ids;
+  size_t qd8_perm_offset, qd8_tiles_offset, qd8_tile_count_offset;
   uint32_t qd8_weight_bits;
   uint32_t qd8_block_size;
   uint32_t qd8_zero_points;

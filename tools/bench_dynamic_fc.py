@@ -28,6 +28,15 @@ in its signed form on the same nibble bytes (read as E2M1 codes by the one, as s
 scales and tensors, in the same process -- the two operators in turn, --rounds times over; `mxfp4w_over_qb4w_b32` is a time
 ratio within the run and `bytes_moved_ratio` as above.
 
+`--grouped` times the GROUPED MXFP4 operator (qnnp_gfx950_create_grouped_fully_connected_nc_f32_qd8_mxfp4w: three launches,
+the routing read on the device) against what a caller could do before it: one `_mxfp4w` operator per group, each set up on its
+own PRE-GATHERED rows, run back to back. The read-back of the routing, the gather and the scatter that this needs are NOT
+timed, and its launches are replayed from a graph without host gaps: both favour the per-group chain. Shapes are
+GROUPSxBATCHxAxKxN; every token takes A distinct groups, uniformly at random. Either side is one run_operator pass recorded
+into a hipGraph and timed with qnnp_gfx950_graph_time (median of five samples of --iters replays), the two in turn, --rounds
+times over. `--crossover` adds, for the first shape's groups, K and N, both product kernels FORCED (the test header's
+"qd8_grouped_kernel") at R = 8, 16 and 32 times the group count: the probe of the rule R <= 16 * groups.
+
 Every operator is timed with qnnp_gfx950_time_operator_rotating over --sets pairs of input and output tensors (the
 launches of one sample recorded into a hipGraph, median of five samples), the five operators in turn, --rounds times
 over; the median round is reported with the spread between rounds, (max - min) / median. The chain's figure is the sum
@@ -35,7 +44,7 @@ of its three operators' medians: kernel time without the gaps between launches, 
 rotate; the weights of one operator cannot, so at small batches they are served by the 256 MiB last-level cache and
 `weights_gb_s` (weight bytes / time) is a cache figure wherever the image fits there, not an HBM figure.
 
-    python tools/bench_dynamic_fc.py [--qb4w | --qb4w-zp | --qb4w-b32 | --mxfp4w] [--shapes 1x4096x4096,...] [--sets 4] [--iters 20] [--rounds 5] [--json out.json]
+    python tools/bench_dynamic_fc.py [--qb4w | --qb4w-zp | --qb4w-b32 | --mxfp4w | --grouped [--crossover]] [--shapes 1x4096x4096,...] [--sets 4] [--iters 20] [--rounds 5] [--json out.json]
 """
 import argparse
 import json
@@ -228,6 +237,86 @@ def mxfp4w_rows(lib, args, shapes, rng, gen, np, torch):
     return rows_out
 
 
+# (groups, batch, A, K, N): a small and a large mixture-of-experts layer at decode batches, and two at prefill sizes
+GROUPED_SHAPES = [(32, 16, 4, 2880, 2880), (128, 64, 4, 2880, 2880), (32, 4096, 4, 2880, 5760), (8, 4096, 2, 4096, 14336)]
+
+
+def graph_us(lib, ops, args):
+    """one pass over `ops` recorded into a graph; microseconds per replay"""
+    lib.graph_begin()
+    try:
+        for op in ops:
+            lib.run_operator(op)
+    finally:
+        graph = lib.graph_end()
+    try:
+        return lib.graph_time(graph, args.warmup, args.iters) * 1e3
+    finally:
+        lib.graph_destroy(graph)
+
+
+def grouped_rows(lib, args, shapes, rng, gen, np, torch):
+    """one record per shape: the grouped operator and the per-group chain on the same weights and routing, alternating; with
+    --crossover also the two forced kernels at R = 8, 16 and 32 times the group count"""
+    rows_out, inf = [], float("inf")
+    probes = [(shapes[0][0], shapes[0][0] * m // 4, 4, shapes[0][3], shapes[0][4], forced)
+              for m in (8, 16, 32) for forced in (1, 2)] if args.crossover else []
+    weights = {}
+    for groups, batch, a, k, n, forced in [s + (0,) for s in shapes] + probes:
+        if (groups, k, n) not in weights:
+            weights.clear()                     # one set of weights at a time on the host
+            weights[groups, k, n] = (rng.integers(0, 256, size=(groups, n, k // 2), dtype=np.uint8),
+                                     rng.integers(118, 123, size=(groups, n, k // 32), dtype=np.uint8),
+                                     rng.standard_normal((groups, n)).astype(np.float32))
+        packed, exponents, bias = weights[groups, k, n]
+        rows = batch * a
+        ids = np.argsort(rng.random((batch, groups)), axis=1)[:, :a].astype(np.int32).reshape(-1)     # A distinct groups per token
+        d_ids = torch.from_numpy(ids).cuda()
+        x = torch.randn(batch * k, dtype=torch.float32, device="cuda", generator=gen)
+        y = torch.empty(rows * n, dtype=torch.float32, device="cuda")
+        lib.set_option("qd8_grouped_kernel", forced)
+        ops = {"grouped": [lib.create_grouped_fully_connected_nc_f32_qd8_mxfp4w(groups, k, n, packed, exponents, bias, -inf, inf)]}
+        keep = []
+        try:
+            lib.setup_grouped_fully_connected_nc_f32_qd8(ops["grouped"][0], batch, a, x, k, d_ids, y, n)
+            lib.set_option("qd8_grouped_kernel", 0)
+            counts = np.bincount(ids, minlength=groups)
+            if not forced:
+                ops["per_group"] = []
+                for g in np.flatnonzero(counts):
+                    op = lib.create_fully_connected_nc_f32_qd8_mxfp4w(k, n, packed[g], exponents[g], bias[g], -inf, inf)
+                    ops["per_group"].append(op)
+                    keep.append((torch.randn(int(counts[g]) * k, dtype=torch.float32, device="cuda", generator=gen),
+                                 torch.empty(int(counts[g]) * n, dtype=torch.float32, device="cuda")))
+                    lib.setup_fully_connected_nc_f32_qd8(op, int(counts[g]), keep[-1][0], k, keep[-1][1], n)
+            for side in ops.values():
+                for op in side:
+                    lib.run_operator(op)
+            t = {key: [] for key in ops}
+            for _ in range(args.rounds):
+                for key, side in ops.items():
+                    t[key].append(graph_us(lib, side, args))
+            us = {key: statistics.median(v) for key, v in t.items()}
+            row = {"groups": groups, "batch": batch, "assignments": a, "rows": rows, "k": k, "n": n, "forced": forced,
+                   "us": {key: round(v, 2) for key, v in us.items()},
+                   "spread": {key: round((max(v) - min(v)) / statistics.median(v), 3) for key, v in t.items()},
+                   "kernel": lib.operator_kernel(ops["grouped"][0]),
+                   "live_groups": int(np.count_nonzero(counts)), "largest_group": int(counts.max()),
+                   "image_mib": round(groups * n * k * (0.5 + 4 / 32) / 2 ** 20, 1),
+                   "rounds": args.rounds, "replays_per_sample": args.iters}
+            if not forced:
+                row["per_group_kernels"] = sorted({lib.operator_kernel(op) for op in ops["per_group"]})
+                row["per_group_over_grouped"] = round(us["per_group"] / us["grouped"], 3)
+            rows_out.append(row)
+            print(json.dumps(row), flush=True)
+        finally:
+            lib.set_option("qd8_grouped_kernel", 0)
+            for side in ops.values():
+                for op in side:
+                    lib.delete_operator(op)
+    return rows_out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--qb4w", action="store_true", help="time the block-wise 4-bit operator against the qc4w one instead")
@@ -237,6 +326,9 @@ def main():
                     help="time the 4-bit operator with blocks of 32 against the zero-point one at block size 64 instead")
     ap.add_argument("--mxfp4w", action="store_true",
                     help="time the MXFP4 operator against the signed 4-bit operator with blocks of 32 instead")
+    ap.add_argument("--grouped", action="store_true",
+                    help="time the grouped MXFP4 operator against one MXFP4 operator per group instead (shapes: GROUPSxBATCHxAxKxN)")
+    ap.add_argument("--crossover", action="store_true", help="with --grouped: both product kernels forced around R = 16 * groups")
     ap.add_argument("--shapes", default=None, help="BATCHxKxN,... instead of the built-in list")
     ap.add_argument("--sets", type=int, default=4)
     ap.add_argument("--iters", type=int, default=20)
@@ -259,7 +351,7 @@ def main():
     rng = np.random.default_rng(23)
     gen = torch.Generator(device="cuda").manual_seed(23)
 
-    shapes = SHAPES if args.shapes is None else [tuple(int(v) for v in item.split("x")) for item in args.shapes.split(",")]
+    shapes = (GROUPED_SHAPES if args.grouped else SHAPES) if args.shapes is None else [tuple(int(v) for v in item.split("x")) for item in args.shapes.split(",")]
     rows_out = qb4w_rows(lib, args, shapes, rng, gen, np, torch) if args.qb4w else []
     if args.qb4w_zp:
         rows_out += qb4w_zp_rows(lib, args, shapes, rng, gen, np, torch)
@@ -267,7 +359,9 @@ def main():
         rows_out += qb4w_b32_rows(lib, args, shapes, rng, gen, np, torch)
     if args.mxfp4w:
         rows_out += mxfp4w_rows(lib, args, shapes, rng, gen, np, torch)
-    for batch, k, n in ([] if args.qb4w or args.qb4w_zp or args.qb4w_b32 or args.mxfp4w else shapes):
+    if args.grouped:
+        rows_out += grouped_rows(lib, args, shapes, rng, gen, np, torch)
+    for batch, k, n in ([] if args.qb4w or args.qb4w_zp or args.qb4w_b32 or args.mxfp4w or args.grouped else shapes):
         kernel = rng.integers(-128, 128, size=(n, k), dtype=np.int8)
         scales = rng.uniform(0.005, 0.02, size=n).astype(np.float32)
         bias = rng.standard_normal(n).astype(np.float32)
