@@ -399,6 +399,113 @@ enum qnnp_status qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8(
     float* output,                       /* [batch_size * A] rows of output_channels floats, device */
     size_t output_stride);
 
+/*
+ * A GATED input (SwiGLU) for every handle above. A gated MLP, dense or expert, is two layers: the first produces gate and up
+ * columns, the second consumes act(gate) * up. These two setups are the second layer's: they take the first layer's output as
+ * it is, and the row kernel computes the product h while it reads, in registers, so that h is never written as floats and no
+ * element-wise launch stands between the two matrix products. No new create: the first setup takes a handle of any of the
+ * six plain creates, the second a handle of the grouped create.
+ *
+ * Input layout. With K = input_channels an input row holds 2 K floats: element 2 k is the gate g and element 2 k + 1 the up
+ * value u of position k -- interleaved, not two halves (the column order of the MXFP4 mixture-of-experts checkpoints; a caller
+ * with separate gate and up matrices interleaves their ROWS when creating the first layer). input_stride >= 2 K.
+ *   SiLU-gated (Llama, Mixtral, Qwen):          alpha = 1,      limit = +INFINITY, up_shift = 0
+ *   the clamped form of the MXFP4 checkpoints:  alpha = 1.702f, limit = 7,         up_shift = 1
+ *
+ * Definition (bit-exact, no tolerance). All arithmetic is float32, every operation rounded once, nothing fused. Per row r and
+ * position k:
+ *   gc = g > limit ? limit : g
+ *   uc = u > limit ? limit : (u < -limit ? -limit : u)
+ *   z  = alpha * gc
+ *   y  = (-|z| < -80.0f) ? -80.0f : -|z|
+ *   n  = rintf(y * 0x1.715476p+0f)
+ *   r1 = y - n * 0x1.62E400p-1f            the product is exact: |n| <= 116 and the constant has 15 significant bits
+ *   r2 = r1 - n * 0x1.7F7D1Cp-20f
+ *   p  = 0x1.0F9F9Cp-7f
+ *   p  = p * r2;  p = p + 0x1.573A1Ap-5f
+ *   p  = p * r2;  p = p + 0x1.555A80p-3f
+ *   p  = p * r2;  p = p + 0x1.FFFDC6p-2f
+ *   p  = p * r2;  p = p + 0x1.FFFFF6p-1f
+ *   p  = p * r2;  p = p + 1.0f
+ *   e  = p * 2^n                           2^n from the bits (n + 127) << 23; n >= -116, so e is a normal number
+ *   d  = 1.0f + e;  q = e / d              an IEEE division
+ *   s  = z > 0 ? 1.0f - q : q              the sigmoid of z
+ *   a  = gc * s;          if |a| <= 0x1p-126f: a = copysignf(0, a)      (<=, not <: step a of the denormal argument)
+ *   b  = uc + up_shift;   if |b| < 0x1p-126f:  b = copysignf(0, b)
+ *   h[r][k] = a * b
+ * If g or u is NaN, h is NaN (NaN compares false, so gc or uc is that NaN; an implementation must not convert a NaN n to an
+ * integer: any n serves, a = gc * s is NaN whatever s is). Infinite g and u follow the formulas: g = -inf gives z = -inf,
+ * y = -80, a = -inf. Everything after that is the first definition of this header with h[r] as the input row x[r]: the
+ * range, scale_r, zp_r, q, and the product and the finish of the handle's weight format, unchanged. A gated run equals, bit
+ * for bit, the same handle's plain run on a float tensor holding h.
+ *
+ * The sigmoid's accuracy: against 1 / (1 + exp(-z)) in float64 the lines above have a largest relative error of
+ * 4.46 * 2^-24 (4 000 001 points of linspace(-100, 100) and 2 000 000 samples of normal(0, 3), those with z > -80; measured
+ * with their numpy restatement on a CPU). For z <= -80 the clamp pins the sigmoid at about exp(-80) = 1.8e-35 (1.5 * 2^-116): no claim there.
+ *
+ * No result depends on the denormal mode. alpha and limit lie in [2^-6, 2^6] (or limit is +INFINITY) and up_shift is zero or a
+ * normal number. The steps, written out:
+ *   s.  A |z| below 2^-100, denormal or flushed (a denormal g, or a small normal g times a small alpha): y * 0x1.715476p+0f rounds
+ *       to n = -0 whatever it was, r2 = y, every p * r2 is far below the last place of the constant added to it, so p = 1, e = 1,
+ *       q = 0.5 and s = 0.5 -- on EITHER branch of z > 0, which a denormal z takes differently in the two modes. For every other
+ *       z: y is normal; with n = 0, r2 = y; with n != 0, r1 and r2 are zero or differences of multiples of 2^-44, far above
+ *       2^-126; a p * r2 below 2^-126 is absorbed by its constant flushed or not; e >= 2^-116, d >= 1 and q >= 2^-117 are normal:
+ *       s is the same normal number in both modes.
+ *   a.  gc * s with an exact magnitude below 2^-126 (only a |g| below 2^-124 gets there: s < 1 / 4 needs |z| > 1, hence |g| > 2^-6)
+ *       is, rounded, a denormal or exactly 2^-126 in one mode and either of those or a zero of the same sign in the other,
+ *       whichever way a mode decides that a result within one rounding of 2^-126 is tiny. The explicit test is therefore
+ *       |a| <= 2^-126, not <: it makes all of them that zero. With < an a of 2^-126 in one mode and 0 in the other would meet
+ *       a b that limit = +INFINITY leaves unbounded, and h could be anything against 0. An exact product of 2^-126 or more is
+ *       no denormal in either mode.
+ *   b.  Two normal numbers that cancel leave zero or a multiple of 2^-149: the same, and a denormal one becomes a zero of its sign
+ *       by the mode or by the explicit test. A denormal u with up_shift = 0 is that denormal in one mode, then flushed to a zero
+ *       of u's sign, and 0 + 0 = +0 in the other: b can differ in the SIGN OF A ZERO, nothing else.
+ *   h.  So a is the same in both modes and b is the same but for the sign of a zero; h = a * b is the same in both modes, or a
+ *       zero of either sign, or a product of two equal normal operands that is a denormal (or within a rounding of 2^-126) in
+ *       one mode and a zero in the other. The "input side" argument above covers all of these: any |x| <= 2^-126 enters the
+ *       range like a zero of either sign -- a range of nothing larger fails the scale test and takes scale 1, -lo * inv and
+ *       x * inv stay at or below 2^-126 * 2^60 and round to zero -- and quantizes to the zero point.
+ *
+ * Statuses: those of the plain setup of the same handle, in its order, with 2 * input_channels wherever the input's channel
+ * count enters (the stride check, the input's byte span for the overlap and device checks, the host-pointer staging of the
+ * plain form; the grouped form's size limits count quantized rows, still K rounded up to 64 bytes each). One check is added,
+ * behind the alignment check and in front of the stride check: invalid_parameter for an alpha that is not a normal number in
+ * [2^-6, 2^6], a limit that is NaN or neither in [2^-6, 2^6] nor +INFINITY, an up_shift that is NaN, infinite, denormal or
+ * above 2^6 in magnitude. A refused setup leaves the previous one runnable, gated or not; a plain setup after a gated one, or
+ * the reverse, replaces it. The scratch has the plain setup's size. Each of the two refuses the other's handles.
+ *
+ * Kernels. Only the first launch differs (hip/f32qd8gatedrows.hip; qnnp_gfx950_dynamic_rows_kernel names it), by K, the number
+ * of positions, as above:
+ *     f32_qd8_gated_rows_wave      K <= 1024       one wave per row; a lane reads 128 contiguous bytes for 16 positions
+ *     f32_qd8_gated_rows_block     K <= 16384      one workgroup per row, the row read once, up to 64 h per lane in registers
+ *     f32_qd8_gated_rows_twopass   K <= 32768      the row is read twice and h computed twice, to the same bits
+ * each with _x4 behind its name where the input base or, with more than one row, the input stride is no multiple of 16 bytes.
+ * No scratch memory. qnnp_gfx950_operator_kernel is unaffected.
+ */
+enum qnnp_status qnnp_gfx950_setup_fully_connected_nc_f32_qd8_gated(
+    qnnp_operator_t fully_connected,     /* of any of the six plain creates */
+    size_t batch_size,
+    const float* input,                  /* [batch_size] rows of 2 * input_channels floats: {gate, up} per position */
+    size_t input_stride,                 /* in elements, >= 2 * input_channels */
+    float alpha,
+    float limit,
+    float up_shift,
+    float* output,
+    size_t output_stride);
+
+enum qnnp_status qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8_gated(
+    qnnp_operator_t fully_connected,     /* of the grouped create */
+    size_t batch_size,                   /* input rows */
+    size_t assignments,                  /* A = groups per input row, 1 .. 8 */
+    const float* input,                  /* [batch_size] rows of 2 * input_channels floats, device */
+    size_t input_stride,                 /* in elements, >= 2 * input_channels */
+    float alpha,
+    float limit,
+    float up_shift,
+    const int32_t* group_ids,            /* [batch_size * A], device; read when the operator runs */
+    float* output,                       /* [batch_size * A] rows of output_channels floats, device */
+    size_t output_stride);
+
 /* Name of the row kernel the operator's last run launched in front of the kernel qnnp_gfx950_operator_kernel names
  * (static string), or NULL: before the first run, or for a handle of another kind. */
 const char* qnnp_gfx950_dynamic_rows_kernel(qnnp_operator_t fully_connected);

@@ -327,6 +327,15 @@ DYNAMIC_API = (
         "tensor output, size_t output_stride", IF_PRESENT,
         doc="batch_size input rows, `assignments` output rows each; group_ids: int32 [batch_size * assignments] in device "
             "memory, read when the operator runs"),
+    _op("qnnp_gfx950_setup_fully_connected_nc_f32_qd8_gated",
+        "ptr op, size_t batch_size, tensor input, size_t input_stride, f32 alpha, f32 limit, f32 up_shift, "
+        "tensor output, size_t output_stride", IF_PRESENT,
+        doc="the setup of any plain dynamic handle on GATED input rows: 2 * input_channels floats, {gate, up} per position; the "
+            "quantized row is gate * sigmoid(alpha * gate) * (up + up_shift), gate and up clamped at `limit` (SiLU: 1, inf, 0)"),
+    _op("qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8_gated",
+        "ptr op, size_t batch_size, size_t assignments, tensor input, size_t input_stride, f32 alpha, f32 limit, "
+        "f32 up_shift, tensor group_ids, tensor output, size_t output_stride", IF_PRESENT,
+        doc="the grouped setup on gated input rows, as setup_fully_connected_nc_f32_qd8_gated"),
     _fn("qnnp_gfx950_dynamic_rows_kernel", "ptr op", IF_PRESENT, restype=c_char_p),
 )
 
@@ -434,7 +443,8 @@ class Gfx950Library(QnnpackLibrary):
     [create|setup]_fully_connected_nc_f32_qd8[_status], and create_fully_connected_nc_f32_qd8_qc4w[_status],
     and create_fully_connected_nc_f32_qd8_qb4w[_status], and create_fully_connected_nc_f32_qd8_qb4w_zp[_status],
     and create_fully_connected_nc_f32_qd8_qb4w_b32[_status], and create_fully_connected_nc_f32_qd8_mxfp4w[_status],
-    and create_grouped_fully_connected_nc_f32_qd8_mxfp4w[_status] / setup_grouped_fully_connected_nc_f32_qd8[_status].
+    and create_grouped_fully_connected_nc_f32_qd8_mxfp4w[_status] / setup_grouped_fully_connected_nc_f32_qd8[_status],
+    and the two setups on gated input rows, setup_[grouped_]fully_connected_nc_f32_qd8_gated[_status].
     """
 
     def __init__(self, path: str):

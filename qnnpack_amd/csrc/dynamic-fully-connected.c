@@ -18,6 +18,11 @@
  * permutation, the tile list and the tile count of hip/qd8f32gemm4g.hip, and the run is three launches: the rows kernel over
  * the INPUT rows, that unit's plan kernel, and its product kernel on a grid fixed here, before any id is known.
  *
+ * The two _gated setups (qnnp_gfx950_setup_[grouped_]fully_connected_nc_f32_qd8_gated) take any of these handles with input
+ * rows of K PAIRS {gate, up}: they share their bodies with the plain setups (the floats per input row are a parameter), the
+ * operator remembers the gate, and launch_rows sends the first launch to hip/f32qd8gatedrows.hip, which quantizes
+ * act(gate) * up without writing it as floats. Nothing behind the first launch knows.
+ *
  * Not part of the seam library (oracle/Makefile).
  */
 #include <math.h>
@@ -42,12 +47,25 @@
 #define QNNP_QD8_MAX_GROUPED_ROWS ((size_t) 1 << 20)          /* exclusive: output rows of the grouped operator */
 #define QNNP_QD8_MAX_GATHER_BYTES ((size_t) 1 << 31)          /* the grouped kernels' 32-bit offset of a gathered row */
 
-static int launch_dynamic_fully_connected(struct qnnp_operator* op, const void* input, const void* input2, void* output)
+/* the first launch of either form: op->batch_size input rows into the scratch, by the plain or the gated row kernels as the
+ * current setup says */
+static int launch_rows(struct qnnp_operator* op, const void* input, int8_t* quantized, struct qnnp_hip_qd8_row_entry* row_table)
 {
-  (void) input2;
-  int8_t* quantized = (int8_t*) op->d_qd8_scratch;
-  struct qnnp_hip_qd8_row_entry* row_table =
-      (struct qnnp_hip_qd8_row_entry*) ((uint8_t*) op->d_qd8_scratch + op->qd8_row_table_offset);
+  if (op->qd8_gated) {
+    const struct qnnp_hip_qd8_gated_rows_args gated_args = {
+      .input = (const float*) input,
+      .quantized = quantized,
+      .row_table = row_table,
+      .rows = (uint32_t) op->batch_size,
+      .k = (uint32_t) op->group_input_channels,
+      .k_pad = op->k_pad,
+      .input_stride = op->input_pixel_stride,
+      .alpha = op->qd8_gate_alpha,
+      .limit = op->qd8_gate_limit,
+      .up_shift = op->qd8_gate_up_shift,
+    };
+    return qnnp_hip_qd8_gated_rows_run(&gated_args, &op->qd8_rows_kernel);
+  }
   const struct qnnp_hip_qd8_rows_args rows_args = {
     .input = (const float*) input,
     .quantized = quantized,
@@ -57,7 +75,16 @@ static int launch_dynamic_fully_connected(struct qnnp_operator* op, const void* 
     .k_pad = op->k_pad,
     .input_stride = op->input_pixel_stride,
   };
-  const int rc = qnnp_hip_qd8_rows_run(&rows_args, &op->qd8_rows_kernel);
+  return qnnp_hip_qd8_rows_run(&rows_args, &op->qd8_rows_kernel);
+}
+
+static int launch_dynamic_fully_connected(struct qnnp_operator* op, const void* input, const void* input2, void* output)
+{
+  (void) input2;
+  int8_t* quantized = (int8_t*) op->d_qd8_scratch;
+  struct qnnp_hip_qd8_row_entry* row_table =
+      (struct qnnp_hip_qd8_row_entry*) ((uint8_t*) op->d_qd8_scratch + op->qd8_row_table_offset);
+  const int rc = launch_rows(op, input, quantized, row_table);
   if (rc != QNNP_HIP_OK) {
     return rc;
   }
@@ -120,16 +147,7 @@ static int launch_grouped_fully_connected(struct qnnp_operator* op, const void* 
   (void) input2;
   uint8_t* scratch = (uint8_t*) op->d_qd8_scratch;
   struct qnnp_hip_qd8_row_entry* row_table = (struct qnnp_hip_qd8_row_entry*) (scratch + op->qd8_row_table_offset);
-  const struct qnnp_hip_qd8_rows_args rows_args = {
-    .input = (const float*) input,
-    .quantized = (int8_t*) scratch,
-    .row_table = row_table,
-    .rows = (uint32_t) op->batch_size,
-    .k = (uint32_t) op->group_input_channels,
-    .k_pad = op->k_pad,
-    .input_stride = op->input_pixel_stride,
-  };
-  const int rc = qnnp_hip_qd8_rows_run(&rows_args, &op->qd8_rows_kernel);
+  const int rc = launch_rows(op, input, (int8_t*) scratch, row_table);
   if (rc != QNNP_HIP_OK) {
     return rc;
   }
@@ -727,8 +745,33 @@ enum qnnp_status qnnp_gfx950_create_grouped_fully_connected_nc_f32_qd8_mxfp4w(
       output_channels, 3, 32, kernel, 4, kernel_scales, 0, NULL, bias, output_min, output_max, fully_connected);
 }
 
+/* what a _gated setup adds to its plain one: NULL for the plain setups, whose input rows hold input_channels floats; with a
+ * gate they hold twice that many, the pairs {gate, up} */
+struct qd8_gate {
+  float alpha, limit, up_shift;
+};
+
+static int gate_is_valid(const struct qd8_gate* gate)
+{
+  const int alpha_ok = isnormal(gate->alpha) && gate->alpha >= 0x1.0p-6f && gate->alpha <= 0x1.0p+6f;
+  const int limit_ok = (gate->limit >= 0x1.0p-6f && gate->limit <= 0x1.0p+6f) || gate->limit == INFINITY;      /* NaN: neither */
+  const int shift_ok = gate->up_shift == 0.0f || (isnormal(gate->up_shift) && fabsf(gate->up_shift) <= 0x1.0p+6f);
+  return alpha_ok && limit_ok && shift_ok;
+}
+
+static void remember_gate(qnnp_operator_t op, const struct qd8_gate* gate)
+{
+  op->qd8_gated = gate != NULL;
+  if (gate != NULL) {
+    op->qd8_gate_alpha = gate->alpha;
+    op->qd8_gate_limit = gate->limit;
+    op->qd8_gate_up_shift = gate->up_shift;
+  }
+}
+
 static enum qnnp_status setup_dynamic_fully_connected(
-    qnnp_operator_t op, size_t batch_size, const float* input, size_t input_stride, float* output, size_t output_stride)
+    const char* function, qnnp_operator_t op, size_t batch_size, const float* input, size_t input_stride,
+    const struct qd8_gate* gate, float* output, size_t output_stride)
 {
   if (op->ukernel_type != qnnp_ukernel_type_dynamic_fully_connected || op->qd8_groups != 0) {
     return qnnp_status_invalid_parameter;
@@ -737,13 +780,20 @@ static enum qnnp_status setup_dynamic_fully_connected(
     op->batch_size = 0;
     return qnnp_status_success;
   }
-  const size_t input_channels = op->group_input_channels, output_channels = op->channels;
+  /* the floats of an input row; the quantized row has group_input_channels elements either way */
+  const size_t input_channels = (gate != NULL ? 2 : 1) * op->group_input_channels, output_channels = op->channels;
   if (input == NULL || output == NULL) {
     qnnp_log_error("cannot set up dynamic fully connected operator: NULL tensor");
     return qnnp_status_invalid_parameter;
   }
   if ((uintptr_t) input % sizeof(float) != 0 || (uintptr_t) output % sizeof(float) != 0) {
     qnnp_log_error("cannot set up dynamic fully connected operator: a tensor is not 4-byte aligned");
+    return qnnp_status_invalid_parameter;
+  }
+  if (gate != NULL && !gate_is_valid(gate)) {
+    qnnp_log_error("cannot set up dynamic fully connected operator with gate parameters alpha %.7g, limit %.7g, up_shift "
+        "%.7g: alpha a normal number in [2^-6, 2^6], limit in [2^-6, 2^6] or +infinity, up_shift zero or a normal number of "
+        "at most 2^6 in magnitude", gate->alpha, gate->limit, gate->up_shift);
     return qnnp_status_invalid_parameter;
   }
   if (input_stride < input_channels || output_stride < output_channels) {
@@ -781,6 +831,7 @@ static enum qnnp_status setup_dynamic_fully_connected(
     op->qd8_scratch_capacity = scratch_bytes;
   }
   op->qd8_row_table_offset = row_table_offset;
+  remember_gate(op, gate);
   op->batch_size = batch_size;
   op->input = input;
   op->input_pixel_stride = input_stride;
@@ -788,7 +839,21 @@ static enum qnnp_status setup_dynamic_fully_connected(
   op->output_pixel_stride = output_stride;
   op->input_span = input_span;
   op->output_span = output_span;
-  return qnnp_bind_tensors(op, "qnnp_gfx950_setup_fully_connected_nc_f32_qd8");
+  return qnnp_bind_tensors(op, function);
+}
+
+/* both plain setups: the lifecycle around the one body */
+static enum qnnp_status setup_dynamic_fully_connected_entered(
+    const char* function, qnnp_operator_t fully_connected, size_t batch_size, const float* input, size_t input_stride,
+    const struct qd8_gate* gate, float* output, size_t output_stride)
+{
+  int token;
+  const enum qnnp_status status = qnnp_enter_setup(function, fully_connected, &token);
+  if (status != qnnp_status_success) {
+    return status;
+  }
+  return qnnp_leave_setup(fully_connected, token, setup_dynamic_fully_connected(
+      function, fully_connected, batch_size, input, input_stride, gate, output, output_stride));
 }
 
 enum qnnp_status qnnp_gfx950_setup_fully_connected_nc_f32_qd8(
@@ -799,14 +864,24 @@ enum qnnp_status qnnp_gfx950_setup_fully_connected_nc_f32_qd8(
     float* output,
     size_t output_stride)
 {
-  int token;
-  const enum qnnp_status status =
-      qnnp_enter_setup("qnnp_gfx950_setup_fully_connected_nc_f32_qd8", fully_connected, &token);
-  if (status != qnnp_status_success) {
-    return status;
-  }
-  return qnnp_leave_setup(fully_connected, token,
-      setup_dynamic_fully_connected(fully_connected, batch_size, input, input_stride, output, output_stride));
+  return setup_dynamic_fully_connected_entered("qnnp_gfx950_setup_fully_connected_nc_f32_qd8", fully_connected, batch_size,
+      input, input_stride, NULL, output, output_stride);
+}
+
+enum qnnp_status qnnp_gfx950_setup_fully_connected_nc_f32_qd8_gated(
+    qnnp_operator_t fully_connected,
+    size_t batch_size,
+    const float* input,
+    size_t input_stride,
+    float alpha,
+    float limit,
+    float up_shift,
+    float* output,
+    size_t output_stride)
+{
+  const struct qd8_gate gate = { .alpha = alpha, .limit = limit, .up_shift = up_shift };
+  return setup_dynamic_fully_connected_entered("qnnp_gfx950_setup_fully_connected_nc_f32_qd8_gated", fully_connected,
+      batch_size, input, input_stride, &gate, output, output_stride);
 }
 
 static inline size_t round_up_16(size_t bytes)
@@ -815,8 +890,8 @@ static inline size_t round_up_16(size_t bytes)
 }
 
 static enum qnnp_status setup_grouped_fully_connected(
-    qnnp_operator_t op, size_t batch_size, size_t assignments, const float* input, size_t input_stride,
-    const int32_t* group_ids, float* output, size_t output_stride)
+    const char* function, qnnp_operator_t op, size_t batch_size, size_t assignments, const float* input, size_t input_stride,
+    const struct qd8_gate* gate, const int32_t* group_ids, float* output, size_t output_stride)
 {
   if (op->ukernel_type != qnnp_ukernel_type_dynamic_fully_connected || op->qd8_groups == 0) {
     return qnnp_status_invalid_parameter;
@@ -825,7 +900,7 @@ static enum qnnp_status setup_grouped_fully_connected(
     op->batch_size = 0;
     return qnnp_status_success;
   }
-  const size_t input_channels = op->group_input_channels, output_channels = op->channels;
+  const size_t input_channels = (gate != NULL ? 2 : 1) * op->group_input_channels, output_channels = op->channels;
   if (input == NULL || output == NULL || group_ids == NULL || assignments == 0) {
     qnnp_log_error("cannot set up grouped dynamic fully connected operator: NULL tensor or group ids, or no assignments");
     return qnnp_status_invalid_parameter;
@@ -833,6 +908,12 @@ static enum qnnp_status setup_grouped_fully_connected(
   if ((uintptr_t) input % sizeof(float) != 0 || (uintptr_t) output % sizeof(float) != 0 ||
       (uintptr_t) group_ids % sizeof(int32_t) != 0) {
     qnnp_log_error("cannot set up grouped dynamic fully connected operator: a tensor or the group ids are not 4-byte aligned");
+    return qnnp_status_invalid_parameter;
+  }
+  if (gate != NULL && !gate_is_valid(gate)) {
+    qnnp_log_error("cannot set up grouped dynamic fully connected operator with gate parameters alpha %.7g, limit %.7g, "
+        "up_shift %.7g: alpha a normal number in [2^-6, 2^6], limit in [2^-6, 2^6] or +infinity, up_shift zero or a normal "
+        "number of at most 2^6 in magnitude", gate->alpha, gate->limit, gate->up_shift);
     return qnnp_status_invalid_parameter;
   }
   if (input_stride < input_channels || output_stride < output_channels) {
@@ -900,6 +981,7 @@ static enum qnnp_status setup_grouped_fully_connected(
   op->qd8_tile_rows = tile_rows;
   op->qd8_max_tiles = (uint32_t) max_tiles;
   op->qd8_group_ids = group_ids;
+  remember_gate(op, gate);
   op->batch_size = batch_size;
   op->input = input;
   op->input_pixel_stride = input_stride;
@@ -907,7 +989,21 @@ static enum qnnp_status setup_grouped_fully_connected(
   op->output_pixel_stride = output_stride;
   op->input_span = input_span;
   op->output_span = output_span;
-  return qnnp_bind_tensors(op, "qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8");
+  return qnnp_bind_tensors(op, function);
+}
+
+/* both grouped setups: the lifecycle around the one body */
+static enum qnnp_status setup_grouped_fully_connected_entered(
+    const char* function, qnnp_operator_t fully_connected, size_t batch_size, size_t assignments, const float* input,
+    size_t input_stride, const struct qd8_gate* gate, const int32_t* group_ids, float* output, size_t output_stride)
+{
+  int token;
+  const enum qnnp_status status = qnnp_enter_setup(function, fully_connected, &token);
+  if (status != qnnp_status_success) {
+    return status;
+  }
+  return qnnp_leave_setup(fully_connected, token, setup_grouped_fully_connected(
+      function, fully_connected, batch_size, assignments, input, input_stride, gate, group_ids, output, output_stride));
 }
 
 enum qnnp_status qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8(
@@ -920,14 +1016,26 @@ enum qnnp_status qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8(
     float* output,
     size_t output_stride)
 {
-  int token;
-  const enum qnnp_status status =
-      qnnp_enter_setup("qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8", fully_connected, &token);
-  if (status != qnnp_status_success) {
-    return status;
-  }
-  return qnnp_leave_setup(fully_connected, token, setup_grouped_fully_connected(
-      fully_connected, batch_size, assignments, input, input_stride, group_ids, output, output_stride));
+  return setup_grouped_fully_connected_entered("qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8", fully_connected,
+      batch_size, assignments, input, input_stride, NULL, group_ids, output, output_stride);
+}
+
+enum qnnp_status qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8_gated(
+    qnnp_operator_t fully_connected,
+    size_t batch_size,
+    size_t assignments,
+    const float* input,
+    size_t input_stride,
+    float alpha,
+    float limit,
+    float up_shift,
+    const int32_t* group_ids,
+    float* output,
+    size_t output_stride)
+{
+  const struct qd8_gate gate = { .alpha = alpha, .limit = limit, .up_shift = up_shift };
+  return setup_grouped_fully_connected_entered("qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8_gated", fully_connected,
+      batch_size, assignments, input, input_stride, &gate, group_ids, output, output_stride);
 }
 
 const char* qnnp_gfx950_dynamic_rows_kernel(qnnp_operator_t fully_connected)

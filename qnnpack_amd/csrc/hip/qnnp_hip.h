@@ -592,6 +592,21 @@ struct qnnp_hip_qd8_rows_args {
  * _twopass (beyond: the row is read twice); with _x4 behind the name where the input base or, with more than one row,
  * its stride is no multiple of 16 bytes (4-byte loads) */
 int qnnp_hip_qd8_rows_run(const struct qnnp_hip_qd8_rows_args* args, const char** kernel_name);
+/* The rows launch after a GATED setup (f32qd8gatedrows.hip): `input` rows hold k pairs {gate, up}, interleaved, so
+ * input_stride >= 2 k, and the row that is quantized is h = act(gate) * (up + up_shift) of the header, computed in registers.
+ * Outputs, regime bounds on k, grids and the _x4 rule are those of qnnp_hip_qd8_rows_run; the names are
+ * f32_qd8_gated_rows_wave / _block / _twopass[_x4]. The three parameters are taken as they are: the setup has checked them. */
+struct qnnp_hip_qd8_gated_rows_args {
+  const float* input;
+  int8_t* quantized;          /* [rows][k_pad] */
+  struct qnnp_hip_qd8_row_entry* row_table;   /* [rows] */
+  uint32_t rows;
+  uint32_t k;                 /* positions: pairs per row */
+  uint32_t k_pad;
+  uint64_t input_stride;      /* float elements between rows */
+  float alpha, limit, up_shift;
+};
+int qnnp_hip_qd8_gated_rows_run(const struct qnnp_hip_qd8_gated_rows_args* args, const char** kernel_name);
 
 struct qnnp_hip_qd8_gemm_args {
   const int8_t* quantized;    /* [rows][k_pad], what the rows launch wrote */

@@ -191,7 +191,12 @@ struct qnnp_operator {
    * an operator is set up by the grouped setup alone: batch_size counts INPUT rows, each of which has qd8_assignments output
    * rows, qd8_group_ids is the caller's device array of batch_size * qd8_assignments ids, and the scratch also holds the
    * permutation (at qd8_perm_offset), the tile list (qd8_tiles_offset, qd8_max_tiles entries of qd8_tile_rows rows) and
-   * the tile count (qd8_tile_count_offset) of hip/qd8f32gemm4g.hip. */
+   * the tile count (qd8_tile_count_offset) of hip/qd8f32gemm4g.hip.
+   * qd8_gated is 1 while the current setup is one of the two _gated ones, whatever the create: the input rows then hold
+   * group_input_channels PAIRS {gate, up} (input_pixel_stride >= twice that), the first launch is hip/f32qd8gatedrows.hip's
+   * with the three qd8_gate_* parameters, and everything behind it is unchanged. */
+  uint32_t qd8_gated;
+  float qd8_gate_alpha, qd8_gate_limit, qd8_gate_up_shift;
   uint32_t qd8_groups;
   uint32_t qd8_assignments;
   uint32_t qd8_tile_rows;

@@ -8,4 +8,4 @@ HIP_SRCS := hip/runtime.hip hip/q8igemm.hip hip/q8gemm256.hip hip/q8gemm256c.hip
 # (qnnpack_amd/csrc/Makefile), like the other operators without a reference counterpart -- not part of C_SRCS / HIP_SRCS, which
 # are also the product half of the seam library.
 DYNAMIC_C_SRCS   := dynamic-fully-connected.c
-DYNAMIC_HIP_SRCS := hip/f32qd8rows.hip hip/qd8f32gemm.hip hip/qd8f32gemm4.hip hip/qd8f32gemm4b.hip hip/qd8f32gemm4z.hip hip/qd8f32gemm4s.hip hip/qd8f32gemm4m.hip hip/qd8f32gemm4g.hip
+DYNAMIC_HIP_SRCS := hip/f32qd8rows.hip hip/f32qd8gatedrows.hip hip/qd8f32gemm.hip hip/qd8f32gemm4.hip hip/qd8f32gemm4b.hip hip/qd8f32gemm4z.hip hip/qd8f32gemm4s.hip hip/qd8f32gemm4m.hip hip/qd8f32gemm4g.hip

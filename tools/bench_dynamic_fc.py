@@ -44,7 +44,14 @@ of its three operators' medians: kernel time without the gaps between launches, 
 rotate; the weights of one operator cannot, so at small batches they are served by the 256 MiB last-level cache and
 `weights_gb_s` (weight bytes / time) is a cache figure wherever the image fits there, not an HBM figure.
 
-    python tools/bench_dynamic_fc.py [--qb4w | --qb4w-zp | --qb4w-b32 | --mxfp4w | --grouped [--crossover]] [--shapes 1x4096x4096,...] [--sets 4] [--iters 20] [--rounds 5] [--json out.json]
+`--gated` times the GATED setups (qnnp_gfx950_setup_[grouped_]fully_connected_nc_f32_qd8_gated, alpha = 1, limit = inf,
+up_shift = 0) against what a caller does without them: a torch element-wise pass that writes silu(gate) * up as floats (sigmoid,
+multiply, multiply: three launches into preallocated buffers) followed by the plain setup of a handle with the same weights.
+Either side is recorded into a hipGraph and timed with qnnp_gfx950_graph_time, the sides in turn, --rounds times over; the torch
+pass and the plain operator are also timed on their own, and the two row launches by themselves (`rows_alone_gb_s`: bytes read and
+written over time). Shapes are FORMxGROUPSxROWSxKxN.
+
+    python tools/bench_dynamic_fc.py [--qb4w | --qb4w-zp | --qb4w-b32 | --mxfp4w | --grouped [--crossover] | --gated] [--shapes 1x4096x4096,...] [--sets 4] [--iters 20] [--rounds 5] [--json out.json]
 """
 import argparse
 import json
@@ -317,6 +324,136 @@ def grouped_rows(lib, args, shapes, rng, gen, np, torch):
     return rows_out
 
 
+# the gated setups: (form, groups, rows, K, N) -- the expert layer of profiles/dynamic_fc_grouped at decode and prefill sizes
+# (A = 1), and a dense down projection (K = 14336 -> N = 4096) with _qb4w_b32 weights at batch 1, 16 and 512
+GATED_SHAPES = [("grouped", 32, 64, 2880, 2880), ("grouped", 32, 16384, 2880, 2880),
+                ("qb4w_b32", 0, 1, 14336, 4096), ("qb4w_b32", 0, 16, 14336, 4096), ("qb4w_b32", 0, 512, 14336, 4096)]
+
+
+def rows_alone_us(lib, args, torch, x, rows, k, gated):
+    """the row launch by itself (qnnp_hip_qd8_[gated_]rows_run, the library's internal launch entry), recorded into a graph"""
+    import ctypes
+    head = [("input", ctypes.c_void_p), ("quantized", ctypes.c_void_p), ("row_table", ctypes.c_void_p), ("rows", ctypes.c_uint32),
+            ("k", ctypes.c_uint32), ("k_pad", ctypes.c_uint32), ("input_stride", ctypes.c_uint64)]
+    tail = [("alpha", ctypes.c_float), ("limit", ctypes.c_float), ("up_shift", ctypes.c_float)] if gated else []
+    launch_args = type("RowsArgs", (ctypes.Structure,), {"_fields_": head + tail})
+    k_pad = (k + 63) // 64 * 64
+    quantized = torch.empty(rows * k_pad, dtype=torch.int8, device="cuda")
+    table = torch.empty(rows * 2, dtype=torch.float32, device="cuda")
+    values = (x.data_ptr(), quantized.data_ptr(), table.data_ptr(), rows, k, k_pad, (2 if gated else 1) * k)
+    a = launch_args(*values, *((1.0, float("inf"), 0.0) if gated else ()))
+    run = getattr(lib.lib, "qnnp_hip_qd8_gated_rows_run" if gated else "qnnp_hip_qd8_rows_run")
+    run.argtypes, run.restype = [ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int
+    name = ctypes.c_char_p()
+    assert run(ctypes.byref(a), ctypes.byref(name)) == 0
+    torch.cuda.synchronize()
+    lib.graph_begin()
+    try:
+        assert run(ctypes.byref(a), None) == 0
+    finally:
+        graph = lib.graph_end()
+    try:
+        return lib.graph_time(graph, args.warmup, args.iters) * 1e3, name.value.decode()
+    finally:
+        lib.graph_destroy(graph)
+
+
+def gated_rows(lib, args, shapes, rng, gen, np, torch):
+    """one record per shape: the gated setup against what a caller does without it -- a torch element-wise pass that writes
+    h = silu(gate) * up as floats, then the plain setup of a handle with the same weights -- each recorded into a graph, the two
+    in turn; and the two row launches by themselves"""
+    rows_out, inf = [], float("inf")
+    weights = {}
+    for form, groups, rows, k, n in shapes:
+        if (form, groups, k, n) not in weights:
+            weights.clear()
+            g = max(groups, 1)
+            weights[form, groups, k, n] = (rng.integers(0, 256, size=(g, n, k // 2), dtype=np.uint8),
+                                          rng.integers(118, 123, size=(g, n, k // 32), dtype=np.uint8),
+                                          rng.standard_normal((g, n)).astype(np.float32))
+        packed, exponents, bias = weights[form, groups, k, n]
+        x = torch.randn(rows * 2 * k, dtype=torch.float32, device="cuda", generator=gen)
+        h = torch.empty(rows * k, dtype=torch.float32, device="cuda")
+        t = torch.empty(rows, k, dtype=torch.float32, device="cuda")
+        y = torch.empty(rows * n, dtype=torch.float32, device="cuda")
+        gate, up = x.view(rows, 2 * k)[:, 0::2], x.view(rows, 2 * k)[:, 1::2]
+        ops = []
+        try:
+            for _ in range(2):          # the same weights twice: one handle is set up gated, the other plain
+                if form == "grouped":
+                    ops.append(lib.create_grouped_fully_connected_nc_f32_qd8_mxfp4w(groups, k, n, packed, exponents, bias, -inf, inf))
+                else:
+                    scales = np.ldexp(np.float32(1), exponents[0].astype(np.int32) - 127).astype(np.float32)
+                    ops.append(lib.create_fully_connected_nc_f32_qd8_qb4w_b32(k, n, packed[0], scales, None, bias[0], -inf, inf))
+            if form == "grouped":
+                d_ids = torch.from_numpy(rng.integers(0, groups, rows).astype(np.int32)).cuda()
+                lib.setup_grouped_fully_connected_nc_f32_qd8_gated(ops[0], rows, 1, x, 2 * k, 1.0, inf, 0.0, d_ids, y, n)
+                lib.setup_grouped_fully_connected_nc_f32_qd8(ops[1], rows, 1, h, k, d_ids, y, n)
+            else:
+                lib.setup_fully_connected_nc_f32_qd8_gated(ops[0], rows, x, 2 * k, 1.0, inf, 0.0, y, n)
+                lib.setup_fully_connected_nc_f32_qd8(ops[1], rows, h, k, y, n)
+
+            def torch_pass():           # three launches into preallocated buffers: nothing is allocated under a capture
+                torch.sigmoid(gate, out=t)
+                t.mul_(gate)
+                torch.mul(t, up, out=h.view(rows, k))
+
+            def graph_of(*steps):
+                lib.graph_begin()
+                try:
+                    for step in steps:
+                        step()
+                except BaseException:
+                    lib.graph_destroy(lib.graph_end())
+                    raise
+                return lib.graph_end()
+            sides = {"gated": (lambda: lib.run_operator(ops[0]),), "torch_then_plain": (torch_pass, lambda: lib.run_operator(ops[1])),
+                     "torch_pass": (torch_pass,), "plain": (lambda: lib.run_operator(ops[1]),)}
+            results = {}
+            for key, steps in sides.items():    # every kernel has run once before anything is captured
+                for step in steps:
+                    step()
+                torch.cuda.synchronize()
+                results[key] = y.clone()
+            # torch's sigmoid is not the definition's to the last bit, so a few elements may land in the neighbouring int8 code
+            differ = float((results["gated"] - results["torch_then_plain"]).abs().max() / results["gated"].abs().max())
+            graphs = {key: graph_of(*steps) for key, steps in sides.items()}
+            h.zero_()
+            lib.graph_launch(graphs["torch_pass"])
+            lib.graph_synchronize(graphs["torch_pass"])
+            assert float(h.abs().sum()) > 0, "the torch pass was not recorded into the graph"
+            times = {key: [] for key in sides}
+            alone = {"gated": [], "plain": []}
+            try:
+                for _ in range(args.rounds):
+                    for key, graph in graphs.items():
+                        times[key].append(lib.graph_time(graph, args.warmup, args.iters) * 1e3)
+                    for key in alone:
+                        alone[key].append(rows_alone_us(lib, args, torch, x if key == "gated" else h, rows, k, key == "gated"))
+            finally:
+                for graph in graphs.values():
+                    lib.graph_destroy(graph)
+            us = {key: statistics.median(v) for key, v in times.items()}
+            rows_us = {key: statistics.median(u for u, _ in v) for key, v in alone.items()}
+            k_pad = (k + 63) // 64 * 64
+            moved = {"gated": rows * (8 * k + k_pad + 8), "plain": rows * (4 * k + k_pad + 8)}
+            row = {"form": form, "groups": groups, "rows": rows, "k": k, "n": n,
+                   "us": {key: round(v, 2) for key, v in us.items()},
+                   "spread": {key: round((max(v) - min(v)) / statistics.median(v), 3) for key, v in times.items()},
+                   "chain_over_gated": round(us["torch_then_plain"] / us["gated"], 3),
+                   "largest_output_difference_over_largest_output": differ,
+                   "rows_alone_us": {key: round(v, 2) for key, v in rows_us.items()},
+                   "rows_alone_gb_s": {key: round(moved[key] / rows_us[key] * 1e-3, 1) for key in rows_us},
+                   "rows_kernels": {key: v[0][1] for key, v in alone.items()},
+                   "kernel": lib.operator_kernel(ops[0]), "rounds": args.rounds, "replays_per_sample": args.iters}
+            rows_out.append(row)
+            print(json.dumps(row), flush=True)
+        finally:
+            for op in ops:
+                lib.delete_operator(op)
+    return rows_out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--qb4w", action="store_true", help="time the block-wise 4-bit operator against the qc4w one instead")
@@ -329,6 +466,9 @@ def main():
     ap.add_argument("--grouped", action="store_true",
                     help="time the grouped MXFP4 operator against one MXFP4 operator per group instead (shapes: GROUPSxBATCHxAxKxN)")
     ap.add_argument("--crossover", action="store_true", help="with --grouped: both product kernels forced around R = 16 * groups")
+    ap.add_argument("--gated", action="store_true",
+                    help="time the gated setups against a torch element-wise pass and the plain setup instead (shapes: FORMxGROUPSxROWSxKxN, "
+                         "FORM grouped or qb4w_b32)")
     ap.add_argument("--shapes", default=None, help="BATCHxKxN,... instead of the built-in list")
     ap.add_argument("--sets", type=int, default=4)
     ap.add_argument("--iters", type=int, default=20)
@@ -346,12 +486,15 @@ def main():
     torch.zeros(1, device="cuda")
     lib = qnnpack_amd.load()
     lib.initialize()
+    if args.gated:      # torch's launches are recorded with the library's: both on one stream that can be captured, not the null stream
+        torch.cuda.set_stream(torch.cuda.Stream())
     lib.set_stream(torch.cuda.current_stream().cuda_stream)
     lib.set_async(False)
     rng = np.random.default_rng(23)
     gen = torch.Generator(device="cuda").manual_seed(23)
 
-    shapes = (GROUPED_SHAPES if args.grouped else SHAPES) if args.shapes is None else [tuple(int(v) for v in item.split("x")) for item in args.shapes.split(",")]
+    shapes = (GROUPED_SHAPES if args.grouped else GATED_SHAPES if args.gated else SHAPES) if args.shapes is None else [
+        tuple(v if v.isalpha() or "_" in v else int(v) for v in item.split("x")) for item in args.shapes.split(",")]
     rows_out = qb4w_rows(lib, args, shapes, rng, gen, np, torch) if args.qb4w else []
     if args.qb4w_zp:
         rows_out += qb4w_zp_rows(lib, args, shapes, rng, gen, np, torch)
@@ -361,7 +504,9 @@ def main():
         rows_out += mxfp4w_rows(lib, args, shapes, rng, gen, np, torch)
     if args.grouped:
         rows_out += grouped_rows(lib, args, shapes, rng, gen, np, torch)
-    for batch, k, n in ([] if args.qb4w or args.qb4w_zp or args.qb4w_b32 or args.mxfp4w or args.grouped else shapes):
+    if args.gated:
+        rows_out += gated_rows(lib, args, shapes, rng, gen, np, torch)
+    for batch, k, n in ([] if args.qb4w or args.qb4w_zp or args.qb4w_b32 or args.mxfp4w or args.grouped or args.gated else shapes):
         kernel = rng.integers(-128, 128, size=(n, k), dtype=np.int8)
         scales = rng.uniform(0.005, 0.02, size=n).astype(np.float32)
         bias = rng.standard_normal(n).astype(np.float32)
