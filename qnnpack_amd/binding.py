@@ -339,6 +339,26 @@ DYNAMIC_API = (
     _fn("qnnp_gfx950_dynamic_rows_kernel", "ptr op", IF_PRESENT, restype=c_char_p),
 )
 
+# The two ends of a mixture-of-experts layer around the grouped operator (include/qnnpack_gfx950_moe.h): a table of its own
+# like FLOAT_API, for the same reason. Every array is device memory (`tensor`), as group_ids is above.
+MOE_API = (
+    _op("qnnp_gfx950_create_topk_router_nc_f32",
+        "size_t groups, size_t assignments, u32 first_group=0, u32 flags=0, out router", IF_PRESENT,
+        doc="the top-k softmax router: per token the `assignments` largest of `groups` logits, as ids minus first_group and "
+            "softmax weights; set it up with setup_topk_router_nc_f32"),
+    _op("qnnp_gfx950_setup_topk_router_nc_f32",
+        "ptr op, size_t batch_size, tensor logits, size_t logits_stride, tensor group_ids, tensor weights", IF_PRESENT,
+        doc="group_ids: int32 and weights: float32, [batch_size * assignments] each, in device memory"),
+    _op("qnnp_gfx950_create_weighted_combine_nc_f32",
+        "size_t channels, size_t assignments, size_t groups, u32 flags=0, out combine", IF_PRESENT,
+        doc="the weighted combine: per token the ordered sum of its `assignments` rows times their weights, over the rows "
+            "whose id lies in [0, groups); set it up with setup_weighted_combine_nc_f32"),
+    _op("qnnp_gfx950_setup_weighted_combine_nc_f32",
+        "ptr op, size_t batch_size, tensor input, size_t input_stride, tensor weights, tensor group_ids, tensor output, "
+        "size_t output_stride", IF_PRESENT,
+        doc="weights and group_ids: [batch_size * assignments] in device memory, read when the operator runs"),
+)
+
 
 def _bind(lib, table) -> None:
     """Set argtypes / restype of the table's symbols on a loaded library."""
@@ -427,7 +447,7 @@ class QnnpackLibrary:
         return Status(self.lib.qnnp_deinitialize())
 
 
-@_with_methods_of(GFX950_API + FLOAT_API + PERCHANNEL_API + SQUEEZE_EXCITE_API + OUTPUT_TABLE_API + DYNAMIC_API)
+@_with_methods_of(GFX950_API + FLOAT_API + PERCHANNEL_API + SQUEEZE_EXCITE_API + OUTPUT_TABLE_API + DYNAMIC_API + MOE_API)
 class Gfx950Library(QnnpackLibrary):
     """Product library: qnnpack.h plus the extensions of include/qnnpack_gfx950.h (GFX950_API), the float32 <-> uint8
     operators of include/qnnpack_gfx950_float.h (FLOAT_API) and the per-channel creates of
@@ -444,7 +464,9 @@ class Gfx950Library(QnnpackLibrary):
     and create_fully_connected_nc_f32_qd8_qb4w[_status], and create_fully_connected_nc_f32_qd8_qb4w_zp[_status],
     and create_fully_connected_nc_f32_qd8_qb4w_b32[_status], and create_fully_connected_nc_f32_qd8_mxfp4w[_status],
     and create_grouped_fully_connected_nc_f32_qd8_mxfp4w[_status] / setup_grouped_fully_connected_nc_f32_qd8[_status],
-    and the two setups on gated input rows, setup_[grouped_]fully_connected_nc_f32_qd8_gated[_status].
+    and the two setups on gated input rows, setup_[grouped_]fully_connected_nc_f32_qd8_gated[_status], and the router and
+    the combine of include/qnnpack_gfx950_moe.h (MOE_API): [create|setup]_topk_router_nc_f32[_status] and
+    [create|setup]_weighted_combine_nc_f32[_status].
     """
 
     def __init__(self, path: str):
@@ -455,6 +477,7 @@ class Gfx950Library(QnnpackLibrary):
         _bind(self.lib, SQUEEZE_EXCITE_API)
         _bind(self.lib, OUTPUT_TABLE_API)
         _bind(self.lib, DYNAMIC_API)
+        _bind(self.lib, MOE_API)
 
     def _check(self, call: str, st: int) -> None:
         if st != 0:

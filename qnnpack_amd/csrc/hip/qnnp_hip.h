@@ -758,6 +758,40 @@ struct qnnp_hip_qd8_mxfp4w_grouped_args {
 };
 int qnnp_hip_qd8_mxfp4w_grouped_run(const struct qnnp_hip_qd8_mxfp4w_grouped_args* args, const char** kernel_name);
 
+/* The two ends of a mixture-of-experts layer (f32topk.hip, f32combine.hip, linked into libqnnpack_gfx950.so only -- see the
+ * Makefile; include/qnnpack_gfx950_moe.h has the arithmetic and the kernel names). No reference counterpart. One launch each.
+ * Every pointer is device memory and 4-byte aligned, every stride counts ELEMENTS; tokens * assignments < 2^20.
+ *
+ * Router: per token the `assignments` largest of `groups` logits (1 .. 1024; assignments 1 .. 8 and at most groups), in
+ * descending order: their indices minus first_group into group_ids[token * assignments ..] and the softmax over them
+ * into weights[token * assignments ..]. */
+struct qnnp_hip_topk_router_args {
+  const float* logits;        /* [tokens] rows of `groups` floats */
+  int32_t* group_ids;         /* [tokens * assignments] */
+  float* weights;             /* [tokens * assignments] */
+  uint64_t logits_stride;     /* float elements between rows, >= groups */
+  uint32_t tokens;
+  uint32_t groups;
+  uint32_t assignments;
+  uint32_t first_group;
+};
+int qnnp_hip_topk_router_run(const struct qnnp_hip_topk_router_args* args, const char** kernel_name);
+/* Combine: output row t = the ordered, flushed sum over a of weights[j] * input row j, j = t * assignments + a, over the
+ * rows whose group_ids[j] lies in [0, groups); no byte of any other row is read. channels < 2^24. */
+struct qnnp_hip_weighted_combine_args {
+  const float* input;         /* [tokens * assignments] rows of `channels` floats */
+  const float* weights;       /* [tokens * assignments] */
+  const int32_t* group_ids;   /* [tokens * assignments] */
+  float* output;              /* [tokens] rows of `channels` floats */
+  uint64_t input_stride;      /* float elements between rows, >= channels */
+  uint64_t output_stride;
+  uint32_t tokens;
+  uint32_t assignments;
+  uint32_t groups;
+  uint32_t channels;
+};
+int qnnp_hip_weighted_combine_run(const struct qnnp_hip_weighted_combine_args* args, const char** kernel_name);
+
 /* softargmax (q8softargmax.hip, linked into libqnnpack_gfx950.so only -- see the Makefile): replaces u8rmax_ukernel__sse2,
  * u8lut32norm_ukernel__scalar and the softargmax case of src/operator-run.c:625-637, 1091-1108. For each of `rows` rows
  * of `channels` bytes, each `*_stride` bytes apart, all in uint32_t:

@@ -36,6 +36,8 @@ enum qnnp_ukernel_type {
   qnnp_ukernel_type_dequantize,         /* dequantize.c */
   qnnp_ukernel_type_squeeze_excite,     /* squeeze-excite.c */
   qnnp_ukernel_type_dynamic_fully_connected,   /* dynamic-fully-connected.c */
+  qnnp_ukernel_type_topk_router,        /* moe.c */
+  qnnp_ukernel_type_weighted_combine,   /* moe.c */
 };
 
 /* One output phase of a strided deconvolution (deconvolution.c): the output pixels whose (oy + pad_top) % stride_h
@@ -214,6 +216,17 @@ struct qnnp_operator {
   size_t qd8_row_table_offset;
   float f32_output_min, f32_output_max;
   const char* qd8_rows_kernel;
+  /* the two ends of a mixture-of-experts layer (moe.c, include/qnnpack_gfx950_moe.h); neither owns device memory.
+   * Top-k router: batch_size rows of moe_groups logits at `input` (input_pixel_stride in elements) -> moe_assignments ids
+   * per row at `output`, minus moe_first_group, and as many floats at moe_weights.
+   * Weighted combine: batch_size * moe_assignments rows of `channels` floats at `input`, the caller's device arrays
+   * moe_weights and moe_group_ids of as many entries, read when the operator runs -> batch_size rows at `output`; a row
+   * counts when its id lies in [0, moe_groups). */
+  uint32_t moe_groups;
+  uint32_t moe_assignments;
+  uint32_t moe_first_group;
+  void* moe_weights;
+  const int32_t* moe_group_ids;
 
   uint8_t input_zero_point;
   uint8_t kernel_zero_point;

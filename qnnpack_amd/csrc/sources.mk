@@ -6,6 +6,7 @@ C_SRCS   := init.c convolution.c deconvolution.c fully-connected.c add.c global-
 HIP_SRCS := hip/runtime.hip hip/q8igemm.hip hip/q8gemm256.hip hip/q8gemm256c.hip hip/q8gemm256x.hip hip/q8gemm128x.hip hip/q8gemm128u.hip hip/q8pwconv.hip hip/q8pwstream.hip hip/q8pwstaged.hip hip/q8pwlongk.hip hip/q8pwgw.hip hip/q8convlds.hip hip/q8convwave.hip hip/q8convws16s.hip hip/q8convpatch.hip hip/q8convc3.hip hip/q8convc3s.hip hip/q8deconv.hip hip/q8dwconv.hip hip/q8dwlds.hip hip/q8dwrow.hip hip/q8dwcol.hip hip/q8dwcol5.hip hip/q8dwmfma.hip hip/q8dwmfma16.hip hip/q8pointwise.hip hip/q8fused.hip hip/q8fusedstrip.hip
 # The dynamically quantized fully connected operator (include/qnnpack_gfx950_dynamic.h): linked into libqnnpack_gfx950.so only
 # (qnnpack_amd/csrc/Makefile), like the other operators without a reference counterpart -- not part of C_SRCS / HIP_SRCS, which
-# are also the product half of the seam library.
-DYNAMIC_C_SRCS   := dynamic-fully-connected.c
-DYNAMIC_HIP_SRCS := hip/f32qd8rows.hip hip/f32qd8gatedrows.hip hip/qd8f32gemm.hip hip/qd8f32gemm4.hip hip/qd8f32gemm4b.hip hip/qd8f32gemm4z.hip hip/qd8f32gemm4s.hip hip/qd8f32gemm4m.hip hip/qd8f32gemm4g.hip
+# are also the product half of the seam library. With it the two ends of a mixture-of-experts layer around its grouped form
+# (include/qnnpack_gfx950_moe.h: moe.c, hip/f32topk.hip, hip/f32combine.hip), bit-exact float32 under the same flags.
+DYNAMIC_C_SRCS   := dynamic-fully-connected.c moe.c
+DYNAMIC_HIP_SRCS := hip/f32qd8rows.hip hip/f32qd8gatedrows.hip hip/qd8f32gemm.hip hip/qd8f32gemm4.hip hip/qd8f32gemm4b.hip hip/qd8f32gemm4z.hip hip/qd8f32gemm4s.hip hip/qd8f32gemm4m.hip hip/qd8f32gemm4g.hip hip/f32topk.hip hip/f32combine.hip

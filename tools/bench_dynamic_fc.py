@@ -51,7 +51,13 @@ Either side is recorded into a hipGraph and timed with qnnp_gfx950_graph_time, t
 pass and the plain operator are also timed on their own, and the two row launches by themselves (`rows_alone_gb_s`: bytes read and
 written over time). Shapes are FORMxGROUPSxROWSxKxN.
 
-    python tools/bench_dynamic_fc.py [--qb4w | --qb4w-zp | --qb4w-b32 | --mxfp4w | --grouped [--crossover] | --gated] [--shapes 1x4096x4096,...] [--sets 4] [--iters 20] [--rounds 5] [--json out.json]
+`--moe` times the two ends of a mixture-of-experts layer (include/qnnpack_gfx950_moe.h), each against what a caller does without
+it, into preallocated buffers: the top-k router against torch.topk + softmax + the int64 -> int32 copy (three launches), and the
+weighted combine against a torch multiply by the weights and a sum over the A axis (two launches and a T x A x N temporary;
+every id counts, torch cannot skip rows). Each side is recorded into a hipGraph and timed as `--gated` is; `combine_gb_s` is
+the bytes the combine reads and writes over its time. Shapes are ExAxNxT.
+
+    python tools/bench_dynamic_fc.py [--qb4w | --qb4w-zp | --qb4w-b32 | --mxfp4w | --grouped [--crossover] | --gated | --moe] [--shapes 1x4096x4096,...] [--sets 4] [--iters 20] [--rounds 5] [--json out.json]
 """
 import argparse
 import json
@@ -454,6 +460,73 @@ def gated_rows(lib, args, shapes, rng, gen, np, torch):
     return rows_out
 
 
+# (experts, A, N, tokens): gpt-oss's routing and hidden size at one token, a small batch and a prefill
+MOE_SHAPES = [(32, 4, 2880, 1), (32, 4, 2880, 64), (32, 4, 2880, 16384)]
+
+
+def moe_rows(lib, args, shapes, rng, gen, np, torch):
+    """one record per shape: router and combine against their torch chains, each side recorded into a graph, the sides in turn"""
+    rows_out = []
+    for e, a, n, tokens in shapes:
+        logits = torch.randn(tokens, e, dtype=torch.float32, device="cuda", generator=gen)
+        rows = torch.randn(tokens * a, n, dtype=torch.float32, device="cuda", generator=gen)
+        ids, w = torch.empty(tokens, a, dtype=torch.int32, device="cuda"), torch.empty(tokens, a, dtype=torch.float32, device="cuda")
+        t_values, t_index = torch.empty_like(w), torch.empty(tokens, a, dtype=torch.int64, device="cuda")
+        t_ids, t_w = torch.empty_like(ids), torch.empty_like(w)
+        y, t_y, t_product = torch.empty(tokens, n, dtype=torch.float32, device="cuda"), torch.empty(tokens, n, dtype=torch.float32, device="cuda"), torch.empty_like(rows)
+        ops = {"router": lib.create_topk_router_nc_f32(e, a), "combine": lib.create_weighted_combine_nc_f32(n, a, e)}
+        try:
+            lib.setup_topk_router_nc_f32(ops["router"], tokens, logits, e, ids, w)
+            lib.setup_weighted_combine_nc_f32(ops["combine"], tokens, rows, n, w, ids, y, n)
+
+            def torch_router():
+                torch.topk(logits, a, dim=1, out=(t_values, t_index))
+                torch.softmax(t_values, dim=1, out=t_w)
+                t_ids.copy_(t_index)
+
+            def torch_combine():
+                torch.mul(rows.view(tokens, a, n), w.view(tokens, a, 1), out=t_product.view(tokens, a, n))
+                torch.sum(t_product.view(tokens, a, n), dim=1, out=t_y)
+
+            sides = {"router": lambda: lib.run_operator(ops["router"]), "torch_router": torch_router,
+                     "combine": lambda: lib.run_operator(ops["combine"]), "torch_combine": torch_combine}
+            for step in sides.values():         # every kernel has run once before anything is captured
+                step()
+            torch.cuda.synchronize()
+            agree = {"ids_equal": float((ids == t_ids).float().mean()), "weights": float((w - t_w).abs().max()),
+                     "combine": float((y - t_y).abs().max() / t_y.abs().max())}
+            graphs = {}
+            for key, step in sides.items():
+                lib.graph_begin()
+                try:
+                    step()
+                finally:
+                    graphs[key] = lib.graph_end()
+            times = {key: [] for key in sides}
+            try:
+                for _ in range(args.rounds):
+                    for key, graph in graphs.items():
+                        times[key].append(lib.graph_time(graph, args.warmup, args.iters) * 1e3)
+            finally:
+                for graph in graphs.values():
+                    lib.graph_destroy(graph)
+            us = {key: statistics.median(v) for key, v in times.items()}
+            moved = tokens * (a * n * 4 + n * 4 + a * 8)
+            row = {"experts": e, "assignments": a, "n": n, "tokens": tokens, "us": {key: round(v, 2) for key, v in us.items()},
+                   "spread": {key: round((max(v) - min(v)) / statistics.median(v), 3) for key, v in times.items()},
+                   "torch_over_router": round(us["torch_router"] / us["router"], 3),
+                   "torch_over_combine": round(us["torch_combine"] / us["combine"], 3),
+                   "combine_gb_s": round(moved / us["combine"] * 1e-3, 1), "agreement": agree,
+                   "kernels": {key: lib.operator_kernel(op) for key, op in ops.items()}, "rounds": args.rounds,
+                   "replays_per_sample": args.iters}
+            rows_out.append(row)
+            print(json.dumps(row), flush=True)
+        finally:
+            for op in ops.values():
+                lib.delete_operator(op)
+    return rows_out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--qb4w", action="store_true", help="time the block-wise 4-bit operator against the qc4w one instead")
@@ -469,6 +542,8 @@ def main():
     ap.add_argument("--gated", action="store_true",
                     help="time the gated setups against a torch element-wise pass and the plain setup instead (shapes: FORMxGROUPSxROWSxKxN, "
                          "FORM grouped or qb4w_b32)")
+    ap.add_argument("--moe", action="store_true",
+                    help="time the top-k router and the weighted combine against their torch chains instead (shapes: ExAxNxT)")
     ap.add_argument("--shapes", default=None, help="BATCHxKxN,... instead of the built-in list")
     ap.add_argument("--sets", type=int, default=4)
     ap.add_argument("--iters", type=int, default=20)
@@ -486,14 +561,14 @@ def main():
     torch.zeros(1, device="cuda")
     lib = qnnpack_amd.load()
     lib.initialize()
-    if args.gated:      # torch's launches are recorded with the library's: both on one stream that can be captured, not the null stream
+    if args.gated or args.moe:      # torch's launches are recorded with the library's: both on one stream that can be captured, not the null stream
         torch.cuda.set_stream(torch.cuda.Stream())
     lib.set_stream(torch.cuda.current_stream().cuda_stream)
     lib.set_async(False)
     rng = np.random.default_rng(23)
     gen = torch.Generator(device="cuda").manual_seed(23)
 
-    shapes = (GROUPED_SHAPES if args.grouped else GATED_SHAPES if args.gated else SHAPES) if args.shapes is None else [
+    shapes = (GROUPED_SHAPES if args.grouped else GATED_SHAPES if args.gated else MOE_SHAPES if args.moe else SHAPES) if args.shapes is None else [
         tuple(v if v.isalpha() or "_" in v else int(v) for v in item.split("x")) for item in args.shapes.split(",")]
     rows_out = qb4w_rows(lib, args, shapes, rng, gen, np, torch) if args.qb4w else []
     if args.qb4w_zp:
@@ -506,7 +581,9 @@ def main():
         rows_out += grouped_rows(lib, args, shapes, rng, gen, np, torch)
     if args.gated:
         rows_out += gated_rows(lib, args, shapes, rng, gen, np, torch)
-    for batch, k, n in ([] if args.qb4w or args.qb4w_zp or args.qb4w_b32 or args.mxfp4w or args.grouped or args.gated else shapes):
+    if args.moe:
+        rows_out += moe_rows(lib, args, shapes, rng, gen, np, torch)
+    for batch, k, n in ([] if args.qb4w or args.qb4w_zp or args.qb4w_b32 or args.mxfp4w or args.grouped or args.gated or args.moe else shapes):
         kernel = rng.integers(-128, 128, size=(n, k), dtype=np.int8)
         scales = rng.uniform(0.005, 0.02, size=n).astype(np.float32)
         bias = rng.standard_normal(n).astype(np.float32)
