@@ -506,6 +506,121 @@ enum qnnp_status qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8_gated(
     float* output,                       /* [batch_size * A] rows of output_channels floats, device */
     size_t output_stride);
 
+/*
+ * A NORMALIZED input (residual add + RMSNorm) for every handle above with input_channels <= 16384. The gated setups are a
+ * second layer's; these two are the FIRST layer's: in a pre-norm transformer block the router's logit FC, the first expert
+ * layer and every dense QKV or MLP-up projection read rmsnorm(x + residual) * gamma. The row kernel computes that row h in
+ * registers while it reads, so that h is never written as floats and the add, square, mean, rsqrt and multiply launches in
+ * front of the operator disappear; where asked, it writes the sum x back as the next block's residual stream. No new create:
+ * the first setup takes a handle of any of the six plain creates, the second a handle of the grouped create.
+ *
+ * Definition (bit-exact, no tolerance). All arithmetic is float32, every operation rounded once, nothing fused. Two flushes:
+ *   flush(v)   = |v| <= 0x1p-126f ? copysignf(0, v) : v          behind a product
+ *   flush_lt(v) = |v| <  0x1p-126f ? copysignf(0, v) : v          on a loaded element and behind a sum of two of them
+ * With K = input_channels (K <= 16384), per row r:
+ *   x[k]  = residual ? flush_lt(flush_lt(input[r][k]) + flush_lt(residual[r][k])) : input[r][k]          k < K
+ *           if residual_out: residual_out[r][k] = x[k]                  the bits of x
+ *   sq[k] = flush(x[k] * x[k]) for k < K;  +0 for K <= k < 16384
+ *   piece sums, j = 0 .. 1023, over u = sq[16 j .. 16 j + 15]:
+ *           u[i] = u[i] + u[i + 8] (i < 8);  then u[i] + u[i + 4] (i < 4);  then i + 2 (i < 2);  then u[0] + u[1];   s[j] = u[0]
+ *   across pieces, for h = 512, 256, 128, 64, 32, 16, 8, 4, 2, 1 IN THIS ORDER:  s[j] = s[j] + s[j + h]  for j < h
+ *   S  = s[0]
+ *   m  = S / (float) K                       an IEEE division; (float) K is exact
+ *   v  = m + epsilon
+ *   r  = 1.0f / sqrtf(v)                     the correctly rounded square root, then an IEEE division
+ *   t  = flush(x[k] * r);   h[r][k] = flush(t * gamma[k])
+ * Everything after that is the first definition of this header with h[r] as the input row x[r]: the range, scale_r, zp_r, q,
+ * and the product and the finish of the handle's weight format, unchanged. An rmsnorm run equals, bit for bit, the same
+ * handle's plain run on a float tensor holding h.
+ *
+ * Why this order. Every sq is +0 or a positive normal number (or +inf, or NaN), and v + (+0) == v in every bit for those: the
+ * tree over 1024 zero-padded pieces gives the bits of the tree over any smaller power-of-two count of pieces that covers the
+ * row. So S is a function of x and K alone -- not of the kernel that ran, its load width or the batch --, and the tree maps
+ * onto the piece layout of the row kernels (piece j = i * 256 + wave * 64 + lane): steps 512 and 256 pair a lane's own
+ * pieces, 128 and 64 pair the waves of a workgroup, 32 to 1 are an xor butterfly inside a wave, in which both partners form
+ * s[j] + s[j ^ h]: float addition is commutative in every bit but a NaN's payload.
+ *
+ * NaN and infinity. A NaN among the x makes S, r and every h NaN; the row definition quantizes NaN to the zero point and an
+ * all-NaN row has scale 1: no payload reaches an output. Only residual_out shows a payload: it is that of the one NaN
+ * operand of the sum where there is one (quieted), unspecified otherwise. An infinite x, or a finite row whose S overflows,
+ * gives v = +inf, sqrtf(v) = +inf and r = +0: t is a zero of x's sign (NaN for the infinite x itself).
+ *
+ * No result depends on the denormal mode. epsilon is a normal number in [2^-40, 1] (checked); gamma is zero or normal with
+ * magnitude at most 2^20 (a precondition, not checked: it lives in device memory). The steps, written out:
+ *   x.  THIS STEP FAILED as first written, x = input + residual: a denormal operand counts as zero in one mode and as itself in
+ *       the other, and a sum of two normal numbers that cancel can be a denormal; residual_out would show either. Hence the
+ *       three flush_lt, which are not needed for h (steps t and h below absorb any |x| < 2^-126) but make residual_out the
+ *       same bits in both modes. flush_lt of a loaded element: a denormal becomes the zero that the other mode reads. The sum
+ *       of two numbers that are each zero or normal is exact whenever it is below 2^-125 in magnitude (both are multiples of
+ *       2^-149), so it is a denormal only as an exact value, which both the mode and flush_lt turn into the same signed zero:
+ *       < suffices, there is no rounding to straddle 2^-126. Without a residual x is the input's bits, denormals included.
+ *   sq. x * x of a normal x with an exact value below 2^-126 is, rounded, a denormal or exactly 2^-126 in one mode and either
+ *       of those or +0 in the other, whichever way a mode decides that a result within one rounding of 2^-126 is tiny; flush
+ *       with <= makes all of them +0. A denormal x squares to less than 2^-252: +0 in either mode.
+ *   S.  The sums run over +0 and positive normal numbers: nothing cancels, every partial sum is +0 or at least 2^-126.
+ *   m.  S / K can be a denormal (K up to 2^14). An m below 2^-100, denormal or flushed, is absorbed by epsilon >= 2^-40, whose
+ *       last place is at least 2^-63: v is the same. Any other m is normal.
+ *   r.  v >= 2^-40 is normal or +inf; sqrtf(v) lies in [2^-20, 2^64] or is +inf; r lies in [2^-64, 2^20] or is +0.
+ *   t.  A normal x times r: as step sq, <= makes a product within a rounding of 2^-126 a zero in either mode. A denormal x
+ *       (no residual) gives |x * r| < 2^-126 * 2^20 = 2^-106 in one mode and a zero in the other.
+ *   h.  t is zero, normal, or that mode-dependent value below 2^-106; gamma is zero or normal, at most 2^20. A product of two
+ *       normal numbers is settled by <= as before. What remains is an h that is below 2^-86 in magnitude in one mode and a
+ *       zero in the other. The "input side" argument of the first definition covers it with 2^-86 in the place of 2^-126:
+ *       a row whose range passes the scale test has hi - lo >= 255 * 2^-60 > 2^-53, whose half last place, 2^-77, absorbs such
+ *       an h at either end of the range; a range of nothing larger fails the test and takes scale 1; and h * inv is below
+ *       2^-86 * 2^60 = 2^-26, which rounds to the zero point like a zero.
+ *
+ * Statuses: those of the plain setup of the same handle, in its order; K is the channel count of input, gamma and both
+ * residual tensors. Added: unsupported_parameter for a handle with input_channels > 16384, answered from the handle alone,
+ * directly behind the check of the handle's kind and before batch_size or any pointer is looked at (there is no three-pass
+ * regime: the norm runs over a model's hidden size, and the in-place residual update is safe because the row stays in
+ * registers). invalid_parameter: a NULL gamma, or a residual_out without a residual (with the NULL tensors); gamma, residual or
+ * residual_out not 4-byte aligned (with the alignment check); an epsilon that is not a normal number in [2^-40, 1] (behind the
+ * alignment check and in front of the stride check, where the gated setups check their parameters); residual_stride < K
+ * where a residual is given (with the stride check); an overlap (with the overlap check): output shares no byte with any
+ * other tensor, residual_out shares none with input, gamma or group_ids, and residual_out is either residual itself, the
+ * same base pointer (in place), or disjoint from it; a tensor -- input, output, gamma, residual, residual_out -- that is not
+ * memory of the operator's device, in the plain form too (host memory included: nothing of these setups is staged).
+ * batch_size == 0 succeeds and the run does nothing. A refused setup leaves the previous one runnable; a plain, gated or
+ * rmsnorm setup replaces whichever came before. Each of the two refuses the other's handles. The scratch has the plain
+ * setup's size. gamma, like group_ids, is read WHEN THE OPERATOR RUNS: overwriting it between runs or between replays of a
+ * graph needs no new setup; so are input and residual, and residual_out is written by every run.
+ *
+ * Kernels. Only the first launch differs (hip/f32qd8rmsnormrows.hip; qnnp_gfx950_dynamic_rows_kernel names it):
+ *     f32_qd8_rmsnorm_rows_wave     K <= 1024     one wave per row; loads, lane exchanges, stores: no LDS memory, no barrier
+ *     f32_qd8_rmsnorm_rows_block    K <= 16384    one workgroup per row, the row read once and kept in registers as x
+ * each with _x4 behind its name where a base of input, residual, residual_out or gamma or, with more than one row,
+ * input_stride or residual_stride is no multiple of 16 bytes. Nothing at or past K is read or written in any float tensor.
+ * No scratch memory. qnnp_gfx950_operator_kernel is unaffected.
+ */
+enum qnnp_status qnnp_gfx950_setup_fully_connected_nc_f32_qd8_rmsnorm(
+    qnnp_operator_t fully_connected,     /* of any of the six plain creates, input_channels <= 16384 */
+    size_t batch_size,
+    const float* input,                  /* [batch_size] rows of input_channels floats, device */
+    size_t input_stride,                 /* in elements */
+    const float* gamma,                  /* [input_channels], device; read when the operator runs */
+    float epsilon,                       /* a normal number in [2^-40, 1] */
+    const float* residual,               /* rows of input_channels floats, device; or NULL */
+    float* residual_out,                 /* rows of input_channels floats, device; NULL, or == residual (in place) */
+    size_t residual_stride,              /* of both residual tensors, in elements */
+    float* output,                       /* device */
+    size_t output_stride);
+
+enum qnnp_status qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8_rmsnorm(
+    qnnp_operator_t fully_connected,     /* of the grouped create, input_channels <= 16384 */
+    size_t batch_size,                   /* input rows */
+    size_t assignments,                  /* A = groups per input row, 1 .. 8 */
+    const float* input,                  /* [batch_size] rows of input_channels floats, device */
+    size_t input_stride,                 /* in elements */
+    const float* gamma,                  /* [input_channels], device; read when the operator runs */
+    float epsilon,
+    const float* residual,
+    float* residual_out,
+    size_t residual_stride,
+    const int32_t* group_ids,            /* [batch_size * A], device; read when the operator runs */
+    float* output,                       /* [batch_size * A] rows of output_channels floats, device */
+    size_t output_stride);
+
 /* Name of the row kernel the operator's last run launched in front of the kernel qnnp_gfx950_operator_kernel names
  * (static string), or NULL: before the first run, or for a handle of another kind. */
 const char* qnnp_gfx950_dynamic_rows_kernel(qnnp_operator_t fully_connected);

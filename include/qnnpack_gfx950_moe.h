@@ -11,7 +11,9 @@
  *                                                                                        over T A input rows)
  *   combine           expert rows, weights, group_ids -> y [T][N]
  *
- * (the fifth is whatever produces the logits: a dense fully connected operator of qnnpack_gfx950_dynamic.h, say).
+ * (the fifth is whatever produces the logits: a dense fully connected operator of qnnpack_gfx950_dynamic.h, say). Both the
+ * logit operator and grouped layer 1 read rmsnorm(x + residual) * gamma in a pre-norm block: set them up with
+ * setup_..._qd8_rmsnorm and setup_grouped_..._qd8_rmsnorm of that header on x itself, and no norm launch stands in front.
  *
  * ---- The router ----
  * create(groups = E in 1 .. 1024, assignments = A in 1 .. 8 and at most E, first_group, flags)

@@ -336,6 +336,16 @@ DYNAMIC_API = (
         "ptr op, size_t batch_size, size_t assignments, tensor input, size_t input_stride, f32 alpha, f32 limit, "
         "f32 up_shift, tensor group_ids, tensor output, size_t output_stride", IF_PRESENT,
         doc="the grouped setup on gated input rows, as setup_fully_connected_nc_f32_qd8_gated"),
+    # gamma and the residual pair are float32 DEVICE arrays (residual and residual_out may be None; residual_out may be residual)
+    _op("qnnp_gfx950_setup_fully_connected_nc_f32_qd8_rmsnorm",
+        "ptr op, size_t batch_size, tensor input, size_t input_stride, tensor gamma, f32 epsilon, tensor residual, "
+        "tensor residual_out, size_t residual_stride, tensor output, size_t output_stride", IF_PRESENT,
+        doc="the setup of any plain dynamic handle (input_channels <= 16384) on NORMALIZED rows: the quantized row is "
+            "rmsnorm(input + residual) * gamma, and input + residual goes to residual_out; every tensor in device memory"),
+    _op("qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8_rmsnorm",
+        "ptr op, size_t batch_size, size_t assignments, tensor input, size_t input_stride, tensor gamma, f32 epsilon, "
+        "tensor residual, tensor residual_out, size_t residual_stride, tensor group_ids, tensor output, size_t output_stride",
+        IF_PRESENT, doc="the grouped setup on normalized rows, as setup_fully_connected_nc_f32_qd8_rmsnorm"),
     _fn("qnnp_gfx950_dynamic_rows_kernel", "ptr op", IF_PRESENT, restype=c_char_p),
 )
 
@@ -464,7 +474,8 @@ class Gfx950Library(QnnpackLibrary):
     and create_fully_connected_nc_f32_qd8_qb4w[_status], and create_fully_connected_nc_f32_qd8_qb4w_zp[_status],
     and create_fully_connected_nc_f32_qd8_qb4w_b32[_status], and create_fully_connected_nc_f32_qd8_mxfp4w[_status],
     and create_grouped_fully_connected_nc_f32_qd8_mxfp4w[_status] / setup_grouped_fully_connected_nc_f32_qd8[_status],
-    and the two setups on gated input rows, setup_[grouped_]fully_connected_nc_f32_qd8_gated[_status], and the router and
+    and the two setups on gated input rows, setup_[grouped_]fully_connected_nc_f32_qd8_gated[_status], and the two on
+    normalized rows, setup_[grouped_]fully_connected_nc_f32_qd8_rmsnorm[_status], and the router and
     the combine of include/qnnpack_gfx950_moe.h (MOE_API): [create|setup]_topk_router_nc_f32[_status] and
     [create|setup]_weighted_combine_nc_f32[_status].
     """

@@ -23,6 +23,11 @@
  * operator remembers the gate, and launch_rows sends the first launch to hip/f32qd8gatedrows.hip, which quantizes
  * act(gate) * up without writing it as floats. Nothing behind the first launch knows.
  *
+ * The two _rmsnorm setups (qnnp_gfx950_setup_[grouped_]fully_connected_nc_f32_qd8_rmsnorm) are the first layer's counterpart:
+ * the same bodies again with a struct qd8_norm, the operator remembers gamma, epsilon and the residual pair, and launch_rows
+ * sends the first launch to hip/f32qd8rmsnormrows.hip, which quantizes rmsnorm(input + residual) * gamma without writing it
+ * as floats and writes the sum back as the residual stream. K is at most 16384 there, and every tensor is device memory.
+ *
  * Not part of the seam library (oracle/Makefile).
  */
 #include <math.h>
@@ -41,14 +46,15 @@
 #include "upload.h"
 
 #define QNNP_QD8_MAX_INPUT_CHANNELS ((size_t) 32768)          /* K * 255 * 128 stays below 2^31 */
+#define QNNP_QD8_MAX_NORM_CHANNELS ((size_t) 16384)           /* the rmsnorm setups: a row stays in a workgroup's registers */
 #define QNNP_QD8_MAX_OUTPUT_CHANNELS ((size_t) 1 << 24)       /* exclusive */
 #define QNNP_QD8_MAX_GROUPS ((size_t) 1024)                   /* the plan kernel has one thread per group */
 #define QNNP_QD8_MAX_ASSIGNMENTS ((size_t) 8)
 #define QNNP_QD8_MAX_GROUPED_ROWS ((size_t) 1 << 20)          /* exclusive: output rows of the grouped operator */
 #define QNNP_QD8_MAX_GATHER_BYTES ((size_t) 1 << 31)          /* the grouped kernels' 32-bit offset of a gathered row */
 
-/* the first launch of either form: op->batch_size input rows into the scratch, by the plain or the gated row kernels as the
- * current setup says */
+/* the first launch of either form: op->batch_size input rows into the scratch, by the plain, the gated or the rmsnorm row
+ * kernels as the current setup says */
 static int launch_rows(struct qnnp_operator* op, const void* input, int8_t* quantized, struct qnnp_hip_qd8_row_entry* row_table)
 {
   if (op->qd8_gated) {
@@ -65,6 +71,23 @@ static int launch_rows(struct qnnp_operator* op, const void* input, int8_t* quan
       .up_shift = op->qd8_gate_up_shift,
     };
     return qnnp_hip_qd8_gated_rows_run(&gated_args, &op->qd8_rows_kernel);
+  }
+  if (op->qd8_rmsnorm) {
+    const struct qnnp_hip_qd8_rmsnorm_rows_args norm_args = {
+      .input = (const float*) input,
+      .quantized = quantized,
+      .row_table = row_table,
+      .rows = (uint32_t) op->batch_size,
+      .k = (uint32_t) op->group_input_channels,
+      .k_pad = op->k_pad,
+      .input_stride = op->input_pixel_stride,
+      .gamma = op->qd8_norm_gamma,
+      .residual = op->qd8_norm_residual,
+      .residual_out = op->qd8_norm_residual_out,
+      .residual_stride = op->qd8_norm_residual_stride,
+      .epsilon = op->qd8_norm_epsilon,
+    };
+    return qnnp_hip_qd8_rmsnorm_rows_run(&norm_args, &op->qd8_rows_kernel);
   }
   const struct qnnp_hip_qd8_rows_args rows_args = {
     .input = (const float*) input,
@@ -759,7 +782,66 @@ static int gate_is_valid(const struct qd8_gate* gate)
   return alpha_ok && limit_ok && shift_ok;
 }
 
-static void remember_gate(qnnp_operator_t op, const struct qd8_gate* gate)
+/* what an _rmsnorm setup adds to its plain one: NULL for the others. The input rows hold input_channels floats as in the plain
+ * setups; gamma has that many, and so has every row of the two residual tensors, which share residual_stride. */
+struct qd8_norm {
+  const float* gamma;
+  float epsilon;
+  const float* residual;       /* or NULL */
+  float* residual_out;         /* NULL, or (with a residual) where input + residual goes: the residual itself, or disjoint */
+  size_t residual_stride;
+};
+
+static int norm_pointers_are_given(const struct qd8_norm* norm)
+{
+  return norm->gamma != NULL && (norm->residual_out == NULL || norm->residual != NULL);
+}
+
+static int norm_pointers_are_aligned(const struct qd8_norm* norm)
+{
+  return ((uintptr_t) norm->gamma | (uintptr_t) norm->residual | (uintptr_t) norm->residual_out) % sizeof(float) == 0;
+}
+
+static int norm_epsilon_is_valid(const struct qd8_norm* norm)
+{
+  return isnormal(norm->epsilon) && norm->epsilon >= 0x1.0p-40f && norm->epsilon <= 1.0f;
+}
+
+/* the overlap rules of the header: the output shares no byte with gamma or a residual tensor (the setup has compared it with
+ * the input and the group ids); residual_out shares none with the input, gamma or the group ids, and is the residual itself
+ * or disjoint from it. group_ids is NULL in the plain form. */
+static int norm_tensors_overlap(
+    const struct qd8_norm* norm, size_t batch_size, size_t k, const void* input, size_t input_span, const void* output,
+    size_t output_span, const void* group_ids, size_t ids_span)
+{
+  const size_t gamma_span = k * sizeof(float);
+  const size_t residual_span = ((batch_size - 1) * norm->residual_stride + k) * sizeof(float);
+  if (qnnp_spans_overlap(norm->gamma, gamma_span, output, output_span)) {
+    return 1;
+  }
+  if (norm->residual != NULL && qnnp_spans_overlap(norm->residual, residual_span, output, output_span)) {
+    return 1;
+  }
+  if (norm->residual_out == NULL) {
+    return 0;
+  }
+  return qnnp_spans_overlap(norm->residual_out, residual_span, output, output_span) ||
+      qnnp_spans_overlap(norm->residual_out, residual_span, input, input_span) ||
+      qnnp_spans_overlap(norm->residual_out, residual_span, norm->gamma, gamma_span) ||
+      (group_ids != NULL && qnnp_spans_overlap(norm->residual_out, residual_span, group_ids, ids_span)) ||
+      ((const float*) norm->residual_out != norm->residual &&
+          qnnp_spans_overlap(norm->residual_out, residual_span, norm->residual, residual_span));
+}
+
+static int norm_tensors_are_on_device(const struct qd8_norm* norm)
+{
+  return qnnp_hip_is_device_pointer(norm->gamma) == 1 &&
+      (norm->residual == NULL || qnnp_hip_is_device_pointer(norm->residual) == 1) &&
+      (norm->residual_out == NULL || qnnp_hip_is_device_pointer(norm->residual_out) == 1);
+}
+
+/* the input form of the setup that is being made: a gate, a norm, or neither (never both) */
+static void remember_input_form(qnnp_operator_t op, const struct qd8_gate* gate, const struct qd8_norm* norm)
 {
   op->qd8_gated = gate != NULL;
   if (gate != NULL) {
@@ -767,14 +849,27 @@ static void remember_gate(qnnp_operator_t op, const struct qd8_gate* gate)
     op->qd8_gate_limit = gate->limit;
     op->qd8_gate_up_shift = gate->up_shift;
   }
+  op->qd8_rmsnorm = norm != NULL;
+  if (norm != NULL) {
+    op->qd8_norm_gamma = norm->gamma;
+    op->qd8_norm_epsilon = norm->epsilon;
+    op->qd8_norm_residual = norm->residual;
+    op->qd8_norm_residual_out = norm->residual_out;
+    op->qd8_norm_residual_stride = norm->residual_stride;
+  }
 }
 
 static enum qnnp_status setup_dynamic_fully_connected(
     const char* function, qnnp_operator_t op, size_t batch_size, const float* input, size_t input_stride,
-    const struct qd8_gate* gate, float* output, size_t output_stride)
+    const struct qd8_gate* gate, const struct qd8_norm* norm, float* output, size_t output_stride)
 {
   if (op->ukernel_type != qnnp_ukernel_type_dynamic_fully_connected || op->qd8_groups != 0) {
     return qnnp_status_invalid_parameter;
+  }
+  if (norm != NULL && op->group_input_channels > QNNP_QD8_MAX_NORM_CHANNELS) {
+    qnnp_log_error("cannot set up dynamic fully connected operator with %zu input channels on normalized rows: at most %zu",
+        op->group_input_channels, QNNP_QD8_MAX_NORM_CHANNELS);
+    return qnnp_status_unsupported_parameter;
   }
   if (batch_size == 0) {
     op->batch_size = 0;
@@ -782,11 +877,12 @@ static enum qnnp_status setup_dynamic_fully_connected(
   }
   /* the floats of an input row; the quantized row has group_input_channels elements either way */
   const size_t input_channels = (gate != NULL ? 2 : 1) * op->group_input_channels, output_channels = op->channels;
-  if (input == NULL || output == NULL) {
-    qnnp_log_error("cannot set up dynamic fully connected operator: NULL tensor");
+  if (input == NULL || output == NULL || (norm != NULL && !norm_pointers_are_given(norm))) {
+    qnnp_log_error("cannot set up dynamic fully connected operator: NULL tensor, or a residual output without a residual");
     return qnnp_status_invalid_parameter;
   }
-  if ((uintptr_t) input % sizeof(float) != 0 || (uintptr_t) output % sizeof(float) != 0) {
+  if ((uintptr_t) input % sizeof(float) != 0 || (uintptr_t) output % sizeof(float) != 0 ||
+      (norm != NULL && !norm_pointers_are_aligned(norm))) {
     qnnp_log_error("cannot set up dynamic fully connected operator: a tensor is not 4-byte aligned");
     return qnnp_status_invalid_parameter;
   }
@@ -796,7 +892,13 @@ static enum qnnp_status setup_dynamic_fully_connected(
         "at most 2^6 in magnitude", gate->alpha, gate->limit, gate->up_shift);
     return qnnp_status_invalid_parameter;
   }
-  if (input_stride < input_channels || output_stride < output_channels) {
+  if (norm != NULL && !norm_epsilon_is_valid(norm)) {
+    qnnp_log_error("cannot set up dynamic fully connected operator with epsilon %.7g: not a normal number in [2^-40, 1]",
+        norm->epsilon);
+    return qnnp_status_invalid_parameter;
+  }
+  if (input_stride < input_channels || output_stride < output_channels ||
+      (norm != NULL && norm->residual != NULL && norm->residual_stride < input_channels)) {
     qnnp_log_error("cannot set up dynamic fully connected operator: row stride smaller than the channel count");
     return qnnp_status_invalid_parameter;
   }
@@ -807,12 +909,21 @@ static enum qnnp_status setup_dynamic_fully_connected(
   }
   const size_t input_span = ((batch_size - 1) * input_stride + input_channels) * sizeof(float);
   const size_t output_span = ((batch_size - 1) * output_stride + output_channels) * sizeof(float);
-  if (qnnp_spans_overlap(input, input_span, output, output_span)) {
-    qnnp_log_error("cannot set up dynamic fully connected operator: the input and output tensors overlap");
+  if (qnnp_spans_overlap(input, input_span, output, output_span) ||
+      (norm != NULL && norm_tensors_overlap(norm, batch_size, input_channels, input, input_span, output, output_span, NULL, 0))) {
+    qnnp_log_error("cannot set up dynamic fully connected operator: the input and output tensors overlap, or the tensors of "
+        "the normalization overlap them or each other");
     return qnnp_status_invalid_parameter;
   }
   if (qnnp_hip_is_device_pointer(input) < 0 || qnnp_hip_is_device_pointer(output) < 0) {
     qnnp_log_error("cannot set up dynamic fully connected operator: a tensor lives on a different device than the operator");
+    return qnnp_status_invalid_parameter;
+  }
+  /* the device reads gamma when the operator runs, and a staged output next to a device residual_out is not built */
+  if (norm != NULL && (qnnp_hip_is_device_pointer(input) != 1 || qnnp_hip_is_device_pointer(output) != 1 ||
+      !norm_tensors_are_on_device(norm))) {
+    qnnp_log_error("cannot set up dynamic fully connected operator on normalized rows: every tensor has to be memory of the "
+        "operator's device");
     return qnnp_status_invalid_parameter;
   }
   /* the quantized rows (k_pad is a multiple of 64: the table behind them is 8-byte aligned), then the row table */
@@ -831,7 +942,7 @@ static enum qnnp_status setup_dynamic_fully_connected(
     op->qd8_scratch_capacity = scratch_bytes;
   }
   op->qd8_row_table_offset = row_table_offset;
-  remember_gate(op, gate);
+  remember_input_form(op, gate, norm);
   op->batch_size = batch_size;
   op->input = input;
   op->input_pixel_stride = input_stride;
@@ -842,10 +953,10 @@ static enum qnnp_status setup_dynamic_fully_connected(
   return qnnp_bind_tensors(op, function);
 }
 
-/* both plain setups: the lifecycle around the one body */
+/* the three plain setups: the lifecycle around the one body */
 static enum qnnp_status setup_dynamic_fully_connected_entered(
     const char* function, qnnp_operator_t fully_connected, size_t batch_size, const float* input, size_t input_stride,
-    const struct qd8_gate* gate, float* output, size_t output_stride)
+    const struct qd8_gate* gate, const struct qd8_norm* norm, float* output, size_t output_stride)
 {
   int token;
   const enum qnnp_status status = qnnp_enter_setup(function, fully_connected, &token);
@@ -853,7 +964,7 @@ static enum qnnp_status setup_dynamic_fully_connected_entered(
     return status;
   }
   return qnnp_leave_setup(fully_connected, token, setup_dynamic_fully_connected(
-      function, fully_connected, batch_size, input, input_stride, gate, output, output_stride));
+      function, fully_connected, batch_size, input, input_stride, gate, norm, output, output_stride));
 }
 
 enum qnnp_status qnnp_gfx950_setup_fully_connected_nc_f32_qd8(
@@ -865,7 +976,7 @@ enum qnnp_status qnnp_gfx950_setup_fully_connected_nc_f32_qd8(
     size_t output_stride)
 {
   return setup_dynamic_fully_connected_entered("qnnp_gfx950_setup_fully_connected_nc_f32_qd8", fully_connected, batch_size,
-      input, input_stride, NULL, output, output_stride);
+      input, input_stride, NULL, NULL, output, output_stride);
 }
 
 enum qnnp_status qnnp_gfx950_setup_fully_connected_nc_f32_qd8_gated(
@@ -881,7 +992,26 @@ enum qnnp_status qnnp_gfx950_setup_fully_connected_nc_f32_qd8_gated(
 {
   const struct qd8_gate gate = { .alpha = alpha, .limit = limit, .up_shift = up_shift };
   return setup_dynamic_fully_connected_entered("qnnp_gfx950_setup_fully_connected_nc_f32_qd8_gated", fully_connected,
-      batch_size, input, input_stride, &gate, output, output_stride);
+      batch_size, input, input_stride, &gate, NULL, output, output_stride);
+}
+
+enum qnnp_status qnnp_gfx950_setup_fully_connected_nc_f32_qd8_rmsnorm(
+    qnnp_operator_t fully_connected,
+    size_t batch_size,
+    const float* input,
+    size_t input_stride,
+    const float* gamma,
+    float epsilon,
+    const float* residual,
+    float* residual_out,
+    size_t residual_stride,
+    float* output,
+    size_t output_stride)
+{
+  const struct qd8_norm norm = { .gamma = gamma, .epsilon = epsilon, .residual = residual, .residual_out = residual_out,
+                                 .residual_stride = residual_stride };
+  return setup_dynamic_fully_connected_entered("qnnp_gfx950_setup_fully_connected_nc_f32_qd8_rmsnorm", fully_connected,
+      batch_size, input, input_stride, NULL, &norm, output, output_stride);
 }
 
 static inline size_t round_up_16(size_t bytes)
@@ -891,22 +1021,28 @@ static inline size_t round_up_16(size_t bytes)
 
 static enum qnnp_status setup_grouped_fully_connected(
     const char* function, qnnp_operator_t op, size_t batch_size, size_t assignments, const float* input, size_t input_stride,
-    const struct qd8_gate* gate, const int32_t* group_ids, float* output, size_t output_stride)
+    const struct qd8_gate* gate, const struct qd8_norm* norm, const int32_t* group_ids, float* output, size_t output_stride)
 {
   if (op->ukernel_type != qnnp_ukernel_type_dynamic_fully_connected || op->qd8_groups == 0) {
     return qnnp_status_invalid_parameter;
+  }
+  if (norm != NULL && op->group_input_channels > QNNP_QD8_MAX_NORM_CHANNELS) {
+    qnnp_log_error("cannot set up grouped dynamic fully connected operator with %zu input channels on normalized rows: at "
+        "most %zu", op->group_input_channels, QNNP_QD8_MAX_NORM_CHANNELS);
+    return qnnp_status_unsupported_parameter;
   }
   if (batch_size == 0) {
     op->batch_size = 0;
     return qnnp_status_success;
   }
   const size_t input_channels = (gate != NULL ? 2 : 1) * op->group_input_channels, output_channels = op->channels;
-  if (input == NULL || output == NULL || group_ids == NULL || assignments == 0) {
+  if (input == NULL || output == NULL || group_ids == NULL || assignments == 0 ||
+      (norm != NULL && !norm_pointers_are_given(norm))) {
     qnnp_log_error("cannot set up grouped dynamic fully connected operator: NULL tensor or group ids, or no assignments");
     return qnnp_status_invalid_parameter;
   }
   if ((uintptr_t) input % sizeof(float) != 0 || (uintptr_t) output % sizeof(float) != 0 ||
-      (uintptr_t) group_ids % sizeof(int32_t) != 0) {
+      (uintptr_t) group_ids % sizeof(int32_t) != 0 || (norm != NULL && !norm_pointers_are_aligned(norm))) {
     qnnp_log_error("cannot set up grouped dynamic fully connected operator: a tensor or the group ids are not 4-byte aligned");
     return qnnp_status_invalid_parameter;
   }
@@ -916,7 +1052,13 @@ static enum qnnp_status setup_grouped_fully_connected(
         "number of at most 2^6 in magnitude", gate->alpha, gate->limit, gate->up_shift);
     return qnnp_status_invalid_parameter;
   }
-  if (input_stride < input_channels || output_stride < output_channels) {
+  if (norm != NULL && !norm_epsilon_is_valid(norm)) {
+    qnnp_log_error("cannot set up grouped dynamic fully connected operator with epsilon %.7g: not a normal number in "
+        "[2^-40, 1]", norm->epsilon);
+    return qnnp_status_invalid_parameter;
+  }
+  if (input_stride < input_channels || output_stride < output_channels ||
+      (norm != NULL && norm->residual != NULL && norm->residual_stride < input_channels)) {
     qnnp_log_error("cannot set up grouped dynamic fully connected operator: row stride smaller than the channel count");
     return qnnp_status_invalid_parameter;
   }
@@ -943,14 +1085,17 @@ static enum qnnp_status setup_grouped_fully_connected(
   const size_t input_span = ((batch_size - 1) * input_stride + input_channels) * sizeof(float);
   const size_t output_span = ((rows - 1) * output_stride + output_channels) * sizeof(float);
   const size_t ids_span = rows * sizeof(int32_t);
-  if (qnnp_spans_overlap(input, input_span, output, output_span) || qnnp_spans_overlap(group_ids, ids_span, output, output_span)) {
-    qnnp_log_error("cannot set up grouped dynamic fully connected operator: the output overlaps the input or the group ids");
+  if (qnnp_spans_overlap(input, input_span, output, output_span) || qnnp_spans_overlap(group_ids, ids_span, output, output_span) ||
+      (norm != NULL &&
+          norm_tensors_overlap(norm, batch_size, input_channels, input, input_span, output, output_span, group_ids, ids_span))) {
+    qnnp_log_error("cannot set up grouped dynamic fully connected operator: the output overlaps the input or the group ids, or "
+        "the tensors of the normalization overlap them or each other");
     return qnnp_status_invalid_parameter;
   }
   /* all three in device memory: the ids are read by the launches, and an output staged through the device would bring
    * back bytes for the rows that were skipped */
   if (qnnp_hip_is_device_pointer(input) != 1 || qnnp_hip_is_device_pointer(output) != 1 ||
-      qnnp_hip_is_device_pointer(group_ids) != 1) {
+      qnnp_hip_is_device_pointer(group_ids) != 1 || (norm != NULL && !norm_tensors_are_on_device(norm))) {
     qnnp_log_error("cannot set up grouped dynamic fully connected operator: the tensors and the group ids have to be memory "
         "of the operator's device");
     return qnnp_status_invalid_parameter;
@@ -981,7 +1126,7 @@ static enum qnnp_status setup_grouped_fully_connected(
   op->qd8_tile_rows = tile_rows;
   op->qd8_max_tiles = (uint32_t) max_tiles;
   op->qd8_group_ids = group_ids;
-  remember_gate(op, gate);
+  remember_input_form(op, gate, norm);
   op->batch_size = batch_size;
   op->input = input;
   op->input_pixel_stride = input_stride;
@@ -992,10 +1137,11 @@ static enum qnnp_status setup_grouped_fully_connected(
   return qnnp_bind_tensors(op, function);
 }
 
-/* both grouped setups: the lifecycle around the one body */
+/* the three grouped setups: the lifecycle around the one body */
 static enum qnnp_status setup_grouped_fully_connected_entered(
     const char* function, qnnp_operator_t fully_connected, size_t batch_size, size_t assignments, const float* input,
-    size_t input_stride, const struct qd8_gate* gate, const int32_t* group_ids, float* output, size_t output_stride)
+    size_t input_stride, const struct qd8_gate* gate, const struct qd8_norm* norm, const int32_t* group_ids, float* output,
+    size_t output_stride)
 {
   int token;
   const enum qnnp_status status = qnnp_enter_setup(function, fully_connected, &token);
@@ -1003,7 +1149,7 @@ static enum qnnp_status setup_grouped_fully_connected_entered(
     return status;
   }
   return qnnp_leave_setup(fully_connected, token, setup_grouped_fully_connected(
-      function, fully_connected, batch_size, assignments, input, input_stride, gate, group_ids, output, output_stride));
+      function, fully_connected, batch_size, assignments, input, input_stride, gate, norm, group_ids, output, output_stride));
 }
 
 enum qnnp_status qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8(
@@ -1017,7 +1163,7 @@ enum qnnp_status qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8(
     size_t output_stride)
 {
   return setup_grouped_fully_connected_entered("qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8", fully_connected,
-      batch_size, assignments, input, input_stride, NULL, group_ids, output, output_stride);
+      batch_size, assignments, input, input_stride, NULL, NULL, group_ids, output, output_stride);
 }
 
 enum qnnp_status qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8_gated(
@@ -1035,7 +1181,28 @@ enum qnnp_status qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8_gated(
 {
   const struct qd8_gate gate = { .alpha = alpha, .limit = limit, .up_shift = up_shift };
   return setup_grouped_fully_connected_entered("qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8_gated", fully_connected,
-      batch_size, assignments, input, input_stride, &gate, group_ids, output, output_stride);
+      batch_size, assignments, input, input_stride, &gate, NULL, group_ids, output, output_stride);
+}
+
+enum qnnp_status qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8_rmsnorm(
+    qnnp_operator_t fully_connected,
+    size_t batch_size,
+    size_t assignments,
+    const float* input,
+    size_t input_stride,
+    const float* gamma,
+    float epsilon,
+    const float* residual,
+    float* residual_out,
+    size_t residual_stride,
+    const int32_t* group_ids,
+    float* output,
+    size_t output_stride)
+{
+  const struct qd8_norm norm = { .gamma = gamma, .epsilon = epsilon, .residual = residual, .residual_out = residual_out,
+                                 .residual_stride = residual_stride };
+  return setup_grouped_fully_connected_entered("qnnp_gfx950_setup_grouped_fully_connected_nc_f32_qd8_rmsnorm", fully_connected,
+      batch_size, assignments, input, input_stride, NULL, &norm, group_ids, output, output_stride);
 }
 
 const char* qnnp_gfx950_dynamic_rows_kernel(qnnp_operator_t fully_connected)

@@ -48,28 +48,6 @@ struct RowsParams {
   uint32_t rows, k, k_pad;
 };
 
-/* the piece at elements e0 .. e0 + 15 of the row; elements from K on read as 0, which neither end of the range sees */
-template <bool VEC>
-__device__ __forceinline__ Piece load_piece(const float* row, uint32_t e0, uint32_t k)
-{
-  Piece p;
-  if (VEC && e0 + kPiece <= k) {
-    const f32x4* src = reinterpret_cast<const f32x4*>(row + e0);
-    const f32x4 a = src[0], b = src[1], c = src[2], d = src[3];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      p.v[i] = a[i];
-      p.v[4 + i] = b[i];
-      p.v[8 + i] = c[i];
-      p.v[12 + i] = d[i];
-    }
-  } else {
-#pragma unroll
-    for (uint32_t i = 0; i < kPiece; i++) p.v[i] = e0 + i < k ? row[e0 + i] : 0.0f;
-  }
-  return p;
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(kRowsThreads)
 void f32_qd8_rows_wave_kernel(const RowsParams p)

@@ -1,7 +1,8 @@
 /*
  * f32qd8rows.hip.h -- what the row kernels of the dynamically quantized fully connected operator share: f32qd8rows.hip (the
  * input row is x itself) and f32qd8gatedrows.hip (the input row holds gate and up values, x = act(gate) * up is computed in
- * registers). A lane's piece is SIXTEEN consecutive elements of x; the range reduction, the row's scale and zero point, the
+ * registers) and f32qd8rmsnormrows.hip (x = rmsnorm(input + residual) * gamma, likewise). A lane's piece is SIXTEEN
+ * consecutive elements of x; the load of a piece of floats, the range reduction, the row's scale and zero point, the
  * quantization of one element and the two stores are the same code in both units, so the quantized row and the row table
  * entry of a given x are the same bytes whichever unit produced them. include/qnnpack_gfx950_dynamic.h has the definition.
  * Float32, every operation rounded once: no multiply is followed by an add anywhere in here, so nothing can fuse.
@@ -32,6 +33,28 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 struct Piece {
   float v[kPiece];
 };
+
+/* the piece at elements e0 .. e0 + 15 of the row; elements from K on read as 0, which neither end of the range sees */
+template <bool VEC>
+__device__ __forceinline__ Piece load_piece(const float* row, uint32_t e0, uint32_t k)
+{
+  Piece p;
+  if (VEC && e0 + kPiece <= k) {
+    const f32x4* src = reinterpret_cast<const f32x4*>(row + e0);
+    const f32x4 a = src[0], b = src[1], c = src[2], d = src[3];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      p.v[i] = a[i];
+      p.v[4 + i] = b[i];
+      p.v[8 + i] = c[i];
+      p.v[12 + i] = d[i];
+    }
+  } else {
+#pragma unroll
+    for (uint32_t i = 0; i < kPiece; i++) p.v[i] = e0 + i < k ? row[e0 + i] : 0.0f;
+  }
+  return p;
+}
 
 __device__ __forceinline__ void piece_range(const Piece& p, float& lo, float& hi)
 {

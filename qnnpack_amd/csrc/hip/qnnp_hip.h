@@ -607,6 +607,27 @@ struct qnnp_hip_qd8_gated_rows_args {
   float alpha, limit, up_shift;
 };
 int qnnp_hip_qd8_gated_rows_run(const struct qnnp_hip_qd8_gated_rows_args* args, const char** kernel_name);
+/* The rows launch after an RMSNORM setup (f32qd8rmsnormrows.hip): the row that is quantized is h = x * r * gamma of the
+ * header, x = input + residual (residual != NULL) or the input, computed in registers; x goes to residual_out where that is
+ * given, which may be `residual` itself. k <= 16384: no twopass regime. Outputs, grids and the regime bound of the wave kernel
+ * are those of qnnp_hip_qd8_rows_run; the names are f32_qd8_rmsnorm_rows_wave / _block[_x4], _x4 where a base of input, gamma,
+ * residual or residual_out or, with more than one row, one of the two strides is no multiple of 16 bytes. Every float pointer
+ * is 4-byte aligned; epsilon is taken as it is: the setup has checked it. */
+struct qnnp_hip_qd8_rmsnorm_rows_args {
+  const float* input;
+  int8_t* quantized;          /* [rows][k_pad] */
+  struct qnnp_hip_qd8_row_entry* row_table;   /* [rows] */
+  uint32_t rows;
+  uint32_t k;
+  uint32_t k_pad;
+  uint64_t input_stride;      /* float elements between rows */
+  const float* gamma;         /* [k] */
+  const float* residual;      /* rows of k floats, or NULL */
+  float* residual_out;        /* rows of k floats, NULL, or == residual */
+  uint64_t residual_stride;   /* float elements between rows, of both */
+  float epsilon;
+};
+int qnnp_hip_qd8_rmsnorm_rows_run(const struct qnnp_hip_qd8_rmsnorm_rows_args* args, const char** kernel_name);
 
 struct qnnp_hip_qd8_gemm_args {
   const int8_t* quantized;    /* [rows][k_pad], what the rows launch wrote */

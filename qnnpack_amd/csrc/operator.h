@@ -196,9 +196,18 @@ struct qnnp_operator {
    * the tile count (qd8_tile_count_offset) of hip/qd8f32gemm4g.hip.
    * qd8_gated is 1 while the current setup is one of the two _gated ones, whatever the create: the input rows then hold
    * group_input_channels PAIRS {gate, up} (input_pixel_stride >= twice that), the first launch is hip/f32qd8gatedrows.hip's
-   * with the three qd8_gate_* parameters, and everything behind it is unchanged. */
+   * with the three qd8_gate_* parameters, and everything behind it is unchanged.
+   * qd8_rmsnorm is 1 while the current setup is one of the two _rmsnorm ones (qd8_gated is then 0, and the reverse): the
+   * first launch is hip/f32qd8rmsnormrows.hip's, which reads the caller's device arrays qd8_norm_gamma and, where not NULL,
+   * qd8_norm_residual, and writes qd8_norm_residual_out where not NULL (rows qd8_norm_residual_stride elements apart). */
   uint32_t qd8_gated;
   float qd8_gate_alpha, qd8_gate_limit, qd8_gate_up_shift;
+  uint32_t qd8_rmsnorm;
+  float qd8_norm_epsilon;
+  const float* qd8_norm_gamma;
+  const float* qd8_norm_residual;
+  float* qd8_norm_residual_out;
+  size_t qd8_norm_residual_stride;
   uint32_t qd8_groups;
   uint32_t qd8_assignments;
   uint32_t qd8_tile_rows;

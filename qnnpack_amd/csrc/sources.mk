@@ -9,4 +9,4 @@ HIP_SRCS := hip/runtime.hip hip/q8igemm.hip hip/q8gemm256.hip hip/q8gemm256c.hip
 # are also the product half of the seam library. With it the two ends of a mixture-of-experts layer around its grouped form
 # (include/qnnpack_gfx950_moe.h: moe.c, hip/f32topk.hip, hip/f32combine.hip), bit-exact float32 under the same flags.
 DYNAMIC_C_SRCS   := dynamic-fully-connected.c moe.c
-DYNAMIC_HIP_SRCS := hip/f32qd8rows.hip hip/f32qd8gatedrows.hip hip/qd8f32gemm.hip hip/qd8f32gemm4.hip hip/qd8f32gemm4b.hip hip/qd8f32gemm4z.hip hip/qd8f32gemm4s.hip hip/qd8f32gemm4m.hip hip/qd8f32gemm4g.hip hip/f32topk.hip hip/f32combine.hip
+DYNAMIC_HIP_SRCS := hip/f32qd8rows.hip hip/f32qd8gatedrows.hip hip/f32qd8rmsnormrows.hip hip/qd8f32gemm.hip hip/qd8f32gemm4.hip hip/qd8f32gemm4b.hip hip/qd8f32gemm4z.hip hip/qd8f32gemm4s.hip hip/qd8f32gemm4m.hip hip/qd8f32gemm4g.hip hip/f32topk.hip hip/f32combine.hip

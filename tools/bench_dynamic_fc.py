@@ -57,7 +57,13 @@ weighted combine against a torch multiply by the weights and a sum over the A ax
 every id counts, torch cannot skip rows). Each side is recorded into a hipGraph and timed as `--gated` is; `combine_gb_s` is
 the bytes the combine reads and writes over its time. Shapes are ExAxNxT.
 
-    python tools/bench_dynamic_fc.py [--qb4w | --qb4w-zp | --qb4w-b32 | --mxfp4w | --grouped [--crossover] | --gated | --moe] [--shapes 1x4096x4096,...] [--sets 4] [--iters 20] [--rounds 5] [--json out.json]
+`--rmsnorm` times the RMSNORM setups (qnnp_gfx950_setup_[grouped_]fully_connected_nc_f32_qd8_rmsnorm, epsilon = 1e-5, a residual
+and a residual_out of its own) against what a caller does without them: the torch chain add, square, mean, add epsilon, rsqrt and
+two multiplies (seven launches into preallocated tensors, h written as floats) followed by the plain setup of a handle with the
+same weights. Each side is recorded into a hipGraph and timed as `--gated` is; the torch chain and the plain operator are also
+timed on their own. Shapes are FORMxGROUPSxROWSxKxN, FORM int8 or grouped.
+
+    python tools/bench_dynamic_fc.py [--qb4w | --qb4w-zp | --qb4w-b32 | --mxfp4w | --grouped [--crossover] | --gated | --rmsnorm | --moe] [--shapes 1x4096x4096,...] [--sets 4] [--iters 20] [--rounds 5] [--json out.json]
 """
 import argparse
 import json
@@ -460,6 +466,108 @@ def gated_rows(lib, args, shapes, rng, gen, np, torch):
     return rows_out
 
 
+# the rmsnorm setups: (form, groups, rows, K, N) -- 2880-wide rows at one token, a small batch and a prefill into a dense int8
+# layer and into the 32-expert grouped layer (A = 1), and one 8192-wide dense shape
+RMSNORM_SHAPES = [("int8", 0, 1, 2880, 2880), ("int8", 0, 64, 2880, 2880), ("int8", 0, 16384, 2880, 2880),
+                  ("grouped", 32, 1, 2880, 2880), ("grouped", 32, 64, 2880, 2880), ("grouped", 32, 16384, 2880, 2880),
+                  ("int8", 0, 512, 8192, 8192)]
+
+
+def rmsnorm_rows(lib, args, shapes, rng, gen, np, torch):
+    """one record per shape: the rmsnorm setup against what a caller does without it -- the torch residual add + RMSNorm chain
+    (seven launches into preallocated tensors, the sum kept as the new residual stream) and the plain setup of a handle with
+    the same weights -- each recorded into a graph, the sides in turn. The rmsnorm side writes residual_out to a tensor of its
+    own, not in place, so that every replay reads the same residual."""
+    rows_out, inf, eps = [], float("inf"), 1e-5
+    for form, groups, rows, k, n in shapes:
+        g = max(groups, 1)
+        x, residual = (torch.randn(rows, k, dtype=torch.float32, device="cuda", generator=gen) for _ in range(2))
+        gamma = torch.rand(k, dtype=torch.float32, device="cuda", generator=gen) + 0.5
+        s, t, h, s_out = (torch.empty(rows, k, dtype=torch.float32, device="cuda") for _ in range(4))
+        m = torch.empty(rows, 1, dtype=torch.float32, device="cuda")
+        y = torch.empty(rows * n, dtype=torch.float32, device="cuda")
+        ops = []
+        try:
+            if form == "grouped":
+                weights = (groups, k, n, rng.integers(0, 256, size=(g, n, k // 2), dtype=np.uint8),
+                           rng.integers(118, 123, size=(g, n, k // 32), dtype=np.uint8), None, -inf, inf)
+                create = lib.create_grouped_fully_connected_nc_f32_qd8_mxfp4w
+            else:
+                weights = (k, n, rng.integers(-128, 128, size=(n, k), dtype=np.int8),
+                           rng.uniform(0.005, 0.02, size=n).astype(np.float32), None, -inf, inf)
+                create = lib.create_fully_connected_nc_f32_qd8
+            for _ in range(2):          # the same weights twice: one handle is set up on normalized rows, the other plain
+                ops.append(create(*weights))
+            if form == "grouped":
+                d_ids = torch.from_numpy(rng.integers(0, groups, rows).astype(np.int32)).cuda()
+                lib.setup_grouped_fully_connected_nc_f32_qd8_rmsnorm(ops[0], rows, 1, x, k, gamma, eps, residual, s_out, k, d_ids, y, n)
+                lib.setup_grouped_fully_connected_nc_f32_qd8(ops[1], rows, 1, h, k, d_ids, y, n)
+            else:
+                lib.setup_fully_connected_nc_f32_qd8_rmsnorm(ops[0], rows, x, k, gamma, eps, residual, s_out, k, y, n)
+                lib.setup_fully_connected_nc_f32_qd8(ops[1], rows, h, k, y, n)
+
+            def torch_chain():          # seven launches into preallocated tensors: nothing is allocated under a capture
+                torch.add(x, residual, out=s)
+                torch.mul(s, s, out=t)
+                torch.mean(t, dim=1, keepdim=True, out=m)
+                m.add_(eps)
+                m.rsqrt_()
+                torch.mul(s, m, out=t)
+                torch.mul(t, gamma, out=h)
+
+            sides = {"rmsnorm": (lambda: lib.run_operator(ops[0]),), "torch_then_plain": (torch_chain, lambda: lib.run_operator(ops[1])),
+                     "torch_chain": (torch_chain,), "plain": (lambda: lib.run_operator(ops[1]),)}
+            results = {}
+            for key, steps in sides.items():    # every kernel has run once before anything is captured
+                for step in steps:
+                    step()
+                torch.cuda.synchronize()
+                results[key] = y.clone()
+            # torch's mean and rsqrt are not the definition's to the last bit, so a few elements may land in the neighbouring int8 code
+            differ = float((results["rmsnorm"] - results["torch_then_plain"]).abs().max() / results["rmsnorm"].abs().max())
+            assert bool((s_out == s).all()), "residual_out is the torch sum, bit for bit"
+            graphs = {}
+            for key, steps in sides.items():
+                lib.graph_begin()
+                try:
+                    for step in steps:
+                        step()
+                finally:
+                    graphs[key] = lib.graph_end()
+            h.zero_()
+            lib.graph_launch(graphs["torch_chain"])
+            lib.graph_synchronize(graphs["torch_chain"])
+            assert float(h.abs().sum()) > 0, "the torch chain was not recorded into the graph"
+            times = {key: [] for key in sides}
+            try:
+                for _ in range(args.rounds):
+                    for key, graph in graphs.items():
+                        times[key].append(lib.graph_time(graph, args.warmup, args.iters) * 1e3)
+            finally:
+                for graph in graphs.values():
+                    lib.graph_destroy(graph)
+            us = {key: statistics.median(v) for key, v in times.items()}
+            k_pad = (k + 63) // 64 * 64
+            row = {"form": form, "groups": groups, "rows": rows, "k": k, "n": n,
+                   "us": {key: round(v, 2) for key, v in us.items()},
+                   "spread": {key: round((max(v) - min(v)) / statistics.median(v), 3) for key, v in times.items()},
+                   "chain_over_rmsnorm": round(us["torch_then_plain"] / us["rmsnorm"], 3),
+                   "largest_output_difference_over_largest_output": differ,
+                   # what the row launch of either side moves: input, residual and residual_out and the quantized row and its entry,
+                   # plus gamma once -- against h alone; and what the torch chain moves in front of the plain side: ten passes over
+                   # a [rows][K] float tensor (add 3, square 2, mean 1, the two multiplies 2 each)
+                   "row_launch_bytes": {"rmsnorm": rows * (12 * k + k_pad + 8) + 4 * k, "plain": rows * (4 * k + k_pad + 8)},
+                   "torch_chain_bytes": rows * 10 * 4 * k,
+                   "rows_kernels": {"rmsnorm": lib.dynamic_rows_kernel(ops[0]), "plain": lib.dynamic_rows_kernel(ops[1])},
+                   "kernel": lib.operator_kernel(ops[0]), "rounds": args.rounds, "replays_per_sample": args.iters}
+            rows_out.append(row)
+            print(json.dumps(row), flush=True)
+        finally:
+            for op in ops:
+                lib.delete_operator(op)
+    return rows_out
+
+
 # (experts, A, N, tokens): gpt-oss's routing and hidden size at one token, a small batch and a prefill
 MOE_SHAPES = [(32, 4, 2880, 1), (32, 4, 2880, 64), (32, 4, 2880, 16384)]
 
@@ -542,6 +650,9 @@ def main():
     ap.add_argument("--gated", action="store_true",
                     help="time the gated setups against a torch element-wise pass and the plain setup instead (shapes: FORMxGROUPSxROWSxKxN, "
                          "FORM grouped or qb4w_b32)")
+    ap.add_argument("--rmsnorm", action="store_true",
+                    help="time the rmsnorm setups against the torch residual add + RMSNorm chain and the plain setup instead (shapes: "
+                         "FORMxGROUPSxROWSxKxN, FORM int8 or grouped)")
     ap.add_argument("--moe", action="store_true",
                     help="time the top-k router and the weighted combine against their torch chains instead (shapes: ExAxNxT)")
     ap.add_argument("--shapes", default=None, help="BATCHxKxN,... instead of the built-in list")
@@ -561,14 +672,14 @@ def main():
     torch.zeros(1, device="cuda")
     lib = qnnpack_amd.load()
     lib.initialize()
-    if args.gated or args.moe:      # torch's launches are recorded with the library's: both on one stream that can be captured, not the null stream
+    if args.gated or args.rmsnorm or args.moe:      # torch's launches are recorded with the library's: both on one stream that can be captured, not the null stream
         torch.cuda.set_stream(torch.cuda.Stream())
     lib.set_stream(torch.cuda.current_stream().cuda_stream)
     lib.set_async(False)
     rng = np.random.default_rng(23)
     gen = torch.Generator(device="cuda").manual_seed(23)
 
-    shapes = (GROUPED_SHAPES if args.grouped else GATED_SHAPES if args.gated else MOE_SHAPES if args.moe else SHAPES) if args.shapes is None else [
+    shapes = (GROUPED_SHAPES if args.grouped else GATED_SHAPES if args.gated else RMSNORM_SHAPES if args.rmsnorm else MOE_SHAPES if args.moe else SHAPES) if args.shapes is None else [
         tuple(v if v.isalpha() or "_" in v else int(v) for v in item.split("x")) for item in args.shapes.split(",")]
     rows_out = qb4w_rows(lib, args, shapes, rng, gen, np, torch) if args.qb4w else []
     if args.qb4w_zp:
@@ -581,9 +692,11 @@ def main():
         rows_out += grouped_rows(lib, args, shapes, rng, gen, np, torch)
     if args.gated:
         rows_out += gated_rows(lib, args, shapes, rng, gen, np, torch)
+    if args.rmsnorm:
+        rows_out += rmsnorm_rows(lib, args, shapes, rng, gen, np, torch)
     if args.moe:
         rows_out += moe_rows(lib, args, shapes, rng, gen, np, torch)
-    for batch, k, n in ([] if args.qb4w or args.qb4w_zp or args.qb4w_b32 or args.mxfp4w or args.grouped or args.gated or args.moe else shapes):
+    for batch, k, n in ([] if args.qb4w or args.qb4w_zp or args.qb4w_b32 or args.mxfp4w or args.grouped or args.gated or args.rmsnorm or args.moe else shapes):
         kernel = rng.integers(-128, 128, size=(n, k), dtype=np.int8)
         scales = rng.uniform(0.005, 0.02, size=n).astype(np.float32)
         bias = rng.standard_normal(n).astype(np.float32)
